@@ -10,8 +10,13 @@ One "step" = one full generation of the local batch: cross-attention K/V project
 three embed sets + 50 x [UNet on the CFG batch 2B + CFG combine + DDIM update].  Inputs are
 resident in HBM before the timed region.  N = 1 runs BASELINE.json configs[1] (SD1.5, 512x512,
 50 steps, batch 4); N > 1 runs configs[2]'s shard, 8 images per GPU (weak scaling, images are
-independent: no collective inside the timed region; one RCCL weight broadcast before it), and adds
-configs[3]'s shard (SDXL 1024x1024, 30 steps, 2 images per GPU) as `secondary` on every rank count.
+independent: no collective inside the timed region; one RCCL weight broadcast before it).
+
+A plain run sets up, warms up, times the K steps and prints the headline line (with `ms_per_step`).  Everything else is
+measured only with --full: the clock / power sample of the headline's workload, the ID cross-attention roofline block,
+the secondary workloads (N = 1: SD1.5 batch 8, ControlNet-inpaint batch 8, SDXL batch 2; N > 1: configs[3]'s SDXL
+shard), the stock PyTorch fp16 baseline and the CPU baseline.  --dump-outputs DIR writes the latents the last timed
+step returned as DIR/images.npy (float32); the weights and inputs are seeded, so equal arguments give equal inputs.
 """
 from __future__ import annotations
 
@@ -108,9 +113,17 @@ def parse():
     p.add_argument("--no-torch-baseline", action="store_true")
     p.add_argument("--no-roofline", action="store_true")
     p.add_argument("--no-secondary", action="store_true",
-                   help="skip the secondary workloads (SDXL batch 2, ControlNet-inpaint batch 8, SD1.5 batch 8) of the default N=1 run")
+                   help="skip the secondary workloads (SDXL batch 2, ControlNet-inpaint batch 8, SD1.5 batch 8) of the --full N=1 run")
     p.add_argument("--lora-rank", type=int, default=128)
-    return p.parse_args()
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need (gpu_state, roofline, secondary, torch / CPU baselines; "
+                        "the --no-* options above select among them)")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the outputs of the last timed step as DIR/<name>.npy (float32)")
+    a = p.parse_args()
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
+    return a
 
 
 def cfg_shared_gflop(family: str, H: int, W_: int) -> float:
@@ -367,7 +380,8 @@ def kernel_digest(only=None) -> str:
 
 def run_workload(a, family, cn, bpg, steps, warmup, rank, world, dev, ddim_override=None, sample=False):
     """Build the engine(s) of one workload, run `warmup` untimed + `steps` timed generations of the local batch between
-    barrier + synchronize pairs; returns (seconds max-over-ranks, description dict, unet, pipe)."""
+    barrier + synchronize pairs; returns (seconds max-over-ranks, description dict, unet, pipe, output of the last timed
+    generation)."""
     from consistentid_amd import distributed, pipeline, synth, unet_spec
     from consistentid_amd.unet import HipUNet
     from consistentid_amd.weights import PackedUNet
@@ -412,7 +426,7 @@ def run_workload(a, family, cn, bpg, steps, warmup, rank, world, dev, ddim_overr
     dt, out = time_generations(pipe, kw, steps, warmup, world, dev, sample=sample, poll=(rank == 0))
     desc = {"family": family, "cn": cn, "cfg": cfg, "H": H, "W": W_, "ddim_steps": ddim_steps, "merge": merge,
             "bpg": bpg, "global_batch": global_batch}
-    return dt, desc, unet, pipe
+    return dt, desc, unet, pipe, out
 
 
 def workload_inputs(family, cn, cfg, bpg, H, W_, ddim_steps, guidance, merge, rank, world, dev):
@@ -453,6 +467,7 @@ def time_generations(pipe, kw, steps, warmup, world, dev, sample=False, poll=Tru
     barrier()
     dt = time.perf_counter() - t0
     if sample:
+        out.images = out.images.clone()     # what the last timed generation returned, whatever the two below reuse
         # clock / power / temperature while the SAME generations run, in two extra untimed ones on every rank (rank 0 polls):
         # polling rocm-smi beside the timed region was measured to slow it by 12 % (545 -> 625 ms per generation)
         smp = GpuStateSampler(dev.index or 0) if poll else None
@@ -507,11 +522,33 @@ def secondary_workloads(a, unet_sd15, dev):
     del pipe, kw
     torch.cuda.empty_cache()
     for key, family, cn, bpg in (("cn_inpaint_b8", "sd15", True, 8), ("sdxl_b2_30steps", "sdxl", False, 2)):
-        dt, d, u, p = run_workload(a, family, cn, bpg, 2, 1, 0, 1, dev)
+        dt, d, u, p, _ = run_workload(a, family, cn, bpg, 2, 1, 0, 1, dev)
         out[key] = entry(dt, d, 2)
         del u, p
         torch.cuda.empty_cache()
     return out
+
+
+DUMP_BYTES_MAX = 64 << 20
+
+
+def dump_outputs(images, directory, rank, world):
+    """--dump-outputs: the latents of the last timed generation (every rank's shard, in global image order) as
+    <directory>/images.npy in float32.  Above DUMP_BYTES_MAX a fixed seeded sample of the elements is written instead."""
+    import numpy as np
+    arr = images.detach().float().cpu().numpy()
+    if world > 1:
+        import torch.distributed as dist
+        parts = [None] * world
+        dist.all_gather_object(parts, arr)
+        arr = np.concatenate(parts)
+    if rank != 0:
+        return
+    if arr.nbytes > DUMP_BYTES_MAX:
+        idx = np.sort(np.random.default_rng(0).choice(arr.size, DUMP_BYTES_MAX // arr.itemsize, replace=False))
+        arr = arr.reshape(-1)[idx]
+    os.makedirs(directory, exist_ok=True)
+    np.save(os.path.join(directory, "images.npy"), arr)
 
 
 def main():
@@ -535,25 +572,30 @@ def main():
     if cn:
         a.family = "sd15"
         a.no_cpu_baseline = True      # the cpu_baseline leg times the plain SD1.5 loop
-    # N = 1: BASELINE config 2 (batch 4).  N > 1: config 3's shard, 8 images per GPU (64 on 8 GPUs) -- with the SDXL shard of
-    # config 4 (2 images per GPU, 16 on 8) as `secondary` on every rank count, so that a scaling run lands on BASELINE shapes
+    # N = 1: BASELINE config 2 (batch 4).  N > 1: config 3's shard, 8 images per GPU (64 on 8 GPUs) -- with --full, the SDXL
+    # shard of config 4 (2 images per GPU, 16 on 8) as `secondary` on every rank count, so that a scaling run lands on BASELINE
+    # shapes
     bpg = a.batch_per_gpu or (8 if cn else (4 if world == 1 else 8) if a.family == "sd15" else 2)
-    dt, d, unet, pipe = run_workload(a, a.family, cn, bpg, a.steps, a.warmup, rank, world, dev, a.ddim_steps, sample=True)
+    dt, d, unet, pipe, out = run_workload(a, a.family, cn, bpg, a.steps, a.warmup, rank, world, dev, a.ddim_steps,
+                                          sample=a.full)
     cfg, H, W_, ddim_steps, global_batch = d["cfg"], d["H"], d["W"], d["ddim_steps"], d["global_batch"]
+    if a.dump_outputs:
+        dump_outputs(out.images, a.dump_outputs, rank, world)
+    del out
     gpu_state = time_generations.last_gpu_state
     # the metric kernel's roofline block, on rank 0, while the headline's engine still exists (N > 1 frees it for the SDXL shard)
     xroof = None
-    if rank == 0 and not a.no_roofline:
+    if rank == 0 and a.full and not a.no_roofline:
         c0 = cfg.block_out_channels[0] if a.family == "sd15" else cfg.block_out_channels[1]
         heads = cfg.num_attention_heads[0] if a.family == "sd15" else cfg.num_attention_heads[1]
         n0 = (H // 8) * (W_ // 8) if a.family == "sd15" else (H // 16) * (W_ // 16)
         xroof = measure_xattn_roofline(unet, 2 * bpg, n0, c0, heads)
     sdxl_scaling = None
-    if world > 1 and default_shape and not cn and not a.no_secondary:
+    if world > 1 and a.full and default_shape and not cn and not a.no_secondary:
         del pipe, unet
         pipe = unet = None
         torch.cuda.empty_cache()
-        dt2, d2, u2, p2 = run_workload(a, "sdxl", False, 2, 2, 1, rank, world, dev)
+        dt2, d2, u2, p2, _ = run_workload(a, "sdxl", False, 2, 2, 1, rank, world, dev)
         sdxl_scaling = {"images_per_s": round(d2["global_batch"] * 2 / dt2, 4), "ms_per_generation": round(dt2 / 2 * 1e3, 1),
                         "workload": workload_name(d2, a.lora_rank, a.no_graph), "timed_generations": 2, "warmup": 1,
                         "n_gpus": world, "scaling": "weak"}
@@ -571,7 +613,7 @@ def main():
             "vs_baseline": None, "dtype": "f16", "data": "synthetic",
             "config": {"workload": workload_name(d, a.lora_rank, a.no_graph),
                        "global_batch": global_batch, "parallelism": f"dp{world} (images sharded, no in-step collective)"},
-            # clock / power / temperature of GPU 0 sampled (rocm-smi) while the timed generations ran
+            # clock / power / temperature of GPU 0 sampled (rocm-smi) while the timed generations ran (--full; null otherwise)
             "gpu_state": gpu_state,
             # every A/B switch of the library / engine present in the environment of this run (none = the shipped defaults)
             "env": {k: v for k, v in sorted(os.environ.items()) if k.startswith("CID_")},
@@ -599,22 +641,23 @@ def main():
         elif not cn:
             res["roofline"] = {"step": step}
         pipe = None
-        if default_run and not cn and not a.no_secondary:
-            res["secondary"] = secondary_workloads(a, unet, dev)
-        if sdxl_scaling is not None:
-            res["secondary"] = {"sdxl_b2_30steps": sdxl_scaling}
-        if world == 1 and not cn and not a.no_torch_baseline:
-            unet = None
-            torch.cuda.empty_cache()
-            res["torch_fp16_baseline"] = torch_fp16_baseline(a.family, ddim_steps, bpg, dev)
-        if world == 1 and not a.no_cpu_baseline:
-            full = (a.family == "sd15" and not a.cpu_baseline_short) or a.cpu_baseline_full
-            res["cpu_baseline"] = cpu_baseline(a.family, ddim_steps, full)
-        elif world > 1:
-            # the CPU leg is timed on rank 0 of the N = 1 run only (it would hold N - 1 GPUs idle for a minute here)
-            res["cpu_baseline"] = {"value": None, "unit": "images/s", "kind": "port",
-                                   "sample": "not timed at N > 1: see the cpu_baseline object of the N = 1 line (same box class; "
-                                             "BASELINE.md section 3 lists the measured values)"}
+        if a.full:
+            if default_run and not cn and not a.no_secondary:
+                res["secondary"] = secondary_workloads(a, unet, dev)
+            if sdxl_scaling is not None:
+                res["secondary"] = {"sdxl_b2_30steps": sdxl_scaling}
+            if world == 1 and not cn and not a.no_torch_baseline:
+                unet = None
+                torch.cuda.empty_cache()
+                res["torch_fp16_baseline"] = torch_fp16_baseline(a.family, ddim_steps, bpg, dev)
+            if world == 1 and not a.no_cpu_baseline:
+                full = (a.family == "sd15" and not a.cpu_baseline_short) or a.cpu_baseline_full
+                res["cpu_baseline"] = cpu_baseline(a.family, ddim_steps, full)
+            elif world > 1:
+                # the CPU leg is timed on rank 0 of the N = 1 run only (it would hold N - 1 GPUs idle for a minute here)
+                res["cpu_baseline"] = {"value": None, "unit": "images/s", "kind": "port",
+                                       "sample": "not timed at N > 1: see the cpu_baseline object of the N = 1 line (same box "
+                                                 "class; BASELINE.md section 3 lists the measured values)"}
         print(json.dumps(res), flush=True)
     if world > 1:
         dist.barrier()

@@ -213,25 +213,38 @@ def test_engines_rebuilt_from_the_broadcast_arena_are_bit_identical(dev, sd15):
     assert torch.equal(m0, m1) and all(torch.equal(x, y) for x, y in zip(d0, d1)), "ControlNet rebuilt from the arena differs"
 
 
-def test_bench_two_ranks_on_one_gpu(dev):
-    """bench.py --gpus 2 end to end on this one GPU (CID_BENCH_SHARE_GPU folds the ranks onto device 0, gloo carries the
-    weight broadcast instead of RCCL): self-spawn under torch.distributed.run, arena broadcast, rank 1 rebuilds its
-    engine from the arena, image sharding by global index, barrier + max-over-ranks timing, one JSON line from rank 0."""
+def test_bench_two_ranks_on_one_gpu(dev, tmp_path):
+    """bench.py --gpus 2 --full end to end on this one GPU (CID_BENCH_SHARE_GPU folds the ranks onto device 0, gloo carries
+    the weight broadcast instead of RCCL): self-spawn under torch.distributed.run, arena broadcast, rank 1 rebuilds its
+    engine from the arena, image sharding by global index, barrier + max-over-ranks timing, the two sampled untimed
+    generations on both ranks, one JSON line from rank 0, --dump-outputs with both ranks' latents in global image order
+    (rank 0's shard = a plain one-rank run of the same 4 images)."""
     import json
     import os
     import subprocess
     import sys
     from pathlib import Path
+    import numpy as np
     root = Path(__file__).resolve().parents[1]
-    env = dict(os.environ, CID_BENCH_SHARE_GPU="1", CID_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
-    env.pop("WORLD_SIZE", None)
-    r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--ddim-steps", "6",
-                        "--batch-per-gpu", "4", "--no-cpu-baseline", "--no-torch-baseline", "--no-roofline"], capture_output=True, text=True, env=env,
-                       timeout=900, cwd=str(root))
-    assert r.returncode == 0, r.stderr[-3000:]
-    line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
-    res = json.loads(line)
+    args = ["--steps", "1", "--warmup", "1", "--ddim-steps", "6", "--batch-per-gpu", "4", "--no-cpu-baseline",
+            "--no-torch-baseline", "--no-roofline"]
+
+    def bench(gpus, out, *extra):
+        env = dict(os.environ, CID_BENCH_SHARE_GPU="1", CID_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
+        env.pop("WORLD_SIZE", None)
+        r = subprocess.run([sys.executable, str(root / "bench.py"), "--gpus", str(gpus), *args, *extra, "--dump-outputs",
+                            str(out)], capture_output=True, text=True, env=env, timeout=900, cwd=str(root))
+        assert r.returncode == 0, r.stderr[-3000:]
+        return json.loads([l for l in r.stdout.splitlines() if l.startswith("{")][-1]), np.load(out / "images.npy")
+
+    res, lat = bench(2, tmp_path / "two", "--full")
     assert res["n_gpus"] == 2 and res["config"]["global_batch"] == 8 and res["value"] > 0 and res["scaling"] == "weak"
+    assert lat.dtype == np.float32 and lat.shape == (8, 4, 64, 64) and np.isfinite(lat).all()
+    res1, one = bench(1, tmp_path / "one")
+    assert res1["n_gpus"] == 1 and one.shape == (4, 4, 64, 64)
+    rel = lambda a, b: float(np.linalg.norm(a - b) / np.linalg.norm(b))
+    assert rel(lat[:4], one) < 1e-3, f"rank 0's shard is not first: rel_l2 {rel(lat[:4], one):.3e} against the one-rank run"
+    assert rel(lat[4:], one) > 0.1, "rank 1 wrote rank 0's images"
 
 
 def test_rccl_backend_executes_on_one_rank(dev):

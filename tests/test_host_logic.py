@@ -183,3 +183,37 @@ def test_bench_cfg_shared_prefix_flops():
     got = bench.cfg_shared_gflop("sd15", 512, 512)
     assert abs(got - want) < 1e-9 and 0.02 < got / (2 * bench.UNET_GFLOP_PER_SAMPLE["sd15"]) < 0.03
     assert bench.cfg_shared_gflop("sdxl", 1024, 1024) == 0.0
+
+
+def test_bench_options_full_off_by_default(monkeypatch):
+    """bench.parse: a plain run measures the headline only (--full off), --steps sets the timed steps, --dump-outputs takes a
+    directory; fewer than one timed step is refused"""
+    import sys
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2"])
+    a = bench.parse()
+    assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, False, None)
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "1", "--full", "--dump-outputs", "out"])
+    a = bench.parse()
+    assert a.full and a.dump_outputs == "out"
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit):
+        bench.parse()
+
+
+def test_bench_dump_outputs_float32_and_capped(tmp_path, monkeypatch):
+    """bench.dump_outputs: the last step's fp16 latents -> <dir>/images.npy in float32, values unchanged; above the size cap a
+    fixed seeded sample of the elements (the same on every run) is written instead"""
+    import bench
+    lat = torch.randn(2, 4, 8, 8, generator=torch.Generator().manual_seed(0)).half()
+    bench.dump_outputs(lat, str(tmp_path / "a"), 0, 1)
+    got = np.load(tmp_path / "a" / "images.npy")
+    assert got.dtype == np.float32 and got.shape == (2, 4, 8, 8) and np.array_equal(got, lat.float().numpy())
+    bench.dump_outputs(lat, str(tmp_path / "b"), 1, 1)         # rank != 0 writes nothing
+    assert not (tmp_path / "b").exists()
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 400)
+    bench.dump_outputs(lat, str(tmp_path / "c"), 0, 1)
+    bench.dump_outputs(lat, str(tmp_path / "d"), 0, 1)
+    c, d = np.load(tmp_path / "c" / "images.npy"), np.load(tmp_path / "d" / "images.npy")
+    assert c.dtype == np.float32 and c.nbytes == 400 and np.array_equal(c, d)
+    assert np.isin(c, lat.float().numpy().reshape(-1)).all()

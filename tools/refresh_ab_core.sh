@@ -16,10 +16,10 @@ PREV=$PWD/consistentid_amd/libcid_prev.so
 timeout 240 python -m pytest tests/test_gpu_kernels.py -q -m gpu -x -k "test_gemm_conv3x3 or test_gemm_linear or test_gemm_layernorm_fold or (test_id_cross_attention and not _v)" > $O/pytest_kernels.txt 2>&1; tail -1 $O/pytest_kernels.txt; t "pytest kernels"
 ab previous CID_LIBRARY=$PREV; ab rebuilt X=1; ab rebuilt X=1; ab previous CID_LIBRARY=$PREV
 cat $O/ab.txt
-timeout 300 bash tools/profile_bench.sh $O/prof --no-cpu-baseline --no-torch-baseline --no-secondary > $O/prof.log 2>&1; t "rocprof stats"
+timeout 300 bash tools/profile_bench.sh $O/prof --full --no-cpu-baseline --no-torch-baseline --no-secondary > $O/prof.log 2>&1; t "rocprof stats"
 rm -rf $O/prof/raw
 python tools/collect_profiles.py $O r04 --stats-only > /dev/null
-timeout 420 python bench.py > $O/bench_default.json 2> $O/bench_default.err; t "bench default"
+timeout 420 python bench.py --full > $O/bench_default.json 2> $O/bench_default.err; t "bench default"
 tail -1 $O/bench_default.json | cut -c1-400
 timeout 200 python tools/kbench.py > $O/kbench.txt 2>&1; t "kbench (rebuilt)"
 bash tools/pmc_run.sh xattn3 $O/pmc_xattn > $O/pmc_xattn.txt 2>&1; rm -rf $O/pmc_xattn/p*/; t "pmc xattn3"

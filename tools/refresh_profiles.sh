@@ -14,10 +14,10 @@ rm -rf $O; mkdir -p $O
 bash tools/pmc_run.sh xattn3 $O/pmc_xattn > $O/pmc_xattn.txt 2>&1
 rm -rf $O/pmc_xattn/p*/
 python tools/collect_profiles.py $O r04 --pmc-only
-bash tools/profile_bench.sh $O/prof --no-cpu-baseline --no-torch-baseline --no-secondary > $O/prof.log 2>&1
+bash tools/profile_bench.sh $O/prof --full --no-cpu-baseline --no-torch-baseline --no-secondary > $O/prof.log 2>&1
 rm -rf $O/prof/raw
 python tools/collect_profiles.py $O r04 --stats-only
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
 python tools/kbench.py > $O/kbench.txt 2>&1
 python tools/xattn_levels.py 2>&1 | grep -v amdgpu.ids > $O/xattn_levels.txt
 # same-box A/B of the round's structural changes: GEGLU N-loop, three-stage DMA ring, query projection with attention epilogue

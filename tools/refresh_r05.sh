@@ -9,9 +9,9 @@ rm -rf $O/pmc_conv0/
 bash tools/profile_bench.sh $O/prof --no-cpu-baseline --no-torch-baseline --no-secondary --no-roofline > $O/prof.log 2>&1      # (no roofline block: its back-to-back loop of the metric kernel must not mix into the in-step table)
 rm -rf $O/prof/raw
 python tools/collect_profiles.py $O r05 --stats-only
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --family sdxl --steps 2 --warmup 1 --no-cpu-baseline --no-torch-baseline > $O/bench_sdxl.json 2> $O/bench_sdxl.err
-python bench.py --family cn-inpaint --steps 2 --warmup 1 --no-torch-baseline > $O/bench_cn_inpaint.json 2> $O/bench_cn.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --family sdxl --steps 2 --warmup 1 --no-cpu-baseline --no-torch-baseline > $O/bench_sdxl.json 2> $O/bench_sdxl.err
+python bench.py --full --family cn-inpaint --steps 2 --warmup 1 --no-torch-baseline > $O/bench_cn_inpaint.json 2> $O/bench_cn.err
 python tools/kbench.py 2>&1 | grep -v amdgpu.ids > $O/kbench.txt
 CID_CONV_H32=0 python tools/kbench.py --only gemm 2>&1 | grep "conv3" > $O/kbench_conv_halo_kernel.txt
 python tools/xattn_levels.py 2>&1 | grep -v amdgpu.ids > $O/xattn_levels.txt

@@ -14,14 +14,14 @@ rm -rf $O/prof/raw
 bash tools/profile_bench.sh $O/prof_sdxl --family sdxl --steps 2 --warmup 1 --no-cpu-baseline --no-torch-baseline --no-roofline > $O/prof_sdxl.log 2>&1
 rm -rf $O/prof_sdxl/raw
 python tools/collect_profiles.py $O r06 --stats-only
-python bench.py > $O/bench_default.json 2> $O/bench_default.err
-python bench.py --family sdxl --steps 2 --warmup 1 --no-cpu-baseline --no-torch-baseline > $O/bench_sdxl.json 2> $O/bench_sdxl.err
-python bench.py --family cn-inpaint --steps 2 --warmup 1 --no-torch-baseline > $O/bench_cn_inpaint.json 2> $O/bench_cn.err
+python bench.py --full > $O/bench_default.json 2> $O/bench_default.err
+python bench.py --full --family sdxl --steps 2 --warmup 1 --no-cpu-baseline --no-torch-baseline > $O/bench_sdxl.json 2> $O/bench_sdxl.err
+python bench.py --full --family cn-inpaint --steps 2 --warmup 1 --no-torch-baseline > $O/bench_cn_inpaint.json 2> $O/bench_cn.err
 python tools/kbench.py 2>&1 | grep -v amdgpu.ids > $O/kbench.txt
 python tools/xattn_levels.py 2>&1 | grep -v amdgpu.ids > $O/xattn_levels.txt
 # same-box A/B of the round's switches
 # (with the reported shader clock and socket power of each run: DESIGN.md 4.8 -- a denser kernel is answered with a lower clock)
-ab() { env "$@" python bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-torch-baseline --no-secondary --no-roofline 2>/dev/null | python -c "
+ab() { env "$@" python bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-torch-baseline --no-secondary --no-roofline 2>/dev/null | python -c "
 import sys, json
 d = json.loads(sys.stdin.read().strip().splitlines()[-1]); g = d.get('gpu_state') or {}
 m = lambda k: (g.get(k) or {}).get('mean')
