@@ -37,6 +37,7 @@ class GemmDesc(C.Structure):
         ("att_kp", C.c_void_p), ("att_vp", C.c_void_p), ("att_kvrow", C.c_void_p),
         ("att_n_txt", C.c_int32), ("att_n_ip", C.c_int32), ("att_ip_scale", C.c_float),
         ("out2", C.c_void_p),
+        ("pad_mode", C.c_int32),
     ]
 
 
@@ -85,6 +86,10 @@ SIGNATURES = {
     "cid_small_attn_f16": (C.c_int, [c_half_p, C.c_int32, c_half_p, C.c_int32, c_half_p, C.c_int32, C.c_int32, c_half_p,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, c_stream]),
     "cid_conv_out_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 5 + [c_stream]),
+    "cid_vae_encode_in_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, c_half_p, c_half_p, c_half_p]
+                              + [C.c_int32] * 5 + [c_half_p, c_stream]),
+    "cid_vae_encode_out_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, c_half_p, C.c_void_p, c_half_p] + [C.c_int32] * 5
+                               + [C.c_float, c_stream]),
     "cid_sincos_embed_f16": (C.c_int, [C.c_void_p, c_half_p, C.c_int32, C.c_int32, c_stream]),
     "cid_linear_small_f16": (C.c_int, [c_half_p, C.c_int32, c_half_p, c_half_p, c_half_p, C.c_int32, c_half_p,
                                        C.c_int32] + [C.c_int32] * 5 + [c_stream]),

@@ -436,8 +436,8 @@ igemm_kernel(GemmArgs a) {
     // row byte offsets (per source pitch) of the current tap, recomputed only when the tap changes
     unsigned xoff1[XPW], xoff2[XPW];
     auto set_tap = [&](int tap) {
-        const int dy = (a.taps == 9) ? tap / 3 - 1 : 0;
-        const int dx = (a.taps == 9) ? tap - (tap / 3) * 3 - 1 : 0;
+        const int dy = (a.taps == 9) ? tap / 3 + a.tap0 : 0;
+        const int dx = (a.taps == 9) ? tap - (tap / 3) * 3 + a.tap0 : 0;
 #pragma unroll
         for (int j = 0; j < XPW; ++j) {
             bool ok = xok[j];
@@ -1256,6 +1256,17 @@ static int plan_gemm(const cid_gemm_desc* d, GemmArgs& a, TileCfg& cfg, bool& ha
                       && (d->up == 0 || d->up == 1), "cid_gemm_f16: bad conv geometry");
         CID_CHECK_ARG(d->M % (d->Ho * d->Wo) == 0, "cid_gemm_f16: M is not batch * Ho * Wo");
     }
+    // pad_mode 1: diffusers' Downsample2D(padding=0) = F.pad(x, (0, 1, 0, 1)) then a stride-2 3x3 conv without padding --
+    // output (y, x) reads input (2y + dy, 2x + dx), dy, dx in {0, 1, 2}; row Hi and column Wi (the pad) read as zero.  Only the
+    // tap offset of the gather changes (set_tap), so the igemm_kernel instances run it; the halo / conv3x3.hip kernels below
+    // are stride-1 only and never see it.
+    CID_CHECK_ARG(d->pad_mode == 0 || d->pad_mode == 1, "cid_gemm_f16: bad pad_mode %d", d->pad_mode);
+    CID_CHECK_ARG(d->pad_mode == 0 || (d->mode == 0 && d->taps == 9 && d->stride == 2 && d->up == 0 && d->Hi % 2 == 0 &&
+                                       d->Wi % 2 == 0 && d->Ho == d->Hi / 2 && d->Wo == d->Wi / 2),
+                  "cid_gemm_f16: pad_mode 1 needs mode 0, taps 9, stride 2, up 0, even Hi / Wi, Ho = Hi / 2 and Wo = Wi / 2 "
+                  "(got mode %d taps %d stride %d up %d, %d x %d -> %d x %d)", d->mode, d->taps, d->stride, d->up, d->Hi, d->Wi,
+                  d->Ho, d->Wo);
+    a.tap0 = d->pad_mode == 1 ? 0 : -1;
 
     if (d->mode == 3) {
         // query projection with the identity cross-attention as its epilogue: tiles of whole heads inside one sample

@@ -41,6 +41,7 @@ struct GemmArgs {
     int ablate;          // profiling knob (CID_GEMM_ABLATE): 1 = no global loads in the loop,
                          // 2 = no MFMA, 3 = no LDS fragment reads / MFMA
     int xcd_pn;          // tile -> XCD partition (xcd_tile below): n-blocks of the 2-D partition (1 | 2 | 4 | 8), 0 = linear runs
+    int tap0;            // first tap offset of a 3x3 conv: -1 (pad 1), 0 (cid_gemm_desc.pad_mode 1, Downsample2D(padding=0))
 };
 
 // Tile of a workgroup.  The hardware deals consecutive workgroup ids round-robin over the 8 XCDs (a private 4-MB L2 each): the

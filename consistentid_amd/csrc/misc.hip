@@ -15,7 +15,7 @@ void cid_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* cid_last_error(void) { return g_err; }
-extern "C" int cid_version(void) { return 100; }
+extern "C" int cid_version(void) { return 101; }   // 101: cid_gemm_desc.pad_mode
 
 namespace {
 

@@ -5,7 +5,8 @@ The reference builds its pipelines with ``ConsistentIDPipeline.from_pretrained(b
 sub-folder per component.  This module reads the components the hot path needs, straight from their files:
 
     <root>/unet/config.json + diffusion_pytorch_model.{safetensors,bin}     -> HipUNet      (required)
-    <root>/vae/config.json  + diffusion_pytorch_model.{safetensors,bin}     -> HipVAEDecoder (optional)
+    <root>/vae/config.json  + diffusion_pytorch_model.{safetensors,bin}     -> HipVAEDecoder (optional; + HipVAEEncoder for the
+                                                                             inpaint pipelines when encoder.* weights are there)
     <controlnet dir>/config.json + diffusion_pytorch_model.{safetensors,bin} -> HipControlNet (separate call, like the
                                                                                 reference: demo/controlnet_demo.py:44-47)
 
@@ -127,6 +128,17 @@ def load_vae(root: Union[str, os.PathLike], device="cuda:0", subfolder: str = "v
     return make_vae_decoder(vae_config_from_diffusers(cfg), sd, device=device)      # fp32 engine for force_upcast (SDXL)
 
 
+def load_vae_encoder(root: Union[str, os.PathLike], device="cuda:0", subfolder: str = "vae"):
+    """-> HipVAEEncoder (``vae.encode`` of the inpaint pipelines' pre-loop) from the same ``vae/`` folder as the decoder."""
+    from .vae import HipVAEEncoder
+    cfg, sd = read_component(os.path.join(os.fspath(root), subfolder) if subfolder else root)
+    return HipVAEEncoder(vae_config_from_diffusers(cfg), sd, device=device)
+
+
+def _has_encoder(sd) -> bool:
+    return any(k.startswith("encoder.") for k in sd)
+
+
 def read_scheduler(root: Union[str, os.PathLike]):
     """``<root>/scheduler/scheduler_config.json`` -> the engine's DDIMScheduler on that config (None without the file).
     The base model's own sampler class (PNDM for SD1.5) is not built; its CONFIG is kept, so that the reference scripts' next
@@ -194,8 +206,19 @@ def from_pretrained(pipeline_cls, root: Union[str, os.PathLike], torch_dtype=tor
     if not os.path.isdir(root):
         raise FileNotFoundError(f"{root}: local diffusers model directory expected (no hub access)")
     unet = load_unet(root, device=device)
-    vae = load_vae(root, device=device) if os.path.isdir(os.path.join(root, "vae")) else None
+    vae = vae_encoder = None
+    if os.path.isdir(os.path.join(root, "vae")):
+        from .pipeline import StableDiffusionInpaintConsistentIDPipeline
+        from .vae import HipVAEEncoder, make_vae_decoder
+        vcfg, vsd = read_component(os.path.join(root, "vae"))
+        vcfg = vae_config_from_diffusers(vcfg)
+        vae = make_vae_decoder(vcfg, vsd, device=device)          # fp32 engine for force_upcast (SDXL)
+        # the encoder only for the two inpaint pipelines (their image= / mask_image= pre-loop), and only if the weights are there
+        if issubclass(pipeline_cls, StableDiffusionInpaintConsistentIDPipeline) and _has_encoder(vsd):
+            vae_encoder = HipVAEEncoder(vcfg, vsd, device=device)
     args = dict(use_graph=use_graph, vae=vae, **kw)
+    if vae_encoder is not None:
+        args["vae_encoder"] = vae_encoder
     if "scheduler" not in args:
         base = read_scheduler(root)
         if base is not None:

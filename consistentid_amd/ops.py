@@ -45,7 +45,7 @@ def gemm(x1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
          taps: int = 1, Hi: int = 0, Wi: int = 0, Ho: int = 0, Wo: int = 0, stride: int = 1, up: int = 0,
          mode: int = 0, vt: Optional[torch.Tensor] = None, n_vt0: int = 0, heads: int = 0, dhead: int = 0,
          ntok: int = 0, ws: Optional[torch.Tensor] = None, ln=None, gn_hw: int = 0, att=None,
-         out2: Optional[torch.Tensor] = None):
+         out2: Optional[torch.Tensor] = None, pad_mode: int = 0):
     """``att`` = (kp, vp, kvrow, n_txt, n_ip, ip_scale) with ``mode=3``: the query projection of the identity cross-attention
     with the two-stream attention as its epilogue (``heads``, ``dhead``, ``ntok`` describe the heads and the tokens per sample).
     ``ln`` = (s, b, eps): LayerNorm folded into the projection -- ``x1`` is the raw residual stream, ``w`` carries gamma,
@@ -54,7 +54,8 @@ def gemm(x1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
     statistics from its epilogue they are attached as ``out._gn_stats = (fp32 [M / rows, 32, 2], rows)`` for
     ``groupnorm`` to pick up (saves its statistics pass).
     ``out2``: a second destination for the same rows (same pitch as ``out``; mode 0): the CFG duplication of a tensor both
-    halves of the batch share, written by the producer."""
+    halves of the batch share, written by the producer.
+    ``pad_mode=1``: Downsample2D(padding=0) -- pad (0, 1, 0, 1), then the stride-2 3x3 conv without padding."""
     lib = _lib.load()
     for name, t in (("x1", x1), ("w", w), ("out", out)):
         _req(t, f"gemm.{name}")
@@ -77,6 +78,7 @@ def gemm(x1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
     d.ldr = ldr if ldr is not None else N
     d.M, d.N, d.taps = M, N, taps
     d.Hi, d.Wi, d.Ho, d.Wo, d.stride, d.up = Hi, Wi, Ho, Wo, stride, up
+    d.pad_mode = pad_mode
     d.mode = mode
     d.vt, d.n_vt0, d.heads, d.dhead, d.dvp, d.ntok = _p(vt), n_vt0, heads, dhead, dvp_of(dhead) if dhead else 0, ntok
     if ws is not None:
@@ -399,6 +401,45 @@ def conv_out(x: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: torch.Te
     for name, t in (("x", x), ("out", out), ("w", w), ("bias", bias)):
         _req(t, f"conv_out.{name}")
     check(lib.cid_conv_out_f16(_p(x), _p(out), _p(w), _p(bias), B, H, W, cin, cout, _stream()), "cid_conv_out_f16")
+    return out
+
+
+def vae_encode_in(image: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *,
+                  mask: Optional[torch.Tensor] = None, normalize: bool = True, blocks: int = 1,
+                  mask_latents: Optional[torch.Tensor] = None):
+    """VAE encoder conv_in with the inpaint pre-processing folded in (cid_vae_encode_in_f16): ``image`` fp32 [Bi, 3, H, W],
+    ``mask`` fp32 [Bm, 1, H, W] or None; ``blocks`` bit 0 = the image, bit 1 = image * (mask < 0.5); ``out`` token-major
+    [nblk * Bi, H * W, cout]; ``mask_latents`` fp16 [Bm, 1, H / 8, W / 8] or None."""
+    lib = _lib.load()
+    _req(image, "vae_encode_in.image", torch.float32)
+    for name, t in (("out", out), ("w", w), ("bias", bias)):
+        _req(t, f"vae_encode_in.{name}")
+    if mask is not None:
+        _req(mask, "vae_encode_in.mask", torch.float32)
+    if mask_latents is not None:
+        _req(mask_latents, "vae_encode_in.mask_latents")
+    Bi, _, H, W = image.shape
+    check(lib.cid_vae_encode_in_f16(_p(image), Bi, _p(mask), mask.shape[0] if mask is not None else 0, _p(out), _p(w),
+                                    _p(bias), H, W, out.shape[-1], int(normalize), blocks, _p(mask_latents), _stream()),
+          "cid_vae_encode_in_f16")
+    return out
+
+
+def vae_encode_out(x: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, B: int, H: int, W: int,
+                   cin: int, L: int, scale: float, eps: Optional[torch.Tensor] = None,
+                   moments: Optional[torch.Tensor] = None):
+    """VAE encoder conv_out + quant_conv (folded into ``w`` / fp32 ``bias``) + posterior (cid_vae_encode_out_f16):
+    ``out`` fp16 [B, L, H, W] = scale * (mean + std * eps) (the mean when ``eps`` is None); ``moments`` fp32 [B, 2L, H, W]."""
+    lib = _lib.load()
+    for name, t in (("x", x), ("out", out), ("w", w)):
+        _req(t, f"vae_encode_out.{name}")
+    _req(bias, "vae_encode_out.bias", torch.float32)
+    if eps is not None:
+        _req(eps, "vae_encode_out.eps")
+    if moments is not None:
+        _req(moments, "vae_encode_out.moments", torch.float32)
+    check(lib.cid_vae_encode_out_f16(_p(x), _p(out), _p(moments), _p(w), _p(bias), _p(eps), B, H, W, cin, L, float(scale),
+                                     _stream()), "cid_vae_encode_out_f16")
     return out
 
 

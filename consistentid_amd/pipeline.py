@@ -6,9 +6,11 @@ the reference's ``__call__`` keyword surface, running on the HIP engine.
   StableDiffusionInpaintConsistentIDPipeline           pipelines/StableDIffusionInpaint_ConsistentID.py:94, loop :305-359
   StableDiffusionControlNetInpaintConsistentIDPipeline pipelines/StableDIffusionControlNetInpaint_ConsistentID.py:94, :375-456
 
-Scope: the per-step path, the ControlNet encoder (row f-1) and the VAE decode (row f-2).
-The once-per-image pre-loop (FaceID, face parsing, CLIP text/vision encoders, FacialEncoder /
-ProjPlusModel, VAE encode) is out of scope this round, so the pipelines take what that pre-loop produces:
+Scope: the per-step path, the ControlNet encoder (row f-1), the VAE decode (row f-2) and the VAE
+encode of the inpaint pipelines (``image=`` / ``mask_image=`` with ``vae_encoder=HipVAEEncoder(...)``; the init image comes in
+through ``image=``, where the reference reads ``input_id_images[0]``).
+The rest of the once-per-image pre-loop (FaceID, face parsing, CLIP text/vision encoders, FacialEncoder /
+ProjPlusModel) is out of scope this round, so the pipelines take what that pre-loop produces:
 ``prompt_embeds`` = cat([null, augmented, text_only]) of shape [3B, 77+4, Dc] exactly as the
 reference assembles it before ``.chunk(3)`` (ref :494-507, :527-531), and ``latents``.
 String prompts / ID images raise NotImplementedError naming the missing component instead of silently doing
@@ -216,15 +218,39 @@ class _DenoiseEngine:
         return lat.clone()
 
 
+def inpaint_draws(generator, *, image_batch: int, batch_size: int, latent_channels: int, h: int, w: int,
+                  unet_channels: int, latents_given: bool, strength: float, device):
+    """The random draws of the inpaint pipelines' pre-loop, in diffusers 0.23's order (prepare_latents, then
+    prepare_mask_latents; inpaint ref :255-292, CN :318-356), each a fp16 ``randn_tensor`` (vae.randn_tensor):
+      1. the posterior eps of the init image [image_batch, L, h, w] -- only if it is encoded: a 4-channel UNet
+         (return_image_latents) or no ``latents`` with ``strength`` < 1 (the add_noise start);
+      2. ``noise`` [batch_size, L, h, w] -- only without ``latents`` (given latents ARE the noise);
+      3. the posterior eps of the masked image [image_batch, L, h, w] -- always: the reference encodes the masked image
+         even for a 4-channel UNet, which then ignores it.
+    Returns (eps_image or None, noise or None, eps_masked)."""
+    from .vae import randn_tensor
+    enc_shape = (image_batch, latent_channels, h, w)
+    eps_image = noise = None
+    if unet_channels == 4 or (not latents_given and strength < 1.0):
+        eps_image = randn_tensor(enc_shape, generator=generator, device=device, dtype=torch.float16)
+    if not latents_given:
+        noise = randn_tensor((batch_size, latent_channels, h, w), generator=generator, device=device, dtype=torch.float16)
+    eps_masked = randn_tensor(enc_shape, generator=generator, device=device, dtype=torch.float16)
+    return eps_image, noise, eps_masked
+
+
 class _BasePipeline:
     default_guidance = 5.0
     vae_scale_factor = 8
 
     def __init__(self, unet: HipUNet, scheduler: Optional[DDIMScheduler] = None, use_graph: bool = True,
-                 num_tokens: int = 4, lora_rank: int = 128, vae=None):
-        """``vae``: a ``consistentid_amd.vae.HipVAEDecoder`` -- enables every ``output_type`` besides "latent"."""
+                 num_tokens: int = 4, lora_rank: int = 128, vae=None, vae_encoder=None):
+        """``vae``: a ``consistentid_amd.vae.HipVAEDecoder`` -- enables every ``output_type`` besides "latent".
+        ``vae_encoder``: a ``consistentid_amd.vae.HipVAEEncoder`` -- lets the inpaint pipelines take ``image=`` and
+        ``mask_image=`` (the reference's pre-loop VAE encode) instead of pre-computed latents."""
         self.unet = unet
         self.vae = vae
+        self.vae_encoder = vae_encoder
         self.num_tokens = num_tokens
         self.lora_rank = lora_rank
         self.device = unet.device
@@ -422,14 +448,67 @@ class StableDiffusionInpaintConsistentIDPipeline(_BasePipeline):
             raise ValueError(f"strength {strength} with {S} inference steps leaves no denoising step")
         if latents is not None:
             return first, latents, True
+        if noise is not None and strength == 1.0:
+            return first, noise, True          # pure noise: no image latents needed (a 9-channel UNet has none here)
         if noise is None or image_latents is None:
             raise ValueError("without latents the inpaint pipelines need image_latents and noise")
-        if strength == 1.0:
-            return first, noise, True
         self.scheduler.set_timesteps(S)
         ca, cn_ = self.scheduler.add_noise_coefficients(self.scheduler.timesteps[first])
         return first, ca * image_latents.float() + cn_ * noise.float(), False
 
+
+    def _encode_images(self, image, mask_image, height, width, latents, strength, generator, prompt_embeds, explicit):
+        """``image=`` / ``mask_image=`` -> (image_latents, noise, mask_latents, masked_image_latents): the pre-loop of inpaint ref
+        :231-295 (CN :254-356) on the HIP encoder.  The mask is binarised at 0.5, masked_image = image * (mask < 0.5); the
+        image is normalised (2x - 1) unless ``image.min() < 0`` (diffusers VaeImageProcessor); both images go through ONE
+        encoder pass; latents = scaling_factor * latent_dist.sample(generator) with the draws of ``inpaint_draws``; image /
+        mask latents are repeated to the batch like diffusers does.  Given ``latents`` are also the blend noise (diffusers
+        prepare_latents: ``noise = latents``)."""
+        if any(v is not None for v in explicit.values()):
+            raise ValueError(f"pass either image / mask_image or pre-computed {sorted(k for k, v in explicit.items() if v is not None)}, "
+                             "not both")
+        if image is None or mask_image is None:
+            raise ValueError("image= (the init image) and mask_image= come together")
+        if not (torch.is_tensor(image) and torch.is_tensor(mask_image)):
+            raise NotImplementedError("PIL / numpy images (image_processor / mask_processor pre-processing and resizing) are "
+                                      "not built: pass float tensors image [B, 3, H, W] and mask_image [B, 1, H, W]")
+        if self.vae_encoder is None:
+            raise ValueError("image= / mask_image= need a VAE encoder: build the pipeline with vae_encoder=HipVAEEncoder(...) "
+                             "(from_pretrained does when vae/ holds encoder weights)")
+        enc = self.vae_encoder
+        img = image.unsqueeze(0) if image.dim() == 3 else image
+        msk = mask_image
+        while msk.dim() < 4:
+            msk = msk.unsqueeze(0)
+        if img.dim() != 4 or img.shape[1] != 3 or not img.is_floating_point():
+            raise ValueError(f"image must be a float tensor [B, 3, H, W] or [3, H, W], got {tuple(image.shape)} {image.dtype}")
+        if msk.dim() != 4 or msk.shape[1] != 1:
+            raise ValueError(f"mask_image must be [B, 1, H, W], [1, H, W] or [H, W], got {tuple(mask_image.shape)}")
+        H, W = img.shape[-2:]
+        height, width = height or H, width or W
+        if (height, width) != (H, W) or tuple(msk.shape[-2:]) != (H, W):
+            raise ValueError(f"image {tuple(img.shape[-2:])}, mask {tuple(msk.shape[-2:])} and height x width {(height, width)} "
+                             "must agree: images are not resized here")
+        Bi = img.shape[0]
+        if msk.shape[0] not in (1, Bi):
+            raise ValueError(f"mask batch {msk.shape[0]} must be 1 or the image batch {Bi}")
+        B = prompt_embeds.shape[0] // 3 if prompt_embeds is not None else Bi
+        if B % Bi or B % msk.shape[0]:
+            raise ValueError(f"batch {B} is not a multiple of the image batch {Bi} / mask batch {msk.shape[0]}")
+        cin = getattr(self.unet.config, "in_channels", 4)
+        L = enc.config.latent_channels
+        normalize = not bool(img.min() < 0)                     # diffusers: "already in [-1, 1]" tensors are left alone
+        eps_img, noise, eps_msk = inpaint_draws(generator, image_batch=Bi, batch_size=B, latent_channels=L, h=H // 8,
+                                                w=W // 8, unet_channels=cin, latents_given=latents is not None,
+                                                strength=strength, device=self.device)
+        enc_img = eps_img is not None
+        enc_msk = cin != 4                     # a 4-channel UNet ignores the masked image: its draw is consumed, no encode
+        r = enc.encode_inpaint(img, msk.float(), normalize=normalize, encode_image=enc_img, encode_masked=enc_msk,
+                               eps_image=eps_img, eps_masked=eps_msk if enc_msk else None)
+        rep = lambda t: None if t is None else t.repeat(B // t.shape[0], 1, 1, 1)
+        if latents is not None:
+            noise = latents
+        return rep(r["image_latents"]), noise, rep(r["mask_latents"]), rep(r["masked_image_latents"])
 
     def _unet_extra(self, latents, mask_latents, masked_image_latents):
         """9-channel inpainting UNets (``unet.config.in_channels == 9``): the per-step
@@ -472,8 +551,18 @@ class StableDiffusionInpaintConsistentIDPipeline(_BasePipeline):
                  prompt_embeds_text_only=None, image_latents: Optional[torch.Tensor] = None,
                  noise: Optional[torch.Tensor] = None, mask_latents: Optional[torch.Tensor] = None,
                  down_block_res_samples=None, mid_block_res_sample=None):
-        """Hot-path inputs replace the image pre-processing / VAE encode of ref :255-352:
-        ``image_latents`` (init latents), ``noise`` and ``mask_latents`` [B,1,h,w] (1 = repaint)."""
+        """Either ``image`` + ``mask_image`` (the pre-loop of ref :231-295 on ``vae_encoder``) or the pre-computed
+        ``image_latents`` (init latents), ``noise`` and ``mask_latents`` [B,1,h,w] (1 = repaint), ``masked_image_latents``.
+        ``image`` is the INIT image [B, 3, H, W] / [3, H, W] float in [0, 1] (or already in [-1, 1]): the reference reads
+        it from ``input_id_images[0]`` (ref :157, :232-235) and ignores its own ``image`` argument, but here
+        ``input_id_images`` belongs to the ID pre-loop, which is not built -- so the init image comes in through ``image=``.
+        ``mask_image`` [B, 1, H, W] / [1, H, W] / [H, W] float, binarised at 0.5 (1 = repaint); H, W = height, width
+        (no resizing).  ``generator`` seeds the posterior samples and the noise in diffusers' order."""
+        if image is not None or mask_image is not None:
+            image_latents, noise, mask_latents, masked_image_latents = self._encode_images(
+                image, mask_image, height, width, latents, strength, generator, prompt_embeds,
+                dict(image_latents=image_latents, noise=noise, mask_latents=mask_latents,
+                     masked_image_latents=masked_image_latents))
         first, latents, scaled = self._strength_window(strength, num_inference_steps, latents, image_latents, noise)
         self._check_hot_path_inputs(prompt, input_id_images, prompt_embeds, latents, output_type)
         extra = self._unet_extra(latents, mask_latents, masked_image_latents)
@@ -520,6 +609,13 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
                  image_latents: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                  mask_latents: Optional[torch.Tensor] = None, down_block_res_samples=None, mid_block_res_sample=None,
                  masked_image_latents: Optional[torch.Tensor] = None):
+        """``image`` / ``mask_image``: as in StableDiffusionInpaintConsistentIDPipeline.__call__ (the init image comes in
+        through ``image=``; the reference reads it from ``input_id_images[0]``, CN :180, :255-258)."""
+        if image is not None or mask_image is not None:
+            image_latents, noise, mask_latents, masked_image_latents = self._encode_images(
+                image, mask_image, height, width, latents, strength, generator, prompt_embeds,
+                dict(image_latents=image_latents, noise=noise, mask_latents=mask_latents,
+                     masked_image_latents=masked_image_latents))
         first_step, latents, scaled = self._strength_window(strength, num_inference_steps, latents, image_latents, noise)
         self._check_hot_path_inputs(prompt, input_id_images, prompt_embeds, latents, output_type)
         extra = self._unet_extra(latents, mask_latents, masked_image_latents)

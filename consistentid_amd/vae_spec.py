@@ -1,5 +1,5 @@
 """VAE topology + parameter inventory (names/shapes of diffusers==0.23.0 ``AutoencoderKL``'s state_dict, which the
-reference's ``from_pretrained`` loads into ``pipe.vae``).  Pure metadata for the decoder engine (vae.py)."""
+reference's ``from_pretrained`` loads into ``pipe.vae``).  Pure metadata for the decoder and encoder engines (vae.py)."""
 from __future__ import annotations
 
 from collections import OrderedDict
@@ -39,6 +39,15 @@ def decoder_blocks(cfg: VAEConfig):
     for i in range(len(rev)):
         prev, out = out, rev[i]
         blocks.append((f"decoder.up_blocks.{i}", prev, out, cfg.layers_per_block + 1, i != len(rev) - 1))
+    return blocks
+
+
+def encoder_blocks(cfg: VAEConfig):
+    """[(name, cin, cout, n_resnets, has_downsampler)] of ``encoder.down_blocks`` in execution order"""
+    boc, out, blocks = cfg.block_out_channels, cfg.block_out_channels[0], []
+    for i in range(len(boc)):
+        cin, out = out, boc[i]
+        blocks.append((f"encoder.down_blocks.{i}", cin, out, cfg.layers_per_block, i != len(boc) - 1))
     return blocks
 
 

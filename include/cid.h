@@ -27,7 +27,7 @@ extern "C" {
 typedef void* cid_stream_t;      /* hipStream_t */
 typedef uint16_t cid_half;       /* IEEE binary16 bit pattern */
 
-int cid_version(void);
+int cid_version(void);          /* 101: cid_gemm_desc grew a trailing pad_mode field (101 and later: set it or zero the struct) */
 const char* cid_last_error(void);
 
 /* ---------------------------------------------------------------------------
@@ -93,6 +93,12 @@ typedef struct cid_gemm_desc {
      * of a tensor both halves of the batch share (ref pipline_StableDiffusion_ConsistentID.py:537-539) written by its
      * producer instead of by a copy launch.  mode 0 only. */
     cid_half* out2;
+    /* Padding of a 3x3 convolution (since cid_version() 101, which grew the struct by this field):
+     *   0: symmetric pad 1 (the rule above; a zero-initialised descriptor keeps it);
+     *   1: D: Downsample2D(padding=0) of the VAE encoder's DownEncoderBlock2D -- F.pad(x, (0, 1, 0, 1)) then a stride-2 conv
+     *      without padding: output (y, x) reads input (2y + dy, 2x + dx), dy, dx in {0, 1, 2}; row Hi and column Wi read as
+     *      zero.  Only with mode 0, taps 9, stride 2, up 0, even Hi / Wi, Ho = Hi / 2, Wo = Wi / 2 (else -22); split-K allowed. */
+    int32_t pad_mode;
 } cid_gemm_desc;
 int cid_gemm_f16(const cid_gemm_desc* d, cid_stream_t stream);
 /* Token rows per statistics block if cid_gemm_f16(d) can emit gn_stats (its tile height), 0 if it cannot (split-K,
@@ -276,6 +282,34 @@ int cid_small_attn_f16(const cid_half* q, int32_t ldq, const cid_half* kv1, int3
                        float scale2, cid_stream_t stream);
 int cid_conv_out_f16(const cid_half* x, cid_half* out, const cid_half* w, const cid_half* bias,
                      int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout, cid_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * VAE encoder ends (csrc/vae_enc.hip).  The inpaint pipelines encode the init image and the masked image before the loop
+ * (pipelines/StableDIffusionInpaint_ConsistentID.py:231-295, StableDIffusionControlNetInpaint_ConsistentID.py:254-356:
+ * mask_processor binarisation, masked_image = init_image * (mask < 0.5), then D: prepare_latents / prepare_mask_latents ->
+ * AutoencoderKL.encode(...).latent_dist.sample(generator) * scaling_factor and F.interpolate(mask, size=(H / 8, W / 8))).
+ * Between these two entries the encoder runs on cid_gemm_f16 (Downsample2D(padding=0): pad_mode 1) / cid_groupnorm_f16 /
+ * cid_softmax_rows_f16.
+ * cid_vae_encode_in_f16: D: Encoder.conv_in (3 -> cout, 3x3 pad 1) with the pre-processing folded into its loads.
+ *   image fp32 NCHW [Bi][3][H][W]; mask fp32 NCHW [Bm][1][H][W], Bm in {1, Bi}, or NULL; normalize != 0: pixel = 2x - 1
+ *   (the diffusers rule for [0, 1] tensors); the masked image is pixel * (mask < 0.5); every pixel is rounded to fp16 after
+ *   normalisation and masking (the reference feeds an fp16 VAE).  blocks: bit 0 the image, bit 1 the masked image (needs the
+ *   mask).  out: token-major fp16 [nblk * Bi][H * W][cout], the image block first; w [cout][9][3], bias [cout];
+ *   cout % 8 == 0, cout <= 320.  mask_latents (or NULL; needs the mask, H % 8 == 0, W % 8 == 0): fp16 NCHW [Bm][1][H/8][W/8]
+ *   = the binarised mask at (8y, 8x), i.e. F.interpolate(mask >= 0.5, size=(H / 8, W / 8)) (nearest, diffusers
+ *   prepare_mask_latents).
+ * cid_vae_encode_out_f16: D: Encoder.conv_out + AutoencoderKL.quant_conv + DiagonalGaussianDistribution.sample / .mode.
+ *   x token-major fp16 [B][H * W][cin] = SiLU(conv_norm_out(mid)); w [2L][9][cin] fp16 = quant_conv folded into conv_out
+ *   (W' = Q W per tap, computed in fp32 and rounded once), bias fp32 [2L] = Q b + q_b; eps fp16 NCHW [B][L][H][W] (the
+ *   randn_tensor draw of sample(generator)) or NULL for the mode; out fp16 NCHW [B][L][H][W] =
+ *   scale * (mean + exp(0.5 * clamp(logvar, -30, 20)) * eps); moments fp32 NCHW [B][2L][H][W] (mean | logvar before the
+ *   clamp, the `parameters` of the distribution) or NULL.  L <= 4, cin % 8 == 0. */
+int cid_vae_encode_in_f16(const float* image, int32_t Bi, const float* mask, int32_t Bm, cid_half* out, const cid_half* w,
+                          const cid_half* bias, int32_t H, int32_t W, int32_t cout, int32_t normalize, int32_t blocks,
+                          cid_half* mask_latents, cid_stream_t stream);
+int cid_vae_encode_out_f16(const cid_half* x, cid_half* out, float* moments, const cid_half* w, const float* bias,
+                           const cid_half* eps, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t L, float scale,
+                           cid_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Timestep path (D: get_timestep_embedding flip_sin_to_cos, TimestepEmbedding,
