@@ -56,8 +56,8 @@ CID_DEVINL float silu_f(float x) { return x * __builtin_amdgcn_rcpf(1.f + __buil
 // erf GELU (diffusers GEGLU uses F.gelu without the tanh approximation): gelu(g) = g Phi(g) = max(g, 0) - |g| / 2 * erfc(|g| / sqrt 2),
 // with erfc(t / sqrt 2) = 2^P(t) for t >= 0, P an odd-free degree-6 minimax fit without constant term (tools/fit_gelu.py:
 // |error of erf| <= 2.4e-7, of gelu <= 5.8e-7 in fp32 -- the class of the Abramowitz & Stegun 7.1.26 form used until round 5,
-// 4.7e-7, and three orders below the fp16 rounding of the product).  Seven FMA-class operations and ONE transcendental per element
-// instead of sixteen and two: the GEGLU epilogue is VALU-bound at K = 320, no cancellation on either side (the
+// 4.7e-7, and three orders below the fp16 rounding of the product).  Seven FMA-class operations, one min and ONE transcendental per
+// element instead of sixteen and two: the GEGLU epilogue is VALU-bound at K = 320, no cancellation on either side (the
 // negative tail is -|g| / 2 * 2^P exactly).
 #ifdef CID_GELU_AS7126      // experiment builds only (build.py --variant ...): the round-5 form, for same-call A/B timing
 CID_DEVINL float gelu_erf_f(float g) {
@@ -74,14 +74,18 @@ CID_DEVINL float gelu_erf_f(float g) {
     return __builtin_fmaf(h, __builtin_copysignf(y, x), h);
 }
 #else
+// P has a positive leading coefficient: it turns upward near |g| = 21 and is positive from |g| = 25.7 on, so its argument is
+// clamped at 16, where 2^P(16) = 2^-228 is already an exact 0 (erfc(16 / sqrt 2) < 2^-188); below the clamp nothing changes.
+// The clamp makes the negative tail -0 and the positive tail g for every finite input (tests/test_gelu_formula.py).
 CID_DEVINL float gelu_erf_f(float g) {
     const float t = __builtin_fabsf(g);
-    float q = __builtin_fmaf(t, 1.775648707e-05f, -6.477678544e-04f);
-    q = __builtin_fmaf(t, q, 7.724069990e-03f);
-    q = __builtin_fmaf(t, q, -5.292676762e-02f);
-    q = __builtin_fmaf(t, q, -4.590827227e-01f);
-    q = __builtin_fmaf(t, q, -1.151116848e+00f);
-    const float e = __builtin_amdgcn_exp2f(t * q);          // erfc(|g| / sqrt 2)
+    const float tc = __builtin_fminf(t, 16.f);
+    float q = __builtin_fmaf(tc, 1.775648707e-05f, -6.477678544e-04f);
+    q = __builtin_fmaf(tc, q, 7.724069990e-03f);
+    q = __builtin_fmaf(tc, q, -5.292676762e-02f);
+    q = __builtin_fmaf(tc, q, -4.590827227e-01f);
+    q = __builtin_fmaf(tc, q, -1.151116848e+00f);
+    const float e = __builtin_amdgcn_exp2f(tc * q);         // erfc(min(|g|, 16) / sqrt 2)
     return __builtin_fmaf(-0.5f * t, e, __builtin_fmaxf(g, 0.f));
 }
 #endif

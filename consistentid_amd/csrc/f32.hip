@@ -128,27 +128,30 @@ gemm_f32_kernel(Gemm32Args a) {
 // rows per statistics block: 64, more for large token maps so that a sample has at most 256 partial blocks
 inline int gn32_rows(int HW) { const int r = (HW + 255) / 256; return r < 64 ? 64 : r; }
 
+// Shifted sums: every block of a sample sums d = x - p_c and d^2, p_c = the sample's first pixel of channel c, so that the
+// variance does not come out of the cancellation E[x^2] - E[x]^2 (its rounding grows with (mean / std)^2).
 __global__ void __launch_bounds__(256)
 gn32_partial_kernel(const float* __restrict__ x, int HW, int C, int rows, float* __restrict__ part /*[B][nblk][C][2]*/) {
     const int b = blockIdx.y, blk = blockIdx.x, nblk = gridDim.x;
     const int r0 = blk * rows, r1 = min(HW, r0 + rows);
     for (int c = threadIdx.x; c < C; c += 256) {            // a thread owns a channel: consecutive threads, consecutive addresses
         float s[4] = {0.f, 0.f, 0.f, 0.f}, q[4] = {0.f, 0.f, 0.f, 0.f};
+        const float pc = x[(long)b * HW * C + c];
         const float* p = x + ((long)b * HW + r0) * C + c;
         int r = r0;
         for (; r + 3 < r1; r += 4, p += 4 * (long)C) {       // four independent loads in flight
-            const float v0 = p[0], v1 = p[C], v2 = p[2 * (long)C], v3 = p[3 * (long)C];
+            const float v0 = p[0] - pc, v1 = p[C] - pc, v2 = p[2 * (long)C] - pc, v3 = p[3 * (long)C] - pc;
             s[0] += v0; q[0] += v0 * v0; s[1] += v1; q[1] += v1 * v1; s[2] += v2; q[2] += v2 * v2; s[3] += v3; q[3] += v3 * v3;
         }
-        for (; r < r1; ++r, p += C) { const float v = *p; s[0] += v; q[0] += v * v; }
+        for (; r < r1; ++r, p += C) { const float v = *p - pc; s[0] += v; q[0] += v * v; }
         float* o = part + (((long)b * nblk + blk) * C + c) * 2;
         o[0] = (s[0] + s[1]) + (s[2] + s[3]); o[1] = (q[0] + q[1]) + (q[2] + q[3]);
     }
 }
 
 __global__ void __launch_bounds__(256)
-gn32_finalize_kernel(const float* __restrict__ part, int nblk, int HW, int C, int groups, float eps,
-                     const float* __restrict__ gamma, const float* __restrict__ beta, float* __restrict__ ss /*[B][C][2]*/) {
+gn32_finalize_kernel(const float* __restrict__ x, const float* __restrict__ part, int nblk, int HW, int C, int groups, float eps,
+                     const float* __restrict__ gamma, float* __restrict__ ss /*[B][C][2]: scale, mean*/) {
     __shared__ double gs[64], gq[64];
     __shared__ double cs[2048], cq[2048];
     const int b = blockIdx.x, cg = C / groups;
@@ -158,30 +161,32 @@ gn32_finalize_kernel(const float* __restrict__ part, int nblk, int HW, int C, in
             const float* p = part + (((long)b * nblk + k) * C + c) * 2;
             s += (double)p[0]; q += (double)p[1];
         }
-        cs[c] = s; cq[c] = q;
+        // channel mean and sum of squared deviations (q - s^2 / HW only cancels as far as the pivot is off the mean)
+        cs[c] = (double)x[(long)b * HW * C + c] + s / HW;
+        cq[c] = fmax(q - s * s / HW, 0.0);
     }
     __syncthreads();
     if ((int)threadIdx.x < groups) {
-        double s = 0.0, q = 0.0;
-        for (int c = threadIdx.x * cg; c < (threadIdx.x + 1) * cg; ++c) { s += cs[c]; q += cq[c]; }
-        const double n = (double)HW * cg, mean = s / n;
-        double var = q / n - mean * mean;
-        if (var < 0.0) var = 0.0;
+        const int c0 = threadIdx.x * cg;
+        double mean = 0.0;
+        for (int c = c0; c < c0 + cg; ++c) mean += cs[c];
+        mean /= cg;
+        double m2 = 0.0;                                     // merge of the channels (Chan et al.): within + between
+        for (int c = c0; c < c0 + cg; ++c) m2 += cq[c] + (double)HW * (cs[c] - mean) * (cs[c] - mean);
         gs[threadIdx.x] = mean;
-        gq[threadIdx.x] = 1.0 / sqrt(var + (double)eps);
+        gq[threadIdx.x] = 1.0 / sqrt(m2 / ((double)HW * cg) + (double)eps);
     }
     __syncthreads();
     for (int c = threadIdx.x; c < C; c += 256) {
         const int g = c / cg;
-        const float sc = (float)gq[g] * gamma[c];
-        ss[((long)b * C + c) * 2 + 0] = sc;
-        ss[((long)b * C + c) * 2 + 1] = beta[c] - (float)gs[g] * sc;
+        ss[((long)b * C + c) * 2 + 0] = (float)gq[g] * gamma[c];
+        ss[((long)b * C + c) * 2 + 1] = (float)gs[g];
     }
 }
 
 __global__ void __launch_bounds__(256)
-gn32_apply_kernel(const float* __restrict__ x, float* __restrict__ out, const float* __restrict__ ss, long per_sample, int C,
-                  int silu) {
+gn32_apply_kernel(const float* __restrict__ x, float* __restrict__ out, const float* __restrict__ ss,
+                  const float* __restrict__ beta, long per_sample, int C, int silu) {
     const int b = blockIdx.y;
     const float* xb = x + (long)b * per_sample;
     float* ob = out + (long)b * per_sample;
@@ -192,7 +197,8 @@ gn32_apply_kernel(const float* __restrict__ x, float* __restrict__ out, const fl
         float r[4] = {v.x, v.y, v.z, v.w};
 #pragma unroll
         for (int i = 0; i < 4; ++i) {
-            float y = r[i] * sb[(c + i) * 2] + sb[(c + i) * 2 + 1];
+            // (x - mean) first: x * scale - mean * scale cancels, and a constant group must give exactly beta
+            float y = __builtin_fmaf(r[i] - sb[(c + i) * 2 + 1], sb[(c + i) * 2], beta[c + i]);
             if (silu) y = y / (1.f + __expf(-y));
             r[i] = y;
         }
@@ -256,11 +262,11 @@ extern "C" int cid_groupnorm_f32(const float* x, float* out, const float* gamma,
     float* ss = part + (size_t)B * nblk * C * 2;
     hipStream_t s = (hipStream_t)stream;
     hipLaunchKernelGGL(gn32_partial_kernel, dim3(nblk, B), dim3(256), 0, s, x, HW, C, rows, part);
-    hipLaunchKernelGGL(gn32_finalize_kernel, dim3(B), dim3(256), 0, s, (const float*)part, nblk, HW, C, groups, eps, gamma, beta, ss);
+    hipLaunchKernelGGL(gn32_finalize_kernel, dim3(B), dim3(256), 0, s, x, (const float*)part, nblk, HW, C, groups, eps, gamma, ss);
     const long per_sample = (long)HW * C;
     long blocks = (per_sample / 4 + 255) / 256;
     if (blocks > 8192) blocks = 8192;
-    hipLaunchKernelGGL(gn32_apply_kernel, dim3((int)blocks, B), dim3(256), 0, s, x, out, (const float*)ss, per_sample, C, silu);
+    hipLaunchKernelGGL(gn32_apply_kernel, dim3((int)blocks, B), dim3(256), 0, s, x, out, (const float*)ss, beta, per_sample, C, silu);
     CID_CHECK_LAUNCH("cid_groupnorm_f32");
     return 0;
 }

@@ -519,9 +519,21 @@ igemm_kernel(GemmArgs a) {
     // LN: LayerNorm statistics of this lane's token of every 16-token tile, from the activation fragments on their way to
     // the MFMAs (v_dot2_f32_f16 against ones / against itself); a lane sees a quarter of a row's k-chunks, the four lane
     // rows are added up after the loop.  Every wave column (wn) computes them for itself: no exchange, no barrier.
+    // Shifted statistics: the sums are of x - p, p = the row's first element (one load per row), so that E[d^2] - E[d]^2
+    // does not cancel at large mean / std (the rounding of single-pass fp32 sums of x grows with (mean / std)^2).  x - p is
+    // exact in fp16 unless |x - p| exceeds about |x| itself, and it is exactly 0 on every element of a constant row.
     float lsum[TM], lsq[TM];
+    half2v lpiv[TM];
 #pragma unroll
-    for (int t = 0; t < TM; ++t) { lsum[t] = 0.f; lsq[t] = 0.f; }
+    for (int t = 0; t < TM; ++t) {
+        lsum[t] = 0.f; lsq[t] = 0.f;
+        half_t p = (half_t)0.f;
+        if constexpr (LN) {
+            const int row = m0 + (wm * TM + t) * 16 + l16;
+            if (row < a.M) p = a.x1[(long)row * a.ld1];
+        }
+        lpiv[t] = half2v{p, p};
+    }
     bool ln_on = true;                 // (N-loop: the row statistics are taken during the first n-tile only)
     auto ln_acc = [&](const half8 (&xf)[TM]) {
         if constexpr (LN) {
@@ -531,7 +543,7 @@ igemm_kernel(GemmArgs a) {
             for (int t = 0; t < TM; ++t)
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
-                    const half2v h = {xf[t][2 * j], xf[t][2 * j + 1]};
+                    const half2v h = half2v{xf[t][2 * j], xf[t][2 * j + 1]} - lpiv[t];     // v_pk_add_f16
                     lsum[t] = __builtin_amdgcn_fdot2(h, one, lsum[t], false);
                     lsq[t] = __builtin_amdgcn_fdot2(h, h, lsq[t], false);
                 }
@@ -547,9 +559,11 @@ igemm_kernel(GemmArgs a) {
                 sm += __shfl_xor(sm, 16, 64); sq += __shfl_xor(sq, 16, 64);
                 sm += __shfl_xor(sm, 32, 64); sq += __shfl_xor(sq, 32, 64);
                 const float inv = 1.f / (float)a.ktot;
-                const float mu = sm * inv;
-                lmean[t] = mu;
-                lrstd[t] = rsqrtf(fmaxf(sq * inv - mu * mu, 0.f) + a.ln_eps);
+                const float md = sm * inv;                      // mean of x - p
+                lmean[t] = (float)lpiv[t][0] + md;
+                // a constant row (every x - p exactly 0) normalizes to exactly beta: rstd = 0 leaves out = ln_b, where
+                // rsqrt(eps) would multiply the rounding noise of acc - mean * s by up to 1 / sqrt(eps)
+                lrstd[t] = sq == 0.f ? 0.f : rsqrtf(fmaxf(sq * inv - md * md, 0.f) + a.ln_eps);
             } else { lmean[t] = 0.f; lrstd[t] = 1.f; }
         }
     };

@@ -89,7 +89,8 @@ CID_DEVINL void wait_vmcnt(int n) {
 int launch_conv_h32(const GemmArgs& a, int bm, hipStream_t s);
 
 // GEGLU projection on 32 x 32 x 16 MFMA tiles with loader / compute wave roles (linear_h32.hip); plan_gemm has checked: one
-// source, taps == 1, no LayerNorm fold, M % 256 == 0, N % 160 == 0, a.nloop divides N / 160, at least three channel slabs
+// source, taps == 1, no LayerNorm fold, M % 256 == 0, N % 160 == 0, a.nloop divides N / 160, at least 16 channel slabs (K >= 1024;
+// the kernel itself needs three, for its bias ring, and checks that)
 int launch_geglu_h32(const GemmArgs& a, hipStream_t s);
 
 }  // namespace cidg

@@ -257,6 +257,9 @@ static int launch_geglu_tm(const GemmArgs& a, hipStream_t s) {
     constexpr int BM = 128 * TM;
     constexpr int SMEM = NSTG * (BM * 128 + WST) + 2 * BIAS_IMG;
     static_assert(SMEM <= 160 * 1024, "LDS budget");
+    // two-entry bias ring: the issue cursor runs up to NSTG - 1 slabs ahead, so with fewer than three channel slabs per n-tile
+    // the bias of n-tile j + 2 could land in entry j & 1 before n-tile j's epilogue has read it
+    CID_CHECK_ARG(a.cslabs >= 3, "cid_gemm_f16: the linear_h32 GEGLU launch needs >= 3 channel slabs (got %d)", a.cslabs);
     static bool configured = false;
     if (!configured) {
         hipError_t herr = hipFuncSetAttribute((const void*)geglu_h32_kernel<TM>, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);

@@ -304,26 +304,37 @@ gn_small_kernel(const half_t* __restrict__ x1, const half_t* __restrict__ x2, in
             v[k] = ch0 < c1 ? *reinterpret_cast<const half4*>(x1 + row * c1 + ch0)
                             : *reinterpret_cast<const half4*>(x2 + row * c2 + (ch0 - c1));
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { const float f = (float)v[k][i]; s += f; q += f * f; }
+            for (int i = 0; i < 4; ++i) s += (float)v[k][i];
         }
         r += step_r; cc += step_c;
         if (cc >= cq) { cc -= cq; ++r; }
     }
-    s = wave_sum(s); q = wave_sum(q);
-    if ((threadIdx.x & 63) == 0) { wsum[threadIdx.x >> 6] = s; wsq[threadIdx.x >> 6] = q; }
+    // two passes over the registers: the mean first, then the sum of (x - mean)^2 -- a single pass of x and x^2 in fp32
+    // loses precision in proportion to (mean / std)^2
+    const double n = (double)HW * (double)cg;
+    s = wave_sum(s);
+    if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
+    __syncthreads();
+    if (threadIdx.x == 0)
+        sstat[0] = (float)(((double)wsum[0] + (double)wsum[1] + (double)wsum[2] + (double)wsum[3]) / n);
+    __syncthreads();
+    const float mean = sstat[0];
+#pragma unroll
+    for (int k = 0; k < GNS_MAXPER; ++k) {
+        if ((int)threadIdx.x + k * 256 < nchunk) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) { const float d = (float)v[k][i] - mean; q = __builtin_fmaf(d, d, q); }
+        }
+    }
+    q = wave_sum(q);
+    if ((threadIdx.x & 63) == 0) wsq[threadIdx.x >> 6] = q;
     __syncthreads();
     if (threadIdx.x == 0) {
-        const double n = (double)HW * (double)cg;
-        const double S = (double)wsum[0] + (double)wsum[1] + (double)wsum[2] + (double)wsum[3];
-        const double Q = (double)wsq[0] + (double)wsq[1] + (double)wsq[2] + (double)wsq[3];
-        const double mean = S / n;
-        double var = Q / n - mean * mean;
-        if (var < 0.0) var = 0.0;
-        sstat[0] = (float)mean;
+        const double var = ((double)wsq[0] + (double)wsq[1] + (double)wsq[2] + (double)wsq[3]) / n;
         sstat[1] = (float)(1.0 / sqrt(var + (double)eps));
     }
     __syncthreads();
-    const float mean = sstat[0], rstd = sstat[1];
+    const float rstd = sstat[1];
     r = r_first; cc = c_first;
 #pragma unroll
     for (int k = 0; k < GNS_MAXPER; ++k) {
