@@ -54,6 +54,7 @@ SIGNATURES = {
     "cid_gemm_stats_rows": (C.c_int, [C.POINTER(GemmDesc)]),
     "cid_self_attn_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 8 + [c_stream]),
     "cid_self_attn_keys_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 9 + [c_stream]),
+    "cid_self_attn_causal_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 9 + [c_stream]),
     "cid_id_xattn_f16": (C.c_int, [c_half_p] * 5 + [C.c_float] + [c_half_p] * 5 + [C.c_void_p]
                          + [C.c_int32] * 6 + [C.c_float, c_stream]),
     "cid_id_xattn_core_f16": (C.c_int, [c_half_p] * 4 + [C.c_void_p] + [C.c_int32] * 6 + [C.c_float, c_stream]),
@@ -83,6 +84,9 @@ SIGNATURES = {
                             + [C.c_int32] * 5 + [C.c_void_p, c_stream]),
     "cid_conv3x3_small_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 7 + [c_stream]),
     "cid_gelu_f16": (C.c_int, [c_half_p, C.c_int64, c_stream]),
+    "cid_quick_gelu_f16": (C.c_int, [c_half_p, C.c_int64, c_stream]),
+    "cid_text_embed_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_half_p, c_half_p, c_half_p, C.c_int32,
+                                     C.c_int32, c_stream]),
     "cid_small_attn_f16": (C.c_int, [c_half_p, C.c_int32, c_half_p, C.c_int32, c_half_p, C.c_int32, C.c_int32, c_half_p,
                                      C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, c_stream]),
     "cid_conv_out_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 5 + [c_stream]),

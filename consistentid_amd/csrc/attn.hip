@@ -72,7 +72,10 @@ struct AttnCfg {
     static constexpr int PPW = (NCH + NWV - 1) / NWV;  // pieces per wave and tile (K and V^T alike)
 };
 
-template <int D, int QT, int NWV, bool MASK>
+// MASK: keys >= n_keys are padding.  CAUSAL (the CLIP text towers): key j is visible to query i iff j <= i and j < n_keys; key
+// tiles wholly above the workgroup's last query (or behind n_keys) are never staged, the others are masked per element.  Key 0
+// is visible to every query, so every row -- pad query rows included -- has a finite maximum from tile 0 on.
+template <int D, int QT, int NWV, bool MASK, bool CAUSAL = false>
 __global__ void __launch_bounds__(64 * NWV, (QT == 1 && D <= 40 && NWV == 4) ? 3 : ((QT == 1 && D <= 80) ? 2 : 1))
 self_attn_kernel(const half_t* __restrict__ q, const half_t* __restrict__ k, const half_t* __restrict__ vt,
                  half_t* __restrict__ out, int N, int heads, int ldq, int ldk, int dvp, int ldo, int n_keys, int xcd_remap) {
@@ -112,6 +115,7 @@ self_attn_kernel(const half_t* __restrict__ q, const half_t* __restrict__ k, con
     constexpr bool BIAS = Cfg::DKP > D;
 #endif
     static_assert(!BIAS || Cfg::DKP - D == 8, "pad is one 16-byte slot");
+    static_assert(!(CAUSAL && BIAS), "causal mode: the running max starts behind the mask (no bias slot)");
     if (Cfg::DKP > D) {
         half8 pad = zero_h8();
         if (BIAS) pad[0] = (half_t)1.f;
@@ -214,7 +218,7 @@ self_attn_kernel(const half_t* __restrict__ q, const half_t* __restrict__ k, con
 
     // ---- software pipeline: K tiles run one tile ahead of V tiles, so that the QK^T MFMAs of tile t+1
     //      are independent of (and interleave with) the softmax VALU work of tile t
-    const int ntiles = N / 64;
+    const int ntiles = CAUSAL ? (min(n_keys, bx * Cfg::BQ + Cfg::BQ) + 63) / 64 : N / 64;
     dma_k(0, 0); dma_v(0, 0);
     if (ntiles > 1) dma_k(64, 1);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
@@ -279,13 +283,25 @@ self_attn_kernel(const half_t* __restrict__ q, const half_t* __restrict__ k, con
                     for (int r = 0; r < 16; ++r)
                         if (tile * 64 + kt * 32 + crow(r, hi) >= n_keys) s_cur[kt][t][r] = -INFINITY;
         }
+        // causal: tiles that reach past this wave's first query or past n_keys are masked per element (j > i or j >= n_keys)
+        if (CAUSAL && (tile * 64 + 63 > q0 || (tile + 1) * 64 > n_keys)) {
+#pragma unroll
+            for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+                for (int t = 0; t < QT; ++t)
+#pragma unroll
+                    for (int r = 0; r < 16; ++r) {
+                        const int j = tile * 64 + kt * 32 + crow(r, hi);
+                        if (j > q0 + t * 32 + idx || j >= n_keys) s_cur[kt][t][r] = -INFINITY;
+                    }
+        }
         // ---- running max of tile `tile` (per query column).
         //      It is only raised when a score exceeds it by more than 2^8 ("defer max"): p <= 256 keeps
         //      full fp16 relative precision and the O / l rescale is skipped almost always.
 #pragma unroll
         for (int t = 0; t < QT; ++t) {
             // (masked launches take the max here, behind the mask; the others get it from the previous step)
-            const float mx = (CID_ATTN_ABL & 16) ? s_cur[0][t][0] : ((MASK || CID_ATTN_HEADMAX) ? tile_max(s_cur, t) : mx_cur[t]);   // BIAS: relative to m_run
+            const float mx = (CID_ATTN_ABL & 16) ? s_cur[0][t][0] : ((MASK || CAUSAL || CID_ATTN_HEADMAX) ? tile_max(s_cur, t) : mx_cur[t]);   // BIAS: relative to m_run
             if (__any(mx > (BIAS ? 8.f : m_run[t] + 8.f))) {
                 float m_new, alpha;
                 if (BIAS) {
@@ -344,7 +360,7 @@ self_attn_kernel(const half_t* __restrict__ q, const half_t* __restrict__ k, con
 #pragma unroll
                 for (int t = 0; t < QT; ++t) { if (!(CID_ATTN_ABL & 2)) oacc[d][t] = mfma32(vf[d], pf[t][ks], oacc[d][t]); else oacc[d][t][ks] += (float)vf[d][0] * (float)pf[t][ks][0]; }
         }
-        if (HAS_NEXT && !MASK && !CID_ATTN_HEADMAX) {
+        if (HAS_NEXT && !MASK && !CAUSAL && !CID_ATTN_HEADMAX) {
 #pragma unroll
             for (int t = 0; t < QT; ++t) mx_nxt[t] = tile_max(s_nxt, t);
         }
@@ -393,13 +409,13 @@ self_attn_kernel(const half_t* __restrict__ q, const half_t* __restrict__ k, con
 #endif
 }
 
-template <int D, int QT, int NWV, bool MASK = false>
+template <int D, int QT, int NWV, bool MASK = false, bool CAUSAL = false>
 int launch_attn(const half_t* q, const half_t* k, const half_t* vt, half_t* out, int B, int N, int heads,
                 int ldq, int ldk, int dvp, int ldo, int n_keys, hipStream_t s) {
     using Cfg = AttnCfg<D, QT, NWV>;
     constexpr int smem = 2 * Cfg::BUF;
     static bool configured = false;
-    auto kern = self_attn_kernel<D, QT, NWV, MASK>;
+    auto kern = self_attn_kernel<D, QT, NWV, MASK, CAUSAL>;
     if (!configured) {
         hipError_t herr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
         if (herr != hipSuccess) {
@@ -477,5 +493,23 @@ extern "C" int cid_self_attn_keys_f16(const cid_half* q, const cid_half* k, cons
 #undef CID_ATTN_MASKED
     if (rc) return rc;
     CID_CHECK_LAUNCH("cid_self_attn_f16");
+    return 0;
+}
+
+extern "C" int cid_self_attn_causal_f16(const cid_half* q, const cid_half* k, const cid_half* vt, cid_half* out,
+                                        int32_t B, int32_t N, int32_t heads, int32_t d, int32_t ldq, int32_t ldk,
+                                        int32_t dvp, int32_t ldo, int32_t n_keys, cid_stream_t stream) {
+    CID_CHECK_ARG(q && k && vt && out, "cid_self_attn_causal_f16: null pointer");
+    CID_CHECK_ARG(d == 64, "cid_self_attn_causal_f16: unsupported head dim %d (64)", d);
+    CID_CHECK_ARG(B > 0 && heads > 0 && N > 0 && N % 64 == 0, "cid_self_attn_causal_f16: N must be a positive multiple of 64 (got %d)", N);
+    CID_CHECK_ARG(n_keys > 0 && n_keys <= N, "cid_self_attn_causal_f16: n_keys must be in (0, N] (got %d, N = %d)", n_keys, N);
+    CID_CHECK_ARG(ldq % 8 == 0 && ldk % 8 == 0 && ldo % 4 == 0 && dvp >= d && ldq >= heads * d && ldk >= heads * d &&
+                  ldo >= heads * d, "cid_self_attn_causal_f16: bad pitches");
+    // text-tower lengths (77 tokens on a 128-token axis): 64 queries per workgroup, so that the first query tile stages one
+    // key tile only
+    const int rc = launch_attn<64, 1, 2, false, true>((const half_t*)q, (const half_t*)k, (const half_t*)vt, (half_t*)out, B,
+                                                      N, heads, ldq, ldk, dvp, ldo, n_keys, (hipStream_t)stream);
+    if (rc) return rc;
+    CID_CHECK_LAUNCH("cid_self_attn_causal_f16");
     return 0;
 }

@@ -188,6 +188,44 @@ gelu_kernel(half_t* __restrict__ x, long n8) {
     }
 }
 
+// CLIP quick GELU in place: x * sigmoid(1.702 x) = x / (1 + 2^(-1.702 log2(e) x)) in fp32.  For x below about -52 the
+// power overflows to +inf and the quotient is -0; for large x it is 0 and the result is x -- never NaN for a finite input.
+// (v_rcp_f32 of +inf is +0; the exp2 / rcp error, 1 ulp each in fp32, is far below the fp16 rounding of the result.)
+__global__ void __launch_bounds__(256)
+quick_gelu_kernel(half_t* __restrict__ x, long n8) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < n8; i += (long)gridDim.x * 256) {
+        half8 h = ld_global_h8(x + i * 8);
+#pragma unroll
+        for (int k = 0; k < 8; ++k) {
+            const float v = (float)h[k];
+            h[k] = (half_t)(v * __builtin_amdgcn_rcpf(1.f + __builtin_amdgcn_exp2f(v * -2.4554670422754636f)));   // 1.702 log2 e
+        }
+        *reinterpret_cast<half8*>(x + i * 8) = h;
+    }
+}
+
+// CLIPTextEmbeddings: token row + position row (fp32 add, one rounding), zero rows on the padded tail of the token axis.
+// One thread per 8 channels of one output row.  The caller checks the ids on the host; an id outside [0, V) that gets here
+// anyway reads nothing and yields a zero token row.
+__global__ void __launch_bounds__(256)
+text_embed_kernel(const int* __restrict__ ids, int T, int Tp, const half_t* __restrict__ tok, const half_t* __restrict__ pos,
+                  half_t* __restrict__ out, int V, int C8, long items) {
+    for (long i = (long)blockIdx.x * 256 + threadIdx.x; i < items; i += (long)gridDim.x * 256) {
+        const long row = i / C8;
+        const int c = (int)(i - row * C8) * 8;
+        const int b = (int)(row / Tp), t = (int)(row - (long)b * Tp);
+        half8 o = zero_h8();
+        if (t < T) {
+            const int id = ids[(long)b * T + t];
+            const half8 e = (unsigned)id < (unsigned)V ? ld_global_h8(tok + (long)id * (C8 * 8) + c) : zero_h8();
+            const half8 p = ld_global_h8(pos + (long)t * (C8 * 8) + c);
+#pragma unroll
+            for (int k = 0; k < 8; ++k) o[k] = (half_t)((float)e[k] + (float)p[k]);
+        }
+        *reinterpret_cast<half8*>(out + row * (C8 * 8) + c) = o;
+    }
+}
+
 // PerceiverAttention core (functions.py:439-447): a handful of latent queries attend to [image tokens ; latents].
 // One wave per (sample, head, query); head width 64 (dim_head is 64 throughout the reference).  Keys live in two row
 // blocks (the torch.cat((x, latents)) of :433 without the copy); a row holds [K | V] (to_kv(...).chunk(2), :434).
@@ -528,6 +566,27 @@ extern "C" int cid_gelu_f16(cid_half* x, int64_t n, cid_stream_t stream) {
     CID_CHECK_ARG(x && n > 0 && n % 8 == 0, "cid_gelu_f16: n must be a positive multiple of 8");
     hipLaunchKernelGGL(gelu_kernel, dim3(grid_for(n / 8, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (half_t*)x, (long)(n / 8));
     CID_CHECK_LAUNCH("cid_gelu_f16");
+    return 0;
+}
+
+extern "C" int cid_quick_gelu_f16(cid_half* x, int64_t n, cid_stream_t stream) {
+    CID_CHECK_ARG(x, "cid_quick_gelu_f16: null pointer");
+    CID_CHECK_ARG(n > 0 && n % 8 == 0, "cid_quick_gelu_f16: n must be a positive multiple of 8 (got %lld)", (long long)n);
+    hipLaunchKernelGGL(quick_gelu_kernel, dim3(grid_for(n / 8, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (half_t*)x,
+                       (long)(n / 8));
+    CID_CHECK_LAUNCH("cid_quick_gelu_f16");
+    return 0;
+}
+
+extern "C" int cid_text_embed_f16(const int32_t* ids, int32_t B, int32_t T, int32_t Tp, const cid_half* tok,
+                                  const cid_half* pos, cid_half* out, int32_t V, int32_t C, cid_stream_t stream) {
+    CID_CHECK_ARG(ids && tok && pos && out, "cid_text_embed_f16: null pointer");
+    CID_CHECK_ARG(B > 0 && T > 0 && Tp >= T && V > 0 && C > 0 && C % 8 == 0,
+                  "cid_text_embed_f16: bad shape (B %d, T %d, Tp %d, V %d, C %d; Tp >= T, C %% 8 == 0)", B, T, Tp, V, C);
+    const long items = (long)B * Tp * (C / 8);
+    hipLaunchKernelGGL(text_embed_kernel, dim3(grid_for(items, 256, 4096)), dim3(256), 0, (hipStream_t)stream, (const int*)ids,
+                       T, Tp, (const half_t*)tok, (const half_t*)pos, (half_t*)out, V, C / 8, items);
+    CID_CHECK_LAUNCH("cid_text_embed_f16");
     return 0;
 }
 

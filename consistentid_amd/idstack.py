@@ -5,7 +5,7 @@ as the reference calls them in ``get_image_embeds`` / ``get_facial_embeds`` (pip
 and assembles ``prompt_embeds = cat([null, augmented, text_only])`` the way ``__call__`` does (:479-507) -- the tensor the
 denoising loop ``.chunk(3)``s.  Inputs are what the encoders upstream produce: CLIP-ViT-H penultimate hidden states of the
 face image / the facial crops / zero images, the 512-d FaceID vector, the text encoder outputs and the trigger-token masks.
-(Those encoders -- CLIP vision and text towers, insightface, BiSeNet -- are still outside this repository.)
+(The CLIP towers are in clip_vision.py / clip_text.py; insightface and BiSeNet stay outside this repository.)
 
 Every Linear is ``cid_gemm_f16``, LayerNorm ``cid_layernorm_f16``; GELU and the tiny latent-query attention are
 ``cid_gelu_f16`` / ``cid_small_attn_f16``.  Row gathers / scatters of the handful of trigger-token rows are index

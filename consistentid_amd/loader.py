@@ -9,9 +9,12 @@ sub-folder per component.  This module reads the components the hot path needs, 
                                                                              inpaint pipelines when encoder.* weights are there)
     <controlnet dir>/config.json + diffusion_pytorch_model.{safetensors,bin} -> HipControlNet (separate call, like the
                                                                                 reference: demo/controlnet_demo.py:44-47)
+    <root>/text_encoder{,_2}/config.json + model{.fp16,}.safetensors | pytorch_model{.fp16,}.bin
+                                                                          -> HipCLIPTextModel (optional; transformers names)
+    <root>/tokenizer{,_2}/                                                -> transformers.CLIPTokenizer (optional)
 
 Local files only (there is no hub access in the engine), ``.fp16`` variants are picked up, sharded checkpoints are
-not.  Tokenizer / text encoders / safety checker folders are left alone: prompt encoding is pre-loop.
+not.  Safety checker / feature extractor folders are left alone.
 ``scheduler/scheduler_config.json`` is read for its betas / steps_offset / timestep spacing (the engine carries its own
 DDIM / Euler coefficient tables, scheduler.py; the base model's sampler class itself is not built).
 
@@ -30,6 +33,11 @@ from .vae_spec import VAEConfig
 
 WEIGHT_NAMES = ("diffusion_pytorch_model.fp16.safetensors", "diffusion_pytorch_model.safetensors",
                 "diffusion_pytorch_model.fp16.bin", "diffusion_pytorch_model.bin")
+
+
+# transformers' file names (text_encoder/, text_encoder_2/), not diffusers' WEIGHT_NAMES
+TEXT_WEIGHT_NAMES = ("model.fp16.safetensors", "model.safetensors", "pytorch_model.fp16.bin", "pytorch_model.bin")
+TEXT_COMPONENTS = ("text_encoder", "tokenizer", "text_encoder_2", "tokenizer_2")
 
 
 def _tup(v, n) -> Tuple[int, ...]:
@@ -84,22 +92,24 @@ def vae_config_from_diffusers(cfg: Dict) -> VAEConfig:
                      scaling_factor=float(cfg.get("scaling_factor", 0.18215)), force_upcast=bool(cfg.get("force_upcast", False)))
 
 
-def read_component(folder: Union[str, os.PathLike]) -> Tuple[Dict, Dict[str, torch.Tensor]]:
-    """(config.json as dict, state_dict on the CPU) of one diffusers component folder"""
+def read_component(folder: Union[str, os.PathLike], weight_names: Sequence[str] = WEIGHT_NAMES
+                   ) -> Tuple[Dict, Dict[str, torch.Tensor]]:
+    """(config.json as dict, state_dict on the CPU) of one diffusers component folder (``weight_names``: the files
+    tried in order; TEXT_WEIGHT_NAMES for the transformers text encoders)"""
     folder = os.fspath(folder)
     cpath = os.path.join(folder, "config.json")
     if not os.path.isfile(cpath):
         raise FileNotFoundError(f"{cpath}: not a diffusers component folder (the engine reads local files only)")
     with open(cpath) as f:
         cfg = json.load(f)
-    for name in WEIGHT_NAMES:
+    for name in weight_names:
         wpath = os.path.join(folder, name)
         if os.path.isfile(wpath):
             break
     else:
-        if os.path.isfile(os.path.join(folder, "diffusion_pytorch_model.safetensors.index.json")):
+        if os.path.isfile(os.path.join(folder, weight_names[1] + ".index.json")):     # (the plain .safetensors name)
             raise NotImplementedError(f"{folder}: sharded checkpoints are not read; merge the shards first")
-        raise FileNotFoundError(f"{folder}: none of {WEIGHT_NAMES}")
+        raise FileNotFoundError(f"{folder}: none of {tuple(weight_names)}")
     if wpath.endswith(".safetensors"):
         from safetensors.torch import load_file
         sd = load_file(wpath, device="cpu")
@@ -133,6 +143,44 @@ def load_vae_encoder(root: Union[str, os.PathLike], device="cuda:0", subfolder: 
     from .vae import HipVAEEncoder
     cfg, sd = read_component(os.path.join(os.fspath(root), subfolder) if subfolder else root)
     return HipVAEEncoder(vae_config_from_diffusers(cfg), sd, device=device)
+
+
+def load_text_encoder(folder: Union[str, os.PathLike], device="cuda:0"):
+    """``text_encoder/`` or ``text_encoder_2/`` (transformers CLIPTextModel / CLIPTextModelWithProjection) -> HipCLIPTextModel"""
+    from .clip_text import HipCLIPTextModel
+    cfg, sd = read_component(folder, TEXT_WEIGHT_NAMES)
+    return HipCLIPTextModel(sd, cfg, device=device)
+
+
+def load_tokenizer(folder: Union[str, os.PathLike]):
+    """``tokenizer/`` or ``tokenizer_2/`` -> transformers.CLIPTokenizer (local files only; transformers is imported here,
+    not by the engine)"""
+    from transformers import CLIPTokenizer
+    return CLIPTokenizer.from_pretrained(os.fspath(folder), local_files_only=True)
+
+
+def read_force_zeros(root: Union[str, os.PathLike]) -> bool:
+    """SDXL's ``force_zeros_for_empty_prompt`` from ``model_index.json`` (diffusers' default True when absent)"""
+    path = os.path.join(os.fspath(root), "model_index.json")
+    if not os.path.isfile(path):
+        return True
+    with open(path) as f:
+        return bool(json.load(f).get("force_zeros_for_empty_prompt", True))
+
+
+def read_text_components(root: Union[str, os.PathLike], device="cuda:0", given: Optional[Dict] = None) -> Dict:
+    """The text encoders and tokenizers of a model directory, by keyword: a component passed in ``given`` is kept as it
+    is (None skips it, as in diffusers); the others are read from their folder when it exists."""
+    given = given or {}
+    out = {}
+    for name in TEXT_COMPONENTS:
+        if name in given:
+            out[name] = given[name]
+            continue
+        folder = os.path.join(os.fspath(root), name)
+        if os.path.isdir(folder):
+            out[name] = load_tokenizer(folder) if name.startswith("tokenizer") else load_text_encoder(folder, device=device)
+    return out
 
 
 def _has_encoder(sd) -> bool:
@@ -189,8 +237,10 @@ def read_scheduler(root: Union[str, os.PathLike]):
 def from_pretrained(pipeline_cls, root: Union[str, os.PathLike], torch_dtype=torch.float16, device="cuda:0",
                     controlnet: Optional[Union[str, os.PathLike, object]] = None, use_graph: bool = True, **kw):
     """``Pipeline.from_pretrained(base_model_path, torch_dtype=torch.float16)`` of the reference scripts (infer.py:17-21;
-    with ``controlnet=`` demo/controlnet_demo.py:44-47): UNet (required) and VAE decoder (when the folder exists) of a
-    local diffusers model directory; ``controlnet`` = a HipControlNet or the folder of a ControlNetModel."""
+    with ``controlnet=`` demo/controlnet_demo.py:44-47): UNet (required), VAE decoder, text encoders and tokenizers (when
+    their folders exist) of a local diffusers model directory; ``controlnet`` = a HipControlNet or the folder of a
+    ControlNetModel.  ``text_encoder=`` / ``tokenizer=`` / ``text_encoder_2=`` / ``tokenizer_2=`` take a ready object, or
+    None to skip that component."""
     if torch_dtype not in (torch.float16, None):
         raise NotImplementedError("the engine computes in fp16 (the reference's own inference dtype, infer.py:19)")
     # diffusers loader keywords the reference scripts pass (infer.py:17-21 variant="fp16"; infer_SDXL.py safety_checker=None;
@@ -199,7 +249,7 @@ def from_pretrained(pipeline_cls, root: Union[str, os.PathLike], torch_dtype=tor
     for name in ("variant", "use_safetensors", "safety_checker", "feature_extractor", "requires_safety_checker",
                  "local_files_only", "cache_dir", "revision", "low_cpu_mem_usage", "add_watermarker"):
         kw.pop(name, None)
-    unknown = [k for k in kw if k not in ("scheduler", "num_tokens", "lora_rank")]
+    unknown = [k for k in kw if k not in ("scheduler", "num_tokens", "lora_rank") + TEXT_COMPONENTS]
     if unknown:
         raise TypeError(f"from_pretrained: unexpected keyword(s) {unknown}")
     root = os.fspath(root)
@@ -216,7 +266,11 @@ def from_pretrained(pipeline_cls, root: Union[str, os.PathLike], torch_dtype=tor
         # the encoder only for the two inpaint pipelines (their image= / mask_image= pre-loop), and only if the weights are there
         if issubclass(pipeline_cls, StableDiffusionInpaintConsistentIDPipeline) and _has_encoder(vsd):
             vae_encoder = HipVAEEncoder(vcfg, vsd, device=device)
-    args = dict(use_graph=use_graph, vae=vae, **kw)
+    text = read_text_components(root, device=device, given={k: kw.pop(k) for k in TEXT_COMPONENTS if k in kw})
+    args = dict(use_graph=use_graph, vae=vae, **kw, **{k: v for k, v in text.items() if v is not None})
+    from .pipeline import ConsistentIDStableDiffusionXLPipeline
+    if issubclass(pipeline_cls, ConsistentIDStableDiffusionXLPipeline):
+        args["force_zeros_for_empty_prompt"] = read_force_zeros(root)
     if vae_encoder is not None:
         args["vae_encoder"] = vae_encoder
     if "scheduler" not in args:

@@ -174,6 +174,17 @@ def self_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Ten
     return out
 
 
+def self_attn_causal(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, *, B: int, N: int,
+                     heads: int, d: int, ldq: int, ldk: int, ldo: int, n_keys: int):
+    """causal self-attention of the CLIP text towers: key j is visible to query i iff j <= i and j < n_keys (d = 64)"""
+    lib = _lib.load()
+    for name, t in (("q", q), ("k", k), ("vt", vt), ("out", out)):
+        _req(t, f"self_attn_causal.{name}")
+    check(lib.cid_self_attn_causal_f16(_p(q), _p(k), _p(vt), _p(out), B, N, heads, d, ldq, ldk, dvp_of(d), ldo, n_keys,
+                                       _stream()), "cid_self_attn_causal_f16")
+    return out
+
+
 def kv_pack_elems(C_: int, heads: int):
     lib = _lib.load()
     return int(lib.cid_kv_pack_elems(C_, heads, 0)), int(lib.cid_kv_pack_elems(C_, heads, 1))
@@ -362,6 +373,26 @@ def gelu_(x: torch.Tensor):
     _req(x, "gelu.x")
     check(lib.cid_gelu_f16(_p(x), x.numel(), _stream()), "cid_gelu_f16")
     return x
+
+
+def quick_gelu_(x: torch.Tensor):
+    """in-place x * sigmoid(1.702 x) (CLIP's quick_gelu)"""
+    lib = _lib.load()
+    _req(x, "quick_gelu.x")
+    check(lib.cid_quick_gelu_f16(_p(x), x.numel(), _stream()), "cid_quick_gelu_f16")
+    return x
+
+
+def text_embed(ids: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, out: torch.Tensor, *, B: int, T: int, Tp: int):
+    """CLIPTextEmbeddings: ``out`` [B, Tp, C] = tok[ids] + pos[:T], zero rows for t >= T.  ``ids`` int32 [B, T] on the GPU,
+    already range-checked by the caller (clip_text.check_ids)"""
+    lib = _lib.load()
+    _req(ids, "text_embed.ids", torch.int32)
+    for name, t in (("tok", tok), ("pos", pos), ("out", out)):
+        _req(t, f"text_embed.{name}")
+    V, C_ = tok.shape
+    check(lib.cid_text_embed_f16(_p(ids), B, T, Tp, _p(tok), _p(pos), _p(out), V, C_, _stream()), "cid_text_embed_f16")
+    return out
 
 
 def small_attn(q: torch.Tensor, kv1: torch.Tensor, kv2: Optional[torch.Tensor], out: torch.Tensor, *, B: int, Lq: int,

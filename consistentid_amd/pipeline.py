@@ -9,8 +9,9 @@ the reference's ``__call__`` keyword surface, running on the HIP engine.
 Scope: the per-step path, the ControlNet encoder (row f-1), the VAE decode (row f-2) and the VAE
 encode of the inpaint pipelines (``image=`` / ``mask_image=`` with ``vae_encoder=HipVAEEncoder(...)``; the init image comes in
 through ``image=``, where the reference reads ``input_id_images[0]``).
-The rest of the once-per-image pre-loop (FaceID, face parsing, CLIP text/vision encoders, FacialEncoder /
-ProjPlusModel) is out of scope this round, so the pipelines take what that pre-loop produces:
+Prompt strings are encoded by ``encode_prompt`` / ``_encode_prompt`` / ``encode_prompt_with_trigger_word`` on the HIP
+text towers (``text_encoder=`` / ``text_encoder_2=``, clip_text.py; prompt_encode.py), the ID tokens by
+``prepare_prompt_embeds``.  FaceID and face parsing stay outside, so ``__call__`` takes what the pre-loop produces:
 ``prompt_embeds`` = cat([null, augmented, text_only]) of shape [3B, 77+4, Dc] exactly as the
 reference assembles it before ``.chunk(3)`` (ref :494-507, :527-531), and ``latents``.
 String prompts / ID images raise NotImplementedError naming the missing component instead of silently doing
@@ -244,11 +245,16 @@ class _BasePipeline:
     vae_scale_factor = 8
 
     def __init__(self, unet: HipUNet, scheduler: Optional[DDIMScheduler] = None, use_graph: bool = True,
-                 num_tokens: int = 4, lora_rank: int = 128, vae=None, vae_encoder=None):
+                 num_tokens: int = 4, lora_rank: int = 128, vae=None, vae_encoder=None, text_encoder=None, tokenizer=None,
+                 text_encoder_2=None, tokenizer_2=None):
         """``vae``: a ``consistentid_amd.vae.HipVAEDecoder`` -- enables every ``output_type`` besides "latent".
         ``vae_encoder``: a ``consistentid_amd.vae.HipVAEEncoder`` -- lets the inpaint pipelines take ``image=`` and
-        ``mask_image=`` (the reference's pre-loop VAE encode) instead of pre-computed latents."""
+        ``mask_image=`` (the reference's pre-loop VAE encode) instead of pre-computed latents.
+        ``text_encoder`` / ``text_encoder_2``: ``consistentid_amd.clip_text.HipCLIPTextModel`` (CLIP-L; SDXL's bigG with
+        projection), ``tokenizer`` / ``tokenizer_2``: ``transformers.CLIPTokenizer`` -- let ``encode_prompt`` take strings."""
         self.unet = unet
+        self.text_encoder, self.tokenizer = text_encoder, tokenizer
+        self.text_encoder_2, self.tokenizer_2 = text_encoder_2, tokenizer_2
         self.vae = vae
         self.vae_encoder = vae_encoder
         self.num_tokens = num_tokens
@@ -305,6 +311,12 @@ class _BasePipeline:
         self.unet.num_tokens = num_tokens
         self.unet.load_adapter_modules(state_dict["adapter_modules"])                  # ref :143-144 (strict)
         # once-per-image ID-conditioning modules (ProjPlusModel / FacialEncoder, ref :93-100, :141-142)
+        # trigger tokens (ref :148-150): both to the tokenizer; SDXL adds only <|image|> to tokenizer_2 (ref SDXL :164-176)
+        if self.tokenizer is not None:
+            self.tokenizer.add_tokens([trigger_word_ID], special_tokens=True)
+            self.tokenizer.add_tokens([trigger_word_facial], special_tokens=True)
+        if self.tokenizer_2 is not None:
+            self.tokenizer_2.add_tokens([trigger_word_ID], special_tokens=True)
         self.image_proj_state = state_dict.get("image_proj")
         self.facial_encoder_state = state_dict.get("FacialEncoder")
         self.id_conditioner = None
@@ -325,8 +337,9 @@ class _BasePipeline:
     def _check_hot_path_inputs(self, prompt, input_id_images, prompt_embeds, latents, output_type):
         if prompt is not None or input_id_images is not None:
             raise NotImplementedError(
-                "the pre-loop (FaceID / face parsing / CLIP encoders / FacialEncoder, ref :437-507) is outside "
-                "this round's scope (SURVEY.md 8f-3): pass prompt_embeds=[3B,81,Dc] and latents")
+                "__call__(prompt=..., input_id_images=...) needs FaceID and face parsing (ref :437-465), which are outside "
+                "this project's scope (SURVEY.md 8f-3): encode the text with encode_prompt_with_trigger_word / "
+                "encode_prompt, build prompt_embeds=[3B,81,Dc] with prepare_prompt_embeds and pass it with latents")
         if prompt_embeds is None or latents is None:
             raise ValueError("prompt_embeds (cat([null, augmented, text_only])) and latents are required")
         if output_type != "latent" and self.vae is None:
@@ -353,7 +366,42 @@ class _BasePipeline:
         return prompt_embeds.chunk(3)   # null, augmented, text-only (ref :527-531)
 
 
-class ConsistentIDStableDiffusionPipeline(_BasePipeline):
+class _SD15PromptEncoding:
+    """Prompt encoding of the SD1.5-family pipelines (SD1.5, inpaint, ControlNet-inpaint): D: encode_prompt /
+    _encode_prompt of diffusers 0.23 on ``self.text_encoder`` (prompt_encode.py), and the reference's
+    ``encode_prompt_with_trigger_word`` (prompt_utils.py) on ``self.tokenizer``."""
+
+    def encode_prompt(self, prompt, device=None, num_images_per_prompt: int = 1, do_classifier_free_guidance: bool = True,
+                      negative_prompt=None, prompt_embeds=None, negative_prompt_embeds=None, lora_scale=None,
+                      clip_skip=None):
+        """-> (prompt_embeds, negative_prompt_embeds), fp16 on the engine's device"""
+        from .prompt_encode import encode_prompt
+        return encode_prompt(self.tokenizer, self.text_encoder, prompt, device or self.device, num_images_per_prompt,
+                             do_classifier_free_guidance, negative_prompt, prompt_embeds, negative_prompt_embeds, lora_scale,
+                             clip_skip)
+
+    def _encode_prompt(self, prompt, device=None, num_images_per_prompt: int = 1, do_classifier_free_guidance: bool = True,
+                       negative_prompt=None, prompt_embeds=None, negative_prompt_embeds=None, lora_scale=None):
+        """legacy form the reference calls (ref :469-475, :494-501): cat([negative, prompt])"""
+        from .prompt_encode import encode_prompt_legacy
+        return encode_prompt_legacy(self.tokenizer, self.text_encoder, prompt, device or self.device, num_images_per_prompt,
+                                    do_classifier_free_guidance, negative_prompt, prompt_embeds, negative_prompt_embeds,
+                                    lora_scale)
+
+    def encode_prompt_with_trigger_word(self, prompt: str, face_caption: str, key_parsing_mask_list=None,
+                                        image_token: str = "<|image|>", facial_token: str = "<|facial|>",
+                                        max_num_facials: int = 5, num_id_images: int = 1, device=None):
+        """ref :311-347 -> (prompt_text_only, clean_input_id, key_parsing_mask_list_align, facial_token_mask,
+        facial_token_idx, facial_token_idx_mask)"""
+        from .prompt_utils import encode_prompt_with_trigger_word
+        if self.tokenizer is None:
+            raise ValueError("no tokenizer: build the pipeline with tokenizer= (from_pretrained reads tokenizer/)")
+        return encode_prompt_with_trigger_word(self.tokenizer, prompt, face_caption,
+                                               {} if key_parsing_mask_list is None else key_parsing_mask_list, image_token,
+                                               facial_token, max_num_facials, num_id_images)
+
+
+class ConsistentIDStableDiffusionPipeline(_SD15PromptEncoding, _BasePipeline):
     def __call__(self, prompt=None, height: Optional[int] = None, width: Optional[int] = None,
                  num_inference_steps: int = 50, guidance_scale: float = 5.0, negative_prompt=None,
                  num_images_per_prompt: Optional[int] = 1, eta: float = 0.0, generator=None,
@@ -377,6 +425,41 @@ class ConsistentIDStableDiffusionPipeline(_BasePipeline):
 
 class ConsistentIDStableDiffusionXLPipeline(_BasePipeline):
     default_guidance = 7.5
+
+    def __init__(self, unet: HipUNet, scheduler: Optional[DDIMScheduler] = None, force_zeros_for_empty_prompt: bool = True,
+                 **kw):
+        """``force_zeros_for_empty_prompt``: the SDXL pipeline config flag (model_index.json; diffusers' default True) --
+        ``encode_prompt`` gives zero negative embeds when no negative prompt is given"""
+        super().__init__(unet, scheduler, **kw)
+        self.force_zeros_for_empty_prompt = force_zeros_for_empty_prompt
+
+    def encode_prompt(self, prompt, prompt_2=None, device=None, num_images_per_prompt: int = 1,
+                      do_classifier_free_guidance: bool = True, negative_prompt=None, negative_prompt_2=None,
+                      prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None,
+                      negative_pooled_prompt_embeds=None, lora_scale=None):
+        """D: StableDiffusionXLPipeline.encode_prompt (ref SDXL :552-565) on the two HIP towers -> (prompt_embeds,
+        negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds)"""
+        from .prompt_encode import encode_prompt_sdxl
+        toks, encs = [self.tokenizer, self.tokenizer_2], [self.text_encoder, self.text_encoder_2]
+        if self.text_encoder is None:
+            toks, encs = toks[1:], encs[1:]
+        return encode_prompt_sdxl(toks, encs, prompt, prompt_2, device or self.device, num_images_per_prompt,
+                                  do_classifier_free_guidance, negative_prompt, negative_prompt_2, prompt_embeds,
+                                  negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds, lora_scale,
+                                  self.force_zeros_for_empty_prompt)
+
+    def encode_prompt_with_trigger_word(self, prompt: str, face_caption: str, key_parsing_mask_list=None,
+                                        image_token: str = "<|image|>", facial_token: str = "<|facial|>",
+                                        max_num_facials: int = 5, num_id_images: int = 1, device=None):
+        """ref SDXL :338-391 -> (prompt_text_only, clean_input_id, clean_input_id2, key_parsing_mask_list_align,
+        facial_token_mask, facial_token_idx, facial_token_idx_mask); see prompt_encode.encode_prompt_with_trigger_word_sdxl
+        for the tokenizer-2 quirk it keeps"""
+        from .prompt_encode import encode_prompt_with_trigger_word_sdxl
+        if self.tokenizer is None or self.tokenizer_2 is None:
+            raise ValueError("the SDXL trigger-word encoding needs tokenizer and tokenizer_2")
+        return encode_prompt_with_trigger_word_sdxl(self.tokenizer, self.tokenizer_2, prompt, face_caption,
+                                                    {} if key_parsing_mask_list is None else key_parsing_mask_list,
+                                                    image_token, facial_token, max_num_facials, num_id_images)
 
     def __call__(self, prompt=None, prompt_2=None, height=None, width=None, num_inference_steps: int = 50,
                  denoising_end=None, guidance_scale: float = 7.5, negative_prompt=None, negative_prompt_2=None,
@@ -432,7 +515,7 @@ class ConsistentIDStableDiffusionXLPipeline(_BasePipeline):
         return StableDiffusionXLPipelineOutput(images=out)
 
 
-class StableDiffusionInpaintConsistentIDPipeline(_BasePipeline):
+class StableDiffusionInpaintConsistentIDPipeline(_SD15PromptEncoding, _BasePipeline):
     default_guidance = 7.5
 
     def _strength_window(self, strength: float, num_inference_steps: int, latents, image_latents, noise):

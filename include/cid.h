@@ -124,6 +124,13 @@ int cid_self_attn_f16(const cid_half* q, const cid_half* k, const cid_half* vt, 
 int cid_self_attn_keys_f16(const cid_half* q, const cid_half* k, const cid_half* vt, cid_half* out,
                            int32_t B, int32_t N, int32_t heads, int32_t d, int32_t ldq, int32_t ldk,
                            int32_t dvp, int32_t ldo, int32_t n_keys, cid_stream_t stream);
+/* Causal form for the CLIP text towers (D: CLIPTextTransformer's causal mask, read by the reference's text_encoder calls
+ * pipline_StableDiffusion_ConsistentID.py:467, SDXL :514-521): key j is visible to query i iff j <= i and j < n_keys.
+ * Same arguments as cid_self_attn_keys_f16; d == 64 only (CLIP-L 12 x 64, OpenCLIP bigG 20 x 64).  Query rows beyond n_keys
+ * come out finite (they see keys 0 .. n_keys - 1) and are for the caller to ignore. */
+int cid_self_attn_causal_f16(const cid_half* q, const cid_half* k, const cid_half* vt, cid_half* out,
+                             int32_t B, int32_t N, int32_t heads, int32_t d, int32_t ldq, int32_t ldk,
+                             int32_t dvp, int32_t ldo, int32_t n_keys, cid_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Fused identity cross-attention = Consistent_IPAttProcessor.__call__
@@ -282,6 +289,21 @@ int cid_small_attn_f16(const cid_half* q, int32_t ldq, const cid_half* kv1, int3
                        float scale2, cid_stream_t stream);
 int cid_conv_out_f16(const cid_half* x, cid_half* out, const cid_half* w, const cid_half* bias,
                      int32_t B, int32_t H, int32_t W, int32_t cin, int32_t cout, cid_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * CLIP text towers (once per prompt; the reference's text_encoder / text_encoder_2 calls,
+ * pipline_StableDiffusion_ConsistentID.py:467-501, SDXL :514-565, through D: CLIPTextModel / CLIPTextModelWithProjection).
+ * Their LayerNorms, projections and MLP are cid_layernorm_f16 / cid_gemm_f16 / cid_linear_small_f16, their attention is
+ * cid_self_attn_causal_f16; these two fill the gaps.
+ *   cid_quick_gelu_f16  in place x * sigmoid(1.702 x) (D: QuickGELUActivation, hidden_act "quick_gelu" of CLIP-L), fp32 math;
+ *                       every finite input gives a finite result (-0 or x where exp overflows).  n % 8 == 0
+ *   cid_text_embed_f16  out[b][t] = tok[ids[b][t]] + pos[t] for t < T, zero rows for T <= t < Tp (D: CLIPTextEmbeddings).
+ *                       ids int32 [B][T]; tok [V][C], pos [>= T][C], out [B][Tp][C]; C % 8 == 0.  The caller checks
+ *                       0 <= id < V on the host (the Python engine raises ValueError); an id outside that range reads
+ *                       nothing and gives a zero token row. */
+int cid_quick_gelu_f16(cid_half* x, int64_t n, cid_stream_t stream);
+int cid_text_embed_f16(const int32_t* ids, int32_t B, int32_t T, int32_t Tp, const cid_half* tok, const cid_half* pos,
+                       cid_half* out, int32_t V, int32_t C, cid_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * VAE encoder ends (csrc/vae_enc.hip).  The inpaint pipelines encode the init image and the masked image before the loop
