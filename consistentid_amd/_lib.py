@@ -38,6 +38,7 @@ class GemmDesc(C.Structure):
         ("att_n_txt", C.c_int32), ("att_n_ip", C.c_int32), ("att_ip_scale", C.c_float),
         ("out2", C.c_void_p),
         ("pad_mode", C.c_int32),
+        ("act", C.c_int32),
     ]
 
 
@@ -94,6 +95,11 @@ SIGNATURES = {
                               + [C.c_int32] * 5 + [c_half_p, c_stream]),
     "cid_vae_encode_out_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, c_half_p, C.c_void_p, c_half_p] + [C.c_int32] * 5
                                + [C.c_float, c_stream]),
+    "cid_parse_stem_f16": (C.c_int, [C.c_void_p, c_half_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [c_stream]),
+    "cid_chan_mean_f16": (C.c_int, [c_half_p, C.c_void_p] + [C.c_int32] * 4 + [c_stream]),
+    "cid_chan_gate_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [c_stream]),
+    "cid_chan_affine_f16": (C.c_int, [c_half_p, C.c_void_p, C.c_void_p, c_half_p, c_half_p] + [C.c_int32] * 3 + [c_stream]),
+    "cid_parse_head_f16": (C.c_int, [c_half_p] + [C.c_int32] * 7 + [C.c_void_p, C.c_void_p, c_stream]),
     "cid_sincos_embed_f16": (C.c_int, [C.c_void_p, c_half_p, C.c_int32, C.c_int32, c_stream]),
     "cid_linear_small_f16": (C.c_int, [c_half_p, C.c_int32, c_half_p, c_half_p, c_half_p, C.c_int32, c_half_p,
                                        C.c_int32] + [C.c_int32] * 5 + [c_stream]),

@@ -114,7 +114,8 @@ CID_DEVINL float row16_sum(float v) {
 // shared epilogue: VMODE transposed-V store, split-K partials, GEGLU, or bias / time-row / residual.
 // LN: the A operand was the RAW residual stream and W carries gamma -- lmean / lrstd are the LayerNorm statistics of this
 // lane's token (row l16 of 16-token tile t), out = rstd * (acc - mean * ln_s[n]) + ln_b[n]  (ln_b includes the bias).
-template <int TM, int TN, bool VMODE, bool LN, bool NLOOP = false>
+// ACT (cid_gemm_desc.act 1, plain epilogue only): ReLU after bias / time row / residual, before the rounding and the stores.
+template <int TM, int TN, bool VMODE, bool LN, bool NLOOP = false, bool ACT = false>
 CID_DEVINL void igemm_epilogue(const GemmArgs& a, f32x4v (&acc)[TM][TN], int m0, int n0, int wm, int wn,
                                int l16, int lq, char* smem, int wave, const float (&lmean)[TM], const float (&lrstd)[TM],
                                int nwaves, int wn_count, const half4 (&rpre)[TM][TN], bool rpre_valid) {
@@ -273,6 +274,10 @@ CID_DEVINL void igemm_epilogue(const GemmArgs& a, f32x4v (&acc)[TM][TN], int m0,
                         for (int i = 0; i < 4; ++i) v[i] += (float)bb[i];
                     }
                 }
+                if constexpr (ACT) {
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) v[i] = __builtin_fmaxf(v[i], 0.f);
+                }
                 half4 o;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) o[i] = (half_t)v[i];
@@ -366,7 +371,8 @@ CID_DEVINL bool prefetch_residual(const GemmArgs& a, half4 (&rpre)[TM][TN], int 
 // ATT_D > 0 (mode 3): the launch is the QUERY PROJECTION of an identity cross-attention whose tile spans whole heads of
 // ATT_D channels; its epilogue keeps the fp16 Q tile in LDS, runs the two-stream attention of those heads on it
 // (xattn_core_unit, one (head, 32-token) unit per wave) and writes O -- q never goes to HBM, one launch less per layer.
-template <int TM, int TN, int WM, int WN, bool VMODE, int NBUF, bool LN, bool NLOOP = false, int ATT_D = 0>
+// ACT: the ReLU epilogue of cid_gemm_desc.act (plain, unsplit launches only: plan_gemm routes them here).
+template <int TM, int TN, int WM, int WN, bool VMODE, int NBUF, bool LN, bool NLOOP = false, int ATT_D = 0, bool ACT = false>
 // (two workgroups per CU asked for even of the four-wave tiles: with a 512-register budget the compiler parks the accumulators
 //  in AGPRs and rotates them through VGPRs at the head of every slab -- 60 v_accvgpr moves beside 20 MFMAs, tools/isa_mix.py)
 __global__ void __launch_bounds__(64 * WM * WN, (NLOOP && TM == 2) ? 4 : 2)
@@ -741,7 +747,7 @@ igemm_kernel(GemmArgs a) {
         }
         return;
     }
-    igemm_epilogue<TM, TN, VMODE, LN>(a, acc, m0, n0, wm, wn, l16, lq, smem, wave, lmean, lrstd, NW, WN, rpre, rpre_valid);
+    igemm_epilogue<TM, TN, VMODE, LN, false, ACT>(a, acc, m0, n0, wm, wn, l16, lq, smem, wave, lmean, lrstd, NW, WN, rpre, rpre_valid);
 #endif
 }
 
@@ -1086,14 +1092,14 @@ splitk_epilogue_kernel(GemmArgs a) {
     }
 }
 
-template <int TM, int TN, int WM, int WN, bool VMODE, bool LN, bool NLOOP = false, int NBUF = 2, int ATT_D = 0>
+template <int TM, int TN, int WM, int WN, bool VMODE, bool LN, bool NLOOP = false, int NBUF = 2, int ATT_D = 0, bool ACT = false>
 int launch_one_ln(const GemmArgs& a, int ncols, hipStream_t s) {
     constexpr int BM = 16 * TM * WM, BN = 16 * TN * WN;
     constexpr int NW = WM * WN;
     constexpr int STAGE = ((BM / 8 + NW - 1) / NW) * NW * 1024 + BN * 128;   // x rows incl. scratch pieces + exactly BN weight rows
     constexpr int SMEM = NBUF * STAGE;
     static_assert(SMEM <= 160 * 1024, "LDS budget");
-    auto kern = igemm_kernel<TM, TN, WM, WN, VMODE, NBUF, LN, NLOOP, ATT_D>;
+    auto kern = igemm_kernel<TM, TN, WM, WN, VMODE, NBUF, LN, NLOOP, ATT_D, ACT>;
     static bool configured = false;
     if (!configured) {
         hipError_t herr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, SMEM);
@@ -1132,6 +1138,14 @@ int launch_att(GemmArgs a, hipStream_t s) {
     a.n_begin = 0; a.n_end = a.N;
     return a.ln_s ? launch_one_ln<TM, TN, WM, WN, false, true, false, 2, ATT_D>(a, a.N, s)
                   : launch_one_ln<TM, TN, WM, WN, false, false, false, 2, ATT_D>(a, a.N, s);
+}
+
+// act 1 (ReLU epilogue): one source of truth for every tile of the plain family -- plan_gemm has kept the launch off the halo /
+// conv3x3.hip kernels, split-K and the three-stage ring
+template <int TM, int TN, int WM, int WN>
+int launch_act(GemmArgs a, hipStream_t s) {
+    a.n_begin = 0; a.n_end = a.N;
+    return launch_one_ln<TM, TN, WM, WN, false, false, false, 2, 0, true>(a, a.N, s);
 }
 
 template <int TM, int TN, int WM, int WN>
@@ -1281,6 +1295,11 @@ static int plan_gemm(const cid_gemm_desc* d, GemmArgs& a, TileCfg& cfg, bool& ha
                   "(got mode %d taps %d stride %d up %d, %d x %d -> %d x %d)", d->mode, d->taps, d->stride, d->up, d->Hi, d->Wi,
                   d->Ho, d->Wo);
     a.tap0 = d->pad_mode == 1 ? 0 : -1;
+    // act 1 (since cid_version() 102): ReLU in the plain epilogue.  Only the igemm_kernel instances carry it (launch_act);
+    // split-K (ws), the GroupNorm statistics and the LayerNorm fold are refused with it, the halo / conv3x3.hip kernels skipped.
+    CID_CHECK_ARG(d->act == 0 || d->act == 1, "cid_gemm_f16: bad act %d", d->act);
+    CID_CHECK_ARG(d->act == 0 || (d->mode == 0 && !d->gn_stats && !d->ws && !d->ln_s),
+                  "cid_gemm_f16: act 1 needs mode 0 and no gn_stats / ws / ln_s (got mode %d)", d->mode);
 
     if (d->mode == 3) {
         // query projection with the identity cross-attention as its epilogue: tiles of whole heads inside one sample
@@ -1430,7 +1449,7 @@ static int plan_gemm(const cid_gemm_desc* d, GemmArgs& a, TileCfg& cfg, bool& ha
         // workgroups) and walk enough slabs for the lookahead to matter
         static int f_nb = -1;
         if (f_nb < 0) { const char* e = getenv("CID_GEMM_NBUF"); f_nb = e ? atoi(e) : 0; }      // A/B switch: 2 = never, 3 = whenever legal
-        const bool legal = (cfg == A256x160 || cfg == B128x160 || cfg == C64x160) && d->mode != 1;
+        const bool legal = (cfg == A256x160 || cfg == B128x160 || cfg == C64x160) && d->mode != 1 && !d->act;
         const long wgs = (long)((a.M + bm - 1) / bm) * ((n_plain + bn - 1) / bn) * a.splitk;
         // (the 256-token tile holds one workgroup per CU whatever its ring: three stages whenever there are slabs to look ahead;
         //  the smaller tiles only where a third stage does not cost a co-resident workgroup)
@@ -1440,7 +1459,7 @@ static int plan_gemm(const cid_gemm_desc* d, GemmArgs& a, TileCfg& cfg, bool& ha
     static int no_halo = -1;
     if (no_halo < 0) { const char* e = getenv("CID_GEMM_NOHALO"); no_halo = e ? atoi(e) : 0; }
     halo = false;
-    if (cfg == A256x160 && !no_halo && d->mode == 0 && d->taps == 9 && d->stride == 1 && d->up == 0 && d->Wo == d->Wi &&
+    if (cfg == A256x160 && !no_halo && !d->act && d->mode == 0 && d->taps == 9 && d->stride == 1 && d->up == 0 && d->Wo == d->Wi &&
         d->Ho == d->Hi) {
         // halo kernel: the 256-token tile must be whole image rows of one image, or whole images
         const int HW = d->Ho * d->Wo;
@@ -1464,7 +1483,7 @@ static int plan_gemm(const cid_gemm_desc* d, GemmArgs& a, TileCfg& cfg, bool& ha
         const int HW = d->taps == 9 ? d->Ho * d->Wo : 0;
         // (Upsample2D's convolution, up == 1: the halo holds input pixels; a tile must be an even number of whole output rows of
         //  one image, starting on an even row)
-        const bool shape_ok = !no_h32 && d->mode == 0 && d->taps == 9 && d->stride == 1 && (d->up == 0 || d->up == 1) &&
+        const bool shape_ok = !no_h32 && !d->act && d->mode == 0 && d->taps == 9 && d->stride == 1 && (d->up == 0 || d->up == 1) &&
                               d->Wo == (d->Wi << d->up) && d->Ho == (d->Hi << d->up) && d->N % 160 == 0 && HW >= 64 &&
                               (!d->rowbias || (a.rows_per_sample >= 64 && a.rows_per_sample % 64 == 0));
         for (int bm_try = 256; shape_ok && !h32 && bm_try >= (only256 ? 256 : 128); bm_try >>= 1) {
@@ -1500,7 +1519,7 @@ extern "C" int cid_gemm_stats_rows(const cid_gemm_desc* d) {
     int bm = 0;
     if (plan_gemm(&q, a, cfg, halo, bm, h32, g32) != 0) return 0;
     const int unit = d->N / 32;
-    const bool ok = d->mode == 0 && a.splitk == 1 && (cfg == A256x160 || cfg == B128x160 || cfg == C64x160) &&
+    const bool ok = d->mode == 0 && d->act == 0 && a.splitk == 1 && (cfg == A256x160 || cfg == B128x160 || cfg == C64x160) &&
                     d->N % 32 == 0 && unit > 0 && 80 % unit == 0 && d->M % bm == 0;
     return ok ? bm : 0;
 }
@@ -1524,6 +1543,20 @@ extern "C" int cid_gemm_f16(const cid_gemm_desc* d, cid_stream_t stream) {
         if (cfg == G128x128) rc = launch_att<2, 4, 4, 2, 64>(a, s);
         else if (cfg == B128x160) rc = a.dhead == 80 ? launch_att<2, 5, 4, 2, 80>(a, s) : launch_att<2, 5, 4, 2, 160>(a, s);
         else rc = a.dhead == 80 ? launch_att<2, 5, 2, 2, 80>(a, s) : launch_att<2, 5, 2, 2, 160>(a, s);
+        if (rc) return rc;
+        CID_CHECK_LAUNCH("cid_gemm_f16");
+        return 0;
+    }
+    if (d->act) {
+        switch (cfg) {
+            case A256x160: rc = launch_act<4, 5, 4, 2>(a, s); break;
+            case B128x160: rc = launch_act<2, 5, 4, 2>(a, s); break;
+            case C64x160:  rc = launch_act<2, 5, 2, 2>(a, s); break;
+            case G256x128: rc = launch_act<4, 4, 4, 2>(a, s); break;
+            case G128x128: rc = launch_act<2, 4, 4, 2>(a, s); break;
+            case O64x64:   rc = launch_act<2, 2, 2, 2>(a, s); break;
+            case O128x32:  rc = launch_act<2, 2, 4, 1>(a, s); break;
+        }
         if (rc) return rc;
         CID_CHECK_LAUNCH("cid_gemm_f16");
         return 0;

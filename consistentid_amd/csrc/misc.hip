@@ -15,7 +15,7 @@ void cid_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* cid_last_error(void) { return g_err; }
-extern "C" int cid_version(void) { return 101; }   // 101: cid_gemm_desc.pad_mode
+extern "C" int cid_version(void) { return 102; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act
 
 namespace {
 

@@ -45,7 +45,7 @@ def gemm(x1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
          taps: int = 1, Hi: int = 0, Wi: int = 0, Ho: int = 0, Wo: int = 0, stride: int = 1, up: int = 0,
          mode: int = 0, vt: Optional[torch.Tensor] = None, n_vt0: int = 0, heads: int = 0, dhead: int = 0,
          ntok: int = 0, ws: Optional[torch.Tensor] = None, ln=None, gn_hw: int = 0, att=None,
-         out2: Optional[torch.Tensor] = None, pad_mode: int = 0):
+         out2: Optional[torch.Tensor] = None, pad_mode: int = 0, act: int = 0):
     """``att`` = (kp, vp, kvrow, n_txt, n_ip, ip_scale) with ``mode=3``: the query projection of the identity cross-attention
     with the two-stream attention as its epilogue (``heads``, ``dhead``, ``ntok`` describe the heads and the tokens per sample).
     ``ln`` = (s, b, eps): LayerNorm folded into the projection -- ``x1`` is the raw residual stream, ``w`` carries gamma,
@@ -55,7 +55,8 @@ def gemm(x1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
     ``groupnorm`` to pick up (saves its statistics pass).
     ``out2``: a second destination for the same rows (same pitch as ``out``; mode 0): the CFG duplication of a tensor both
     halves of the batch share, written by the producer.
-    ``pad_mode=1``: Downsample2D(padding=0) -- pad (0, 1, 0, 1), then the stride-2 3x3 conv without padding."""
+    ``pad_mode=1``: Downsample2D(padding=0) -- pad (0, 1, 0, 1), then the stride-2 3x3 conv without padding.
+    ``act=1``: ReLU after bias / rowbias / res (mode 0; not with ``ws``, ``ln`` or ``gn_hw``)."""
     lib = _lib.load()
     for name, t in (("x1", x1), ("w", w), ("out", out)):
         _req(t, f"gemm.{name}")
@@ -79,6 +80,7 @@ def gemm(x1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
     d.M, d.N, d.taps = M, N, taps
     d.Hi, d.Wi, d.Ho, d.Wo, d.stride, d.up = Hi, Wi, Ho, Wo, stride, up
     d.pad_mode = pad_mode
+    d.act = act
     d.mode = mode
     d.vt, d.n_vt0, d.heads, d.dhead, d.dvp, d.ntok = _p(vt), n_vt0, heads, dhead, dvp_of(dhead) if dhead else 0, ntok
     if ws is not None:
@@ -96,7 +98,7 @@ def gemm(x1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
         _req(lb, "gemm.ln_b", torch.float32)
         d.ln_s, d.ln_b, d.ln_eps = ls.data_ptr(), lb.data_ptr(), float(eps)
     stats = None
-    if gn_hw > GN_SMALL_MAX_HW and GN_EPILOGUE_STATS:      # (smaller samples: cid_groupnorm_f16 is one launch anyway)
+    if gn_hw > GN_SMALL_MAX_HW and GN_EPILOGUE_STATS and not act:      # (smaller samples: cid_groupnorm_f16 is one launch anyway)
         rows = int(lib.cid_gemm_stats_rows(C.byref(d)))
         if rows > 0 and gn_hw % rows == 0:
             stats = torch.empty(M // rows, 32, 2, dtype=torch.float32, device=out.device)
@@ -472,6 +474,75 @@ def vae_encode_out(x: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: to
     check(lib.cid_vae_encode_out_f16(_p(x), _p(out), _p(moments), _p(w), _p(bias), _p(eps), B, H, W, cin, L, float(scale),
                                      _stream()), "cid_vae_encode_out_f16")
     return out
+
+
+# --------------------------------------------------------------------------- face parser (csrc/parsing.hip)
+def parse_stem(img: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: torch.Tensor):
+    """BiSeNet stem (cid_parse_stem_f16): ``img`` uint8 [B, H, W, 3] -> ImageNet normalisation -> conv 7x7/2 (fp32 ``w``
+    [64, 7, 7, 3], BN folded, fp32 ``bias`` [64]) -> ReLU -> maxpool 3x3/2 -> ``out`` fp16 [B, H/4 * W/4, 64]."""
+    lib = _lib.load()
+    _req(img, "parse_stem.img", torch.uint8)
+    _req(out, "parse_stem.out")
+    _req(w, "parse_stem.w", torch.float32)
+    _req(bias, "parse_stem.bias", torch.float32)
+    B, H, W, _ = img.shape
+    check(lib.cid_parse_stem_f16(_p(img), _p(out), _p(w), _p(bias), B, H, W, _stream()), "cid_parse_stem_f16")
+    return out
+
+
+def chan_mean(x: torch.Tensor, out: torch.Tensor, *, B: int, HW: int, C_: int, ld: Optional[int] = None):
+    """fp32 ``out`` [B, C] = the mean over the HW tokens of ``x`` [B, HW, ld] (cid_chan_mean_f16)."""
+    lib = _lib.load()
+    _req(x, "chan_mean.x")
+    _req(out, "chan_mean.out", torch.float32)
+    check(lib.cid_chan_mean_f16(_p(x), _p(out), B, HW, C_, ld if ld is not None else C_, _stream()), "cid_chan_mean_f16")
+    return out
+
+
+def chan_gate(mean: torch.Tensor, out: torch.Tensor, w1: torch.Tensor, b1: Optional[torch.Tensor] = None,
+              w2: Optional[torch.Tensor] = None, b2: Optional[torch.Tensor] = None, *, act: int):
+    """fp32 ``out`` [B, N] = act(W1 m + b1), or act(W2 ReLU(W1 m + b1) + b2) with ``w2``; act 0 none, 1 ReLU, 2 sigmoid
+    (cid_chan_gate_f32).  Every tensor fp32, weights [out, in]."""
+    lib = _lib.load()
+    for name, t in (("mean", mean), ("out", out), ("w1", w1), ("b1", b1), ("w2", w2), ("b2", b2)):
+        if t is not None:
+            _req(t, f"chan_gate.{name}", torch.float32)
+    B, K = mean.shape
+    N1 = w1.shape[0]
+    N = w2.shape[0] if w2 is not None else N1
+    check(lib.cid_chan_gate_f32(_p(mean), _p(out), _p(w1), _p(b1), _p(w2), _p(b2), B, K, N1, N, act, _stream()),
+          "cid_chan_gate_f32")
+    return out
+
+
+def chan_affine(x: torch.Tensor, s: torch.Tensor, out: torch.Tensor, *, B: int, HW: int, C_: int,
+                t: Optional[torch.Tensor] = None, res: Optional[torch.Tensor] = None):
+    """``out`` = x * s[b][c] + (t[b][c] | res | x) (cid_chan_affine_f16); ``s`` / ``t`` fp32 [B, C]."""
+    lib = _lib.load()
+    _req(x, "chan_affine.x")
+    _req(out, "chan_affine.out")
+    _req(s, "chan_affine.s", torch.float32)
+    if t is not None:
+        _req(t, "chan_affine.t", torch.float32)
+    if res is not None:
+        _req(res, "chan_affine.res")
+    check(lib.cid_chan_affine_f16(_p(x), _p(s), _p(t), _p(res), _p(out), B, HW, C_, _stream()), "cid_chan_affine_f16")
+    return out
+
+
+def parse_head(logits: torch.Tensor, labels: torch.Tensor, *, ncls: int, B: int, h: int, w: int, H: int, W: int,
+               ld: Optional[int] = None, logits_out: Optional[torch.Tensor] = None):
+    """bilinear (align_corners=True) upsampling of ``logits`` fp16 [B, h * w, ld] to H x W and the first-maximum argmax over
+    the first ``ncls`` channels -> ``labels`` uint8 [B, H, W]; ``logits_out`` fp32 [B, ncls, H, W] or None
+    (cid_parse_head_f16)."""
+    lib = _lib.load()
+    _req(logits, "parse_head.logits")
+    _req(labels, "parse_head.labels", torch.uint8)
+    if logits_out is not None:
+        _req(logits_out, "parse_head.logits_out", torch.float32)
+    check(lib.cid_parse_head_f16(_p(logits), ld if ld is not None else logits.shape[-1], ncls, B, h, w, H, W, _p(labels),
+                                 _p(logits_out), _stream()), "cid_parse_head_f16")
+    return labels
 
 
 def sincos_embed(v: torch.Tensor, out: torch.Tensor, *, rows: int, dim: int):

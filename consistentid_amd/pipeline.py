@@ -11,11 +11,13 @@ encode of the inpaint pipelines (``image=`` / ``mask_image=`` with ``vae_encoder
 through ``image=``, where the reference reads ``input_id_images[0]``).
 Prompt strings are encoded by ``encode_prompt`` / ``_encode_prompt`` / ``encode_prompt_with_trigger_word`` on the HIP
 text towers (``text_encoder=`` / ``text_encoder_2=``, clip_text.py; prompt_encode.py), the ID tokens by
-``prepare_prompt_embeds``.  FaceID and face parsing stay outside, so ``__call__`` takes what the pre-loop produces:
+``prepare_prompt_embeds``.  The SD1.5 pipeline also runs the reference's whole pre-loop (``prepare_id_prompt_embeds``:
+the caller's FaceID app, HipBiSeNet face parsing, the facial crops, the CLIP vision tower) for ``prompt`` +
+``input_id_images``; every ``__call__`` also takes what the pre-loop produces:
 ``prompt_embeds`` = cat([null, augmented, text_only]) of shape [3B, 77+4, Dc] exactly as the
 reference assembles it before ``.chunk(3)`` (ref :494-507, :527-531), and ``latents``.
-String prompts / ID images raise NotImplementedError naming the missing component instead of silently doing
-something else; ``output_type`` other than "latent" needs the pipeline to be built with ``vae=HipVAEDecoder(...)``.
+Elsewhere (SDXL, inpaint), and in SD1.5 without its pre-loop components, string prompts / ID images raise
+NotImplementedError naming what is missing instead of silently doing something else; ``output_type`` other than "latent" needs the pipeline to be built with ``vae=HipVAEDecoder(...)``.
 
 B > 1 is this framework's extension (the reference is effectively B = 1 per call,
 SURVEY.md Appendix B): B independent samples, each with its own CFG pair.
@@ -299,11 +301,34 @@ class _BasePipeline:
     def load_ConsistentID_model(self, pretrained_model_name_or_path_or_dict, weight_name: str = "", subfolder: str = "",
                                 trigger_word_ID: str = "<|image|>", trigger_word_facial: str = "<|facial|>",
                                 image_encoder_path: str = "", bise_net_cp: str = "", torch_dtype=torch.float16,
-                                num_tokens: int = 4, lora_rank: int = 128, **kwargs):
+                                num_tokens: int = 4, lora_rank: int = 128, face_app=None, **kwargs):
         """Reference: pipline_StableDiffusion_ConsistentID.py:36-150.  The ``adapter_modules`` entry of the checkpoint
         (dict, ``.bin`` or ``.safetensors`` path; local files only) is merged into the engine in place -- the UNet must
         have been built with ``keep_base=True``.  FacialEncoder / image_proj weights build the ID-conditioning engine
-        (``prepare_prompt_embeds``, row f-3); CLIP / FaceAnalysis / BiSeNet construction (ref :54-69) is not done here."""
+        (``prepare_prompt_embeds``, row f-3).
+        ``image_encoder_path``: a local transformers CLIPVisionModelWithProjection folder (config.json + weights) ->
+        ``self.image_encoder`` (HipCLIPVision, ref :54-56).  ``bise_net_cp``: a ``face_parsing.pth`` file (or its state dict)
+        -> ``self.bise_net`` (HipBiSeNet, ref :67-71).  ``face_app``: the FaceID model, any object with insightface's
+        ``get(np.ndarray RGB image) -> [face, ...]`` whose faces carry ``normed_embedding`` (ref :58-59, :216-226) ->
+        ``self.app``.  Empty strings / None leave a component out; a path that does not exist raises FileNotFoundError
+        (hub ids are never resolved)."""
+        for what, path in (("image_encoder_path", image_encoder_path), ("bise_net_cp", bise_net_cp)):
+            if isinstance(path, (str, os.PathLike)) and os.fspath(path) and not os.path.exists(path):
+                raise FileNotFoundError(f"{what}: {os.fspath(path)!r} does not exist (local paths only, hub ids are not resolved)")
+        self.image_encoder = self.bise_net = None
+        if image_encoder_path:
+            from . import loader
+            from .clip_vision import HipCLIPVision
+            cfg, sd = loader.read_component(image_encoder_path, loader.TEXT_WEIGHT_NAMES)
+            self.image_encoder = HipCLIPVision(sd, num_heads=cfg["num_attention_heads"], patch_size=cfg.get("patch_size", 14),
+                                               device=self.device, hidden_act=cfg.get("hidden_act", "gelu"),
+                                               layer_norm_eps=cfg.get("layer_norm_eps", 1e-5))
+            self.clip_image_size = int(cfg.get("image_size", 224))
+        if isinstance(bise_net_cp, dict) or bise_net_cp:
+            from .face_parsing import HipBiSeNet
+            sd = bise_net_cp if isinstance(bise_net_cp, dict) else torch.load(bise_net_cp, map_location="cpu", weights_only=True)
+            self.bise_net = HipBiSeNet(sd, n_classes=19, device=self.device)
+        self.app = face_app
         from .checkpoint import load_checkpoint
         state_dict = load_checkpoint(pretrained_model_name_or_path_or_dict, weight_name, subfolder)
         self.lora_rank, self.num_tokens, self.torch_dtype = lora_rank, num_tokens, torch_dtype
@@ -337,9 +362,9 @@ class _BasePipeline:
     def _check_hot_path_inputs(self, prompt, input_id_images, prompt_embeds, latents, output_type):
         if prompt is not None or input_id_images is not None:
             raise NotImplementedError(
-                "__call__(prompt=..., input_id_images=...) needs FaceID and face parsing (ref :437-465), which are outside "
-                "this project's scope (SURVEY.md 8f-3): encode the text with encode_prompt_with_trigger_word / "
-                "encode_prompt, build prompt_embeds=[3B,81,Dc] with prepare_prompt_embeds and pass it with latents")
+                f"{type(self).__name__}.__call__(prompt=..., input_id_images=...) is built for the SD1.5 pipeline only "
+                "(ConsistentIDStableDiffusionPipeline): encode the text with encode_prompt_with_trigger_word / "
+                "encode_prompt, build prompt_embeds with prepare_prompt_embeds and pass it with latents")
         if prompt_embeds is None or latents is None:
             raise ValueError("prompt_embeds (cat([null, augmented, text_only])) and latents are required")
         if output_type != "latent" and self.vae is None:
@@ -401,7 +426,125 @@ class _SD15PromptEncoding:
                                                facial_token, max_num_facials, num_id_images)
 
 
-class ConsistentIDStableDiffusionPipeline(_SD15PromptEncoding, _BasePipeline):
+class _IDPreLoop:
+    """The SD1.5 reference's pre-loop (pipline_StableDiffusion_ConsistentID.py:177-376, :437-507): FaceID (the caller's
+    ``face_app``), face parsing (HipBiSeNet), the facial crops and the CLIP vision tower (HipCLIPVision), then the
+    ID-conditioning modules (HipIDConditioner).  Public methods keep the reference's names and return values."""
+
+    FACE_CAPTION = "The person has one face, one nose, two eyes, two ears, and one mouth."   # ref :283
+    PARSE_SIZE = 512
+
+    def _missing_id_components(self) -> List[str]:
+        need = (("FaceID app (load_ConsistentID_model(face_app=...))", getattr(self, "app", None)),
+                ("BiSeNet (bise_net_cp=)", getattr(self, "bise_net", None)),
+                ("image encoder (image_encoder_path=)", getattr(self, "image_encoder", None)),
+                ("ID weights (image_proj + FacialEncoder)", getattr(self, "id_conditioner", None)),
+                ("text encoder", self.text_encoder), ("tokenizer", self.tokenizer))
+        return [name for name, v in need if v is None]
+
+    def get_prepare_faceid(self, face_image) -> torch.Tensor:
+        """ref :216-226: the first face's ``normed_embedding`` [1, 512], zeros when the app finds no face"""
+        faces = self.app.get(np.array(face_image))
+        if len(faces) == 0:
+            return torch.zeros(1, 512)
+        return torch.from_numpy(np.asarray(faces[0].normed_embedding)).unsqueeze(0)
+
+    def get_prepare_llva_caption(self, input_image_file, model_path=None, prompt=None) -> str:
+        """ref :265-287: the reference's built-in template (its LLaVA call is commented out)"""
+        return self.FACE_CAPTION
+
+    def parsing_face_mask(self, raw_image_refer):
+        """ref :229-262 -> (colour overlay uint8 [512, 512, 3] (BGR blend), label map uint8 [512, 512])"""
+        from PIL import Image
+        from .face_prep import parsing_overlay
+        image = raw_image_refer.convert("RGB").resize((self.PARSE_SIZE, self.PARSE_SIZE), Image.BILINEAR)
+        labels = self.bise_net(image, size=None)[0].cpu().numpy()
+        return parsing_overlay(np.asarray(image), labels), labels
+
+    def get_prepare_facemask(self, input_image_file):
+        """ref :289-309 -> (key_parsing_mask_list, colour overlay)"""
+        from .face_prep import masks_for_unique_values, select_face_masks
+        overlay, labels = self.parsing_face_mask(input_image_file)
+        return select_face_masks(masks_for_unique_values(labels)), overlay
+
+    def get_prepare_clip_image(self, input_image_file, key_parsing_mask_list, image_size: int = 512,
+                               max_num_facials: int = 5, change_facial: bool = True):
+        """ref :350-376 -> (facial_clip_image [max_num_facials, 3, 224, 224] fp32, facial_mask [max_num_facials, S, S]); the
+        part masks come from the 512 x 512 label map, so the reference's CenterCrop(image_size) keeps them whole"""
+        from .face_prep import clip_preprocess, fetch_mask_raw_image
+        clips, masks = [], []
+        for key in key_parsing_mask_list:
+            m = key_parsing_mask_list[key]
+            a = np.asarray(m, dtype=np.float32) / 255
+            if a.shape != (image_size, image_size):
+                raise ValueError(f"facial mask {key!r} is {a.shape}, expected {image_size} x {image_size}")
+            masks.append(torch.from_numpy(a))
+            clips.append(torch.from_numpy(clip_preprocess(fetch_mask_raw_image(input_image_file, m))))
+        n = len(clips)
+        clips += [torch.zeros(3, 224, 224) for _ in range(max_num_facials - n)]
+        masks += [torch.zeros(image_size, image_size) for _ in range(max_num_facials - n)]
+        return torch.stack(clips), torch.stack(masks)
+
+    def _clip_hidden(self, pixel_values: torch.Tensor) -> torch.Tensor:
+        return self.image_encoder.hidden_states(pixel_values.to(self.device, torch.float16), -2)
+
+    def get_image_embeds(self, faceid_embeds, face_image, s_scale: float, shortcut: bool = False):
+        """ref :197-209 -> (prompt tokens, uncond prompt tokens) of ProjPlusModel"""
+        from .face_prep import clip_preprocess
+        pix = torch.from_numpy(clip_preprocess(face_image))[None]
+        hs = self._clip_hidden(torch.cat([pix, torch.zeros_like(pix)]))
+        ip = self.id_conditioner.image_proj_model
+        fid = faceid_embeds.to(self.device, torch.float16)
+        return (ip(fid, hs[:1], shortcut=shortcut, scale=s_scale),
+                ip(torch.zeros_like(fid), hs[1:], shortcut=shortcut, scale=s_scale))
+
+    def get_facial_embeds(self, prompt_embeds, negative_prompt_embeds, facial_clip_images, facial_token_masks,
+                          valid_facial_token_idx_mask):
+        """ref :177-195 -> (facial prompt embeds, uncond facial prompt embeds); facial_clip_images [B, n, 3, 224, 224]"""
+        B, n = facial_clip_images.shape[:2]
+        hs = self._clip_hidden(torch.cat([facial_clip_images.reshape(B * n, *facial_clip_images.shape[2:]),
+                                          torch.zeros_like(facial_clip_images[0, :1])]))
+        emb = hs[:B * n].reshape(B, n, *hs.shape[1:])
+        uncond = hs[B * n:].expand(B * n, *hs.shape[1:]).reshape(B, n, *hs.shape[1:])
+        fe = self.id_conditioner.FacialEncoder
+        return (fe(prompt_embeds, emb, facial_token_masks, valid_facial_token_idx_mask),
+                fe(negative_prompt_embeds, uncond, facial_token_masks, valid_facial_token_idx_mask))
+
+    def prepare_id_prompt_embeds(self, prompt: str, input_id_images, negative_prompt=None) -> torch.Tensor:
+        """``prompt_embeds`` [3, 77 + num_tokens, Dc] = cat([null, augmented, text_only]) of ONE prompt and its ID images,
+        assembled as ref :437-507 does.  The CLIP tower runs each distinct image once: the face, its real crops and one zero
+        image, whose hidden states stand for every padded crop and every uncond input."""
+        missing = self._missing_id_components()
+        if missing:
+            raise NotImplementedError("prompt + input_id_images need: " + ", ".join(missing))
+        if not isinstance(prompt, str):
+            raise NotImplementedError("one prompt string per call (the reference breaks on lists, SURVEY.md Appendix B)")
+        images = input_id_images if isinstance(input_id_images, list) else [input_id_images]
+        img = images[0]                                                                    # ref :436
+        dev = self.device
+        faceid = self.get_prepare_faceid(img)                                              # :438
+        caption = self.get_prepare_llva_caption(img)
+        masks, _ = self.get_prepare_facemask(img)
+        text_only, clean_ids, masks_align, fmask, _, fidx_mask = self.encode_prompt_with_trigger_word(
+            prompt, caption, masks, max_num_facials=5, num_id_images=len(images))           # :445-458
+        text_embeds = self.text_encoder(clean_ids.to(dev))[0]                               # :467
+        both = self._encode_prompt(text_only, dev, 1, True, negative_prompt)               # :469-477
+        neg, pos = both[:1], both[1:]
+        from .face_prep import clip_preprocess
+        crops, _ = self.get_prepare_clip_image(img, masks_align, image_size=512, max_num_facials=5)    # :482
+        n = len(masks_align)
+        pix = torch.cat([torch.from_numpy(clip_preprocess(img))[None], crops[:n], torch.zeros(1, 3, 224, 224)])
+        hs = self._clip_hidden(pix)
+        face_hs, crop_hs, zero_hs = hs[:1], hs[1:1 + n], hs[1 + n:]
+        facial = torch.cat([crop_hs, zero_hs.expand(5 - n, *zero_hs.shape[1:])])[None]
+        return self.id_conditioner(
+            text_embeds=text_embeds, negative_embeds=neg, text_only_embeds=pos, faceid_embeds=faceid,
+            clip_embeds=face_hs, uncond_clip_embeds=zero_hs, facial_embeds=facial,
+            uncond_facial_embeds=zero_hs.expand(5, *zero_hs.shape[1:])[None], facial_token_mask=fmask.to(dev),
+            valid_facial_mask=fidx_mask.to(dev))
+
+
+class ConsistentIDStableDiffusionPipeline(_IDPreLoop, _SD15PromptEncoding, _BasePipeline):
     def __call__(self, prompt=None, height: Optional[int] = None, width: Optional[int] = None,
                  num_inference_steps: int = 50, guidance_scale: float = 5.0, negative_prompt=None,
                  num_images_per_prompt: Optional[int] = 1, eta: float = 0.0, generator=None,
@@ -410,6 +553,28 @@ class ConsistentIDStableDiffusionPipeline(_SD15PromptEncoding, _BasePipeline):
                  cross_attention_kwargs=None, original_size=None, target_size=None, callback=None,
                  callback_steps: int = 1, input_id_images=None, start_merge_step: int = 0,
                  class_tokens_mask=None, prompt_embeds_text_only=None):
+        """``pipe(prompt, input_id_images=[face], ...)`` runs the reference's pre-loop (prepare_id_prompt_embeds) and, without
+        ``latents``, draws them like diffusers' prepare_latents (randn_tensor on the generator's device); or pass
+        ``prompt_embeds`` (cat([null, augmented, text_only])) and ``latents`` directly."""
+        if prompt is not None or input_id_images is not None:
+            missing = self._missing_id_components()
+            if missing:
+                raise NotImplementedError("__call__(prompt=..., input_id_images=...) needs: " + ", ".join(missing)
+                                          + "; or build prompt_embeds with prepare_prompt_embeds and pass it with latents")
+            if prompt is None or input_id_images is None:
+                raise ValueError("prompt and input_id_images go together (ref :434-438)")
+            if prompt_embeds is not None:
+                raise ValueError("give either prompt + input_id_images or prompt_embeds, not both")
+            if num_images_per_prompt != 1:
+                raise NotImplementedError("num_images_per_prompt > 1 (the reference breaks on it, SURVEY.md Appendix B)")
+            prompt_embeds = self.prepare_id_prompt_embeds(prompt, input_id_images, negative_prompt)
+            if latents is None:
+                from .vae import randn_tensor
+                height = height or self.unet.config.sample_size * self.vae_scale_factor
+                width = width or self.unet.config.sample_size * self.vae_scale_factor
+                shape = (1, self.unet.in_channels, height // self.vae_scale_factor, width // self.vae_scale_factor)
+                latents = randn_tensor(shape, generator=generator, device=self.device, dtype=torch.float16)   # ref :517-526
+            prompt = input_id_images = None
         self._check_hot_path_inputs(prompt, input_id_images, prompt_embeds, latents, output_type)
         assert guidance_scale >= 1.0, "the reference asserts classifier-free guidance (ref :434,:441)"
         assert eta == 0.0, "DDIM eta = 0 only"

@@ -27,7 +27,7 @@ extern "C" {
 typedef void* cid_stream_t;      /* hipStream_t */
 typedef uint16_t cid_half;       /* IEEE binary16 bit pattern */
 
-int cid_version(void);          /* 101: cid_gemm_desc grew a trailing pad_mode field (101 and later: set it or zero the struct) */
+int cid_version(void);          /* 102: cid_gemm_desc grew a trailing act field (101: pad_mode; set them or zero the struct) */
 const char* cid_last_error(void);
 
 /* ---------------------------------------------------------------------------
@@ -99,6 +99,13 @@ typedef struct cid_gemm_desc {
      *      without padding: output (y, x) reads input (2y + dy, 2x + dx), dy, dx in {0, 1, 2}; row Hi and column Wi read as
      *      zero.  Only with mode 0, taps 9, stride 2, up 0, even Hi / Wi, Ho = Hi / 2, Wo = Wi / 2 (else -22); split-K allowed. */
     int32_t pad_mode;
+    /* Activation of the plain epilogue (since cid_version() 102, which grew the struct by this field):
+     *   0: none (a zero-initialised descriptor keeps it);
+     *   1: ReLU after bias + rowbias + res, before the fp16 rounding and the stores (out and out2) -- the ConvBNReLU /
+     *      BasicBlock `F.relu(bn(conv(x)) [+ shortcut])` of the face parser (models/BiSeNet/model.py:26-29, resnet.py:36-48,
+     *      run once per image by pipline_StableDiffusion_ConsistentID.py:243).  Mode 0 only, without gn_stats, ws
+     *      (split-K) or ln_s (else -22); the launch runs on the gather kernels of every tile width. */
+    int32_t act;
 } cid_gemm_desc;
 int cid_gemm_f16(const cid_gemm_desc* d, cid_stream_t stream);
 /* Token rows per statistics block if cid_gemm_f16(d) can emit gn_stats (its tile height), 0 if it cannot (split-K,
@@ -332,6 +339,39 @@ int cid_vae_encode_in_f16(const float* image, int32_t Bi, const float* mask, int
 int cid_vae_encode_out_f16(const cid_half* x, cid_half* out, float* moments, const cid_half* w, const float* bias,
                            const cid_half* eps, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t L, float scale,
                            cid_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Face parser (csrc/parsing.hip): BiSeNet (models/BiSeNet/model.py:230-254, resnet.py:58-80) as the reference runs it, once
+ * per reference image: `self.bise_net(img)[0]` on a 512 x 512 resize (pipline_StableDiffusion_ConsistentID.py:229-244).
+ * Its convolutions are cid_gemm_f16 calls (BatchNorm folded into W and bias on the host, ReLU = cid_gemm_desc.act 1; the
+ * 1x1 stride-2 shortcut is a taps-9 stride-2 conv whose weight is zero outside the centre tap); these fill the gaps.
+ *   cid_parse_stem_f16  resnet.py:72-74 with ToTensor + Normalize((0.485, 0.456, 0.406), (0.229, 0.224, 0.225)) of
+ *                       :231-234 in front: img uint8 NHWC [B][H][W][3] -> (x / 255 - mean) / std -> conv 7x7 / 2 pad 3
+ *                       (zero padding of the normalised image; w fp32 [64][7][7][3] = [out][ky][kx][rgb], BN folded;
+ *                       bias fp32 [64]) -> ReLU -> maxpool 3x3 / 2 pad 1 -> token-major fp16 [B][(H / 4) (W / 4)][64].
+ *                       H, W multiples of 32; 1 <= B <= 16383 (four workgroup layers per image).
+ *   cid_chan_mean_f16   F.avg_pool2d(x, x.size()[2:]) (model.py:78, :111, :203): out fp32 [B][C] = mean over the HW tokens
+ *                       of x [B][HW][ld] (first C channels); C % 8 == 0, ld % 8 == 0.
+ *   cid_chan_gate_f32   the 1x1 convolutions on those means, one launch: y = W1 m (+ b1) (W1 fp32 [N1][K]); with w2:
+ *                       y = W2 ReLU(y) (+ b2) (W2 fp32 [N][N1], FFM conv1 / relu / conv2, model.py:204-206); then
+ *                       act 0 none, 1 ReLU (conv_avg, :112), 2 sigmoid (ARM conv_atten / bn_atten, :79-81; FFM :207).
+ *                       out fp32 [B][N]; K, N1, N <= 512; N == N1 without w2.
+ *   cid_chan_affine_f16 out[b][p][c] = x[b][p][c] * s[b][c] + add, add = t[b][c] (fp32 [B][C], ARM32 + conv_avg: :82,
+ *                       :115), res[b][p][c] (ARM16 + feat32_up: :120) or x itself when both are NULL (FFM :208-209);
+ *                       fp32 math, rounded once; [B][HW][C] contiguous, C % 8 == 0; out may be x.
+ *   cid_parse_head_f16  F.interpolate(logits, (H, W), mode='bilinear', align_corners=True) (model.py:251) in fp32, then
+ *                       the first-maximum argmax over the classes (numpy's `.argmax(0)`, :244 of the pipeline): logits
+ *                       fp16 [B][h * w][ld] (the first ncls channels), labels uint8 [B][H][W]; logits_out (or NULL) fp32
+ *                       NCHW [B][ncls][H][W], the upsampled logits (the reference's `out`).  ncls <= min(ld, 256). */
+int cid_parse_stem_f16(const uint8_t* img, cid_half* out, const float* w, const float* bias, int32_t B, int32_t H, int32_t W,
+                       cid_stream_t stream);
+int cid_chan_mean_f16(const cid_half* x, float* out, int32_t B, int32_t HW, int32_t C, int32_t ld, cid_stream_t stream);
+int cid_chan_gate_f32(const float* mean, float* out, const float* w1, const float* b1, const float* w2, const float* b2,
+                      int32_t B, int32_t K, int32_t N1, int32_t N, int32_t act, cid_stream_t stream);
+int cid_chan_affine_f16(const cid_half* x, const float* s, const float* t, const cid_half* res, cid_half* out, int32_t B,
+                        int32_t HW, int32_t C, cid_stream_t stream);
+int cid_parse_head_f16(const cid_half* logits, int32_t ld, int32_t ncls, int32_t B, int32_t h, int32_t w, int32_t H,
+                       int32_t W, uint8_t* labels, float* logits_out, cid_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Timestep path (D: get_timestep_embedding flip_sin_to_cos, TimestepEmbedding,
