@@ -39,6 +39,7 @@ class GemmDesc(C.Structure):
         ("out2", C.c_void_p),
         ("pad_mode", C.c_int32),
         ("act", C.c_int32),
+        ("w_up4", C.c_void_p),
     ]
 
 
@@ -53,6 +54,7 @@ SIGNATURES = {
     "cid_last_error": (C.c_char_p, []),
     "cid_gemm_f16": (C.c_int, [C.POINTER(GemmDesc), c_stream]),
     "cid_gemm_stats_rows": (C.c_int, [C.POINTER(GemmDesc)]),
+    "cid_upconv_fold_f16": (C.c_int, [c_half_p, c_half_p, C.c_int32, C.c_int32, c_stream]),
     "cid_self_attn_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 8 + [c_stream]),
     "cid_self_attn_keys_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 9 + [c_stream]),
     "cid_self_attn_causal_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 9 + [c_stream]),

@@ -54,10 +54,24 @@ typedef __attribute__((address_space(3))) void lds_void;
 
 CID_DEVINL int key(int r) { return (r >> 1) & 7; }
 
-template <int TM>
+// NT = 9: the convolution as written above.  NT = 4: the PHASE mode for Upsample2D (a.w4) -- after a nearest
+// 2x upsample the three taps along an axis touch two input rows / columns, so the outputs of one parity (Y & 1, X & 1) are a
+// 2x2 convolution of the INPUT image with summed taps (cid_upconv_fold_f16: W4[parity][n][2 ry + rx][c]).  A tile is BM input
+// pixels (whole input rows of one image) whose BM outputs of ONE parity it computes: the loaders stage an input-resolution
+// halo exactly as for up == 0, tap (ry, rx) reads halo row + (ry + py - 1, rx + px - 1), four slabs per channel slab instead
+// of nine, and the epilogue stores tile row (y, x) to output pixel (2 y + py, 2 x + px).  Tiles are numbered (image, parity,
+// block): an image owns H W / BM consecutive statistics blocks as before.
+template <int TM, int NT>
 __global__ void __launch_bounds__(512, 1)
 conv_h32_kernel(GemmArgs a) {
 #if defined(__HIP_DEVICE_COMPILE__)
+    constexpr bool PH = NT == 4;
+    // channel slabs per trip of the (unrolled) slab loop: the ring stage of slab k is k % NSTG, a compile-time number only if
+    // a trip covers a multiple of NSTG slabs -- one channel slab of nine taps, three of four
+    constexpr int U = (NT % 3 == 0) ? 1 : 3;
+    // halo piece slots per window: the halo of the next channel slab is issued in windows 0 .. NT - 3 (the counted wait in
+    // front of the barrier that publishes it lets the issues of the last two windows fly)
+    constexpr int HPW = (HQ + NT - 3) / (NT - 2);
     constexpr int BM = 128 * TM;
     constexpr int RQ = BM * 20 / 256;            // residual row chunks (16 B) per loader lane
     constexpr int NSEG = BM / 32;                // 32-token segments of the tile (GroupNorm statistics)
@@ -71,14 +85,22 @@ conv_h32_kernel(GemmArgs a) {
     int nb_, mb_;
     cidg::xcd_tile(a, nb_, mb_);                  // XCD-aware tile order (gemm_args.h)
     const int n0 = nb_ * BN;
-    const int m0 = mb_ * BM;
-    const int W = a.Wo, H = a.Ho, HW = H * W;
+    // phase mode: the geometry below is that of the INPUT image (up = 0), m0 the first input pixel of the tile
+    const int W = PH ? a.Wi : a.Wo, H = PH ? a.Hi : a.Ho, HW = H * W;
+    int m0 = mb_ * BM, par = 0;
+    if constexpr (PH) {
+        const int tpp = HW / BM;                  // tiles per image and parity
+        const int img = mb_ / (4 * tpp), r = mb_ - img * 4 * tpp;
+        par = r / tpp;
+        m0 = (img * tpp + (r - par * tpp)) * BM;
+    }
+    const int py = par >> 1, px = par & 1;
     const int seg_tok = BM < HW ? BM : HW;
     const int rs = seg_tok / W;
     // up = 1 (Upsample2D: nearest-2x, then the convolution): the halo holds INPUT pixels -- output pixel (y, x), tap (ty, tx)
     // reads input pixel ((y + ty - 1) >> 1, (x + tx - 1) >> 1) -- rs / 2 + 2 input rows of Wi + 2 columns per tile (a tile is
     // whole output rows of one image there: plan_gemm)
-    const int up = a.up;
+    const int up = PH ? 0 : a.up;
     const int Wi = W >> up, Hi = H >> up;
     const int hs = ((rs >> up) + 2) * (Wi + 2);
     const int nh = (BM / seg_tok) * hs;
@@ -107,7 +129,8 @@ conv_h32_kernel(GemmArgs a) {
         const __amdgpu_buffer_rsrc_t rs_x1 = __builtin_amdgcn_make_buffer_rsrc((void*)a.x1, 0, a.bytes_x1, 0x00020000);
         const __amdgpu_buffer_rsrc_t rs_x2 = __builtin_amdgcn_make_buffer_rsrc((void*)(a.x2 ? a.x2 : a.x1), 0,
                                                                                a.x2 ? a.bytes_x2 : 0, 0x00020000);
-        const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.bytes_w, 0x00020000);
+        const __amdgpu_buffer_rsrc_t rs_w = PH ? __builtin_amdgcn_make_buffer_rsrc((void*)a.w4, 0, (unsigned)a.N * ctot * 32u, 0x00020000)
+                                               : __builtin_amdgcn_make_buffer_rsrc((void*)a.w, 0, a.bytes_w, 0x00020000);
         half8 resv[RQ];
         unsigned hoff1[HQ], hoff2[HQ], woff[WQ];
 #pragma unroll
@@ -117,7 +140,7 @@ conv_h32_kernel(GemmArgs a) {
             const int hy = rem / (Wi + 2), hx = rem - hy * (Wi + 2);
             const int img = img0 + seg;
             const int yy = (y0 >> up) + hy - 1, xx = hx - 1;          // input pixel of halo row hr
-            const bool ok = (hr < nh) && (yy >= 0) && (yy < Hi) && (xx >= 0) && (xx < Wi) && ((long)img * HW < a.M);
+            const bool ok = (hr < nh) && (yy >= 0) && (yy < Hi) && (xx >= 0) && (xx < Wi) && ((long)img * HW < (PH ? a.M >> 2 : a.M));
             const long row = ((long)img * Hi + yy) * Wi + xx;
             const int swz = (c8 ^ key(hr)) * 8;
             hoff1[q] = ok ? (unsigned)((row * a.ld1 + swz) * 2) : OOB;
@@ -126,13 +149,14 @@ conv_h32_kernel(GemmArgs a) {
 #pragma unroll
         for (int q = 0; q < WQ; ++q) {
             const int R = (lw + 4 * q) * 8 + r8;
-            woff[q] = (unsigned)(((long)(n0 + R) * a.ktot + (c8 ^ key(R)) * 8) * 2);
+            if constexpr (PH) woff[q] = (unsigned)((((long)par * a.N + n0 + R) * (4 * ctot) + (c8 ^ key(R)) * 8) * 2);
+            else woff[q] = (unsigned)(((long)(n0 + R) * a.ktot + (c8 ^ key(R)) * 8) * 2);
         }
         const int nq = (HP - lw + 3) >> 2;            // valid halo slots of this loader: pieces lw, lw + 4, ... < HP
-        auto hcount = [&](int tap) { const int c = nq - 2 * tap; return tap > 6 ? 0 : (c < 0 ? 0 : (c > 2 ? 2 : c)); };
-        auto issue_w = [&](int cs, int tap) {         // weight slab (cs, tap) into stage tap % 3
+        auto hcount = [&](int tap) { const int c = nq - HPW * tap; return tap > NT - 3 ? 0 : (c < 0 ? 0 : (c > HPW ? HPW : c)); };
+        auto issue_w = [&](int cs, int tap, int stg) {      // weight slab (cs, tap) into ring stage stg (compile-time at every call)
             const unsigned soff = (unsigned)((tap * ctot + cs * BK) * 2);
-            char* dst = wbuf + (tap % NSTG) * WST;
+            char* dst = wbuf + stg * WST;
 #pragma unroll
             for (int q = 0; q < WQ; ++q)
                 __builtin_amdgcn_raw_ptr_buffer_load_lds(rs_w, (lds_void*)(dst + (lw + 4 * q) * 1024), 16, woff[q], soff, 0, 0);
@@ -151,6 +175,7 @@ conv_h32_kernel(GemmArgs a) {
         // slab (three per window, windows 1..7) so that they travel under the last slabs' MFMAs
         const bool res_on = a.res != nullptr;
         auto rcount = [&](int tap, bool last) {
+            if constexpr (PH) return 0;               // (the phase mode carries no residual: plan_gemm)
             if (!(last && res_on && tap >= 1 && tap <= 7)) return 0;
             const int left = RQ - (tap - 1) * 3;
             return left <= 0 ? 0 : (left > 3 ? 3 : left);
@@ -168,37 +193,45 @@ conv_h32_kernel(GemmArgs a) {
         };
         // window (cs, tap), behind the barrier that publishes slab (cs, tap): the weight slab two ahead, two halo slots of
         // cs + 1, residual chunks in the last channel slab
-        auto window = [&](int cs, int tap) {
+        auto window = [&](int cs, int tap, int stg) {      // stg: the ring stage of the slab two ahead
             const bool last = cs + 1 >= cs_end;
-            if (tap + 2 < 9) issue_w(cs, tap + 2);
-            else if (!last) issue_w(cs + 1, tap + 2 - 9);
-            if (!last && tap <= 6) { issue_h1(cs + 1, 2 * tap); issue_h1(cs + 1, 2 * tap + 1); }
+            if (tap + 2 < NT) issue_w(cs, tap + 2, stg);
+            else if (!last) issue_w(cs + 1, tap + 2 - NT, stg);
+            if (!last && tap <= NT - 3) {
+#pragma unroll
+                for (int j = 0; j < HPW; ++j) issue_h1(cs + 1, HPW * tap + j);
+            }
             // the counted vmcnt below relies on the issue ORDER weights, halo, residual: the residual rows are ordinary
             // global loads the compiler could otherwise hoist above the (non-aliasing) DMA intrinsics of this window
             asm volatile("" ::: "memory");
             if (rcount(tap, last)) issue_res(tap);
         };
         auto wcount = [&](int tap, bool last) {       // loads issued by window (cs, tap)
-            return ((tap + 2 < 9 || !last) ? WQ : 0) + (last ? 0 : hcount(tap)) + rcount(tap, last);
+            return ((tap + 2 < NT || !last) ? WQ : 0) + (last ? 0 : hcount(tap)) + rcount(tap, last);
         };
         // ---- prologue: halo of the first channel slab, weight slabs 0 and 1
 #pragma unroll
         for (int q = 0; q < HQ; ++q) issue_h1(cs_begin, q);
-        issue_w(cs_begin, 0);
-        issue_w(cs_begin, 1);
+        issue_w(cs_begin, 0, 0);
+        issue_w(cs_begin, 1, 1);
         wait_vmcnt(WQ);
         __builtin_amdgcn_s_barrier();                 // publishes slab (cs_begin, 0)
-        for (int cs = cs_begin; cs < cs_end; ++cs) {
-            const bool last = cs + 1 >= cs_end;
+        for (int cs0 = cs_begin; cs0 < cs_end; cs0 += U) {
 #pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                window(cs, tap);
-                // the next slab's weights have landed; younger issues may fly: everything of this window, and what the
-                // previous window issued behind its weight pieces (tap 0: the previous window is tap 8, weights only)
-                int n = wcount(tap, last);
-                if (tap >= 1) n += (last ? 0 : hcount(tap - 1)) + rcount(tap - 1, last);
-                wait_vmcnt(n);
-                __builtin_amdgcn_s_barrier();         // publishes the next slab
+            for (int u = 0; u < U; ++u) {
+                const int cs = cs0 + u;
+                if (U > 1 && cs >= cs_end) break;
+                const bool last = cs + 1 >= cs_end;
+#pragma unroll
+                for (int tap = 0; tap < NT; ++tap) {
+                    window(cs, tap, (u * NT + tap + 2) % NSTG);
+                    // the next slab's weights have landed; younger issues may fly: everything of this window, and what the
+                    // previous window issued behind its weight pieces (tap 0: the previous window is the last tap, weights only)
+                    int n = wcount(tap, last);
+                    if (tap >= 1) n += (last ? 0 : hcount(tap - 1)) + rcount(tap - 1, last);
+                    wait_vmcnt(n);
+                    __builtin_amdgcn_s_barrier();     // publishes the next slab
+                }
             }
         }
         // ---- loader epilogue: residual rows -> staging tile; bias[n] + time row[sample][n] of the (<= 4) samples of the tile
@@ -248,9 +281,10 @@ conv_h32_kernel(GemmArgs a) {
 #pragma unroll
                 for (int i = 0; i < 16; ++i) acc[t][c][i] = 0.f;
         int xaddr[TM];
+        const int pshift = (py - 1) * (W + 2) + (px - 1);      // (phase mode: halo shift of folded tap (0, 0))
         auto set_slab = [&](int cs, int tap) {
-            const int ty = tap / 3;
-            const int shift = (ty - 1) * (W + 2) + (tap - ty * 3 - 1);
+            const int ty = PH ? (tap >> 1) : tap / 3;
+            const int shift = PH ? pshift + ty * (W + 2) + (tap & 1) : (ty - 1) * (W + 2) + (tap - ty * 3 - 1);
             const int hsel = (cs & 1) * HS;
 #pragma unroll
             for (int t = 0; t < TM; ++t) {
@@ -303,10 +337,14 @@ conv_h32_kernel(GemmArgs a) {
         half8 xf0[TM], wf0[5], xf1[TM], wf1[5];
         set_slab(cs_begin, 0);
         read_frags(0, 0, xf0, wf0);
-        for (int cs = cs_begin; cs < cs_end; ++cs) {
+        for (int cs0 = cs_begin; cs0 < cs_end; cs0 += U) {
 #pragma unroll
-            for (int tap = 0; tap < 9; ++tap) {
-                const int st = tap % NSTG, stn = (tap + 1) % NSTG;      // (nine slabs per channel slab, three stages: static)
+          for (int u = 0; u < U; ++u) {
+            const int cs = cs0 + u;
+            if (U > 1 && cs >= cs_end) break;
+#pragma unroll
+            for (int tap = 0; tap < NT; ++tap) {
+                const int st = (u * NT + tap) % NSTG, stn = (u * NT + tap + 1) % NSTG;      // (U * NT slabs per trip, three stages: static)
                 read_frags(st, 1, xf1, wf1);
                 mma(xf0, wf0);
                 interleave();
@@ -325,12 +363,13 @@ conv_h32_kernel(GemmArgs a) {
                 __builtin_amdgcn_s_barrier();
                 __builtin_amdgcn_sched_barrier(0);
                 // fourth k-step, the next slab's first fragments travel under it (behind the last slab: stale LDS, unused)
-                if (tap < 8) set_slab(cs, tap + 1); else set_slab(cs + 1, 0);
+                if (tap < NT - 1) set_slab(cs, tap + 1); else set_slab(cs + 1, 0);
                 read_frags(stn, 0, xf0, wf0);
                 mma(xf1, wf1);
                 interleave();
                 __builtin_amdgcn_sched_barrier(0);
             }
+          }
         }
         // ---- compute epilogue ---------------------------------------------------------------------------------------------
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -375,8 +414,14 @@ conv_h32_kernel(GemmArgs a) {
         const int e = it * 512 + tid;
         const int row = e / 20, ch = e - row * 20;
         const half8 v = *reinterpret_cast<const half8*>(T + row * TP + ch * 8);
-        *reinterpret_cast<half8*>(a.out + (long)(m0 + row) * a.ldo + n0 + ch * 8) = v;
-        if (a.out2) *reinterpret_cast<half8*>(a.out2 + (long)(m0 + row) * a.ldo + n0 + ch * 8) = v;
+        long orow = m0 + row;
+        if constexpr (PH) {                           // input pixel (img, y, x) -> output pixel (img, 2 y + py, 2 x + px)
+            const int p = m0 + row, img = p / HW, rem = p - img * HW;
+            const int y = rem / W, x = rem - y * W;
+            orow = ((long)img * (2 * H) + 2 * y + py) * (2 * W) + 2 * x + px;
+        }
+        *reinterpret_cast<half8*>(a.out + orow * a.ldo + n0 + ch * 8) = v;
+        if (a.out2) *reinterpret_cast<half8*>(a.out2 + orow * a.ldo + n0 + ch * 8) = v;
     }
     if (a.gn_stats != nullptr) {
         // GroupNorm statistics of the tensor just written: (sum, sum of squares) of the fp16 outputs per statistics unit of
@@ -431,7 +476,7 @@ conv_h32_kernel(GemmArgs a) {
 #pragma unroll
                 for (int i = 0; i < 5; ++i) sum += v[i];
             }
-            a.gn_stats[((long)(m0 / BM) * (a.N / a.gn_unit) + n0 / a.gn_unit + u) * 2 + which] = (float)sum;
+            a.gn_stats[((long)mb_ * (a.N / a.gn_unit) + n0 / a.gn_unit + u) * 2 + which] = (float)sum;
         }
     }
 #endif
@@ -439,12 +484,14 @@ conv_h32_kernel(GemmArgs a) {
 
 }  // namespace
 
-template <int TM>
+template <int TM, int NT>
 static int launch_tm(const GemmArgs& a, hipStream_t s) {
     constexpr int BM = 128 * TM;
-    const int W = a.Wo, HW = a.Ho * a.Wo;
+    constexpr bool PH = NT == 4;                  // (phase mode: the tile geometry is that of the input image)
+    const int W = PH ? a.Wi : a.Wo, HW = PH ? a.Hi * a.Wi : a.Ho * a.Wo;
+    const int up = PH ? 0 : a.up;
     const int seg = BM < HW ? BM : HW;
-    const int nh = (BM / seg) * (((seg / W) >> a.up) + 2) * ((W >> a.up) + 2);
+    const int nh = (BM / seg) * (((seg / W) >> up) + 2) * ((W >> up) + 2);
     int smem = 2 * ((nh + 7) / 8) * 1024 + NSTG * WST;
     if (smem < epi_bytes(BM)) smem = epi_bytes(BM);      // (an input-resolution halo is small: the epilogue images set the size)
     if (smem > 160 * 1024) {
@@ -453,7 +500,7 @@ static int launch_tm(const GemmArgs& a, hipStream_t s) {
     }
     static bool configured = false;
     if (!configured) {
-        hipError_t herr = hipFuncSetAttribute((const void*)conv_h32_kernel<TM>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t herr = hipFuncSetAttribute((const void*)conv_h32_kernel<TM, NT>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (herr != hipSuccess) {
             cid_set_error("cid_gemm_f16: cannot reserve 160 KB of LDS (%s)", hipGetErrorString(herr));
             return -5;
@@ -463,10 +510,11 @@ static int launch_tm(const GemmArgs& a, hipStream_t s) {
     dim3 grid(a.N / BN, a.M / BM, 1);
     GemmArgs b = a;
     b.xcd_pn = cidg::choose_xcd_pn((int)grid.x, (int)grid.y, 2.0 * a.N * a.ktot, (double)a.bytes_x1 + a.bytes_x2);
-    hipLaunchKernelGGL(conv_h32_kernel<TM>, grid, dim3(512), smem, s, b);
+    hipLaunchKernelGGL((conv_h32_kernel<TM, NT>), grid, dim3(512), smem, s, b);
     return 0;
 }
 
 int cidg::launch_conv_h32(const GemmArgs& a, int bm, hipStream_t s) {
-    return bm == 256 ? launch_tm<2>(a, s) : launch_tm<1>(a, s);
+    if (a.w4) return bm == 256 ? launch_tm<2, 4>(a, s) : launch_tm<1, 4>(a, s);
+    return bm == 256 ? launch_tm<2, 9>(a, s) : launch_tm<1, 9>(a, s);
 }

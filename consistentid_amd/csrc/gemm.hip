@@ -1295,6 +1295,13 @@ static int plan_gemm(const cid_gemm_desc* d, GemmArgs& a, TileCfg& cfg, bool& ha
                   "(got mode %d taps %d stride %d up %d, %d x %d -> %d x %d)", d->mode, d->taps, d->stride, d->up, d->Hi, d->Wi,
                   d->Ho, d->Wo);
     a.tap0 = d->pad_mode == 1 ? 0 : -1;
+    // w_up4 (since cid_version() 103): the folded weights of an Upsample2D convolution (cid_upconv_fold_f16).  The launch may
+    // then run as four 2x2 phase convolutions at input resolution (conv3x3.hip, routed below); where it cannot, w serves.
+    CID_CHECK_ARG(!d->w_up4 || (d->taps == 9 && d->up == 1 && d->stride == 1 && d->mode == 0 && !d->res),
+                  "cid_gemm_f16: w_up4 needs taps 9, up 1, stride 1, mode 0 and no res (got taps %d up %d stride %d mode %d)",
+                  d->taps, d->up, d->stride, d->mode);
+    CID_CHECK_ARG(((uintptr_t)d->w_up4 & 15) == 0, "cid_gemm_f16: w_up4 must be 16-byte aligned");
+    a.w4 = nullptr;
     // act 1 (since cid_version() 102): ReLU in the plain epilogue.  Only the igemm_kernel instances carry it (launch_act);
     // split-K (ws), the GroupNorm statistics and the LayerNorm fold are refused with it, the halo / conv3x3.hip kernels skipped.
     CID_CHECK_ARG(d->act == 0 || d->act == 1, "cid_gemm_f16: bad act %d", d->act);
@@ -1486,7 +1493,26 @@ static int plan_gemm(const cid_gemm_desc* d, GemmArgs& a, TileCfg& cfg, bool& ha
         const bool shape_ok = !no_h32 && !d->act && d->mode == 0 && d->taps == 9 && d->stride == 1 && (d->up == 0 || d->up == 1) &&
                               d->Wo == (d->Wi << d->up) && d->Ho == (d->Hi << d->up) && d->N % 160 == 0 && HW >= 64 &&
                               (!d->rowbias || (a.rows_per_sample >= 64 && a.rows_per_sample % 64 == 0));
+        // Upsample2D with folded weights (w_up4): the phase mode -- a tile is bm_try INPUT pixels of one output parity, whole
+        // input rows of one image; same tile-count rules.  One source, no time row (the UNets' Upsample2D has neither); the
+        // nine-tap path below serves everything else.  CID_UPCONV_FOLD=0: never (A/B switch).
+        static int fold_on = -1;
+        if (fold_on < 0) { const char* e = getenv("CID_UPCONV_FOLD"); fold_on = e ? atoi(e) : 1; }
+        const bool fold_ok = shape_ok && fold_on && d->w_up4 && d->up == 1 && d->c2 == 0 && !d->rowbias && !d->res &&
+                             (long)d->N * d->c1 * 32 < 0x7fffffffL;
         for (int bm_try = 256; shape_ok && !h32 && bm_try >= (only256 ? 256 : 128); bm_try >>= 1) {
+            if (fold_ok) {
+                const int HWi = d->Hi * d->Wi;
+                const long tiles = (long)(d->M / bm_try) * (d->N / 160);
+                if (HWi % bm_try == 0 && bm_try % d->Wi == 0 && d->M % bm_try == 0 && (bm_try / d->Wi + 2) * (d->Wi + 2) <= 400 &&
+                    tiles >= 256 && !(bm_try == 128 && a.cslabs > 10)) {
+                    h32 = true; halo = false;
+                    bm = bm_try;
+                    a.splitk = 1;
+                    a.w4 = (const half_t*)d->w_up4;
+                    continue;
+                }
+            }
             const int seg = bm_try < HW ? bm_try : HW;
             if (seg % d->Wo != 0 || HW % seg != 0 || bm_try % seg != 0 || d->M % bm_try != 0) continue;
             if (d->up && (seg != bm_try || (seg / d->Wo) % 2 != 0)) continue;

@@ -42,6 +42,8 @@ struct GemmArgs {
                          // 2 = no MFMA, 3 = no LDS fragment reads / MFMA
     int xcd_pn;          // tile -> XCD partition (xcd_tile below): n-blocks of the 2-D partition (1 | 2 | 4 | 8), 0 = linear runs
     int tap0;            // first tap offset of a 3x3 conv: -1 (pad 1), 0 (cid_gemm_desc.pad_mode 1, Downsample2D(padding=0))
+    const half_t* w4;    // cid_gemm_desc.w_up4 when plan_gemm routes an Upsample2D convolution to the phase mode of conv3x3.hip
+                         // (four 2x2 convolutions at input resolution: W4[parity][n][tap4][c]), else nullptr
 };
 
 // Tile of a workgroup.  The hardware deals consecutive workgroup ids round-robin over the 8 XCDs (a private 4-MB L2 each): the
@@ -85,7 +87,9 @@ CID_DEVINL void wait_vmcnt(int n) {
 }
 
 // 3x3 stride-1 halo convolution, bm-token (256 | 128) x 160-channel tiles on v_mfma_f32_32x32x16_f16 (conv3x3.hip); plan_gemm
-// has checked: a tile = whole image rows of one image or whole images, halo <= 400 rows, N % 160 == 0, M % bm == 0
+// has checked: a tile = whole image rows of one image or whole images, halo <= 400 rows, N % 160 == 0, M % bm == 0.
+// a.w4 set: the phase mode (up == 1, one source, no residual / time row; a tile = bm INPUT pixels of one output parity, whole
+// input rows of one image)
 int launch_conv_h32(const GemmArgs& a, int bm, hipStream_t s);
 
 // GEGLU projection on 32 x 32 x 16 MFMA tiles with loader / compute wave roles (linear_h32.hip); plan_gemm has checked: one

@@ -15,7 +15,7 @@ void cid_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* cid_last_error(void) { return g_err; }
-extern "C" int cid_version(void) { return 102; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act
+extern "C" int cid_version(void) { return 103; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4
 
 namespace {
 
@@ -500,6 +500,33 @@ add_inplace_kernel(half_t* __restrict__ y, const half_t* __restrict__ a, long n,
     }
 }
 
+// Upsample2D weight fold (cid_upconv_fold_f16): one thread per element of w4[parity][n][tap4][c].  Along an axis, parity p and
+// folded tap r take the source taps [lo, hi]: (p, r) = (0, 0): {0}, (0, 1): {1, 2}, (1, 0): {0, 1}, (1, 1): {2}.
+__global__ void __launch_bounds__(256)
+upconv_fold_kernel(const half_t* __restrict__ w, half_t* __restrict__ w4, int N, int C) {
+    const long total = 16L * N * C;
+    for (long e = (long)blockIdx.x * 256 + threadIdx.x; e < total; e += (long)gridDim.x * 256) {
+        const int c = (int)(e % C);
+        long r = e / C;
+        const int tap4 = (int)(r & 3);
+        r >>= 2;
+        const int n = (int)(r % N), par = (int)(r / N);
+        const int py = par >> 1, px = par & 1, ry = tap4 >> 1, rx = tap4 & 1;
+        const int ylo = py + ry == 0 ? 0 : (py + ry == 2 ? 2 : (py ? 0 : 1)), yhi = py + ry == 0 ? 0 : (py + ry == 2 ? 2 : (py ? 1 : 2));
+        const int xlo = px + rx == 0 ? 0 : (px + rx == 2 ? 2 : (px ? 0 : 1)), xhi = px + rx == 0 ? 0 : (px + rx == 2 ? 2 : (px ? 1 : 2));
+        const half_t* src = w + (long)n * 9 * C + c;
+        float acc = 0.f;
+        bool first = true;
+        for (int ty = ylo; ty <= yhi; ++ty)                 // fixed order: ty-major, then tx
+            for (int tx = xlo; tx <= xhi; ++tx) {
+                const float v = (float)src[(long)(ty * 3 + tx) * C];
+                acc = first ? v : __fadd_rn(acc, v);
+                first = false;
+            }
+        w4[e] = (half_t)acc;
+    }
+}
+
 inline int grid_for(long items, int per_block, int cap) {
     long g = (items + per_block - 1) / per_block;
     return (int)(g > cap ? cap : (g < 1 ? 1 : g));
@@ -561,6 +588,14 @@ extern "C" int cid_conv3x3_small_f16(const cid_half* x, cid_half* out, const cid
     return 0;
 }
 
+
+extern "C" int cid_upconv_fold_f16(const cid_half* w, cid_half* w4, int32_t N, int32_t C, cid_stream_t stream) {
+    CID_CHECK_ARG(w && w4 && N > 0 && C > 0 && 16L * N * C < 0x7fffffffL, "cid_upconv_fold_f16: bad arguments (N = %d, C = %d)", N, C);
+    hipLaunchKernelGGL(upconv_fold_kernel, dim3(grid_for(16L * N * C, 256, 8192)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)w, (half_t*)w4, N, C);
+    CID_CHECK_LAUNCH("cid_upconv_fold_f16");
+    return 0;
+}
 
 extern "C" int cid_gelu_f16(cid_half* x, int64_t n, cid_stream_t stream) {
     CID_CHECK_ARG(x && n > 0 && n % 8 == 0, "cid_gelu_f16: n must be a positive multiple of 8");

@@ -45,7 +45,7 @@ def gemm(x1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
          taps: int = 1, Hi: int = 0, Wi: int = 0, Ho: int = 0, Wo: int = 0, stride: int = 1, up: int = 0,
          mode: int = 0, vt: Optional[torch.Tensor] = None, n_vt0: int = 0, heads: int = 0, dhead: int = 0,
          ntok: int = 0, ws: Optional[torch.Tensor] = None, ln=None, gn_hw: int = 0, att=None,
-         out2: Optional[torch.Tensor] = None, pad_mode: int = 0, act: int = 0):
+         out2: Optional[torch.Tensor] = None, pad_mode: int = 0, act: int = 0, w_up4: Optional[torch.Tensor] = None):
     """``att`` = (kp, vp, kvrow, n_txt, n_ip, ip_scale) with ``mode=3``: the query projection of the identity cross-attention
     with the two-stream attention as its epilogue (``heads``, ``dhead``, ``ntok`` describe the heads and the tokens per sample).
     ``ln`` = (s, b, eps): LayerNorm folded into the projection -- ``x1`` is the raw residual stream, ``w`` carries gamma,
@@ -56,11 +56,13 @@ def gemm(x1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
     ``out2``: a second destination for the same rows (same pitch as ``out``; mode 0): the CFG duplication of a tensor both
     halves of the batch share, written by the producer.
     ``pad_mode=1``: Downsample2D(padding=0) -- pad (0, 1, 0, 1), then the stride-2 3x3 conv without padding.
-    ``act=1``: ReLU after bias / rowbias / res (mode 0; not with ``ws``, ``ln`` or ``gn_hw``)."""
+    ``act=1``: ReLU after bias / rowbias / res (mode 0; not with ``ws``, ``ln`` or ``gn_hw``).
+    ``w_up4``: the folded weights of an Upsample2D convolution (:func:`upconv_fold` of ``w``; ``taps=9, up=1``): the launch
+    runs as four 2x2 phase convolutions at input resolution where the library can tile it so, from ``w`` otherwise."""
     lib = _lib.load()
     for name, t in (("x1", x1), ("w", w), ("out", out)):
         _req(t, f"gemm.{name}")
-    for name, t in (("x2", x2), ("bias", bias), ("rowbias", rowbias), ("res", res), ("vt", vt), ("out2", out2)):
+    for name, t in (("x2", x2), ("bias", bias), ("rowbias", rowbias), ("res", res), ("vt", vt), ("out2", out2), ("w_up4", w_up4)):
         if t is not None:
             _req(t, f"gemm.{name}")
     d = GemmDesc()
@@ -81,6 +83,7 @@ def gemm(x1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
     d.Hi, d.Wi, d.Ho, d.Wo, d.stride, d.up = Hi, Wi, Ho, Wo, stride, up
     d.pad_mode = pad_mode
     d.act = act
+    d.w_up4 = _p(w_up4)
     d.mode = mode
     d.vt, d.n_vt0, d.heads, d.dhead, d.dvp, d.ntok = _p(vt), n_vt0, heads, dhead, dvp_of(dhead) if dhead else 0, ntok
     if ws is not None:
@@ -109,6 +112,18 @@ def gemm(x1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
     elif hasattr(out, "_gn_stats"):
         del out._gn_stats            # a reused output tensor must not carry the statistics of what it held before
     return out
+
+
+def upconv_fold(w: torch.Tensor) -> torch.Tensor:
+    """Packed nine-tap weights ``[N, 9 * C]`` of an Upsample2D convolution (``weights._conv3``) -> the folded
+    ``[4 parities * N, 4 taps * C]`` tensor for ``gemm(..., w_up4=)`` (cid_upconv_fold_f16; once per weight load)."""
+    _req(w, "upconv_fold.w")
+    N, C_ = w.shape[0], w.shape[1] // 9
+    if w.dim() != 2 or w.shape[1] != 9 * C_ or not w.is_contiguous():
+        raise _lib.CidError(f"upconv_fold: expected contiguous [N, 9 * C] weights, got {tuple(w.shape)}")
+    w4 = torch.empty(4 * N, 4 * C_, dtype=torch.float16, device=w.device)
+    check(_lib.load().cid_upconv_fold_f16(_p(w), _p(w4), N, C_, _stream()), "cid_upconv_fold_f16")
+    return w4
 
 
 LN_EPS = 1e-5        # diffusers BasicTransformerBlock LayerNorms (SURVEY.md 8c): shared by layernorm(), the folded projections and the fused kernels

@@ -498,7 +498,7 @@ class HipUNet:
                 Ho, Wo = H * 2, Wd * 2
                 y = self._empty(B * Ho * Wo, c)
                 ops.gemm(x, W[f"{n}.w"], y, M=B * Ho * Wo, N=c, c1=c, bias=W[f"{n}.b"], taps=9,
-                         Hi=H, Wi=Wd, Ho=Ho, Wo=Wo, stride=1, up=1, ws=self._gemm_ws, gn_hw=Ho * Wo)
+                         Hi=H, Wi=Wd, Ho=Ho, Wo=Wo, stride=1, up=1, ws=self._gemm_ws, gn_hw=Ho * Wo, w_up4=W.get(f"{n}.w4"))
                 x, H, Wd = y, Ho, Wo
         g = self._gn(x, c, B, H * Wd, W["conv_norm_out.g"], W["conv_norm_out.b"], cfg.norm_eps, True)
         out = self._empty(B, cfg.out_channels, H, Wd)

@@ -145,6 +145,9 @@ class PackedUNet:
             if blk.sampler:
                 n = f"{blk.name}.{blk.sampler}.conv"
                 W[f"{n}.w"], W[f"{n}.b"] = _conv3(sd[f"{n}.weight"], dev), _h(sd[f"{n}.bias"], dev)
+                if blk.sampler.startswith("upsamplers") and W[f"{n}.w"].is_cuda:
+                    # Upsample2D: the nine taps folded into four 2x2 phase convolutions (ops.gemm w_up4), once per load
+                    W[f"{n}.w4"] = ops.upconv_fold(W[f"{n}.w"])
         self.temb_total = off
         W["temb_all.w"] = _h(torch.cat([t.to(torch.float32) for t in tw], 0), dev)
         W["temb_all.b"] = _h(torch.cat([t.to(torch.float32) for t in tb], 0), dev)

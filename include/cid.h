@@ -27,7 +27,7 @@ extern "C" {
 typedef void* cid_stream_t;      /* hipStream_t */
 typedef uint16_t cid_half;       /* IEEE binary16 bit pattern */
 
-int cid_version(void);          /* 102: cid_gemm_desc grew a trailing act field (101: pad_mode; set them or zero the struct) */
+int cid_version(void);          /* 103: cid_gemm_desc grew a trailing w_up4 pointer (102: act, 101: pad_mode; set them or zero the struct) */
 const char* cid_last_error(void);
 
 /* ---------------------------------------------------------------------------
@@ -106,11 +106,25 @@ typedef struct cid_gemm_desc {
      *      run once per image by pipline_StableDiffusion_ConsistentID.py:243).  Mode 0 only, without gn_stats, ws
      *      (split-K) or ln_s (else -22); the launch runs on the gather kernels of every tile width. */
     int32_t act;
+    /* Folded weights of an Upsample2D convolution (since cid_version() 103, which grew the struct by this field), or NULL:
+     * W4[parity][N][tap4][c1] as written by cid_upconv_fold_f16 from w.  After a nearest 2x upsample the three taps along an
+     * axis touch two input rows / columns, so the outputs of one parity (Y & 1, X & 1) are a 2x2 convolution of the INPUT
+     * image with summed taps: 4/9 of the multiplications.  Only with taps 9, up 1, stride 1, mode 0 and no res (else -22).
+     * The launch uses it where csrc/conv3x3.hip can tile the image by parity (N % 160 == 0, one source, no rowbias, whole input
+     * rows per tile, enough tiles to fill the chip); every other launch computes from w as if the field were NULL, and with
+     * NULL the call is what it was before 103, bit for bit.  The sums are rounded to fp16 once, so the two paths differ by
+     * that rounding (relative L2 ~ 1.5e-4).  CID_UPCONV_FOLD=0 in the environment ignores the field (A/B switch). */
+    const cid_half* w_up4;
 } cid_gemm_desc;
 int cid_gemm_f16(const cid_gemm_desc* d, cid_stream_t stream);
 /* Token rows per statistics block if cid_gemm_f16(d) can emit gn_stats (its tile height), 0 if it cannot (split-K,
  * tile widths off the 160-channel grid, ragged M): the caller then lets cid_groupnorm_f16 take its own statistics. */
 int cid_gemm_stats_rows(const cid_gemm_desc* d);
+/* Fold the packed nine-tap weights w[N][9][C] (tap = 3 ty + tx) of an Upsample2D convolution into w4[4][N][4][C] for
+ * cid_gemm_desc.w_up4: parity = 2 py + px, tap4 = 2 ry + rx.  Along y, parity 0 reads input rows (y - 1, y) with taps
+ * ({0}, {1, 2}), parity 1 reads rows (y, y + 1) with taps ({0, 1}, {2}); the same along x.  Every entry is the fp32 sum of
+ * its 1, 2 or 4 source taps added in the order ty-major, then tx, rounded to fp16 once.  Run once when weights are packed. */
+int cid_upconv_fold_f16(const cid_half* w, cid_half* w4, int32_t N, int32_t C, cid_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Self-attention core (replaces the softmax(QK^T)V of Consistent_AttProcessor,

@@ -1,6 +1,8 @@
 #!/usr/bin/env python
 """Run ONE kernel shape a few times (for rocprofv3 --pmc passes).
-  python tools/pmc_one.py conv0|lin0|ff20|qkv0|lin2|geglu0|geglu2|attn0|xattn0|xattn3 [iters]
+  python tools/pmc_one.py conv0|upconv0|upconv1|lin0|ff20|qkv0|lin2|geglu0|geglu2|attn0|xattn0|xattn3 [iters]
+  (upconv0 / upconv1 = the Upsample2D convolutions 32 -> 64 at 640 channels / 16 -> 32 at 1280 with folded weights: four 2x2 phase
+   convolutions, or the nine taps with CID_UPCONV_FOLD=0)
   (geglu2 = the GEGLU projection of SD1.5's 16 x 16 level: csrc/linear_h32.hip, or gemm.hip's form with CID_GEGLU_H32=0)"""
 import os
 import sys
@@ -23,6 +25,14 @@ if which in ("conv0", "conv2", "conv3"):
     out = torch.empty(M, c, dtype=torch.float16, device=dev)
     ws = torch.empty(64 << 20, dtype=torch.uint8, device=dev)
     fn = lambda: ops.gemm(x, w, out, M=M, N=c, c1=c, bias=b, taps=9, Hi=side, Wi=side, Ho=side, Wo=side, ws=ws)
+elif which in ("upconv0", "upconv1"):
+    side, c = {"upconv0": (32, 640), "upconv1": (16, 1280)}[which]
+    M = B2 * 4 * side * side
+    x, w, b = rnd(B2 * side * side, c), rnd(c, 9 * c), rnd(c)
+    w4 = ops.upconv_fold(w)
+    out = torch.empty(M, c, dtype=torch.float16, device=dev)
+    ws = torch.empty(64 << 20, dtype=torch.uint8, device=dev)
+    fn = lambda: ops.gemm(x, w, out, M=M, N=c, c1=c, bias=b, taps=9, Hi=side, Wi=side, Ho=2 * side, Wo=2 * side, up=1, ws=ws, w_up4=w4)
 elif which == "lin0":
     M, c = B2 * 4096, 320
     x, w, b = rnd(M, c), rnd(c, c), rnd(c)
