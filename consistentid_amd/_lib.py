@@ -43,6 +43,16 @@ class GemmDesc(C.Structure):
     ]
 
 
+class GemmPlanInfo(C.Structure):
+    """struct cid_gemm_plan_info (include/cid.h)."""
+    _fields_ = [(n, C.c_int32) for n in ("family", "bm", "bn", "splitk", "nloop", "nbuf", "ln", "act", "vmode",
+                                         "splitk_epilogue", "stats_rows")]
+
+
+# CID_GEMM_FAMILY_* (include/cid.h), by value
+GEMM_FAMILIES = ("igemm", "igemm_halo", "conv_h32", "conv_h32_phase", "geglu_h32", "igemm_att")
+
+
 class StepSeg(C.Structure):
     """struct cid_step_seg (include/cid.h)."""
     _fields_ = [("dst", C.c_void_p), ("offset", C.c_int64), ("nbytes", C.c_int64)]
@@ -54,6 +64,7 @@ SIGNATURES = {
     "cid_last_error": (C.c_char_p, []),
     "cid_gemm_f16": (C.c_int, [C.POINTER(GemmDesc), c_stream]),
     "cid_gemm_stats_rows": (C.c_int, [C.POINTER(GemmDesc)]),
+    "cid_gemm_plan": (C.c_int, [C.POINTER(GemmDesc), C.POINTER(GemmPlanInfo)]),
     "cid_upconv_fold_f16": (C.c_int, [c_half_p, c_half_p, C.c_int32, C.c_int32, c_stream]),
     "cid_self_attn_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 8 + [c_stream]),
     "cid_self_attn_keys_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 9 + [c_stream]),

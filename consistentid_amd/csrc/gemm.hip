@@ -1214,8 +1214,17 @@ int cidg::choose_xcd_pn(int gx, int gy, double w_bytes, double x_bytes) {
 
 enum TileCfg { A256x160, B128x160, C64x160, G256x128, G128x128, O64x64, O128x32 };
 
+// token rows per GroupNorm statistics block of a planned launch (its tile height), 0 where it cannot emit them: the plain,
+// unsplit, ReLU-free epilogue of the 160-wide tiles, whole tiles only
+static int stats_rows_of(const cid_gemm_desc* d, const GemmArgs& a, TileCfg cfg, int bm) {
+    const int unit = d->N / 32;
+    const bool ok = d->mode == 0 && d->act == 0 && a.splitk == 1 && (cfg == A256x160 || cfg == B128x160 || cfg == C64x160) &&
+                    d->N % 32 == 0 && unit > 0 && 80 % unit == 0 && bm > 0 && d->M % bm == 0;
+    return ok ? bm : 0;
+}
+
 // argument checks + tile / split-K choice of one cid_gemm_f16 call (no launch): shared by the call itself and by
-// cid_gemm_stats_rows, which tells the host how the GroupNorm statistics of that call will be blocked
+// cid_gemm_plan (and through it cid_gemm_stats_rows, which tells the host how the GroupNorm statistics will be blocked)
 static int plan_gemm(const cid_gemm_desc* d, GemmArgs& a, TileCfg& cfg, bool& halo, int& bm_out, bool& h32, bool& g32) {
     h32 = false;
     g32 = false;
@@ -1527,11 +1536,58 @@ static int plan_gemm(const cid_gemm_desc* d, GemmArgs& a, TileCfg& cfg, bool& ha
     }
     bm_out = bm;
     // GroupNorm statistics come out of the plain, unsplit epilogue of the 160-wide tiles, whole tiles only
-    if (a.gn_stats) {
-        const bool ok = d->mode == 0 && a.splitk == 1 && (cfg == A256x160 || cfg == B128x160 || cfg == C64x160) &&
-                        d->N % 32 == 0 && 80 % a.gn_unit == 0 && d->M % bm == 0;
-        CID_CHECK_ARG(ok, "cid_gemm_f16: gn_stats requested for a launch that cannot emit them (ask cid_gemm_stats_rows first)");
+    if (a.gn_stats)
+        CID_CHECK_ARG(stats_rows_of(d, a, cfg, bm) > 0,
+                      "cid_gemm_f16: gn_stats requested for a launch that cannot emit them (ask cid_gemm_stats_rows first)");
+    return 0;
+}
+
+// The launch of a planned call: which kernel family runs it and which template instance of that family.  decide_launch is
+// the ONE place that turns plan_gemm's findings into that choice; cid_gemm_f16 launches what it returns and cid_gemm_plan
+// reports it, so the report cannot drift from the launch.
+struct LaunchChoice {
+    int family;          // CID_GEMM_FAMILY_*
+    int bm, bn;          // tile
+    bool ln, act, vmode; // LN / ACT instance; a second, VMODE launch writes the transposed V third (mode 2)
+    bool sk_epilogue;    // splitk_epilogue_kernel follows
+};
+
+static LaunchChoice decide_launch(const cid_gemm_desc* d, GemmArgs& a, TileCfg cfg, bool halo, int bm, bool h32, bool g32) {
+    static const int cfg_bn[] = { 160, 160, 160, 128, 128, 64, 32 };
+    LaunchChoice c;
+    c.bm = bm; c.bn = cfg_bn[cfg];
+    c.ln = false; c.act = false; c.vmode = false; c.sk_epilogue = false;
+    if (g32) { c.family = CID_GEMM_FAMILY_GEGLU_H32; c.bn = 160; }
+    else if (a.mode == 3) { c.family = CID_GEMM_FAMILY_IGEMM_ATT; c.ln = a.ln_s != nullptr; }
+    else if (d->act) { c.family = CID_GEMM_FAMILY_IGEMM; c.act = true; }
+    else if (h32) { c.family = a.w4 ? CID_GEMM_FAMILY_CONV_H32_PHASE : CID_GEMM_FAMILY_CONV_H32; }
+    else if (halo) { c.family = CID_GEMM_FAMILY_IGEMM_HALO; c.sk_epilogue = a.splitk > 1; }
+    else {
+        c.family = CID_GEMM_FAMILY_IGEMM;
+        c.ln = a.ln_s != nullptr;
+        c.vmode = a.mode == 2 && a.N > a.n_vt0;
+        c.sk_epilogue = a.splitk > 1;
     }
+    // the ring depth is a launch parameter of the gather kernels only (launch_one reads it); the other kernels fix their staging
+    if (c.family != CID_GEMM_FAMILY_IGEMM && c.family != CID_GEMM_FAMILY_IGEMM_ATT) a.nbuf = 0;
+    return c;
+}
+
+extern "C" int cid_gemm_plan(const cid_gemm_desc* d, cid_gemm_plan_info* out) {
+    CID_CHECK_ARG(out, "cid_gemm_plan: null output");
+    GemmArgs a;
+    TileCfg cfg;
+    bool halo, h32, g32;
+    int bm = 0;
+    int rc = plan_gemm(d, a, cfg, halo, bm, h32, g32);
+    if (rc) return rc;
+    const LaunchChoice c = decide_launch(d, a, cfg, halo, bm, h32, g32);
+    out->family = c.family;
+    out->bm = c.bm; out->bn = c.bn;
+    out->splitk = a.splitk; out->nloop = a.nloop; out->nbuf = a.nbuf;
+    out->ln = c.ln; out->act = c.act; out->vmode = c.vmode;
+    out->splitk_epilogue = c.sk_epilogue;
+    out->stats_rows = stats_rows_of(d, a, cfg, bm);
     return 0;
 }
 
@@ -1539,15 +1595,8 @@ extern "C" int cid_gemm_stats_rows(const cid_gemm_desc* d) {
     if (!d) return 0;
     cid_gemm_desc q = *d;
     q.gn_stats = nullptr;
-    GemmArgs a;
-    TileCfg cfg;
-    bool halo, h32, g32;
-    int bm = 0;
-    if (plan_gemm(&q, a, cfg, halo, bm, h32, g32) != 0) return 0;
-    const int unit = d->N / 32;
-    const bool ok = d->mode == 0 && d->act == 0 && a.splitk == 1 && (cfg == A256x160 || cfg == B128x160 || cfg == C64x160) &&
-                    d->N % 32 == 0 && unit > 0 && 80 % unit == 0 && d->M % bm == 0;
-    return ok ? bm : 0;
+    cid_gemm_plan_info info;
+    return cid_gemm_plan(&q, &info) == 0 ? info.stats_rows : 0;
 }
 
 extern "C" int cid_gemm_f16(const cid_gemm_desc* d, cid_stream_t stream) {
@@ -1557,57 +1606,49 @@ extern "C" int cid_gemm_f16(const cid_gemm_desc* d, cid_stream_t stream) {
     int bm = 0;
     int rc = plan_gemm(d, a, cfg, halo, bm, h32, g32);
     if (rc) return rc;
+    const LaunchChoice c = decide_launch(d, a, cfg, halo, bm, h32, g32);
     hipStream_t s = (hipStream_t)stream;
-    if (g32) {
-        a.n_begin = 0; a.n_end = a.N;
-        rc = cidg::launch_geglu_h32(a, s);
-        if (rc) return rc;
-        CID_CHECK_LAUNCH("cid_gemm_f16");
-        return 0;
-    }
-    if (a.mode == 3) {
-        if (cfg == G128x128) rc = launch_att<2, 4, 4, 2, 64>(a, s);
-        else if (cfg == B128x160) rc = a.dhead == 80 ? launch_att<2, 5, 4, 2, 80>(a, s) : launch_att<2, 5, 4, 2, 160>(a, s);
-        else rc = a.dhead == 80 ? launch_att<2, 5, 2, 2, 80>(a, s) : launch_att<2, 5, 2, 2, 160>(a, s);
-        if (rc) return rc;
-        CID_CHECK_LAUNCH("cid_gemm_f16");
-        return 0;
-    }
-    if (d->act) {
-        switch (cfg) {
-            case A256x160: rc = launch_act<4, 5, 4, 2>(a, s); break;
-            case B128x160: rc = launch_act<2, 5, 4, 2>(a, s); break;
-            case C64x160:  rc = launch_act<2, 5, 2, 2>(a, s); break;
-            case G256x128: rc = launch_act<4, 4, 4, 2>(a, s); break;
-            case G128x128: rc = launch_act<2, 4, 4, 2>(a, s); break;
-            case O64x64:   rc = launch_act<2, 2, 2, 2>(a, s); break;
-            case O128x32:  rc = launch_act<2, 2, 4, 1>(a, s); break;
-        }
-        if (rc) return rc;
-        CID_CHECK_LAUNCH("cid_gemm_f16");
-        return 0;
-    }
-    if (h32) {
-        a.n_begin = 0; a.n_end = a.N;
-        rc = cidg::launch_conv_h32(a, bm, s);
-        if (rc) return rc;
-        CID_CHECK_LAUNCH("cid_gemm_f16");
-        return 0;
-    }
-    if (halo) {
-        rc = launch_halo<4, 5, 4, 2>(a, s);
-        if (rc) return rc;
-        CID_CHECK_LAUNCH("cid_gemm_f16");
-        return 0;
-    }
-    switch (cfg) {
-        case A256x160: rc = launch<4, 5, 4, 2>(a, s); break;
-        case B128x160: rc = launch<2, 5, 4, 2>(a, s); break;
-        case C64x160:  rc = launch<2, 5, 2, 2>(a, s); break;
-        case G256x128: rc = launch<4, 4, 4, 2>(a, s); break;
-        case G128x128: rc = launch<2, 4, 4, 2>(a, s); break;
-        case O64x64:   rc = launch<2, 2, 2, 2>(a, s); break;
-        case O128x32:  rc = launch<2, 2, 4, 1>(a, s); break;
+    switch (c.family) {
+        case CID_GEMM_FAMILY_GEGLU_H32:
+            a.n_begin = 0; a.n_end = a.N;
+            rc = cidg::launch_geglu_h32(a, s);
+            break;
+        case CID_GEMM_FAMILY_IGEMM_ATT:
+            if (cfg == G128x128) rc = launch_att<2, 4, 4, 2, 64>(a, s);
+            else if (cfg == B128x160) rc = a.dhead == 80 ? launch_att<2, 5, 4, 2, 80>(a, s) : launch_att<2, 5, 4, 2, 160>(a, s);
+            else rc = a.dhead == 80 ? launch_att<2, 5, 2, 2, 80>(a, s) : launch_att<2, 5, 2, 2, 160>(a, s);
+            break;
+        case CID_GEMM_FAMILY_CONV_H32:
+        case CID_GEMM_FAMILY_CONV_H32_PHASE:
+            a.n_begin = 0; a.n_end = a.N;
+            rc = cidg::launch_conv_h32(a, c.bm, s);
+            break;
+        case CID_GEMM_FAMILY_IGEMM_HALO:
+            rc = launch_halo<4, 5, 4, 2>(a, s);
+            break;
+        default:
+            if (c.act) {
+                switch (cfg) {
+                    case A256x160: rc = launch_act<4, 5, 4, 2>(a, s); break;
+                    case B128x160: rc = launch_act<2, 5, 4, 2>(a, s); break;
+                    case C64x160:  rc = launch_act<2, 5, 2, 2>(a, s); break;
+                    case G256x128: rc = launch_act<4, 4, 4, 2>(a, s); break;
+                    case G128x128: rc = launch_act<2, 4, 4, 2>(a, s); break;
+                    case O64x64:   rc = launch_act<2, 2, 2, 2>(a, s); break;
+                    case O128x32:  rc = launch_act<2, 2, 4, 1>(a, s); break;
+                }
+            } else {
+                switch (cfg) {
+                    case A256x160: rc = launch<4, 5, 4, 2>(a, s); break;
+                    case B128x160: rc = launch<2, 5, 4, 2>(a, s); break;
+                    case C64x160:  rc = launch<2, 5, 2, 2>(a, s); break;
+                    case G256x128: rc = launch<4, 4, 4, 2>(a, s); break;
+                    case G128x128: rc = launch<2, 4, 4, 2>(a, s); break;
+                    case O64x64:   rc = launch<2, 2, 2, 2>(a, s); break;
+                    case O128x32:  rc = launch<2, 2, 4, 1>(a, s); break;
+                }
+            }
+            break;
     }
     if (rc) return rc;
     CID_CHECK_LAUNCH("cid_gemm_f16");

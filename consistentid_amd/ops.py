@@ -38,6 +38,70 @@ def dvp_of(d: int) -> int:
 
 
 # --------------------------------------------------------------------------- GEMM / conv
+_DUMMY = 64      # a 16-byte-aligned stand-in address for gemm_plan (the planner tests pointers for NULL and alignment only)
+
+
+def _addr(t, name: str, dtype=torch.float16, check_tensor: bool = True) -> Optional[int]:
+    """device address of an operand: a tensor (checked), None, or -- for :func:`gemm_plan` -- True / an integer address"""
+    if t is None:
+        return None
+    if isinstance(t, torch.Tensor):
+        if check_tensor:
+            _req(t, name, dtype)
+        return t.data_ptr()
+    return _DUMMY if t is True else int(t)
+
+
+def _gemm_desc(x1, w, out, *, M: int, N: int, c1: int, ld1: Optional[int] = None,
+               x2=None, c2: int = 0, ld2: Optional[int] = None, ldo: Optional[int] = None,
+               bias=None, rowbias=None, ld_rowbias: int = 0,
+               rows_per_sample: int = 1, res=None, ldr: Optional[int] = None,
+               taps: int = 1, Hi: int = 0, Wi: int = 0, Ho: int = 0, Wo: int = 0, stride: int = 1, up: int = 0,
+               mode: int = 0, vt=None, n_vt0: int = 0, heads: int = 0, dhead: int = 0,
+               ntok: int = 0, ws=None, ln=None, att=None,
+               out2=None, pad_mode: int = 0, act: int = 0, w_up4=None, ws_bytes: Optional[int] = None,
+               check_tensors: bool = True) -> GemmDesc:
+    """The cid_gemm_desc of a :func:`gemm` / :func:`gemm_plan` call (everything but gn_stats, which the caller attaches)."""
+    a = lambda t, name, dtype=torch.float16: _addr(t, f"gemm.{name}", dtype, check_tensors)
+    d = GemmDesc()
+    d.x1, d.w, d.out = a(x1, "x1"), a(w, "w"), a(out, "out")
+    d.x2, d.bias, d.rowbias, d.res = a(x2, "x2"), a(bias, "bias"), a(rowbias, "rowbias"), a(res, "res")
+    d.vt, d.out2, d.w_up4 = a(vt, "vt"), a(out2, "out2"), a(w_up4, "w_up4")
+    d.c1, d.c2 = c1, c2
+    d.ld1 = ld1 if ld1 is not None else c1
+    d.ld2 = ld2 if ld2 is not None else c2
+    n_out = N // 2 if mode == 1 else (n_vt0 if mode == 2 else N)
+    d.ldo = ldo if ldo is not None else n_out
+    d.ld_rowbias, d.rows_per_sample = ld_rowbias, rows_per_sample
+    d.ldr = ldr if ldr is not None else N
+    d.M, d.N, d.taps = M, N, taps
+    d.Hi, d.Wi, d.Ho, d.Wo, d.stride, d.up = Hi, Wi, Ho, Wo, stride, up
+    d.pad_mode = pad_mode
+    d.act = act
+    d.mode = mode
+    d.n_vt0, d.heads, d.dhead, d.dvp, d.ntok = n_vt0, heads, dhead, dvp_of(dhead) if dhead else 0, ntok
+    if ws is not None:
+        if isinstance(ws, torch.Tensor):
+            d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
+        else:
+            d.ws, d.ws_bytes = _DUMMY, int(ws_bytes or 0)
+    if att is not None:
+        kp, vp, kvrow, n_txt, n_ip, ip_scale = (True, True, True, 77, 4, 1.0) if att is True else att
+        d.att_kp, d.att_vp, d.att_kvrow = a(kp, "att_kp"), a(vp, "att_vp"), a(kvrow, "att_kvrow", torch.int32)
+        d.att_n_txt, d.att_n_ip, d.att_ip_scale = int(n_txt), int(n_ip), float(ip_scale)
+    if ln is not None:
+        ls, lb, eps = (True, True, LN_EPS) if ln is True else ln
+        d.ln_s, d.ln_b, d.ln_eps = a(ls, "ln_s", torch.float32), a(lb, "ln_b", torch.float32), float(eps)
+    return d
+
+
+def _stats_rows(rows: int, gn_hw: int, act: int) -> int:
+    """tile height of the GroupNorm statistics :func:`gemm` attaches for a consumer over ``gn_hw`` tokens per sample (0 = none)"""
+    if gn_hw > GN_SMALL_MAX_HW and GN_EPILOGUE_STATS and not act and rows > 0 and gn_hw % rows == 0:
+        return rows                # (smaller samples: cid_groupnorm_f16 is one launch anyway)
+    return 0
+
+
 def gemm(x1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int, c1: int, ld1: Optional[int] = None,
          x2: Optional[torch.Tensor] = None, c2: int = 0, ld2: Optional[int] = None, ldo: Optional[int] = None,
          bias: Optional[torch.Tensor] = None, rowbias: Optional[torch.Tensor] = None, ld_rowbias: int = 0,
@@ -61,49 +125,17 @@ def gemm(x1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
     runs as four 2x2 phase convolutions at input resolution where the library can tile it so, from ``w`` otherwise."""
     lib = _lib.load()
     for name, t in (("x1", x1), ("w", w), ("out", out)):
-        _req(t, f"gemm.{name}")
-    for name, t in (("x2", x2), ("bias", bias), ("rowbias", rowbias), ("res", res), ("vt", vt), ("out2", out2), ("w_up4", w_up4)):
-        if t is not None:
-            _req(t, f"gemm.{name}")
-    d = GemmDesc()
-    d.out2 = _p(out2)
-    d.x1, d.x2 = _p(x1), _p(x2)
-    d.c1, d.c2 = c1, c2
-    d.ld1 = ld1 if ld1 is not None else c1
-    d.ld2 = ld2 if ld2 is not None else c2
-    d.w = _p(w)
-    d.out = _p(out)
-    n_out = N // 2 if mode == 1 else (n_vt0 if mode == 2 else N)
-    d.ldo = ldo if ldo is not None else n_out
-    d.bias = _p(bias)
-    d.rowbias, d.ld_rowbias, d.rows_per_sample = _p(rowbias), ld_rowbias, rows_per_sample
-    d.res = _p(res)
-    d.ldr = ldr if ldr is not None else N
-    d.M, d.N, d.taps = M, N, taps
-    d.Hi, d.Wi, d.Ho, d.Wo, d.stride, d.up = Hi, Wi, Ho, Wo, stride, up
-    d.pad_mode = pad_mode
-    d.act = act
-    d.w_up4 = _p(w_up4)
-    d.mode = mode
-    d.vt, d.n_vt0, d.heads, d.dhead, d.dvp, d.ntok = _p(vt), n_vt0, heads, dhead, dvp_of(dhead) if dhead else 0, ntok
-    if ws is not None:
-        d.ws, d.ws_bytes = ws.data_ptr(), ws.numel() * ws.element_size()
-    if att is not None:
-        kp, vp, kvrow, n_txt, n_ip, ip_scale = att
-        _req(kp, "gemm.att_kp")
-        _req(vp, "gemm.att_vp")
-        _req(kvrow, "gemm.att_kvrow", torch.int32)
-        d.att_kp, d.att_vp, d.att_kvrow = kp.data_ptr(), vp.data_ptr(), kvrow.data_ptr()
-        d.att_n_txt, d.att_n_ip, d.att_ip_scale = int(n_txt), int(n_ip), float(ip_scale)
-    if ln is not None:
-        ls, lb, eps = ln
-        _req(ls, "gemm.ln_s", torch.float32)
-        _req(lb, "gemm.ln_b", torch.float32)
-        d.ln_s, d.ln_b, d.ln_eps = ls.data_ptr(), lb.data_ptr(), float(eps)
+        if not isinstance(t, torch.Tensor):
+            raise _lib.CidError(f"gemm.{name}: a tensor is required (addresses are for gemm_plan)")
+    d = _gemm_desc(x1, w, out, M=M, N=N, c1=c1, ld1=ld1, x2=x2, c2=c2, ld2=ld2, ldo=ldo, bias=bias, rowbias=rowbias,
+                   ld_rowbias=ld_rowbias, rows_per_sample=rows_per_sample, res=res, ldr=ldr, taps=taps, Hi=Hi, Wi=Wi, Ho=Ho,
+                   Wo=Wo, stride=stride, up=up, mode=mode, vt=vt, n_vt0=n_vt0, heads=heads, dhead=dhead, ntok=ntok, ws=ws,
+                   ln=ln, att=att, out2=out2, pad_mode=pad_mode, act=act, w_up4=w_up4)
     stats = None
-    if gn_hw > GN_SMALL_MAX_HW and GN_EPILOGUE_STATS and not act:      # (smaller samples: cid_groupnorm_f16 is one launch anyway)
-        rows = int(lib.cid_gemm_stats_rows(C.byref(d)))
-        if rows > 0 and gn_hw % rows == 0:
+    rows = 0
+    if gn_hw > GN_SMALL_MAX_HW:
+        rows = _stats_rows(int(lib.cid_gemm_stats_rows(C.byref(d))), gn_hw, act)
+        if rows > 0:
             stats = torch.empty(M // rows, 32, 2, dtype=torch.float32, device=out.device)
             d.gn_stats = stats.data_ptr()
     check(lib.cid_gemm_f16(C.byref(d), _stream()), "cid_gemm_f16")
@@ -112,6 +144,24 @@ def gemm(x1: torch.Tensor, w: torch.Tensor, out: torch.Tensor, *, M: int, N: int
     elif hasattr(out, "_gn_stats"):
         del out._gn_stats            # a reused output tensor must not carry the statistics of what it held before
     return out
+
+
+def gemm_plan(x1=True, w=True, out=True, **kw) -> dict:
+    """What :func:`gemm` with the same keywords would launch (cid_gemm_plan: host code, no launch, no GPU needed): ``family``
+    (one of ``_lib.GEMM_FAMILIES``), tile ``bm`` x ``bn``, ``splitk``, ``nloop``, ``nbuf``, the ``ln`` / ``act`` / ``vmode``
+    instance flags, ``splitk_epilogue``, ``stats_rows`` (tile height if the launch can emit GroupNorm statistics, else 0) and
+    ``stats`` (whether :func:`gemm` would attach them for this ``gn_hw``).  Every operand may be a tensor, ``True`` (present,
+    at a dummy 16-byte-aligned address) or None; ``ws=True`` takes its size from ``ws_bytes``, ``ln=True`` / ``att=True``
+    stand for present operands with the usual constants.  Raises CidError where :func:`gemm` would."""
+    lib = _lib.load()
+    gn_hw = kw.pop("gn_hw", 0)
+    d = _gemm_desc(x1, w, out, check_tensors=False, **kw)
+    info = _lib.GemmPlanInfo()
+    check(lib.cid_gemm_plan(C.byref(d), C.byref(info)), "cid_gemm_plan")
+    plan = {n: int(getattr(info, n)) for n, _ in info._fields_}
+    plan["family"] = _lib.GEMM_FAMILIES[plan["family"]]
+    plan["stats"] = int(_stats_rows(plan["stats_rows"], gn_hw, d.act) > 0)
+    return plan
 
 
 def upconv_fold(w: torch.Tensor) -> torch.Tensor:

@@ -27,7 +27,8 @@ extern "C" {
 typedef void* cid_stream_t;      /* hipStream_t */
 typedef uint16_t cid_half;       /* IEEE binary16 bit pattern */
 
-int cid_version(void);          /* 103: cid_gemm_desc grew a trailing w_up4 pointer (102: act, 101: pad_mode; set them or zero the struct) */
+int cid_version(void);          /* 104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
+                                 * pointer (102: act, 101: pad_mode; set them or zero the struct) */
 const char* cid_last_error(void);
 
 /* ---------------------------------------------------------------------------
@@ -84,7 +85,8 @@ typedef struct cid_gemm_desc {
     /* GroupNorm statistics of `out` for its consumer (D: ResnetBlock2D.norm1 / norm2, Transformer2DModel.norm,
      * conv_norm_out read what a conv / proj_out just wrote): fp32 [M / rows][32][2] = (sum, sum of squares) of the fp16
      * outputs over `rows` consecutive tokens x N / 32 consecutive channels, rows = cid_gemm_stats_rows(d) (> 0 required);
-     * consumed by cid_groupnorm_stats_f16.  mode 0 only. */
+     * consumed by cid_groupnorm_stats_f16.  mode 0 only.  (A launch that runs from w_up4 blocks them by its tiles instead:
+     * `rows` outputs of ONE parity of one image, ordered image, parity, tile -- the same sums per sample.) */
     float* gn_stats;
     /* mode 3 */
     const cid_half* att_kp; const cid_half* att_vp; const int32_t* att_kvrow;
@@ -120,6 +122,28 @@ int cid_gemm_f16(const cid_gemm_desc* d, cid_stream_t stream);
 /* Token rows per statistics block if cid_gemm_f16(d) can emit gn_stats (its tile height), 0 if it cannot (split-K,
  * tile widths off the 160-channel grid, ragged M): the caller then lets cid_groupnorm_f16 take its own statistics. */
 int cid_gemm_stats_rows(const cid_gemm_desc* d);
+/* What cid_gemm_f16(d) would launch (since cid_version() 104).  Host code only: it runs the same argument checks and the same
+ * plan and kernel choice as the call itself (one function decides both), launches nothing and needs no GPU; pointers are only
+ * tested for NULL and alignment.  Returns what cid_gemm_f16 would return before launching (0, or -22 with cid_last_error()). */
+enum {
+    CID_GEMM_FAMILY_IGEMM = 0,           /* gather kernel (csrc/gemm.hip igemm_kernel) */
+    CID_GEMM_FAMILY_IGEMM_HALO = 1,      /* stride-1 3x3 halo kernel (igemm_halo_kernel) */
+    CID_GEMM_FAMILY_CONV_H32 = 2,        /* csrc/conv3x3.hip, nine taps */
+    CID_GEMM_FAMILY_CONV_H32_PHASE = 3,  /* csrc/conv3x3.hip, four 2x2 phase convolutions from w_up4 */
+    CID_GEMM_FAMILY_GEGLU_H32 = 4,       /* csrc/linear_h32.hip */
+    CID_GEMM_FAMILY_IGEMM_ATT = 5        /* gather kernel with the attention epilogue (mode 3) */
+};
+typedef struct cid_gemm_plan_info {
+    int32_t family;            /* CID_GEMM_FAMILY_* */
+    int32_t bm, bn;            /* tile: token rows x weight rows (mode 1: interleaved value / gate rows) */
+    int32_t splitk;            /* K partitions (gridDim.z); > 1 needs ws */
+    int32_t nloop;             /* n-tiles walked by one workgroup (GEGLU launches) */
+    int32_t nbuf;              /* LDS ring stages of the gather kernels (2 | 3); 0 for the families that fix their own staging */
+    int32_t ln, act, vmode;    /* LayerNorm-fold instance; ReLU instance; a second launch writes the transposed V third (mode 2) */
+    int32_t splitk_epilogue;   /* the split-K reduction kernel follows the launch */
+    int32_t stats_rows;        /* cid_gemm_stats_rows(d): tile height if gn_stats can be emitted, else 0 */
+} cid_gemm_plan_info;
+int cid_gemm_plan(const cid_gemm_desc* d, cid_gemm_plan_info* out);
 /* Fold the packed nine-tap weights w[N][9][C] (tap = 3 ty + tx) of an Upsample2D convolution into w4[4][N][4][C] for
  * cid_gemm_desc.w_up4: parity = 2 py + px, tap4 = 2 ry + rx.  Along y, parity 0 reads input rows (y - 1, y) with taps
  * ({0}, {1, 2}), parity 1 reads rows (y, y + 1) with taps ({0, 1}, {2}); the same along x.  Every entry is the fp32 sum of

@@ -76,12 +76,13 @@ def test_python_front_end_refuses_cpu_tensors(lib):
 
 
 def test_conv_tile_plan_without_gpu(lib):
-    """cid_gemm_stats_rows is host code: it runs plan_gemm and reports the tile height a launch would use for GroupNorm
-    statistics -- which doubles as a probe of the convolution tile rules (csrc/gemm.hip plan_gemm, csrc/conv3x3.hip):
-    256-token tiles where they fill the chip, 128-token tiles for short K, no statistics from split-K launches."""
-    from consistentid_amd._lib import GemmDesc
+    """cid_gemm_plan / cid_gemm_stats_rows are host code: they run plan_gemm and report the launch a call would make and the
+    tile height it would use for GroupNorm statistics -- a probe of the convolution tile rules (csrc/gemm.hip plan_gemm,
+    csrc/conv3x3.hip): 256-token tiles where they fill the chip, 128-token tiles for short K, no statistics from split-K
+    launches, strided convolutions on the gather kernel."""
+    from consistentid_amd._lib import GEMM_FAMILIES, GemmDesc, GemmPlanInfo
 
-    def rows(B, side, cin, cout, up=0, stride=1, taps=9, ws=True):
+    def plan(B, side, cin, cout, up=0, stride=1, taps=9, ws=True):
         d = GemmDesc()
         d.x1, d.w, d.out = 64, 64, 64
         so = side << up if stride == 1 else side // 2
@@ -90,17 +91,44 @@ def test_conv_tile_plan_without_gpu(lib):
         d.Hi, d.Wi, d.Ho, d.Wo, d.stride, d.up = side, side, so, so, stride, up
         if ws:
             d.ws, d.ws_bytes = 64, 64 << 20
-        return lib.cid_gemm_stats_rows(C.byref(d))
+        info = GemmPlanInfo()
+        assert lib.cid_gemm_plan(C.byref(d), C.byref(info)) == 0, lib.cid_last_error()
+        assert info.stats_rows == lib.cid_gemm_stats_rows(C.byref(d))       # (the older query is a thin caller of the new one)
+        assert info.splitk_epilogue == int(info.splitk > 1) and info.bn == 160 and (info.ln, info.act, info.vmode, info.nloop) == (0, 0, 0, 1)
+        return info
+
+    def rows(*a, **kw):
+        return plan(*a, **kw).stats_rows
+
+    def launch(*a, **kw):
+        p = plan(*a, **kw)
+        return GEMM_FAMILIES[p.family], p.bm, p.splitk
 
     assert rows(8, 64, 320, 320) == 256          # level 0: 256 tiles of 256 tokens (conv3x3.hip)
+    assert launch(8, 64, 320, 320) == ("conv_h32", 256, 1)
     assert rows(8, 64, 960, 320) == 256
+    assert launch(8, 64, 960, 320) == ("conv_h32", 256, 1)
     assert rows(4, 64, 320, 320) == 128          # CFG-deduplicated level 0: 128-token tiles, five channel slabs
+    assert launch(4, 64, 320, 320) == ("conv_h32", 128, 1)
     assert rows(8, 32, 640, 640) == 128          # 32 x 32 level, ten channel slabs
+    assert launch(8, 32, 640, 640) == ("conv_h32", 128, 1)
     assert rows(8, 32, 1280, 640) == 0           # ... twenty: halo kernel + split-K, no statistics
+    assert launch(8, 32, 1280, 640) == ("igemm_halo", 256, 2)
     assert rows(8, 32, 1280, 1280) == 256        # (1280 output channels: 256 tiles again)
+    assert launch(8, 32, 1280, 1280) == ("conv_h32", 256, 1)
     assert rows(8, 16, 1280, 1280) == 0          # 16 x 16 level: split-K
+    assert launch(8, 16, 1280, 1280) == ("igemm_halo", 256, 4)
     assert rows(8, 32, 640, 640, up=1) == 256    # Upsample2D conv 32 -> 64: 512 tiles of 256 output tokens
+    assert launch(8, 32, 640, 640, up=1) == ("conv_h32", 256, 1)
     assert rows(8, 16, 1280, 1280, up=1) == 256
+    assert launch(8, 16, 1280, 1280, up=1) == ("conv_h32", 256, 1)
     assert rows(8, 8, 1280, 1280, up=1) == 0     # 8 -> 16: 64 tiles, split-K
+    assert launch(8, 8, 1280, 1280, up=1) == ("igemm", 256, 4)
     assert rows(4, 128, 320, 320) == 128         # SDXL 128 x 128 level: a 256-token halo would be 520 rows (> 400)
-    assert rows(8, 64, 320, 320, stride=2) in (0, 256, 128)     # (strided convolutions stay on the gather path; any tile)
+    assert launch(4, 128, 320, 320) == ("conv_h32", 128, 1)
+    # strided convolutions (the UNets' Downsample2D at CFG batch 8) stay on the gather kernel: 256 x 160 tiles, split-K up to
+    # 256 workgroups, its reduction kernel, the three-stage ring; no statistics
+    for side, c, sk in ((64, 320, 4), (32, 640, 8), (16, 1280, 16)):
+        p = plan(8, side, c, c, stride=2)
+        assert (GEMM_FAMILIES[p.family], p.bm, p.bn, p.splitk, p.splitk_epilogue, p.nbuf, p.stats_rows) == ("igemm", 256, 160, sk, 1, 3, 0)
+    assert launch(8, 64, 320, 320, stride=2, ws=False) == ("igemm", 64, 1)       # (without a workspace: unsplit 64-token tiles)

@@ -1,0 +1,103 @@
+"""Host checks of the GEMM dispatcher (no GPU): cid_gemm_plan / ops.gemm_plan report what cid_gemm_f16 would launch -- the
+launch reads the same decision (csrc/gemm.hip decide_launch) -- so the planner can be held to the census of the launches the
+models make (tests/golden/gemm_calls.json, tests/gemm_census.py) anywhere."""
+import ctypes as C
+
+import pytest
+
+import gemm_census
+
+FIXTURE = gemm_census.load()
+RECORDS = gemm_census.all_records(FIXTURE)
+KEYS = gemm_census.keys_of(RECORDS)
+
+
+def test_fixture_plans_match_planner(lib):
+    """Planner drift: every recorded descriptor must still plan to the recorded launch (family, tile, split-K, N-loop, ring
+    depth, instance flags, statistics).  A rule change that moves a model's shape shows here, with the shape."""
+    moved = []
+    for wl, rows in FIXTURE.items():
+        for rec, plan in rows:
+            now = dict(zip(gemm_census.PLAN_FIELDS, gemm_census.plan_of(rec)))
+            if now != plan:
+                diff = {k: (plan[k], now[k]) for k in plan if plan[k] != now[k]}
+                moved.append(f"{wl}: {gemm_census.variant_key(rec, plan)} M={rec['M']} N={rec['N']} K={rec['taps'] * (rec['c1'] + rec['c2'])}"
+                             f" (recorded, now): {diff}")
+    assert not moved, f"{len(moved)} of {len(RECORDS)} recorded launches plan differently now:\n  " + "\n  ".join(moved[:40]) + \
+                      f"\nif the change is meant, regenerate the fixture: {gemm_census.REGENERATE}"
+
+
+def test_fixture_is_the_census_it_claims_to_be(lib):
+    """integers only, every workload present, and the launches the census was built to pin are in it by name"""
+    assert set(FIXTURE) == {"sd15_512x512_cfg8", "sd15_512x512_cfg2", "sd15_512x768_cfg2", "sd15_controlnet_inpaint_cfg16",
+                            "sdxl_1024x1024_cfg4", "sdxl_864x1152_cfg2", "vae_decode_512x512", "vae_encode_512x512", "clip_text_l",
+                            "clip_text_bigg", "clip_vision_vit_h", "id_stack", "bisenet_512x512"}
+    assert all(rows for rows in FIXTURE.values())
+    assert all(type(v) is int for rec, plan in RECORDS for v in list(rec.values()) + list(plan.values()))
+    families = {gemm_census.families()[p["family"]] for _, p in RECORDS}
+    assert families == set(gemm_census.families()), f"families no workload reaches: {set(gemm_census.families()) - families}"
+    # the UNets' Downsample2D convolutions (stride 2, pad 1, 320 / 640 / 1280 channels) at the benchmark's CFG batch:
+    # 256x160 gather tiles, nine taps, split-K with its epilogue kernel, three-stage ring
+    down = [(r, p) for r, p in FIXTURE["sd15_512x512_cfg8"] if r["taps"] == 9 and r["stride"] == 2]
+    assert sorted(r["N"] for r, _ in down) == [320, 640, 1280]
+    for r, p in down:
+        assert (gemm_census.families()[p["family"]], p["bm"], p["bn"], p["nbuf"], p["splitk_epilogue"]) == ("igemm", 256, 160, 3, 1) \
+            and p["splitk"] > 1, (r, p)
+        assert gemm_census.variant_key(r, p) == "igemm-256x160-nb3-m0-t9-s2-u0-p0-sk-bias"
+
+
+def test_every_reached_variant_has_a_parity_case(lib):
+    """Every variant key of the census is either a case of test_gpu_gemm_census.test_variant_parity or, for mode 3 (the
+    attention epilogue, which a descriptor alone cannot drive), the key of a launch test_id_cross_attention makes."""
+    import test_gpu_gemm_census as table
+    from test_gpu_kernels import XATTN_CASES, xattn_mode3_launches
+    mode3 = set()
+    for case in XATTN_CASES:
+        for kw in xattn_mode3_launches(*case):
+            rec = gemm_census.record_of(**dict(kw, att=True, ln=True if kw["ln"] else None))
+            plan = dict(zip(gemm_census.PLAN_FIELDS, gemm_census.plan_of(rec)))
+            mode3.add(gemm_census.variant_key(rec, plan))
+    assert mode3, "test_id_cross_attention makes no mode-3 launch"
+    covered = set(table.TABLE) | mode3
+    assert all(KEYS[k][0]["mode"] != 3 for k in table.TABLE) and all(k.startswith("igemm_att-") for k in mode3)
+    uncovered = sorted(set(KEYS) - covered)
+    print(f"[census] {len(KEYS)} variant keys: {len(table.TABLE)} table cases, {len(set(KEYS) & mode3)} matched by test_id_cross_attention")
+    assert not uncovered, "launch variants the models reach without a parity case (add a test_id_cross_attention " \
+                          f"parametrization for a mode-3 key):\n  " + "\n  ".join(uncovered)
+    assert "igemm-256x160-nb3-m0-t9-s2-u0-p0-sk-bias" in table.TABLE
+
+
+def test_gemm_plan_argument_validation(lib):
+    from consistentid_amd import ops
+    from consistentid_amd._lib import CidError, GemmDesc, GemmPlanInfo
+    info = GemmPlanInfo()
+    d = GemmDesc()
+    assert lib.cid_gemm_plan(C.byref(d), None) == -22 and b"null output" in lib.cid_last_error()
+    assert lib.cid_gemm_plan(None, C.byref(info)) == -22 and b"null pointer" in lib.cid_last_error()
+    assert lib.cid_gemm_plan(C.byref(d), C.byref(info)) == -22 and b"null pointer" in lib.cid_last_error()
+    d.x1, d.w, d.out = 64, 64, 64
+    d.c1, d.ld1, d.ldo, d.M, d.N, d.taps = 320, 320, 320, 256, 320, 1
+    assert lib.cid_gemm_plan(C.byref(d), C.byref(info)) == 0
+    assert (info.family, info.bm, info.bn, info.splitk, info.nloop, info.nbuf) == (0, 64, 160, 1, 1, 2)
+    assert info.stats_rows == lib.cid_gemm_stats_rows(C.byref(d)) == 64
+    # the query refuses what the launch refuses, with the launch's message
+    d.taps = 3
+    assert lib.cid_gemm_plan(C.byref(d), C.byref(info)) == -22 and b"taps must be 1 or 9" in lib.cid_last_error()
+    d.taps, d.out = 1, 72
+    assert lib.cid_gemm_plan(C.byref(d), C.byref(info)) == -22 and b"16-byte aligned" in lib.cid_last_error()
+    d.out, d.pad_mode = 64, 1
+    assert lib.cid_gemm_plan(C.byref(d), C.byref(info)) == -22 and b"pad_mode 1 needs" in lib.cid_last_error()
+    d.pad_mode, d.act, d.ws, d.ws_bytes = 0, 1, 64, 1 << 20
+    assert lib.cid_gemm_plan(C.byref(d), C.byref(info)) == -22 and b"act 1 needs" in lib.cid_last_error()
+    d.act, d.gn_stats, d.N, d.ldo = 0, 64, 96, 96          # statistics from a launch off the 160-channel grid
+    assert lib.cid_gemm_plan(C.byref(d), C.byref(info)) == -22 and b"cannot emit" in lib.cid_last_error()
+    # the wrapper: dummy operands, the launch's errors as CidError, statistics only for a consumer that takes them
+    p = ops.gemm_plan(M=8 * 4096, N=320, c1=320, taps=9, Hi=64, Wi=64, Ho=64, Wo=64, bias=True, gn_hw=4096)
+    assert (p["family"], p["bm"], p["bn"], p["stats_rows"], p["stats"]) == ("conv_h32", 256, 160, 256, 1)
+    assert ops.gemm_plan(M=8 * 4096, N=320, c1=320, taps=9, Hi=64, Wi=64, Ho=64, Wo=64, bias=True, gn_hw=0)["stats"] == 0
+    with pytest.raises(CidError, match="c2 > 0 needs x2"):
+        ops.gemm_plan(M=256, N=320, c1=320, c2=320)
+    with pytest.raises(CidError, match="mode 3 needs att_kp"):
+        ops.gemm_plan(M=1024, N=640, c1=640, mode=3, heads=8, dhead=80, ntok=1024)
+    with pytest.raises(CidError, match="a tensor is required"):
+        ops.gemm(True, True, True, M=256, N=320, c1=320)

@@ -16,17 +16,39 @@ def rnd(*shape, seed=0, scale=1.0):
     return (torch.randn(*shape, generator=g) * scale).half()
 
 
+def plan_tag(*operands, **kw):
+    """what ``ops.gemm`` with these arguments launches (ops.gemm_plan: the dispatcher's own decision), as the short text the
+    PLAN tables below state per case: family, tile, split-K, N-loop, three-stage ring"""
+    from consistentid_amd import ops
+    p = ops.gemm_plan(*operands, **kw)
+    return " ".join([p["family"], f"{p['bm']}x{p['bn']}"] + [f"sk{p['splitk']}"] * (p["splitk"] > 1)
+                    + [f"nl{p['nloop']}"] * (p["nloop"] > 1) + ["nb3"] * (p["nbuf"] == 3))
+
+
 # ----------------------------------------------------------------------------- GEMM
+LINEAR_PLANS = {      # what each case below launches (asserted through ops.gemm_plan)
+    (300, 320, 320): "igemm 64x160",
+    (6400, 640, 128): "igemm 64x160",
+    (8192, 640, 320): "igemm 128x160",
+    (25600, 320, 64): "igemm 128x160",
+    (100, 96, 64): "igemm 128x32",
+    (2048, 1280, 2560): "igemm 256x160 sk4 nb3",
+    (512, 1280, 11520): "igemm 256x160 sk16 nb3",
+}
+
+
 @pytest.mark.parametrize("M,N,K,bias,res", [
     (300, 320, 320, True, True),        # 64x160 tiles, ragged M
-    (6400, 640, 128, True, False),      # 128x160 tiles
-    (25600, 320, 64, False, True),      # 128x320 tiles
-    (100, 96, 64, True, False),         # 64x64 tiles (odd width)
-    (2048, 1280, 2560, True, True),     # deep K, split-K
-    (512, 1280, 11520, True, False),    # 8x8 level conv-sized K, split-K 8
+    (6400, 640, 128, True, False),      # 64x160 tiles (400 of them; two channel slabs)
+    (8192, 640, 320, True, False),      # 128x160 tiles (256 of them): the UNets' 320 -> 640 shortcut at CFG batch 8
+    (25600, 320, 64, False, True),      # 128x160 tiles
+    (100, 96, 64, True, False),         # 128x32 tiles (a width off the 64 grid)
+    (2048, 1280, 2560, True, True),     # deep K, 256x160 tiles, split-K 4
+    (512, 1280, 11520, True, False),    # 8x8 level conv-sized K, split-K 16
 ])
 def test_gemm_linear(dev, M, N, K, bias, res):
     from consistentid_amd import ops
+    assert plan_tag(M=M, N=N, c1=K, bias=bias or None, res=res or None, ws=True, ws_bytes=64 << 20) == LINEAR_PLANS[M, N, K]
     x, w = rnd(M, K, seed=1), rnd(N, K, seed=2, scale=K ** -0.5)
     b = rnd(N, seed=3) if bias else None
     r = rnd(M, N, seed=4) if res else None
@@ -43,11 +65,21 @@ def test_gemm_linear(dev, M, N, K, bias, res):
     check_close(out, ref, f"gemm {M}x{N}x{K}")
 
 
+GEGLU_PLANS = {      # what each GEGLU case of the two tests below launches (asserted through ops.gemm_plan)
+    (512, 64): "igemm 128x128", (25600, 64): "igemm 128x128", (3000, 320): "igemm 128x128",
+    (32768, 320): "igemm 128x128 nl10", (8192, 640): "igemm 128x128 nl5", (2048, 1280): "geglu_h32 256x160 nl2",
+    (4096 + 128, 320): "igemm 128x128",
+    (65536, 320): "igemm 128x128 nl20", (16384, 640): "igemm 128x128 nl10",
+}
+
+
 @pytest.mark.parametrize("M,C", [(512, 64), (25600, 64), (3000, 320),
-                                 # the UNet's own shapes: N-loop launches (one workgroup walks 10 / 5 / 2 n-tiles of its token tile)
+                                 # the UNet's own shapes: N-loop launches (one workgroup walks 10 / 5 n-tiles of its token tile;
+                                 # at 1280 channels two 160-wide n-tiles of linear_h32.hip); 4096 + 128: ragged M, no N-loop
                                  (32768, 320), (8192, 640), (2048, 1280), (4096 + 128, 320)])
 def test_gemm_geglu(dev, M, C):
     from consistentid_amd import ops, weights
+    assert plan_tag(M=M, N=8 * C, c1=C, bias=True, mode=1) == GEGLU_PLANS[M, C]
     x, w, b = rnd(M, C, seed=1), rnd(8 * C, C, seed=2, scale=C ** -0.5), rnd(8 * C, seed=3)
     h, gate = (x.float() @ w.float().T + b.float()).chunk(2, dim=-1)
     ref = h * F.gelu(gate)
@@ -58,15 +90,18 @@ def test_gemm_geglu(dev, M, C):
     check_close(out, ref, f"geglu M={M} C={C}")
 
 
-@pytest.mark.parametrize("M,C,bias", [(65536, 320, True),     # 256 workgroups of linear_h32.hip walking all 16 n-tiles (CFG batch 16)
-                                      (16384, 640, False),    # SDXL's 64 x 64 level at CFG batch 4, no bias
-                                      (2048, 1280, True)])    # two n-tiles per workgroup, twenty channel slabs
+@pytest.mark.parametrize("M,C,bias", [(65536, 320, True),     # short K (five channel slabs): the 16 x 16 x 32 kernel, N-loop of 20 (CFG batch 16)
+                                      (16384, 640, False),    # SDXL's 64 x 64 level at CFG batch 4, no bias: that kernel too, N-loop of 10
+                                      (2048, 1280, True)])    # linear_h32.hip: two n-tiles per workgroup, twenty channel slabs
 def test_gemm_geglu_h32(dev, M, C, bias):
     """The GEGLU launches of linear_h32.hip (32 x 32 x 16 MFMA tiles, wave roles, N-loop, in-lane value / gate pairing and the
-    lane-32 swap in front of the 16-byte stores): against the fp32 formula, bit-identical run to run, and within rounding of
-    the 16 x 16 x 32 kernel it replaces on these shapes (CID_GEGLU_H32=0 is read once per process, so that kernel is reached
-    through a shape it still owns: the same rows with a ragged tail)."""
+    lane-32 swap in front of the 16-byte stores; plan_gemm gives it K >= 1024 only) and the N-loop launches of the 16 x 16 x 32
+    kernel at the shorter K: against the fp32 formula, bit-identical run to run, and within rounding of the plain 16 x 16 x 32
+    launch on the same rows (CID_GEGLU_H32=0 is read once per process, so that launch is reached through a shape it still
+    owns: the same rows with a ragged tail)."""
     from consistentid_amd import ops, weights
+    assert plan_tag(M=M, N=8 * C, c1=C, bias=bias or None, mode=1) == GEGLU_PLANS[M, C]
+    assert plan_tag(M=M + 64, N=8 * C, c1=C, bias=bias or None, mode=1) == "igemm 128x128"
     x, w, b = rnd(M, C, seed=1), rnd(8 * C, C, seed=2, scale=C ** -0.5), rnd(8 * C, seed=3)
     pre = x.float() @ w.float().T + (b.float() if bias else 0.0)
     h, gate = pre.chunk(2, dim=-1)
@@ -214,13 +249,33 @@ def _tok(x):   # NCHW -> [B*HW, C]
     return x.permute(0, 2, 3, 1).reshape(-1, x.shape[1]).contiguous()
 
 
+CONV_PLANS = {      # what each case below launches (asserted through ops.gemm_plan)
+    (2, 64, 0, 64, 16, 1, 0): "igemm 64x64",
+    (2, 64, 0, 96, 16, 2, 0): "igemm 128x32",
+    (2, 64, 0, 64, 8, 1, 1): "igemm 64x64",
+    (1, 64, 64, 160, 12, 1, 0): "igemm 64x160 sk3",
+    (2, 320, 0, 320, 64, 1, 0): "igemm_halo 256x160 sk4",
+    (8, 320, 0, 320, 64, 1, 0): "conv_h32 256x160",
+    (8, 640, 0, 640, 32, 1, 0): "conv_h32 128x160",
+    (8, 1280, 0, 1280, 16, 1, 0): "igemm_halo 256x160 sk4",
+    (8, 1280, 640, 1280, 16, 1, 0): "igemm_halo 256x160 sk4",
+    (4, 320, 0, 320, 64, 1, 0): "conv_h32 128x160",
+    (8, 320, 320, 320, 64, 1, 0): "conv_h32 256x160",
+    (8, 640, 0, 640, 32, 1, 1): "conv_h32 256x160",
+    (8, 1280, 0, 1280, 16, 1, 1): "conv_h32 256x160",
+    (2, 320, 0, 640, 32, 1, 1): "conv_h32 128x160",
+    (3, 320, 320, 320, 32, 1, 1): "igemm 256x160 sk3 nb3",
+    (8, 1280, 1280, 1280, 8, 1, 0): "igemm_halo 256x160 sk16",
+}
+
+
 @pytest.mark.parametrize("B,C1,C2,Cout,H,stride,up", [
     (2, 64, 0, 64, 16, 1, 0),
-    (2, 64, 0, 96, 16, 2, 0),
+    (2, 64, 0, 96, 16, 2, 0),         # stride 2 on the 128x32 tiles (a width off the 64 grid)
     (2, 64, 0, 64, 8, 1, 1),
     (1, 64, 64, 160, 12, 1, 0),       # skip concat via two sources
-    (2, 320, 0, 320, 64, 1, 0),       # SD1.5 level-0 shape, 128x320 tiles need >= 200 tiles -> B*HW=8192/128*1 = 64 -> mid tiles
-    (8, 320, 0, 320, 64, 1, 0),       # 256x160 tiles
+    (2, 320, 0, 320, 64, 1, 0),       # SD1.5 level-0 shape at CFG batch 2: 64 tiles of 256 tokens, halo kernel + split-K 4
+    (8, 320, 0, 320, 64, 1, 0),       # 256x160 tiles of conv3x3.hip
     (8, 640, 0, 640, 32, 1, 0),       # 32 x 32 level: 128-token tiles of conv3x3.hip (256 of them)
     (8, 1280, 0, 1280, 16, 1, 0),     # 16 x 16 level: a tile = one whole image, split-K 4 (gemm.hip halo kernel)
     (8, 1280, 640, 1280, 16, 1, 0),   # ... with a skip concat (30 channel slabs over four slices: uneven)
@@ -229,7 +284,7 @@ def _tok(x):   # NCHW -> [B*HW, C]
     (8, 640, 0, 640, 32, 1, 1),       # Upsample2D conv 32 -> 64 (level 0): conv3x3.hip with an input-resolution halo, 512 tiles
     (8, 1280, 0, 1280, 16, 1, 1),     # ... 16 -> 32 (level 1): a tile = eight output rows, four input rows
     (2, 320, 0, 640, 32, 1, 1),       # ... on 128-token tiles (two output rows, one input row + frame)
-    (3, 320, 320, 320, 32, 1, 1),     # ... two sources, 96 tiles x 2 (odd sample count)
+    (3, 320, 320, 320, 32, 1, 1),     # ... two sources, odd sample count: 96 tiles, so the gather kernel + split-K 3
     (8, 1280, 1280, 1280, 8, 1, 0),   # 8x8 level, concat, split-K
 ])
 def test_gemm_conv3x3(dev, B, C1, C2, Cout, H, stride, up):
@@ -247,10 +302,11 @@ def test_gemm_conv3x3(dev, B, C1, C2, Cout, H, stride, up):
     Ho, Wo = ref.shape[-2:]
     M = B * Ho * Wo
     out = torch.empty(M, Cout, dtype=torch.float16, device=dev)
-    ops.gemm(_tok(x1).to(dev), weights._conv3(w, dev), out, M=M, N=Cout, c1=C1,
-             x2=_tok(x2).to(dev) if C2 else None, c2=C2, bias=b.to(dev), rowbias=temb.to(dev), ld_rowbias=Cout,
-             rows_per_sample=Ho * Wo, taps=9, Hi=H, Wi=Wd, Ho=Ho, Wo=Wo, stride=stride, up=up,
-             ws=torch.empty(64 << 20, dtype=torch.uint8, device=dev))
+    kw = dict(M=M, N=Cout, c1=C1, x2=_tok(x2).to(dev) if C2 else None, c2=C2, bias=b.to(dev), rowbias=temb.to(dev),
+              ld_rowbias=Cout, rows_per_sample=Ho * Wo, taps=9, Hi=H, Wi=Wd, Ho=Ho, Wo=Wo, stride=stride, up=up,
+              ws=torch.empty(64 << 20, dtype=torch.uint8, device=dev))
+    assert plan_tag(**kw) == CONV_PLANS[B, C1, C2, Cout, H, stride, up]
+    ops.gemm(_tok(x1).to(dev), weights._conv3(w, dev), out, **kw)
     torch.cuda.synchronize()
     check_close(out, _tok(ref), f"conv3x3 B{B} C{C1}+{C2}->{Cout} H{H} s{stride} up{up}")
 
@@ -409,11 +465,22 @@ def test_conv_out_shapes(dev, B, H, W, c, cout):
     assert torch.equal(outs[0], outs[1])
 
 
-@pytest.mark.parametrize("M,N,K,taps,H", [(8192, 320, 320, 1, 0),       # 256-token tiles, plain epilogue
-                                           (2048, 640, 640, 1, 0),       # 128-token tiles
+OUT2_PLANS = {      # what each case below launches (asserted through ops.gemm_plan)
+    (8192, 320, 320, 1): "igemm 64x160", (2048, 640, 640, 1): "igemm 64x160 nb3", (16384, 320, 320, 1): "igemm 128x160",
+    (512, 1280, 1280, 1): "igemm 64x160 sk3",
+    (2 * 64 * 64, 320, 320, 9): "igemm_halo 256x160 sk4", (2 * 32 * 32, 640, 640, 9): "igemm_halo 256x160 sk8",
+    (8 * 64 * 64, 320, 320, 9): "conv_h32 256x160", (4 * 64 * 64, 320, 320, 9): "conv_h32 128x160",
+}
+
+
+@pytest.mark.parametrize("M,N,K,taps,H", [(8192, 320, 320, 1, 0),       # 64-token tiles, plain epilogue
+                                           (2048, 640, 640, 1, 0),       # 64-token tiles, three-stage ring
+                                           (16384, 320, 320, 1, 0),      # 128-token tiles: the CFG-deduplicated level 0 at CFG batch 8
                                            (512, 1280, 1280, 1, 0),      # 64-token tiles / split-K epilogue
-                                           (2 * 64 * 64, 320, 320, 9, 64),   # conv3x3.hip, 256-token tiles
-                                           (2 * 32 * 32, 640, 640, 9, 32)])  # conv3x3.hip, 128-token tiles
+                                           (2 * 64 * 64, 320, 320, 9, 64),   # halo kernel + split-K epilogue
+                                           (2 * 32 * 32, 640, 640, 9, 32),   # ... with split-K 8
+                                           (8 * 64 * 64, 320, 320, 9, 64),   # conv3x3.hip, 256-token tiles
+                                           (4 * 64 * 64, 320, 320, 9, 64)])  # conv3x3.hip, 128-token tiles
 def test_gemm_second_destination(dev, M, N, K, taps, H):
     """cid_gemm_desc.out2: the producer writes its rows twice (the CFG duplication of a tensor both halves share) -- both
     copies bit-identical to the single-destination launch, on every epilogue that stores rows"""
@@ -426,6 +493,7 @@ def test_gemm_second_destination(dev, M, N, K, taps, H):
     one = torch.empty(M, N, dtype=torch.float16, device=dev)
     ops.gemm(x.to(dev), w.to(dev), one, **kw)
     two = torch.full((2 * M, N), float("nan"), dtype=torch.float16, device=dev)
+    assert plan_tag(out2=two[M:], **kw) == plan_tag(**kw) == OUT2_PLANS[M, N, K, taps]
     ops.gemm(x.to(dev), w.to(dev), two[:M], out2=two[M:], **kw)
     torch.cuda.synchronize()
     assert torch.equal(two[:M], one) and torch.equal(two[M:], one)
@@ -581,7 +649,7 @@ def _xattn_weights(C, Dc, rank, seed):
                 out_down=f(rank, C, sc=1 / rank, sd=14), out_up=f(C, rank, sc=0.05, sd=15))
 
 
-@pytest.mark.parametrize("B,N,C,heads,Dc,fused", [
+XATTN_CASES = [       # B, N, C, heads, Dc, fused
     (2, 256, 320, 8, 768, False),
     (2, 4096, 320, 8, 768, True),      # SD1.5 level 0
     (2, 1024, 640, 8, 768, True),
@@ -592,7 +660,21 @@ def _xattn_weights(C, Dc, rank, seed):
     (1, 256, 1280, 20, 2048, True),
     (2, 128, 64, 2, 128, True),        # tiny UNet widths
     (1, 256, 128, 2, 128, False),
-])
+]
+
+
+def xattn_mode3_launches(B, N, C, heads, Dc, fused):
+    """the mode-3 launches (query projection with the attention epilogue) test_id_cross_attention makes for a case: the
+    integer keywords of ``ops.gemm``, once without and once with norm2 folded (``ln``).  Shared with
+    tests/test_gemm_plan_host.py, which holds the census of the models' mode-3 variants to this list."""
+    from consistentid_amd import ops
+    if not (fused and C >= 640 and ops.qattn_supported(C, heads, N, 77, 4)):
+        return []
+    kw = dict(M=B * N, N=C, c1=C, mode=3, heads=heads, dhead=C // heads, ntok=N)
+    return [dict(kw, ln=False), dict(kw, ln=True)]
+
+
+@pytest.mark.parametrize("B,N,C,heads,Dc,fused", XATTN_CASES)
 def test_id_cross_attention(dev, B, N, C, heads, Dc, fused):
     from consistentid_amd import ops
     from consistentid_amd.weights import LOG2E
@@ -640,21 +722,20 @@ def test_id_cross_attention(dev, B, N, C, heads, Dc, fused):
         ops.gemm(o2, mo.half().to(dev).contiguous(), out2, M=M, N=C, c1=C, bias=W["bo"].half().to(dev), res=xd, ldr=C)
         torch.cuda.synchronize()
         check_vs_fp16_arm(out2, ref, arm, f"id-xattn split path N={N} C={C} heads={heads}")
-        if ops.qattn_supported(C, heads, N, L - n_ip, n_ip):
+        m3 = [{k: v for k, v in kw.items() if k != "ln"} for kw in xattn_mode3_launches(B, N, C, heads, Dc, fused)]
+        if m3:
             # cid_gemm_f16 mode 3: the query projection runs the attention as its epilogue.  The Q tile is rounded to fp16
             # exactly like the q tensor of the split path and goes through the same unit function: O is bit-identical.
             o3 = torch.empty(M, C, dtype=torch.float16, device=dev)
             att = (kp, vp, kvrow.to(dev), L - n_ip, n_ip, ip_scale)
-            ops.gemm(ln2, mq.half().to(dev).contiguous(), o3, M=M, N=C, c1=C, mode=3, heads=heads, dhead=C // heads, ntok=N,
-                     att=att)
+            ops.gemm(ln2, mq.half().to(dev).contiguous(), o3, att=att, **m3[0])
             torch.cuda.synchronize()
             assert torch.equal(o3, o2), f"attention epilogue differs from GEMM + core (rel {rel_l2(o3, o2):.2e})"
             # ... and with norm2 folded into the projection (what the engine launches at <= 2048 tokens)
             from consistentid_amd import weights
             wl, s_, b_ = weights.fold_ln(mq.half().to(dev), ln[0].to(dev), ln[1].to(dev), None)
             o4 = torch.empty(M, C, dtype=torch.float16, device=dev)
-            ops.gemm(xd.view(M, C), wl, o4, M=M, N=C, c1=C, mode=3, heads=heads, dhead=C // heads, ntok=N,
-                     ln=(s_.view(torch.float32), b_.view(torch.float32), 1e-5), att=att)
+            ops.gemm(xd.view(M, C), wl, o4, ln=(s_.view(torch.float32), b_.view(torch.float32), 1e-5), att=att, **m3[1])
             out4 = torch.empty(B, N, C, dtype=torch.float16, device=dev)
             ops.gemm(o4, mo.half().to(dev).contiguous(), out4, M=M, N=C, c1=C, bias=W["bo"].half().to(dev), res=xd, ldr=C)
             torch.cuda.synchronize()
