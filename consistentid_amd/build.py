@@ -16,7 +16,7 @@ HERE = Path(__file__).resolve().parent
 CSRC = HERE / "csrc"
 BUILD = HERE / "_build"
 LIB = HERE / "libcid.so"
-SOURCES = ["gemm.hip", "conv3x3.hip", "linear_h32.hip", "attn.hip", "xattn.hip", "xattn3.hip", "norm.hip", "misc.hip", "f32.hip", "vae_enc.hip", "parsing.hip"]
+SOURCES = ["gemm.hip", "gemm_plan.hip", "conv3x3.hip", "linear_h32.hip", "attn.hip", "xattn.hip", "xattn3.hip", "norm.hip", "misc.hip", "f32.hip", "vae_enc.hip", "parsing.hip"]
 # sources that exist in experiment builds only, switched on by a define (build_variant)
 VARIANT_SOURCES = {}
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-Wno-unused-value"]
@@ -82,7 +82,7 @@ def build_variant(name: str, defines, verbose: bool = True) -> Path:
 
 def build(force: bool = False, verbose: bool = True) -> Path:
     BUILD.mkdir(exist_ok=True)
-    deps = [CSRC / s for s in SOURCES] + [CSRC / "common.h", CSRC / "gemm_args.h", CSRC / "xattn_frag.h", CSRC / "xattn_core.h", HERE.parent / "include" / "cid.h"]
+    deps = [CSRC / s for s in SOURCES] + sorted(CSRC.glob("*.h")) + [HERE.parent / "include" / "cid.h"]
     stamp = BUILD / "stamp"
     want = _digest(deps)
     if not force and LIB.exists() and stamp.exists() and stamp.read_text() == want:

@@ -25,7 +25,7 @@
 // measured: the slab round trip (160 KB per workgroup, 41 MB per launch) costs what the separate reduce launch costs, written
 // through (sc1) or not -- 32 x 32 level, 640 -> 640: 70-77 us against 66 us for the halo kernel of gemm.hip + its reduce
 // launch.  Levels with fewer than 256 tiles of 256 tokens run 128-token tiles here while K is short (LDS-bound: six fragment
-// reads per five MFMAs), else stay on gemm.hip's halo kernel + splitk_epilogue_kernel (plan_gemm).
+// reads per five MFMAs), else stay on gemm.hip's halo kernel + splitk_epilogue_kernel (gemm_plan.hip, route_conv3x3).
 //
 // Roofline: MFMA-bound in cycles (96 % of the issue rate); in time the chip is POWER-bound under it -- all 256 CUs in this
 // loop sustain 1.35-1.4 GHz (cycle counter against wall time, tools/probes/conv_loop.hip), i.e. 1.4 PFLOP/s of the 2.5 PFLOP/s
@@ -99,7 +99,7 @@ conv_h32_kernel(GemmArgs a) {
     const int rs = seg_tok / W;
     // up = 1 (Upsample2D: nearest-2x, then the convolution): the halo holds INPUT pixels -- output pixel (y, x), tap (ty, tx)
     // reads input pixel ((y + ty - 1) >> 1, (x + tx - 1) >> 1) -- rs / 2 + 2 input rows of Wi + 2 columns per tile (a tile is
-    // whole output rows of one image there: plan_gemm)
+    // whole output rows of one image there: route_conv3x3)
     const int up = PH ? 0 : a.up;
     const int Wi = W >> up, Hi = H >> up;
     const int hs = ((rs >> up) + 2) * (Wi + 2);
@@ -175,7 +175,7 @@ conv_h32_kernel(GemmArgs a) {
         // slab (three per window, windows 1..7) so that they travel under the last slabs' MFMAs
         const bool res_on = a.res != nullptr;
         auto rcount = [&](int tap, bool last) {
-            if constexpr (PH) return 0;               // (the phase mode carries no residual: plan_gemm)
+            if constexpr (PH) return 0;               // (the phase mode carries no residual: check_args)
             if (!(last && res_on && tap >= 1 && tap <= 7)) return 0;
             const int left = RQ - (tap - 1) * 3;
             return left <= 0 ? 0 : (left > 3 ? 3 : left);

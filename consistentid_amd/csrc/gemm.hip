@@ -39,7 +39,6 @@
 #include "xattn_core.h"
 #include "gemm_args.h"
 #include "../../include/cid.h"
-#include <stdlib.h>
 
 // Profiling knobs (CID_GEMM_ABLATE bits: 1 no DMA in the loop, 2 no MFMA, 4 no halo DMA, 8 no halo fragment
 // reads) exist only in -DCID_GEMM_ABLATION builds: a runtime branch around the fragment reads splits the
@@ -371,7 +370,7 @@ CID_DEVINL bool prefetch_residual(const GemmArgs& a, half4 (&rpre)[TM][TN], int 
 // ATT_D > 0 (mode 3): the launch is the QUERY PROJECTION of an identity cross-attention whose tile spans whole heads of
 // ATT_D channels; its epilogue keeps the fp16 Q tile in LDS, runs the two-stream attention of those heads on it
 // (xattn_core_unit, one (head, 32-token) unit per wave) and writes O -- q never goes to HBM, one launch less per layer.
-// ACT: the ReLU epilogue of cid_gemm_desc.act (plain, unsplit launches only: plan_gemm routes them here).
+// ACT: the ReLU epilogue of cid_gemm_desc.act (plain, unsplit launches only: the planner routes them here).
 template <int TM, int TN, int WM, int WN, bool VMODE, int NBUF, bool LN, bool NLOOP = false, int ATT_D = 0, bool ACT = false>
 // (two workgroups per CU asked for even of the four-wave tiles: with a 512-register budget the compiler parks the accumulators
 //  in AGPRs and rotates them through VGPRs at the head of every slab -- 60 v_accvgpr moves beside 20 MFMAs, tools/isa_mix.py)
@@ -726,7 +725,7 @@ igemm_kernel(GemmArgs a) {
         __builtin_amdgcn_s_barrier();
         {
             const int idx = lane & 31, hi = lane >> 5;
-            const long row = a.att_kvrow[m0 / a.ntok];                 // (a tile lies inside one sample: plan_gemm)
+            const long row = a.att_kvrow[m0 / a.ntok];                 // (a tile lies inside one sample: tiles_mode3)
             constexpr int QKS = (ATT_D + 15) / 16, DVT = (ATT_D + 31) / 32;
             constexpr int NHL = BN / ATT_D, NTG = BM / 32;
             const int h0 = n0 / ATT_D;
@@ -1118,12 +1117,12 @@ int launch_one_ln(const GemmArgs& a, int ncols, hipStream_t s) {
 
 template <int TM, int TN, int WM, int WN, bool VMODE>
 int launch_one(const GemmArgs& a, int ncols, hipStream_t s) {
-    if constexpr (!VMODE && TN == 4 && WM * WN == 8) {      // the GEGLU tiles: N-loop form (plan_gemm sets a.nloop)
+    if constexpr (!VMODE && TN == 4 && WM * WN == 8) {      // the GEGLU tiles: N-loop form (plan_nloop sets a.nloop)
         if (a.nloop > 1)
             return a.ln_s ? launch_one_ln<TM, TN, WM, WN, false, true, true>(a, ncols, s)
                           : launch_one_ln<TM, TN, WM, WN, false, false, true>(a, ncols, s);
     }
-    // deeper ring (plan_gemm sets a.nbuf) for the 160-wide family: 3 stages = 156 / 108 / 84 KB at 256 / 128 / 64 tokens
+    // deeper ring (plan_ring sets a.nbuf) for the 160-wide family: 3 stages = 156 / 108 / 84 KB at 256 / 128 / 64 tokens
     if constexpr (!VMODE && TN == 5) {
         if (a.nbuf == 3)
             return a.ln_s ? launch_one_ln<TM, TN, WM, WN, false, true, false, 3>(a, ncols, s)
@@ -1132,20 +1131,26 @@ int launch_one(const GemmArgs& a, int ncols, hipStream_t s) {
     return a.ln_s ? launch_one_ln<TM, TN, WM, WN, VMODE, true>(a, ncols, s) : launch_one_ln<TM, TN, WM, WN, VMODE, false>(a, ncols, s);
 }
 
-// mode 3: query projection + attention epilogue on tiles of whole heads (two ring stages: the Q / O tile reuses them)
+// mode 3: query projection + attention epilogue on tiles of whole heads (two ring stages: the Q / O tile reuses them).  Like
+// launch_act and launch_halo it covers the whole width: n_begin = 0, n_end = N, as the planner's fill_args left them.
 template <int TM, int TN, int WM, int WN, int ATT_D>
-int launch_att(GemmArgs a, hipStream_t s) {
-    a.n_begin = 0; a.n_end = a.N;
+int launch_att(const GemmArgs& a, hipStream_t s) {
     return a.ln_s ? launch_one_ln<TM, TN, WM, WN, false, true, false, 2, ATT_D>(a, a.N, s)
                   : launch_one_ln<TM, TN, WM, WN, false, false, false, 2, ATT_D>(a, a.N, s);
 }
 
-// act 1 (ReLU epilogue): one source of truth for every tile of the plain family -- plan_gemm has kept the launch off the halo /
+// act 1 (ReLU epilogue): one source of truth for every tile of the plain family -- the planner has kept the launch off the halo /
 // conv3x3.hip kernels, split-K and the three-stage ring
 template <int TM, int TN, int WM, int WN>
-int launch_act(GemmArgs a, hipStream_t s) {
-    a.n_begin = 0; a.n_end = a.N;
+int launch_act(const GemmArgs& a, hipStream_t s) {
     return launch_one_ln<TM, TN, WM, WN, false, false, false, 2, 0, true>(a, a.N, s);
+}
+
+// the fp32 partials of a split-K launch -> the plain epilogue
+void launch_splitk_epilogue(const GemmArgs& a, hipStream_t s) {
+    const long items = (long)a.M * (a.N >> 2);
+    const int grid = (int)((items + 255) / 256 > 2048 ? 2048 : (items + 255) / 256);
+    hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(grid), dim3(256), 0, s, a);
 }
 
 template <int TM, int TN, int WM, int WN>
@@ -1163,15 +1168,10 @@ int launch_halo(GemmArgs a, hipStream_t s) {
         }
         configured = true;
     }
-    a.n_begin = 0; a.n_end = a.N;
     dim3 grid((a.N + BN - 1) / BN, (a.M + BM - 1) / BM, a.splitk);
     a.xcd_pn = cidg::choose_xcd_pn((int)grid.x, (int)grid.y, 2.0 * a.N * a.ktot, (double)a.bytes_x1 + a.bytes_x2);
     hipLaunchKernelGGL(kern, grid, dim3(64 * NW), SMEM, s, a);
-    if (a.splitk > 1) {
-        const long items = (long)a.M * (a.N >> 2);
-        const int g = (int)((items + 255) / 256 > 2048 ? 2048 : (items + 255) / 256);
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(g), dim3(256), 0, s, a);
-    }
+    if (a.splitk > 1) launch_splitk_epilogue(a, s);
     return 0;
 }
 
@@ -1181,11 +1181,7 @@ int launch(GemmArgs a, hipStream_t s) {
     a.n_begin = 0; a.n_end = n_plain;
     int rc = launch_one<TM, TN, WM, WN, false>(a, n_plain, s);
     if (rc) return rc;
-    if (a.splitk > 1) {
-        const long items = (long)a.M * (a.N >> 2);
-        const int grid = (int)((items + 255) / 256 > 2048 ? 2048 : (items + 255) / 256);
-        hipLaunchKernelGGL(splitk_epilogue_kernel, dim3(grid), dim3(256), 0, s, a);
-    }
+    if (a.splitk > 1) launch_splitk_epilogue(a, s);
     if (a.mode == 2 && a.N > a.n_vt0) {
         // the V third: flipped operand roles, transposed store
         GemmArgs v = a;
@@ -1197,438 +1193,33 @@ int launch(GemmArgs a, hipStream_t s) {
 
 }  // namespace
 
-int cidg::choose_xcd_pn(int gx, int gy, double w_bytes, double x_bytes) {
-    static int on = -1;
-    if (on < 0) { const char* e = getenv("CID_XCD_2D"); on = e ? atoi(e) : 1; }
-    if (!on || ((long)gx * gy) % 8 != 0) return 0;
-    int best = 0;
-    double cost = 0.0;
-    for (int pn = 1; pn <= 8; pn *= 2) {
-        const int pm = 8 / pn;
-        if (gx % pn != 0 || gy % pm != 0) continue;
-        const double c = pm * w_bytes + pn * x_bytes;
-        if (best == 0 || c < cost) { best = pn; cost = c; }      // (ties keep the smaller pn: the order of rounds 2-5)
-    }
-    return best;
-}
-
-enum TileCfg { A256x160, B128x160, C64x160, G256x128, G128x128, O64x64, O128x32 };
-
-// token rows per GroupNorm statistics block of a planned launch (its tile height), 0 where it cannot emit them: the plain,
-// unsplit, ReLU-free epilogue of the 160-wide tiles, whole tiles only
-static int stats_rows_of(const cid_gemm_desc* d, const GemmArgs& a, TileCfg cfg, int bm) {
-    const int unit = d->N / 32;
-    const bool ok = d->mode == 0 && d->act == 0 && a.splitk == 1 && (cfg == A256x160 || cfg == B128x160 || cfg == C64x160) &&
-                    d->N % 32 == 0 && unit > 0 && 80 % unit == 0 && bm > 0 && d->M % bm == 0;
-    return ok ? bm : 0;
-}
-
-// argument checks + tile / split-K choice of one cid_gemm_f16 call (no launch): shared by the call itself and by
-// cid_gemm_plan (and through it cid_gemm_stats_rows, which tells the host how the GroupNorm statistics will be blocked)
-static int plan_gemm(const cid_gemm_desc* d, GemmArgs& a, TileCfg& cfg, bool& halo, int& bm_out, bool& h32, bool& g32) {
-    h32 = false;
-    g32 = false;
-    CID_CHECK_ARG(d && d->x1 && d->w && d->out, "cid_gemm_f16: null pointer");
-    CID_CHECK_ARG(d->taps == 1 || d->taps == 9, "cid_gemm_f16: taps must be 1 or 9 (got %d)", d->taps);
-    CID_CHECK_ARG(d->c1 > 0 && d->c1 % 32 == 0 && d->c2 >= 0 && d->c2 % 32 == 0 && (d->c1 + d->c2) % 64 == 0 &&
-                  (d->c2 == 0 || d->c1 % 64 == 0),
-                  "cid_gemm_f16: channel counts must be multiples of 64 (c1=%d c2=%d)", d->c1, d->c2);
-    CID_CHECK_ARG(d->c2 == 0 || d->x2, "cid_gemm_f16: c2 > 0 needs x2");
-    CID_CHECK_ARG(d->N > 0 && d->N % 32 == 0 && d->M > 0, "cid_gemm_f16: bad M/N (%d, %d)", d->M, d->N);
-    CID_CHECK_ARG(d->mode >= 0 && d->mode <= 3, "cid_gemm_f16: bad mode %d", d->mode);
-    CID_CHECK_ARG(d->ld1 % 8 == 0 && d->ldo % 8 == 0 && (d->c2 == 0 || d->ld2 % 8 == 0) && (!d->res || d->ldr % 8 == 0),
-                  "cid_gemm_f16: row pitches (ld1, ld2, ldo, ldr) must keep 16-byte alignment");
-    CID_CHECK_ARG((((uintptr_t)d->out | (uintptr_t)d->res | (uintptr_t)d->out2) & 15) == 0,
-                  "cid_gemm_f16: out / out2 / res must be 16-byte aligned (rows are stored and the residual is read in 16-byte chunks)");
-    CID_CHECK_ARG((d->ln_s == nullptr) == (d->ln_b == nullptr), "cid_gemm_f16: ln_s and ln_b come together");
-    CID_CHECK_ARG(!d->ln_s || (d->taps == 1 && d->c2 == 0 && !d->bias && d->ln_eps > 0.f),
-                  "cid_gemm_f16: the LayerNorm fold applies to one-source linears; the bias belongs in ln_b");
-    a.x1 = (const half_t*)d->x1; a.x2 = (const half_t*)d->x2;
-    a.c1 = d->c1; a.c2 = d->c2; a.ld1 = d->ld1; a.ld2 = d->ld2;
-    a.w = (const half_t*)d->w; a.out = (half_t*)d->out; a.ldo = d->ldo;
-    a.out2 = (half_t*)d->out2;
-    CID_CHECK_ARG(!d->out2 || d->mode == 0, "cid_gemm_f16: out2 (a second destination) goes with the plain epilogue, mode 0");
-    a.bias = (const half_t*)d->bias;
-    a.rowbias = (const half_t*)d->rowbias; a.ld_rowbias = d->ld_rowbias;
-    a.rows_per_sample = d->rows_per_sample > 0 ? d->rows_per_sample : 1;
-    a.res = (const half_t*)d->res; a.ldr = d->ldr;
-    a.M = d->M; a.N = d->N; a.taps = d->taps;
-    a.Hi = d->Hi; a.Wi = d->Wi; a.Ho = d->Ho; a.Wo = d->Wo; a.stride = d->stride; a.up = d->up;
-    a.mode = d->mode;
-    a.vt = (half_t*)d->vt; a.n_vt0 = d->n_vt0; a.heads = d->heads; a.dhead = d->dhead;
-    a.dvp = d->dvp; a.ntok = d->ntok;
-    a.cslabs = (d->c1 + d->c2) / BK;
-    a.ktot = d->taps * (d->c1 + d->c2);
-    a.nslab = a.ktot / BK;
-    a.splitk = 1;
-    a.nloop = 1;
-    a.nbuf = 2;
-    a.xcd_pn = 0;
-    a.att_kp = (const half_t*)d->att_kp; a.att_vp = (const half_t*)d->att_vp; a.att_kvrow = (const int*)d->att_kvrow;
-    a.att_n_txt = d->att_n_txt; a.att_n_ip = d->att_n_ip; a.att_scale = d->att_ip_scale;
-    a.att_krow = a.att_vrow = 0;
-    a.ws = (float*)d->ws;
-    a.ln_s = d->ln_s; a.ln_b = d->ln_b; a.ln_eps = d->ln_eps;
-    a.gn_stats = d->gn_stats; a.gn_unit = d->N / 32;
-    {
-#if defined(CID_GEMM_ABLATION)      // experiment builds only (build.py --variant ... CID_GEMM_ABLATION)
-        static int ablate = -1;
-        if (ablate < 0) { const char* e = getenv("CID_GEMM_ABLATE"); ablate = e ? atoi(e) : 0; }
-        a.ablate = ablate;
-#else
-        a.ablate = 0;
-#endif
-    }
-    {
-        // rows addressable through x1 / x2: the input image for convs, M rows for linears
-        const long rows_in = (d->taps == 9) ? (long)(d->M / (d->Ho * d->Wo)) * d->Hi * d->Wi : (long)d->M;
-        const long b1 = ((rows_in - 1) * d->ld1 + d->c1) * 2, b2 = d->c2 ? ((rows_in - 1) * d->ld2 + d->c2) * 2 : 0;
-        const long bw = (long)d->N * a.ktot * 2;
-        CID_CHECK_ARG(b1 < 0x7fffffffL && b2 < 0x7fffffffL && bw < 0x7fffffffL, "cid_gemm_f16: tensor exceeds 2 GiB");
-        a.bytes_x1 = (unsigned)b1; a.bytes_x2 = (unsigned)b2; a.bytes_w = (unsigned)bw;
-    }
-    a.n_begin = 0; a.n_end = a.N;
-    if (d->taps == 9) {
-        CID_CHECK_ARG(d->Hi > 0 && d->Wi > 0 && d->Ho > 0 && d->Wo > 0 && (d->stride == 1 || d->stride == 2)
-                      && (d->up == 0 || d->up == 1), "cid_gemm_f16: bad conv geometry");
-        CID_CHECK_ARG(d->M % (d->Ho * d->Wo) == 0, "cid_gemm_f16: M is not batch * Ho * Wo");
-    }
-    // pad_mode 1: diffusers' Downsample2D(padding=0) = F.pad(x, (0, 1, 0, 1)) then a stride-2 3x3 conv without padding --
-    // output (y, x) reads input (2y + dy, 2x + dx), dy, dx in {0, 1, 2}; row Hi and column Wi (the pad) read as zero.  Only the
-    // tap offset of the gather changes (set_tap), so the igemm_kernel instances run it; the halo / conv3x3.hip kernels below
-    // are stride-1 only and never see it.
-    CID_CHECK_ARG(d->pad_mode == 0 || d->pad_mode == 1, "cid_gemm_f16: bad pad_mode %d", d->pad_mode);
-    CID_CHECK_ARG(d->pad_mode == 0 || (d->mode == 0 && d->taps == 9 && d->stride == 2 && d->up == 0 && d->Hi % 2 == 0 &&
-                                       d->Wi % 2 == 0 && d->Ho == d->Hi / 2 && d->Wo == d->Wi / 2),
-                  "cid_gemm_f16: pad_mode 1 needs mode 0, taps 9, stride 2, up 0, even Hi / Wi, Ho = Hi / 2 and Wo = Wi / 2 "
-                  "(got mode %d taps %d stride %d up %d, %d x %d -> %d x %d)", d->mode, d->taps, d->stride, d->up, d->Hi, d->Wi,
-                  d->Ho, d->Wo);
-    a.tap0 = d->pad_mode == 1 ? 0 : -1;
-    // w_up4 (since cid_version() 103): the folded weights of an Upsample2D convolution (cid_upconv_fold_f16).  The launch may
-    // then run as four 2x2 phase convolutions at input resolution (conv3x3.hip, routed below); where it cannot, w serves.
-    CID_CHECK_ARG(!d->w_up4 || (d->taps == 9 && d->up == 1 && d->stride == 1 && d->mode == 0 && !d->res),
-                  "cid_gemm_f16: w_up4 needs taps 9, up 1, stride 1, mode 0 and no res (got taps %d up %d stride %d mode %d)",
-                  d->taps, d->up, d->stride, d->mode);
-    CID_CHECK_ARG(((uintptr_t)d->w_up4 & 15) == 0, "cid_gemm_f16: w_up4 must be 16-byte aligned");
-    a.w4 = nullptr;
-    // act 1 (since cid_version() 102): ReLU in the plain epilogue.  Only the igemm_kernel instances carry it (launch_act);
-    // split-K (ws), the GroupNorm statistics and the LayerNorm fold are refused with it, the halo / conv3x3.hip kernels skipped.
-    CID_CHECK_ARG(d->act == 0 || d->act == 1, "cid_gemm_f16: bad act %d", d->act);
-    CID_CHECK_ARG(d->act == 0 || (d->mode == 0 && !d->gn_stats && !d->ws && !d->ln_s),
-                  "cid_gemm_f16: act 1 needs mode 0 and no gn_stats / ws / ln_s (got mode %d)", d->mode);
-
-    if (d->mode == 3) {
-        // query projection with the identity cross-attention as its epilogue: tiles of whole heads inside one sample
-        CID_CHECK_ARG(d->att_kp && d->att_vp && d->att_kvrow, "cid_gemm_f16: mode 3 needs att_kp / att_vp / att_kvrow");
-        CID_CHECK_ARG(d->taps == 1 && d->c2 == 0 && !d->bias && !d->rowbias && !d->res && !d->gn_stats,
-                      "cid_gemm_f16: mode 3 is a plain projection (no bias / residual / statistics)");
-        CID_CHECK_ARG(d->heads > 0 && d->dhead > 0 && d->N == d->heads * d->dhead && (d->dhead == 64 || d->dhead == 80 || d->dhead == 160),
-                      "cid_gemm_f16: mode 3 needs N = heads * dhead with dhead in {64, 80, 160} (got %d x %d, N = %d)", d->heads, d->dhead, d->N);
-        CID_CHECK_ARG(d->att_n_txt == 77 && d->att_n_ip == 4, "cid_gemm_f16: mode 3 is built for the reference's 77 + 4 context (got %d + %d)",
-                      d->att_n_txt, d->att_n_ip);
-        CID_CHECK_ARG(d->ntok > 0 && d->M % d->ntok == 0 && d->ntok % 64 == 0, "cid_gemm_f16: mode 3 needs ntok (tokens per sample, a multiple of 64)");
-        const int qks = (d->dhead + 15) / 16, dvt = (d->dhead + 31) / 32;
-        a.att_krow = (long)d->heads * 3 * qks * 512;
-        a.att_vrow = (long)d->heads * dvt * 6 * 512;
-        if (d->dhead == 64) { cfg = G128x128; bm_out = 128; CID_CHECK_ARG(d->N % 128 == 0 && d->ntok % 128 == 0, "cid_gemm_f16: mode 3, dhead 64: N and ntok multiples of 128"); }
-        else {
-            // 160-wide tiles span whole heads (two of 80 channels, one of 160): N must be a whole number of them
-            CID_CHECK_ARG(d->N % 160 == 0, "cid_gemm_f16: mode 3, dhead %d: N = %d is not a multiple of the 160-channel tile", d->dhead, d->N);
-            if (d->ntok % 128 == 0 && (long)(d->M / 128) * (d->N / 160) >= 256) { cfg = B128x160; bm_out = 128; }
-            else { cfg = C64x160; bm_out = 64; }
-        }
-        halo = false;
-        return 0;
-    }
-    // ---- tile choice: aim for >= 2 waves on each of the 1024 SIMDs ------------------------
-    const int n_plain = (d->mode == 2) ? d->n_vt0 : d->N;
-    const long target = 2048;
-    auto waves = [&](int bm_, int bn_, int w) {
-        return (long)((a.M + bm_ - 1) / bm_) * ((n_plain + bn_ - 1) / bn_) * w;
-    };
-    int bm = 0, bn = 0, nw = 0;
-    // GEGLU with short K (few slabs): the erf epilogue and the pipeline prologue dominate a tile's
-    // life, so prefer the tile that lets two workgroups share a CU and overlap them (measured:
-    // 156 -> 115 us at M=32768, N=2560, K=320; plain epilogues do not benefit)
-    // 256-token tiles only for deep K AND at least 1024 of them (in situ: SDXL's M = 4096, K = 1280 level +0.9 % end to end
-    // with the big tile, SD1.5's M = 2048 level +0.3 % with the small one)
-    bool small_tiles = (d->mode == 1) && (a.nslab <= 10 || waves(256, 128, 1) < 1024);
-    if (d->mode == 1) {
-        static int g_tile = -1;
-        if (g_tile < 0) { const char* e = getenv("CID_GEGLU_TILE"); g_tile = e ? atoi(e) : 0; }
-        if (g_tile == 1) small_tiles = false;
-        if (g_tile == 2) small_tiles = true;
-        if (d->N % 128 != 0) { cfg = O64x64; bm = 64; bn = 64; nw = 4; }
-        else if (waves(256, 128, 8) >= target && !small_tiles) { cfg = G256x128; bm = 256; bn = 128; nw = 8; }
-        else { cfg = G128x128; bm = 128; bn = 128; nw = 8; }
-    } else if (n_plain % 160 == 0) {
-        // plain epilogue: the largest tile that still yields >= 256 workgroups, if necessary with the help
-        // of split-K (small-M levels are weight-traffic bound: W is re-read once per token tile)
-        static int f_tile = -1, f_sk = -1;
-        if (f_tile < 0) { const char* e = getenv("CID_GEMM_TILE"); f_tile = e ? atoi(e) : 0; }
-        if (f_sk < 0) { const char* e = getenv("CID_GEMM_SK"); f_sk = e ? atoi(e) : 0; }
-        const bool can_split = (d->mode == 0) && a.ws != nullptr && !a.ln_s;
-        auto tiles = [&](int bm_) { return (long)((a.M + bm_ - 1) / bm_) * (n_plain / 160); };
-        auto sk_for = [&](int bm_) {
-            long t = tiles(bm_);
-            int sk = (int)((256 + t - 1) / t);
-            if (!can_split) sk = 1;
-            if (sk > 16) sk = 16;
-            while (sk > 1 && a.nslab / sk < 6) --sk;
-            while (sk > 1 && (int64_t)sk * a.M * a.N * 4 > d->ws_bytes) --sk;
-            return sk;
-        };
-        int pick = 0;
-        bool nosplit = false;
-        static int prefer128 = -1;
-        if (prefer128 < 0) { const char* e = getenv("CID_GEMM_PREFER128"); prefer128 = e ? atoi(e) : 1; }
-        if (f_tile) pick = f_tile;
-        else if (d->taps == 1 && tiles(256) >= 256) {
-            // enough 256-token tiles without split-K; the fused QKV projection (no split possible, short K) prefers
-            // twice as many half-size tiles when the big ones only just fill the chip (measured 63 -> 55 us at SDXL's
-            // 32x32 level, 45 -> 42 us at SD1.5's 32x32 level)
-            // (and 45 -> 41 us at SD1.5's 64x64 level, where the big tiles number exactly 512: CID_GEMM_TILE A/B, round 4)
-            // Round 6 re-measured the rule for every linear (CID_GEMM_TILE A/B at SD1.5 CFG batch 8 / 16 and SDXL batch 4,
-            // profiles/r06_tile_rule.txt): 128-token tiles win wherever they number >= 256 -- 320 -> 320 at 64 x 64 17.8 -> 14.9 us
-            // (33.1 -> 26.9 at CFG batch 16), SDXL's 640 -> 640 24.4 -> 21.1, ff2 at 1280 channels 68.6 -> 63.2 (unsplit instead of
-            // 256-token tiles + split-K 2).  One 256-token workgroup per CU loads, multiplies and stores in lock step with every
-            // other CU; two half-size workgroups per CU are out of phase.  CID_GEMM_PREFER128=0: the rule of rounds 3-5.
-            pick = (prefer128 || (d->mode == 2 && tiles(256) <= 512 && tiles(128) >= 512)) ? 2 : 1;
-            nosplit = true;
-        } else if (d->taps == 1 && tiles(128) >= 256 && (a.nslab <= 40 || prefer128)) { pick = 2; nosplit = true; }   // no fp32 partials
-        else if (d->taps == 1 && tiles(64) >= 256 && a.nslab <= 20) { pick = 3; nosplit = true; }      // beats 256-tiles + split-K
-        else if (tiles(256) * sk_for(256) >= 256) pick = 1;                                             // (tools/sweep_tiles*.sh)
-        else if (tiles(128) * sk_for(128) >= 256) pick = 2;
-        else pick = 3;
-        if (pick == 1)      { cfg = A256x160; bm = 256; bn = 160; nw = 8; }
-        else if (pick == 2) { cfg = B128x160; bm = 128; bn = 160; nw = 8; }
-        else                { cfg = C64x160;  bm = 64;  bn = 160; nw = 4; }
-        a.splitk = f_sk ? f_sk : (nosplit ? 1 : sk_for(bm));
-        if (!can_split || (int64_t)a.splitk * a.M * a.N * 4 > d->ws_bytes || a.nslab < a.splitk) a.splitk = 1;
-    } else if (d->mode == 0 && n_plain % 128 == 0) {
-        // widths off the 160 grid (VAE decoder: 128 / 256 / 512 channels, attention score / value GEMMs)
-        if (waves(256, 128, 8) >= target) { cfg = G256x128; bm = 256; bn = 128; nw = 8; }
-        else { cfg = G128x128; bm = 128; bn = 128; nw = 8; }
-    } else if (n_plain % 64 == 0) { cfg = O64x64; bm = 64; bn = 64; nw = 4; }
-    else { cfg = O128x32; bm = 128; bn = 32; nw = 4; }
-    if (d->mode == 1) CID_CHECK_ARG(d->N % 64 == 0, "cid_gemm_f16: GEGLU needs N %% 64 == 0");
-    if (d->mode == 1 && (cfg == G128x128 || cfg == G256x128) && d->taps == 1 && d->c2 == 0 && a.M % bm == 0) {
-        // N-loop: one workgroup walks several n-tiles of its token tile (igemm_kernel, NLOOP) -- as many as leave one round of
-        // resident workgroups; the count must divide the n-tiles (the flattened slab sequence has no ragged tail)
-        static int f_nl = -1;
-        if (f_nl < 0) { const char* e = getenv("CID_GEGLU_NLOOP"); f_nl = e ? atoi(e) : 0; }      // A/B switch: 1 = off, n = force
-        const int nt = d->N / bn;
-        const long tiles = (long)(a.M / bm) * nt;
-        int nl = f_nl > 0 ? f_nl : (int)(tiles / (cfg == G128x128 ? 512 : 256));      // (128-token tiles: two workgroups per CU)
-        if (nl > nt) nl = nt;
-        while (nl > 1 && nt % nl != 0) --nl;
-        if (nl > 1 && (long)nl * bn * a.ktot * 2 < 0x7fffffffL) a.nloop = nl;
-    }
-    if (d->mode == 1 && d->taps == 1 && d->c2 == 0 && !a.ln_s && d->N % 160 == 0 && a.M % 256 == 0 && a.cslabs >= 16) {
-        // linear_h32.hip: 256 x 160 tiles of 32 x 32 x 16 MFMAs, loader / compute wave roles, N-loop -- the 16 x 16 x 32 tiles
-        // above are LDS-bandwidth-bound on this op (profiles/r06_gemm_ablation.txt).  Deep K only (>= 1024 channels): the erf
-        // epilogue of that kernel is exposed once per n-tile (one compute wave per SIMD), which costs more than the leaner loop
-        // gains at K = 320 (86 vs 73 us at SD1.5's 64 x 64 level), draws at K = 640 and wins at K = 1280 (64 vs 77 us).  One
-        // round of 256 workgroups: every workgroup walks tiles / 256 n-tiles (a divisor of the n-tile count); launches that
-        // cannot fill the chip stay above.
-        static int f_g32 = -1;
-        if (f_g32 < 0) { const char* e = getenv("CID_GEGLU_H32"); f_g32 = e ? atoi(e) : 1; }      // A/B switch: 0 = off
-        const int nt = d->N / 160;
-        const long tiles = (long)(a.M / 256) * nt;
-        int nl = (int)(tiles / 256);
-        if (nl > nt) nl = nt;
-        while (nl > 1 && nt % nl != 0) --nl;
-        if (f_g32 && tiles >= 256 && nl >= 1 && (long)nl * 160 * a.ktot * 2 < 0x7fffffffL) {
-            g32 = true;
-            a.nloop = nl;
-            bm = 256;
-        }
-    }
-    if (d->mode == 2) {
-        CID_CHECK_ARG(d->vt && d->ntok % 16 == 0 && d->M % d->ntok == 0 && d->n_vt0 % bn == 0 && d->dhead > 0
-                      && d->heads > 0 && d->dvp >= d->dhead && (d->N - d->n_vt0) % 16 == 0,
-                      "cid_gemm_f16: bad QKV/V^T description");
-    }
-    // split-K for small-M / deep-K problems (plain epilogue only)
-    if (d->mode == 0 && a.ws && !a.ln_s && a.nslab >= 16 && n_plain % 160 != 0) {
-        const long w = waves(bm, bn, nw);
-        if (w < target) {
-            int sk = (int)((target + w - 1) / w);
-            if (sk > 8) sk = 8;
-            while (sk > 1 && a.nslab / sk < 8) --sk;
-            while (sk > 1 && (int64_t)sk * a.M * a.N * 4 > d->ws_bytes) --sk;
-            a.splitk = sk;
-        }
-    }
-    {
-        // three-stage ring: launches of the 128- / 64-token tiles that put at most one workgroup on a CU anyway (<= 256
-        // workgroups) and walk enough slabs for the lookahead to matter
-        static int f_nb = -1;
-        if (f_nb < 0) { const char* e = getenv("CID_GEMM_NBUF"); f_nb = e ? atoi(e) : 0; }      // A/B switch: 2 = never, 3 = whenever legal
-        const bool legal = (cfg == A256x160 || cfg == B128x160 || cfg == C64x160) && d->mode != 1 && !d->act;
-        const long wgs = (long)((a.M + bm - 1) / bm) * ((n_plain + bn - 1) / bn) * a.splitk;
-        // (the 256-token tile holds one workgroup per CU whatever its ring: three stages whenever there are slabs to look ahead;
-        //  the smaller tiles only where a third stage does not cost a co-resident workgroup)
-        const bool want = cfg == A256x160 ? (a.nslab / a.splitk >= 4) : (wgs <= 256 && a.nslab / a.splitk >= 8);
-        if (legal && (f_nb == 3 || (f_nb == 0 && want))) a.nbuf = 3;
-    }
-    static int no_halo = -1;
-    if (no_halo < 0) { const char* e = getenv("CID_GEMM_NOHALO"); no_halo = e ? atoi(e) : 0; }
-    halo = false;
-    if (cfg == A256x160 && !no_halo && !d->act && d->mode == 0 && d->taps == 9 && d->stride == 1 && d->up == 0 && d->Wo == d->Wi &&
-        d->Ho == d->Hi) {
-        // halo kernel: the 256-token tile must be whole image rows of one image, or whole images
-        const int HW = d->Ho * d->Wo;
-        const int seg = 256 < HW ? 256 : HW;
-        const bool rows_ok = (seg % d->Wo == 0) && (HW % seg == 0) && (256 % seg == 0) && (d->M % 256 == 0);
-        const int nh = (256 / seg) * (seg / d->Wo + 2) * (d->Wo + 2);
-        if (rows_ok && nh <= 448) {
-            halo = true;
-            if (a.splitk > a.cslabs) a.splitk = a.cslabs;     // split over whole channel slabs only
-        }
-    }
-    {
-        // conv3x3.hip (32 x 32 MFMA tiles, loader / compute wave roles) for the stride-1 3x3 convolutions on the 160-channel
-        // grid, unsplit: 256-token tiles where they fill the chip; 128-token tiles where those do and K is short (they are
-        // LDS-bound: measured faster than 256-token tiles + split-K up to 10 channel slabs -- the 32 x 32 level's 640 -> 640,
-        // the first resnet of the CFG-deduplicated level 0 -- and slower beyond).  Three weight stages next to two halo buffers
-        // need a halo of <= 400 rows.  Everything else stays on the halo kernel above (+ splitk_epilogue_kernel).
-        static int no_h32 = -1;
-        static int only256 = 0;
-        if (no_h32 < 0) { const char* e = getenv("CID_CONV_H32"); no_h32 = (e && atoi(e) == 0) ? 1 : 0; only256 = (e && atoi(e) == 2) ? 1 : 0; }
-        const int HW = d->taps == 9 ? d->Ho * d->Wo : 0;
-        // (Upsample2D's convolution, up == 1: the halo holds input pixels; a tile must be an even number of whole output rows of
-        //  one image, starting on an even row)
-        const bool shape_ok = !no_h32 && !d->act && d->mode == 0 && d->taps == 9 && d->stride == 1 && (d->up == 0 || d->up == 1) &&
-                              d->Wo == (d->Wi << d->up) && d->Ho == (d->Hi << d->up) && d->N % 160 == 0 && HW >= 64 &&
-                              (!d->rowbias || (a.rows_per_sample >= 64 && a.rows_per_sample % 64 == 0));
-        // Upsample2D with folded weights (w_up4): the phase mode -- a tile is bm_try INPUT pixels of one output parity, whole
-        // input rows of one image; same tile-count rules.  One source, no time row (the UNets' Upsample2D has neither); the
-        // nine-tap path below serves everything else.  CID_UPCONV_FOLD=0: never (A/B switch).
-        static int fold_on = -1;
-        if (fold_on < 0) { const char* e = getenv("CID_UPCONV_FOLD"); fold_on = e ? atoi(e) : 1; }
-        const bool fold_ok = shape_ok && fold_on && d->w_up4 && d->up == 1 && d->c2 == 0 && !d->rowbias && !d->res &&
-                             (long)d->N * d->c1 * 32 < 0x7fffffffL;
-        for (int bm_try = 256; shape_ok && !h32 && bm_try >= (only256 ? 256 : 128); bm_try >>= 1) {
-            if (fold_ok) {
-                const int HWi = d->Hi * d->Wi;
-                const long tiles = (long)(d->M / bm_try) * (d->N / 160);
-                if (HWi % bm_try == 0 && bm_try % d->Wi == 0 && d->M % bm_try == 0 && (bm_try / d->Wi + 2) * (d->Wi + 2) <= 400 &&
-                    tiles >= 256 && !(bm_try == 128 && a.cslabs > 10)) {
-                    h32 = true; halo = false;
-                    bm = bm_try;
-                    a.splitk = 1;
-                    a.w4 = (const half_t*)d->w_up4;
-                    continue;
-                }
-            }
-            const int seg = bm_try < HW ? bm_try : HW;
-            if (seg % d->Wo != 0 || HW % seg != 0 || bm_try % seg != 0 || d->M % bm_try != 0) continue;
-            if (d->up && (seg != bm_try || (seg / d->Wo) % 2 != 0)) continue;
-            const int nh = (bm_try / seg) * (((seg / d->Wo) >> d->up) + 2) * ((d->Wo >> d->up) + 2);
-            if (nh > 400) continue;
-            const long tiles = (long)(d->M / bm_try) * (d->N / 160);
-            if (tiles < 256 || (bm_try == 128 && a.cslabs > 10)) continue;
-            h32 = true; halo = false;
-            bm = bm_try;
-            a.splitk = 1;
-        }
-    }
-    bm_out = bm;
-    // GroupNorm statistics come out of the plain, unsplit epilogue of the 160-wide tiles, whole tiles only
-    if (a.gn_stats)
-        CID_CHECK_ARG(stats_rows_of(d, a, cfg, bm) > 0,
-                      "cid_gemm_f16: gn_stats requested for a launch that cannot emit them (ask cid_gemm_stats_rows first)");
-    return 0;
-}
-
-// The launch of a planned call: which kernel family runs it and which template instance of that family.  decide_launch is
-// the ONE place that turns plan_gemm's findings into that choice; cid_gemm_f16 launches what it returns and cid_gemm_plan
-// reports it, so the report cannot drift from the launch.
-struct LaunchChoice {
-    int family;          // CID_GEMM_FAMILY_*
-    int bm, bn;          // tile
-    bool ln, act, vmode; // LN / ACT instance; a second, VMODE launch writes the transposed V third (mode 2)
-    bool sk_epilogue;    // splitk_epilogue_kernel follows
-};
-
-static LaunchChoice decide_launch(const cid_gemm_desc* d, GemmArgs& a, TileCfg cfg, bool halo, int bm, bool h32, bool g32) {
-    static const int cfg_bn[] = { 160, 160, 160, 128, 128, 64, 32 };
-    LaunchChoice c;
-    c.bm = bm; c.bn = cfg_bn[cfg];
-    c.ln = false; c.act = false; c.vmode = false; c.sk_epilogue = false;
-    if (g32) { c.family = CID_GEMM_FAMILY_GEGLU_H32; c.bn = 160; }
-    else if (a.mode == 3) { c.family = CID_GEMM_FAMILY_IGEMM_ATT; c.ln = a.ln_s != nullptr; }
-    else if (d->act) { c.family = CID_GEMM_FAMILY_IGEMM; c.act = true; }
-    else if (h32) { c.family = a.w4 ? CID_GEMM_FAMILY_CONV_H32_PHASE : CID_GEMM_FAMILY_CONV_H32; }
-    else if (halo) { c.family = CID_GEMM_FAMILY_IGEMM_HALO; c.sk_epilogue = a.splitk > 1; }
-    else {
-        c.family = CID_GEMM_FAMILY_IGEMM;
-        c.ln = a.ln_s != nullptr;
-        c.vmode = a.mode == 2 && a.N > a.n_vt0;
-        c.sk_epilogue = a.splitk > 1;
-    }
-    // the ring depth is a launch parameter of the gather kernels only (launch_one reads it); the other kernels fix their staging
-    if (c.family != CID_GEMM_FAMILY_IGEMM && c.family != CID_GEMM_FAMILY_IGEMM_ATT) a.nbuf = 0;
-    return c;
-}
-
-extern "C" int cid_gemm_plan(const cid_gemm_desc* d, cid_gemm_plan_info* out) {
-    CID_CHECK_ARG(out, "cid_gemm_plan: null output");
-    GemmArgs a;
-    TileCfg cfg;
-    bool halo, h32, g32;
-    int bm = 0;
-    int rc = plan_gemm(d, a, cfg, halo, bm, h32, g32);
-    if (rc) return rc;
-    const LaunchChoice c = decide_launch(d, a, cfg, halo, bm, h32, g32);
-    out->family = c.family;
-    out->bm = c.bm; out->bn = c.bn;
-    out->splitk = a.splitk; out->nloop = a.nloop; out->nbuf = a.nbuf;
-    out->ln = c.ln; out->act = c.act; out->vmode = c.vmode;
-    out->splitk_epilogue = c.sk_epilogue;
-    out->stats_rows = stats_rows_of(d, a, cfg, bm);
-    return 0;
-}
-
-extern "C" int cid_gemm_stats_rows(const cid_gemm_desc* d) {
-    if (!d) return 0;
-    cid_gemm_desc q = *d;
-    q.gn_stats = nullptr;
-    cid_gemm_plan_info info;
-    return cid_gemm_plan(&q, &info) == 0 ? info.stats_rows : 0;
-}
-
+// cid_gemm_f16: launch what the planner decided (gemm_plan.hip) -- (family, TileCfg) -> template instance
 extern "C" int cid_gemm_f16(const cid_gemm_desc* d, cid_stream_t stream) {
-    GemmArgs a;
-    TileCfg cfg;
-    bool halo, h32, g32;
-    int bm = 0;
-    int rc = plan_gemm(d, a, cfg, halo, bm, h32, g32);
+    using namespace cidg;
+    GemmPlan p;
+    int rc = plan(d, p);
     if (rc) return rc;
-    const LaunchChoice c = decide_launch(d, a, cfg, halo, bm, h32, g32);
+    const GemmArgs& a = p.a;
     hipStream_t s = (hipStream_t)stream;
-    switch (c.family) {
+    switch (p.family) {
         case CID_GEMM_FAMILY_GEGLU_H32:
-            a.n_begin = 0; a.n_end = a.N;
-            rc = cidg::launch_geglu_h32(a, s);
+            rc = launch_geglu_h32(a, s);
             break;
         case CID_GEMM_FAMILY_IGEMM_ATT:
-            if (cfg == G128x128) rc = launch_att<2, 4, 4, 2, 64>(a, s);
-            else if (cfg == B128x160) rc = a.dhead == 80 ? launch_att<2, 5, 4, 2, 80>(a, s) : launch_att<2, 5, 4, 2, 160>(a, s);
+            if (p.cfg == G128x128) rc = launch_att<2, 4, 4, 2, 64>(a, s);
+            else if (p.cfg == B128x160) rc = a.dhead == 80 ? launch_att<2, 5, 4, 2, 80>(a, s) : launch_att<2, 5, 4, 2, 160>(a, s);
             else rc = a.dhead == 80 ? launch_att<2, 5, 2, 2, 80>(a, s) : launch_att<2, 5, 2, 2, 160>(a, s);
             break;
         case CID_GEMM_FAMILY_CONV_H32:
         case CID_GEMM_FAMILY_CONV_H32_PHASE:
-            a.n_begin = 0; a.n_end = a.N;
-            rc = cidg::launch_conv_h32(a, c.bm, s);
+            rc = launch_conv_h32(a, p.bm, s);
             break;
         case CID_GEMM_FAMILY_IGEMM_HALO:
             rc = launch_halo<4, 5, 4, 2>(a, s);
             break;
         default:
-            if (c.act) {
-                switch (cfg) {
+            if (p.act) {
+                switch (p.cfg) {
                     case A256x160: rc = launch_act<4, 5, 4, 2>(a, s); break;
                     case B128x160: rc = launch_act<2, 5, 4, 2>(a, s); break;
                     case C64x160:  rc = launch_act<2, 5, 2, 2>(a, s); break;
@@ -1638,7 +1229,7 @@ extern "C" int cid_gemm_f16(const cid_gemm_desc* d, cid_stream_t stream) {
                     case O128x32:  rc = launch_act<2, 2, 4, 1>(a, s); break;
                 }
             } else {
-                switch (cfg) {
+                switch (p.cfg) {
                     case A256x160: rc = launch<4, 5, 4, 2>(a, s); break;
                     case B128x160: rc = launch<2, 5, 4, 2>(a, s); break;
                     case C64x160:  rc = launch<2, 5, 2, 2>(a, s); break;

@@ -1,7 +1,9 @@
 // Launch arguments shared by the implicit-GEMM kernels (gemm.hip) and the 3x3 halo convolution on 32 x 32 MFMA tiles
-// (conv3x3.hip): filled by plan_gemm (gemm.hip) from a cid_gemm_desc.
+// (conv3x3.hip), and the plan of a cid_gemm_f16 call: both filled by cidg::plan (gemm_plan.hip) from a cid_gemm_desc.
 #pragma once
 #include "common.h"
+
+struct cid_gemm_desc;
 
 namespace cidg {
 
@@ -24,7 +26,7 @@ struct GemmArgs {
     int cslabs;          // (c1 + c2) / 64
     int splitk;          // gridDim.z
     int nloop;           // consecutive n-tiles walked by ONE workgroup (GEGLU launches; 1 = one tile per workgroup)
-    int nbuf;            // LDS stages of the DMA ring (2, or 3 where plan_gemm finds the launch latency-bound)
+    int nbuf;            // LDS stages of the DMA ring (2, or 3 where the planner finds the launch latency-bound)
     // mode 3 (query projection with the identity cross-attention as its epilogue): packed K / V^T of the context rows
     // (cid_kv_pack_f16), context row of every sample, halfs per packed row, context layout, ID-stream scale
     const half_t* att_kp; const half_t* att_vp; const int* att_kvrow;
@@ -42,7 +44,7 @@ struct GemmArgs {
                          // 2 = no MFMA, 3 = no LDS fragment reads / MFMA
     int xcd_pn;          // tile -> XCD partition (xcd_tile below): n-blocks of the 2-D partition (1 | 2 | 4 | 8), 0 = linear runs
     int tap0;            // first tap offset of a 3x3 conv: -1 (pad 1), 0 (cid_gemm_desc.pad_mode 1, Downsample2D(padding=0))
-    const half_t* w4;    // cid_gemm_desc.w_up4 when plan_gemm routes an Upsample2D convolution to the phase mode of conv3x3.hip
+    const half_t* w4;    // cid_gemm_desc.w_up4 when the planner routes an Upsample2D convolution to the phase mode of conv3x3.hip
                          // (four 2x2 convolutions at input resolution: W4[parity][n][tap4][c]), else nullptr
 };
 
@@ -71,7 +73,24 @@ CID_DEVINL void xcd_tile(const GemmArgs& a, int& nb, int& mb) {
 
 // host side: pn in {1, 2, 4, 8} (pm = 8 / pn) minimising pm * weight bytes + pn * activation bytes among the partitions the
 // grid divides into; 0 (linear runs, the old order) when none does.  CID_XCD_2D=0 pins the old order (A/B switch).
+// (gemm_plan.hip, next to the other switches)
 int choose_xcd_pn(int gx, int gy, double w_bytes, double x_bytes);
+
+// The plan of one cid_gemm_f16 call (gemm_plan.hip, host code): the filled launch arguments, the tile, the kernel family and
+// the template instance of that family.  cid_gemm_f16 launches it (gemm.hip), cid_gemm_plan reports it and
+// cid_gemm_stats_rows reads its stats_rows, so the report cannot drift from the launch.
+enum TileCfg { A256x160, B128x160, C64x160, G256x128, G128x128, O64x64, O128x32 };
+struct GemmPlan {
+    GemmArgs a;
+    TileCfg cfg;
+    int bm, bn;          // tile
+    int family;          // CID_GEMM_FAMILY_*
+    bool ln, act, vmode; // LN / ACT instance; a second, VMODE launch writes the transposed V third (mode 2)
+    bool sk_epilogue;    // splitk_epilogue_kernel follows
+    int stats_rows;      // token rows per GroupNorm statistics block (the tile height), 0 where the launch cannot emit them
+};
+// argument checks + the plan of one call (no launch): 0, or -22 with cid_set_error (the texts of cid_gemm_f16)
+int plan(const cid_gemm_desc* d, GemmPlan& p);
 
 // s_waitcnt vmcnt(N) with a run-time (wave-uniform) N
 CID_DEVINL void wait_vmcnt(int n) {
@@ -86,13 +105,13 @@ CID_DEVINL void wait_vmcnt(int n) {
 #undef CID_VM
 }
 
-// 3x3 stride-1 halo convolution, bm-token (256 | 128) x 160-channel tiles on v_mfma_f32_32x32x16_f16 (conv3x3.hip); plan_gemm
+// 3x3 stride-1 halo convolution, bm-token (256 | 128) x 160-channel tiles on v_mfma_f32_32x32x16_f16 (conv3x3.hip); the planner
 // has checked: a tile = whole image rows of one image or whole images, halo <= 400 rows, N % 160 == 0, M % bm == 0.
 // a.w4 set: the phase mode (up == 1, one source, no residual / time row; a tile = bm INPUT pixels of one output parity, whole
 // input rows of one image)
 int launch_conv_h32(const GemmArgs& a, int bm, hipStream_t s);
 
-// GEGLU projection on 32 x 32 x 16 MFMA tiles with loader / compute wave roles (linear_h32.hip); plan_gemm has checked: one
+// GEGLU projection on 32 x 32 x 16 MFMA tiles with loader / compute wave roles (linear_h32.hip); the planner has checked: one
 // source, taps == 1, no LayerNorm fold, M % 256 == 0, N % 160 == 0, a.nloop divides N / 160, at least 16 channel slabs (K >= 1024;
 // the kernel itself needs three, for its bias ring, and checks that)
 int launch_geglu_h32(const GemmArgs& a, hipStream_t s);

@@ -21,8 +21,8 @@
 // The erf epilogue (about 900 VALU per 64 x 160 tile and wave) is NOT overlapped inside a workgroup: beside a saturated MFMA
 // wave a SIMD issues one VALU instruction per 11.7 cycles however many waves offer them (profiles/r06_issue_rates.txt), so the
 // loader waves cannot take it; and a second accumulator set to drain in the MFMAs' own shadow only fits a 32 x 160 wave tile,
-// whose loop is LDS-bound again (built and measured: profiles/r06_geglu_h32.txt, 112 vs 74 us at level 0).  plan_gemm
-// therefore routes this kernel for deep K only (>= 1024 channels: one exposed epilogue per twenty slabs): SD1.5's 16 x 16
+// whose loop is LDS-bound again (built and measured: profiles/r06_geglu_h32.txt, 112 vs 74 us at level 0).  The planner
+// (gemm_plan.hip, route_linear_h32) therefore routes this kernel for deep K only (>= 1024 channels: one exposed epilogue per twenty slabs): SD1.5's 16 x 16
 // level 65 vs 75 us, SDXL's 32 x 32 level (60 of its 70 layers) 103 vs 118 us hot, 104 vs 126 us inside the step.
 // Roofline: MFMA; algorithmic work 2 M N K flop, bytes (M K + N K + M N / 2) * 2.  Inside a denoise step the shorter kernel
 // is paid back as a lower chip clock at lower power, not as time (profiles/r06_dvfs_ab.txt).

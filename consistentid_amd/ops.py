@@ -4,6 +4,7 @@ hand-written HIP kernel launch in libcid.so.  Nothing here computes on the CPU."
 from __future__ import annotations
 
 import ctypes as C
+import functools
 import os
 from typing import Optional
 
@@ -200,20 +201,24 @@ def ln_fold(M: int) -> bool:
     return _LN_FOLD_MODE == "1" or (_LN_FOLD_MODE == "auto" and M <= 2048)
 
 
-_GEGLU_H32 = os.environ.get("CID_GEGLU_H32", "1") != "0"
 _GEGLU_FOLD_MAX = int(os.environ.get("CID_GEGLU_FOLD_MAX", "8192"))      # A/B switch (2048 = the rule of rounds 3-5)
+
+
+@functools.lru_cache(maxsize=None)
+def _geglu_on_h32(M: int, C_: int) -> bool:
+    """does the unfolded GEGLU projection of ``M`` tokens x ``C_`` channels run on csrc/linear_h32.hip?  (the planner's answer)"""
+    return gemm_plan(M=M, N=8 * C_, c1=C_, mode=1, bias=True)["family"] == "geglu_h32"
 
 
 def ln_fold_geglu(M: int, C_: int) -> bool:
     """norm3 folded into the GEGLU projection?  Like :func:`ln_fold`, except where the launch runs on csrc/linear_h32.hip
-    (deep K, >= 256 tiles of 256 x 160: plan_gemm's rule), which takes a plain LayerNorm-ed input: layernorm + that kernel
-    measured 8 + 64 us against 84 us for the folded 16 x 16 x 32 form at SD1.5's 16 x 16 level (profiles/r06_kbench.txt)"""
-    h32 = _GEGLU_H32 and C_ >= 1024 and M % 256 == 0 and (M // 256) * (8 * C_ // 160) >= 256 and (8 * C_) % 160 == 0
+    (the planner's route_linear_h32, asked through :func:`gemm_plan`), which takes a plain LayerNorm-ed input: layernorm + that
+    kernel measured 8 + 64 us against 84 us for the folded 16 x 16 x 32 form at SD1.5's 16 x 16 level (profiles/r06_kbench.txt)"""
     if _LN_FOLD_MODE != "auto":
         return ln_fold(M)
     # (the GEGLU launch takes its row statistics during the first n-tile only: folded it stays ahead of layernorm + GEMM up to
     #  8192 tokens -- 69.7 vs 8.0 + 65.0 us at SD1.5's 32 x 32 level, profiles/r06_kbench.txt; 86.0 vs 10.2 + 73.9 at 64 x 64)
-    return M <= _GEGLU_FOLD_MAX and not h32
+    return M <= _GEGLU_FOLD_MAX and not _geglu_on_h32(M, C_)
 
 
 # the query projection of the cross-attention with the attention epilogue (gemm mode 3): folded up to 8192 tokens per launch

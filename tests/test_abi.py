@@ -76,8 +76,8 @@ def test_python_front_end_refuses_cpu_tensors(lib):
 
 
 def test_conv_tile_plan_without_gpu(lib):
-    """cid_gemm_plan / cid_gemm_stats_rows are host code: they run plan_gemm and report the launch a call would make and the
-    tile height it would use for GroupNorm statistics -- a probe of the convolution tile rules (csrc/gemm.hip plan_gemm,
+    """cid_gemm_plan / cid_gemm_stats_rows are host code: they run the planner (cidg::plan) and report the launch a call would make and the
+    tile height it would use for GroupNorm statistics -- a probe of the convolution tile rules (csrc/gemm_plan.hip,
     csrc/conv3x3.hip): 256-token tiles where they fill the chip, 128-token tiles for short K, no statistics from split-K
     launches, strided convolutions on the gather kernel."""
     from consistentid_amd._lib import GEMM_FAMILIES, GemmDesc, GemmPlanInfo

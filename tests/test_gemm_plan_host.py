@@ -1,11 +1,14 @@
 """Host checks of the GEMM dispatcher (no GPU): cid_gemm_plan / ops.gemm_plan report what cid_gemm_f16 would launch -- the
-launch reads the same decision (csrc/gemm.hip decide_launch) -- so the planner can be held to the census of the launches the
-models make (tests/golden/gemm_calls.json, tests/gemm_census.py) anywhere."""
+launch reads the same decision (csrc/gemm_plan.hip cidg::plan) -- so the planner can be held to the census of the launches the
+models make (tests/golden/gemm_calls.json, tests/gemm_census.py) anywhere, and to the characterisation grid around it
+(tests/golden/gemm_plan_grid.json, tests/gemm_plan_grid.py) under every planner switch."""
 import ctypes as C
+import json
 
 import pytest
 
 import gemm_census
+import gemm_plan_grid
 
 FIXTURE = gemm_census.load()
 RECORDS = gemm_census.all_records(FIXTURE)
@@ -101,3 +104,44 @@ def test_gemm_plan_argument_validation(lib):
         ops.gemm_plan(M=1024, N=640, c1=640, mode=3, heads=8, dhead=80, ntok=1024)
     with pytest.raises(CidError, match="a tensor is required"):
         ops.gemm(True, True, True, M=256, N=320, c1=320)
+
+
+def test_plan_grid_replays_under_every_switch(lib):
+    """The characterisation grid: every case (census descriptors, their neighbours, the refusals) must plan to the recorded
+    return code, plan fields and refusal text under the default switches and under each non-default value of each planner
+    switch -- one child process per setting (the switches are read once per process), one after another."""
+    z = gemm_plan_grid.load()
+    cases = gemm_plan_grid.expand(z["descs"], z["neighbours"])
+    assert len(z["default"]) == len(cases) and set(z["settings"]) == set(gemm_plan_grid.SETTINGS)
+    moved = []
+    for setting in ("",) + gemm_plan_grid.SETTINGS:
+        got, want = gemm_plan_grid.run_child("plan", gemm_plan_grid.GOLDEN, setting), gemm_plan_grid.expected(z, setting)
+        assert len(got) == len(want)
+        moved += [f"{setting or 'defaults'}: case {i} {cases[i]}\n      recorded {w}\n      now      {g}"
+                  for i, (g, w) in enumerate(zip(got, want)) if g != w]
+    assert not moved, f"{len(moved)} grid answers changed:\n  " + "\n  ".join(moved[:20]) + \
+                      f"\nif the change is meant, regenerate the fixture: {gemm_plan_grid.REGENERATE}"
+
+
+def _ln_fold_geglu_spec(M: int, C_: int, geglu_h32: bool) -> bool:
+    """ops.ln_fold_geglu as it stood while it restated the planner's linear_h32 rule in Python (CID_LN_FOLD and
+    CID_GEGLU_FOLD_MAX at their defaults; ``geglu_h32``: CID_GEGLU_H32 != 0): the specification of what it answers now"""
+    h32 = geglu_h32 and C_ >= 1024 and M % 256 == 0 and (M // 256) * (8 * C_ // 160) >= 256 and (8 * C_) % 160 == 0
+    return M <= 8192 and not h32
+
+
+def test_ln_fold_geglu_matches_its_old_predicate(lib, tmp_path):
+    """ops.ln_fold_geglu asks the planner whether the unfolded projection runs on linear_h32.hip; over every GEGLU shape of
+    the census and of the grid it must answer what its own copy of the rule answered, with CID_GEGLU_H32 unset and = 0"""
+    z = gemm_plan_grid.load()
+    shapes = {(r["M"], r["c1"]) for r, _ in RECORDS if r["mode"] == 1}
+    reached = len(shapes)
+    shapes |= {(c["M"], c["c1"]) for c in gemm_plan_grid.expand(z["descs"], z["neighbours"])
+               if c["mode"] == 1 and c["taps"] == 1 and c["c2"] == 0 and c["N"] == 8 * c["c1"] and c["c1"] % 64 == 0 and c["M"] > 0}
+    shapes = sorted(shapes)
+    assert reached >= 10 and len(shapes) > reached and any(_ln_fold_geglu_spec(M, c, False) != _ln_fold_geglu_spec(M, c, True) for M, c in shapes)
+    (tmp_path / "shapes.json").write_text(json.dumps(shapes))
+    for setting, on in (("", True), ("CID_GEGLU_H32=0", False)):
+        got = gemm_plan_grid.run_child("fold", tmp_path / "shapes.json", setting)
+        wrong = [(M, c, bool(g)) for (M, c), g in zip(shapes, got) if bool(g) != _ln_fold_geglu_spec(M, c, on)]
+        assert not wrong, f"ops.ln_fold_geglu under {setting or 'the defaults'} differs from its old predicate at (M, C_, now): {wrong}"

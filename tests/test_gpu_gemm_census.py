@@ -93,7 +93,7 @@ def test_variant_parity(dev, key):
     rec, plan = TABLE[key]
     # 1. the planner still sends this shape to this variant
     now = dict(zip(gemm_census.PLAN_FIELDS, gemm_census.plan_of(rec)))
-    assert gemm_census.variant_key(rec, now) == key, f"plan_gemm moved this shape: {gemm_census.variant_key(rec, now)}\n{rec}\n{now}"
+    assert gemm_census.variant_key(rec, now) == key, f"the planner moved this shape: {gemm_census.variant_key(rec, now)}\n{rec}\n{now}"
     M, N, c1, c2, taps, mode = (rec[k] for k in ("M", "N", "c1", "c2", "taps", "mode"))
     K = taps * (c1 + c2)
     ln = bool(rec["has_ln_s"])

@@ -95,7 +95,7 @@ def test_gemm_geglu(dev, M, C):
                                       (2048, 1280, True)])    # linear_h32.hip: two n-tiles per workgroup, twenty channel slabs
 def test_gemm_geglu_h32(dev, M, C, bias):
     """The GEGLU launches of linear_h32.hip (32 x 32 x 16 MFMA tiles, wave roles, N-loop, in-lane value / gate pairing and the
-    lane-32 swap in front of the 16-byte stores; plan_gemm gives it K >= 1024 only) and the N-loop launches of the 16 x 16 x 32
+    lane-32 swap in front of the 16-byte stores; route_linear_h32 gives it K >= 1024 only) and the N-loop launches of the 16 x 16 x 32
     kernel at the shorter K: against the fp32 formula, bit-identical run to run, and within rounding of the plain 16 x 16 x 32
     launch on the same rows (CID_GEGLU_H32=0 is read once per process, so that launch is reached through a shape it still
     owns: the same rows with a ragged tail)."""

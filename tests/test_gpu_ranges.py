@@ -52,10 +52,10 @@ def test_gelu_every_fp16_value(dev):
 
 
 def _routes_to_linear_h32(M, C):
-    """plan_gemm's rule for the GEGLU launch of linear_h32.hip (gemm.hip, the `mode == 1 && taps == 1 ...` branch): one source,
+    """The planner's rule for the GEGLU launch of linear_h32.hip (gemm_plan.hip, route_linear_h32): one source,
     no LayerNorm fold, N % 160 == 0, M % 256 == 0, at least 16 channel slabs of 64, >= 256 tiles of 256 x 160.  The library
     has no query for the kernel it picked, so the tests assert the route through this mirror of the rule.
-    Keep in sync with plan_gemm in consistentid_amd/csrc/gemm.hip (the branch that sets g32); CID_GEGLU_H32=0 turns it off."""
+    Keep in sync with route_linear_h32 in consistentid_amd/csrc/gemm_plan.hip; CID_GEGLU_H32=0 turns it off."""
     N = 8 * C
     return N % 160 == 0 and M % 256 == 0 and C // 64 >= 16 and (M // 256) * (N // 160) >= 256
 

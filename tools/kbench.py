@@ -76,7 +76,7 @@ def main():
             fl = 2.0 * M * cout * cin * taps
             rows.append((label, f"M={M}", t * 1e6, fl / t / 1e12, "TF/s", cnt))
             alg_bytes[label] = 2.0 * (x.shape[0] * cin + cout * taps * cin + M * cout)
-            if up:      # the same Upsample2D convolution from folded weights (four 2x2 phase convolutions where plan_gemm tiles it so)
+            if up:      # the same Upsample2D convolution from folded weights (four 2x2 phase convolutions where the planner tiles it so)
                 w4 = ops.upconv_fold(w)
                 t4 = timeit(lambda: ops.gemm(x, w, out, M=M, N=cout, c1=cin, bias=b, ws=ws, w_up4=w4, **kw))
                 rows.append((label + " folded", f"M={M}", t4 * 1e6, fl / t4 / 1e12, "TF/s (9-tap flop)", 0))
