@@ -15,7 +15,7 @@ void cid_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* cid_last_error(void) { return g_err; }
-extern "C" int cid_version(void) { return 104; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4, 104: cid_gemm_plan
+extern "C" int cid_version(void) { return 105; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4, 104: cid_gemm_plan, 105: cid_cfg_multistep_step_f16
 
 namespace {
 
@@ -489,6 +489,69 @@ cfg_ddim_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, const 
     }
 }
 
+// CFG + one step of a linear multistep sampler (PNDM, DPM-Solver++ 2M, DDIM with eta > 0): cid.h, "multistep row".  Every
+// per-step value -- coefficients, the ring slot that receives m, the save / restore flags, the noise row -- is read from the
+// 16-word device row, so the launch is the same for every step.  A ring slot, `saved` and `z` are loaded only where the
+// row gives them a non-zero coefficient (wave-uniform branches): an unwritten buffer may hold NaN, and 0 * NaN is NaN.
+__global__ void __launch_bounds__(256)
+cfg_multistep_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, float* hist, half_t* saved,
+                     const half_t* __restrict__ z, int z_rows, const float* __restrict__ row, float g,
+                     const half_t* __restrict__ mask, const half_t* __restrict__ init, const half_t* __restrict__ noise,
+                     long n /* B * per_sample, multiple of 8 */) {
+    const float a = row[0], b = row[1], cx = row[2], cm = row[3], cz = z ? row[11] : 0.f;
+    const float ch[4] = {row[4], row[5], row[6], row[7]};
+    const float ci = mask ? row[9] : 0.f, cn = mask ? row[10] : 0.f;
+    const int* irow = reinterpret_cast<const int*>(row);
+    const int w = irow[12], flags = irow[13];
+    const int zr = irow[14] < 0 ? 0 : (irow[14] > z_rows - 1 ? z_rows - 1 : irow[14]);   // a bad row cannot index past z
+    const bool put = w >= 0 && w < 4, save = flags & 1, restore = flags & 2;
+    for (long q = ((long)blockIdx.x * 256 + threadIdx.x) * 8; q < n; q += (long)gridDim.x * 256 * 8) {
+        const half8 eu = ld_global_h8(eps + q), ec = ld_global_h8(eps + n + q), xl = ld_global_h8(lat + q);
+        const half8 src = restore ? ld_global_h8(saved + q) : xl;
+        float m[8], v[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float u = (float)eu[i], c = (float)ec[i];
+            const float e = u + g * (c - u);
+            m[i] = a * (float)xl[i] + b * e;
+            v[i] = cx * (float)src[i] + cm * m[i];
+        }
+#pragma unroll
+        for (int s = 0; s < 4; ++s)
+            if (ch[s] != 0.f) {
+                const float* hp = hist + (long)s * n + q;
+                const f32x4 h0 = *reinterpret_cast<const f32x4*>(hp), h1 = *reinterpret_cast<const f32x4*>(hp + 4);
+#pragma unroll
+                for (int i = 0; i < 4; ++i) { v[i] += ch[s] * h0[i]; v[4 + i] += ch[s] * h1[i]; }
+            }
+        if (cz != 0.f) {
+            const half8 zv = ld_global_h8(z + (long)zr * n + q);
+#pragma unroll
+            for (int i = 0; i < 8; ++i) v[i] += cz * (float)zv[i];
+        }
+        if (put) {                                   // after the reads: the row may still weigh the slot's previous content
+            float* hp = hist + (long)w * n + q;
+            const f32x4 m0 = {m[0], m[1], m[2], m[3]}, m1 = {m[4], m[5], m[6], m[7]};
+            *reinterpret_cast<f32x4*>(hp) = m0;
+            *reinterpret_cast<f32x4*>(hp + 4) = m1;
+        }
+        if (save) *reinterpret_cast<half8*>(saved + q) = xl;
+        half8 mk, in0, nz;
+        if (mask) { mk = ld_global_h8(mask + q); in0 = ld_global_h8(init + q); nz = ld_global_h8(noise + q); }
+        half8 o;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            float r = v[i];
+            if (mask) {
+                const float k = (float)mk[i];
+                r = (1.f - k) * (ci * (float)in0[i] + cn * (float)nz[i]) + k * r;
+            }
+            o[i] = (half_t)r;
+        }
+        *reinterpret_cast<half8*>(lat + q) = o;
+    }
+}
+
 __global__ void __launch_bounds__(256)
 add_inplace_kernel(half_t* __restrict__ y, const half_t* __restrict__ a, long n, long na) {
     for (long q = ((long)blockIdx.x * 256 + threadIdx.x) * 8; q < n; q += (long)gridDim.x * 256 * 8) {
@@ -686,6 +749,23 @@ extern "C" int cid_cfg_ddim_step_f16(const cid_half* eps, cid_half* latents, con
                        (const half_t*)eps, (half_t*)latents, coef, guidance, (const half_t*)mask, (const half_t*)init,
                        (const half_t*)noise, n);
     CID_CHECK_LAUNCH("cid_cfg_ddim_step_f16");
+    return 0;
+}
+
+extern "C" int cid_cfg_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
+                                          const cid_half* z, int32_t z_rows, const void* row, float guidance,
+                                          const cid_half* mask, const cid_half* init, const cid_half* noise,
+                                          int32_t B, int32_t per_sample, cid_stream_t stream) {
+    CID_CHECK_ARG(eps && latents && hist && saved && row, "cid_cfg_multistep_step_f16: null pointer");
+    CID_CHECK_ARG((z == nullptr) == (z_rows == 0) && z_rows >= 0, "cid_cfg_multistep_step_f16: z and z_rows must come together");
+    CID_CHECK_ARG((mask == nullptr) == (init == nullptr) && (mask == nullptr) == (noise == nullptr),
+                  "cid_cfg_multistep_step_f16: mask/init/noise must come together");
+    const long n = (long)B * per_sample;
+    CID_CHECK_ARG(B > 0 && per_sample > 0 && n % 8 == 0, "cid_cfg_multistep_step_f16: B * per_sample must be a multiple of 8");
+    hipLaunchKernelGGL(cfg_multistep_kernel, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z, (int)z_rows,
+                       (const float*)row, guidance, (const half_t*)mask, (const half_t*)init, (const half_t*)noise, n);
+    CID_CHECK_LAUNCH("cid_cfg_multistep_step_f16");
     return 0;
 }
 

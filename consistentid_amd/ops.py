@@ -647,6 +647,41 @@ def cfg_ddim_step(eps: torch.Tensor, latents: torch.Tensor, coef: torch.Tensor, 
     return latents
 
 
+def cfg_multistep_step(eps: torch.Tensor, latents: torch.Tensor, hist: torch.Tensor, saved: torch.Tensor, row: torch.Tensor,
+                       guidance: float, *, B: int, per_sample: int, z: Optional[torch.Tensor] = None,
+                       mask: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None,
+                       noise: Optional[torch.Tensor] = None):
+    """CFG + one step of PNDM / DPM-Solver++ 2M / DDIM with eta (cid.h, "multistep row").  ``row``: 16 fp32 words on the
+    device (the integer words bit-cast), ``hist`` fp32 [4, B * per_sample], ``saved`` fp16 [B * per_sample], ``z`` fp16
+    [rows, B * per_sample] or None."""
+    lib = _lib.load()
+    n = B * per_sample
+    _req(eps, "cfg_multistep_step.eps")
+    _req(latents, "cfg_multistep_step.latents")
+    _req(hist, "cfg_multistep_step.hist", torch.float32)
+    _req(saved, "cfg_multistep_step.saved")
+    _req(row, "cfg_multistep_step.row", torch.float32)
+    if eps.numel() != 2 * n or latents.numel() != n or hist.numel() != 4 * n or saved.numel() != n or row.numel() != 16:
+        raise _lib.CidError(f"cfg_multistep_step: eps / latents / hist / saved / row hold {eps.numel()} / {latents.numel()} / "
+                            f"{hist.numel()} / {saved.numel()} / {row.numel()} elements; B * per_sample = {n} needs "
+                            f"{2 * n} / {n} / {4 * n} / {n} / 16")
+    z_rows = 0
+    if z is not None:
+        _req(z, "cfg_multistep_step.z")
+        if z.numel() == 0 or z.numel() % n:
+            raise _lib.CidError(f"cfg_multistep_step.z: {z.numel()} elements are not rows of B * per_sample = {n}")
+        z_rows = z.numel() // n
+    for name, t in (("mask", mask), ("init", init), ("noise", noise)):
+        if t is not None:
+            _req(t, f"cfg_multistep_step.{name}")
+            if t.numel() != n:
+                raise _lib.CidError(f"cfg_multistep_step.{name}: {t.numel()} elements, B * per_sample = {n}")
+    check(lib.cid_cfg_multistep_step_f16(_p(eps), _p(latents), _p(hist), _p(saved), _p(z), z_rows, _p(row), float(guidance),
+                                         _p(mask), _p(init), _p(noise), B, per_sample, _stream()),
+          "cid_cfg_multistep_step_f16")
+    return latents
+
+
 def add_inplace(y: torch.Tensor, a: torch.Tensor):
     lib = _lib.load()
     _req(y, "add_inplace.y")

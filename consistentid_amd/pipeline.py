@@ -32,7 +32,8 @@ import numpy as np
 import torch
 
 from . import ops
-from .scheduler import DDIMScheduler, EulerDiscreteScheduler  # noqa: F401
+from .scheduler import (C_IN, DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler,  # noqa: F401
+                        PNDMScheduler, pack_step_rows)
 from .unet import HipUNet
 
 
@@ -60,6 +61,7 @@ class _DenoiseEngine:
         self._graphs: Dict[bool, Any] = {}      # captured step, without / with the ControlNet forward
         self._warm_keys = set()
         self._static: Dict[str, torch.Tensor] = {}
+        self.step_path: Optional[str] = None    # the step launch of the last run: "cfg_ddim" or "cfg_multistep"
 
     def _static_tensor(self, name: str, like: torch.Tensor, dtype=None) -> torch.Tensor:
         """persistent device buffer (stable address across generations -> the captured graph stays valid)"""
@@ -80,8 +82,11 @@ class _DenoiseEngine:
             controlnet=None, control_image=None, conditioning_scale: float = 1.0,
             control_guidance_start: float = 0.0, control_guidance_end: float = 1.0,
             callback: Optional[Callable[[int, int, torch.Tensor], None]] = None, callback_steps: int = 1,
-            scale_initial: bool = True, unet_extra: Optional[torch.Tensor] = None):
-        """``first_step``: the loop runs schedule entries [first_step, S) -- the inpaint pipelines' ``strength`` < 1
+            scale_initial: bool = True, unet_extra: Optional[torch.Tensor] = None, eta: float = 0.0,
+            variance_noise: Optional[torch.Tensor] = None):
+        """``eta`` > 0 (DDIMScheduler only) with ``variance_noise`` [executed steps, B, C, h, w]: the noise diffusers' DDIM
+        ``step(..., eta=, variance_noise=)`` adds, one tensor per executed step in loop order.
+        ``first_step``: the loop runs schedule entries [first_step, S) -- the inpaint pipelines' ``strength`` < 1
         window (get_timesteps, inpaint ref :246-252); the embed switch and the ControlNet keep window count steps from
         there, exactly like the reference's ``for i, t in enumerate(timesteps)`` over the truncated list.
         ``unet_extra`` [B, 5, h, w]: cat([mask, masked_image_latents]) of a 9-channel inpainting UNet (inpaint ref
@@ -106,14 +111,42 @@ class _DenoiseEngine:
         sch.set_timesteps(num_inference_steps)
         ts = sch.timesteps
         inpaint = inpaint_mask is not None
-        coefs = torch.from_numpy(sch.coefficient_table(inpaint)).to(dev)
+        # the step launch: cid_cfg_ddim_step_f16 for the two first-order updates (DDIM at eta = 0, Euler), cid_cfg_multistep_
+        # step_f16 for PNDM, DPM-Solver++ and DDIM with eta > 0 (history ring, remembered sample, noise row)
+        eta = float(eta)
+        if eta != 0.0 and not isinstance(sch, DDIMScheduler):
+            raise ValueError(f"eta = {eta}: only DDIMScheduler has an eta term ({type(sch).__name__} is deterministic); "
+                             "set pipe.scheduler = DDIMScheduler.from_config(pipe.scheduler.config) or pass eta = 0")
+        if eta < 0.0:
+            raise ValueError(f"eta = {eta}: DDIM's eta is in [0, 1]")
+        multistep = bool(getattr(sch, "multistep", False)) or eta > 0.0
+        self.step_path = "cfg_multistep" if multistep else "cfg_ddim"
+        z_buf = None
+        if multistep:
+            rows = sch.coefficient_rows(inpaint, first_step, np.float32, **({"eta": eta} if eta > 0.0 else {}))
+            coefs = torch.from_numpy(pack_step_rows(rows)).to(dev)
+            if eta > 0.0:
+                n_run = len(ts) - first_step
+                if variance_noise is None or tuple(variance_noise.shape) != (n_run, *lat.shape):
+                    raise ValueError(f"eta = {eta} needs variance_noise of shape {(n_run, *lat.shape)} (one tensor per executed "
+                                     f"step), got {None if variance_noise is None else tuple(variance_noise.shape)}")
+                z_buf = S("z", variance_noise, torch.float16)
+        else:
+            coefs = torch.from_numpy(sch.coefficient_table(inpaint)).to(dev)
         tvals = torch.tensor(ts.astype(np.float32), device=dev)
         ar = torch.arange(B, dtype=torch.int32, device=dev)
         kv_pre = torch.cat([ar, ar + B]).contiguous()       # i <= start_merge_step: (null, text)
         kv_post = torch.cat([ar + (3 * B if null_embeds_post is not None else 0), ar + 2 * B]).contiguous()  # afterwards
         t_buf = S("t", torch.zeros(1), torch.float32)
-        coef_buf = S("coef", torch.zeros(5), torch.float32)      # c_x, c_eps, c_init, c_noise, model-input scale
-        in_scale = coef_buf[4:5]
+        if multistep:
+            coef_buf = S("ms_row", torch.zeros(16), torch.int32)     # the multistep row (cid.h): 12 fp32 words, 4 int32 words
+            row_f32 = coef_buf.view(torch.float32)
+            in_scale = row_f32[C_IN:C_IN + 1]
+            hist = S("ms_hist", torch.zeros(4, lat.numel()), torch.float32)      # fp32 ring of earlier model outputs
+            saved = S("ms_saved", torch.zeros(lat.numel()), torch.float16)       # the sample PNDM steps from twice
+        else:
+            coef_buf = S("coef", torch.zeros(5), torch.float32)      # c_x, c_eps, c_init, c_noise, model-input scale
+            in_scale = coef_buf[4:5]
         kvrow = S("kvrow", kv_pre, torch.int32)
         added = None
         pooled_post = None
@@ -168,7 +201,7 @@ class _DenoiseEngine:
         # step, copies row `counter` into the buffers the step's kernels read and increments the counter
         n_ts = len(ts)
         merged_at = torch.tensor([(i - first_step) > start_merge_step for i in range(n_ts)], device=dev)
-        cols = [(t_buf, tvals.view(n_ts, 1)), (coef_buf, coefs.view(n_ts, 5).float()),
+        cols = [(t_buf, tvals.view(n_ts, 1)), (coef_buf, coefs.view(n_ts, 16) if multistep else coefs.view(n_ts, 5).float()),
                 (kvrow, torch.where(merged_at[:, None], kv_post[None], kv_pre[None]))]
         if cn_kvrow is not None:
             cols.append((cn_kvrow, torch.where(merged_at[:, None], (ar + B)[None], ar[None])))
@@ -185,7 +218,7 @@ class _DenoiseEngine:
         # every static buffer exists now: a new one (S() cleared _graph) or a new configuration invalidates the captured
         # graphs AND their eager warm-up (the first step after a shape change must run eagerly again)
         key = (B, tuple(lat.shape), float(guidance_scale), inpaint, time_ids is not None, dres is not None,
-               controlnet is not None, float(conditioning_scale), extra is not None)
+               controlnet is not None, float(conditioning_scale), extra is not None, multistep, z_buf is not None)
         if key != self._graph_key or self._graph is None:
             self._graphs.clear()
             self._warm_keys.clear()
@@ -198,8 +231,12 @@ class _DenoiseEngine:
                 d, m = controlnet.forward_tokens(lat, t_buf, cn_kvrow, B, cn_cond, conditioning_scale, temb=cn_temb_buf,
                                                  in_scale=in_scale)
             eps = unet.forward_tokens(lat, t_buf, kvrow, 2 * B, added, d, m, temb=temb_buf, in_scale=in_scale, extra=extra)
-            ops.cfg_ddim_step(eps, lat, coef_buf, guidance_scale, B=B, per_sample=per_sample,
-                              mask=mask, init=init, noise=noise)
+            if multistep:
+                ops.cfg_multistep_step(eps, lat, hist, saved, row_f32, guidance_scale, B=B, per_sample=per_sample, z=z_buf,
+                                       mask=mask, init=init, noise=noise)
+            else:
+                ops.cfg_ddim_step(eps, lat, coef_buf, guidance_scale, B=B, per_sample=per_sample,
+                                  mask=mask, init=init, noise=noise)
 
         for i in range(first_step, len(ts)):
             with_cn = controlnet is not None and cn_keep[i] > 0.0     # keep = 0: the residuals are zero (CN :397-403)
@@ -284,10 +321,31 @@ class _BasePipeline:
 
     @scheduler.setter
     def scheduler(self, sch):
-        if not hasattr(sch, "coefficient_table"):
+        if not (hasattr(sch, "coefficient_table") or hasattr(sch, "coefficient_rows")):
             raise TypeError(f"{type(sch).__name__}: the engine takes consistentid_amd.scheduler.DDIMScheduler / "
-                            "EulerDiscreteScheduler (build one with .from_config(diffusers_scheduler.config))")
+                            "EulerDiscreteScheduler / PNDMScheduler / DPMSolverMultistepScheduler (build one with "
+                            ".from_config(diffusers_scheduler.config))")
         self._engine.scheduler = sch
+
+    def _variance_noise(self, eta: float, generator, variance_noise, latents, num_inference_steps: int, first_step: int = 0):
+        """``eta`` of the reference ``__call__``s (prepare_extra_step_kwargs -> DDIMScheduler.step(eta=, generator=)): with
+        DDIM and eta > 0 every executed step adds sigma_t * randn.  The tensors are drawn here, before the loop, one
+        ``randn_tensor`` [B, C, h, w] fp16 per executed step in loop order on ``generator`` -- after every pre-loop draw, so
+        the generator's stream is consumed in diffusers' order -- or taken from ``variance_noise`` [steps, B, C, h, w]."""
+        if eta == 0.0:
+            if variance_noise is not None:
+                raise ValueError("variance_noise without eta: the noise term has the coefficient eta * sigma_t")
+            return None
+        if not isinstance(self.scheduler, DDIMScheduler):
+            raise ValueError(f"eta = {eta}: only DDIMScheduler has an eta term ({type(self.scheduler).__name__} is deterministic); "
+                             "set pipe.scheduler = DDIMScheduler.from_config(pipe.scheduler.config) or pass eta = 0")
+        if variance_noise is not None:
+            return variance_noise
+        from .vae import randn_tensor
+        self.scheduler.set_timesteps(num_inference_steps)
+        shape = tuple(latents.shape)
+        return torch.stack([randn_tensor(shape, generator=generator, device=self.device, dtype=torch.float16)
+                            for _ in range(len(self.scheduler.timesteps) - first_step)])
 
     # -- surface kept from the reference ------------------------------------------------------
     @classmethod
@@ -552,7 +610,7 @@ class ConsistentIDStableDiffusionPipeline(_IDPreLoop, _SD15PromptEncoding, _Base
                  negative_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
                  cross_attention_kwargs=None, original_size=None, target_size=None, callback=None,
                  callback_steps: int = 1, input_id_images=None, start_merge_step: int = 0,
-                 class_tokens_mask=None, prompt_embeds_text_only=None):
+                 class_tokens_mask=None, prompt_embeds_text_only=None, variance_noise: Optional[torch.Tensor] = None):
         """``pipe(prompt, input_id_images=[face], ...)`` runs the reference's pre-loop (prepare_id_prompt_embeds) and, without
         ``latents``, draws them like diffusers' prepare_latents (randn_tensor on the generator's device); or pass
         ``prompt_embeds`` (cat([null, augmented, text_only])) and ``latents`` directly."""
@@ -577,11 +635,11 @@ class ConsistentIDStableDiffusionPipeline(_IDPreLoop, _SD15PromptEncoding, _Base
             prompt = input_id_images = None
         self._check_hot_path_inputs(prompt, input_id_images, prompt_embeds, latents, output_type)
         assert guidance_scale >= 1.0, "the reference asserts classifier-free guidance (ref :434,:441)"
-        assert eta == 0.0, "DDIM eta = 0 only"
+        variance_noise = self._variance_noise(eta, generator, variance_noise, latents, num_inference_steps)
         null_e, aug_e, text_e = self._split(prompt_embeds)
         out = self._engine.run(latents, null_e, aug_e, text_e, num_inference_steps=num_inference_steps,
                                guidance_scale=guidance_scale, start_merge_step=start_merge_step,
-                               callback=callback, callback_steps=callback_steps)
+                               callback=callback, callback_steps=callback_steps, eta=eta, variance_noise=variance_noise)
         out = self._postprocess(out, output_type, legacy_numpy=True)   # no safety checker: has_nsfw_concept = None
         if not return_dict:
             return (out, None)
@@ -635,12 +693,14 @@ class ConsistentIDStableDiffusionXLPipeline(_BasePipeline):
                  original_size=None, crops_coords_top_left=(0, 0), target_size=None, input_id_images=None,
                  start_merge_step: int = 0, class_tokens_mask=None, prompt_embeds_text_only=None,
                  pooled_prompt_embeds_text_only=None, add_time_ids: Optional[torch.Tensor] = None,
-                 negative_prompt_embeds_facial: Optional[torch.Tensor] = None):
+                 negative_prompt_embeds_facial: Optional[torch.Tensor] = None,
+                 variance_noise: Optional[torch.Tensor] = None):
         """pooled_prompt_embeds = pooled embeds used AFTER the merge step, pooled_prompt_embeds_text_only
         BEFORE it, negative_pooled_prompt_embeds for the unconditional half (ref SDXL :620-631);
         add_time_ids [2B, 6] (ref :531-539)."""
         self._check_hot_path_inputs(prompt, input_id_images, prompt_embeds, latents, output_type)
-        assert guidance_scale >= 1.0 and eta == 0.0
+        assert guidance_scale >= 1.0
+        variance_noise = self._variance_noise(eta, generator, variance_noise, latents, num_inference_steps)
         # The SDXL loop has TWO unconditional sets (ref SDXL :586-590, :620-631): cat([negative text embeds, uncond ID
         # tokens]) up to start_merge_step, cat([FacialEncoder(negative embeds), uncond ID tokens]) afterwards.
         # prompt_embeds = cat([null_text_only, augmented, text_only, null_facial]) (4B rows); with 3B rows the one null
@@ -673,7 +733,7 @@ class ConsistentIDStableDiffusionXLPipeline(_BasePipeline):
                                guidance_scale=guidance_scale, start_merge_step=start_merge_step, null_embeds_post=null_post,
                                pooled=(negative_pooled_prompt_embeds, pooled_prompt_embeds_text_only,
                                        pooled_prompt_embeds), time_ids=add_time_ids,
-                               callback=callback, callback_steps=callback_steps)
+                               callback=callback, callback_steps=callback_steps, eta=eta, variance_noise=variance_noise)
         out = self._postprocess(out, output_type)
         if not return_dict:
             return (out,)
@@ -798,7 +858,7 @@ class StableDiffusionInpaintConsistentIDPipeline(_SD15PromptEncoding, _BasePipel
                  input_id_images=None, start_merge_step: int = 0, class_tokens_mask=None,
                  prompt_embeds_text_only=None, image_latents: Optional[torch.Tensor] = None,
                  noise: Optional[torch.Tensor] = None, mask_latents: Optional[torch.Tensor] = None,
-                 down_block_res_samples=None, mid_block_res_sample=None):
+                 down_block_res_samples=None, mid_block_res_sample=None, variance_noise: Optional[torch.Tensor] = None):
         """Either ``image`` + ``mask_image`` (the pre-loop of ref :231-295 on ``vae_encoder``) or the pre-computed
         ``image_latents`` (init latents), ``noise`` and ``mask_latents`` [B,1,h,w] (1 = repaint), ``masked_image_latents``.
         ``image`` is the INIT image [B, 3, H, W] / [3, H, W] float in [0, 1] (or already in [-1, 1]): the reference reads
@@ -816,12 +876,13 @@ class StableDiffusionInpaintConsistentIDPipeline(_SD15PromptEncoding, _BasePipel
         extra = self._unet_extra(latents, mask_latents, masked_image_latents)
         null_e, aug_e, text_e = self._split(prompt_embeds)
         b_mask, b_init, b_noise = self._blend_inputs(extra, mask_latents, image_latents, noise)
+        variance_noise = self._variance_noise(eta, generator, variance_noise, latents, num_inference_steps, first)
         out = self._engine.run(latents, null_e, aug_e, text_e, num_inference_steps=num_inference_steps,
                                guidance_scale=guidance_scale, start_merge_step=start_merge_step,
                                down_residuals=down_block_res_samples, mid_residual=mid_block_res_sample,
                                inpaint_mask=b_mask, inpaint_init=b_init, inpaint_noise=b_noise,
                                callback=callback, callback_steps=callback_steps, first_step=first, scale_initial=scaled,
-                               unet_extra=extra)
+                               unet_extra=extra, eta=eta, variance_noise=variance_noise)
         out = self._postprocess(out, output_type)
         if not return_dict:
             return (out, None)
@@ -856,7 +917,7 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
                  input_id_images=None, start_merge_step: int = 0, class_tokens_mask=None, prompt_embeds_text_only=None,
                  image_latents: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                  mask_latents: Optional[torch.Tensor] = None, down_block_res_samples=None, mid_block_res_sample=None,
-                 masked_image_latents: Optional[torch.Tensor] = None):
+                 masked_image_latents: Optional[torch.Tensor] = None, variance_noise: Optional[torch.Tensor] = None):
         """``image`` / ``mask_image``: as in StableDiffusionInpaintConsistentIDPipeline.__call__ (the init image comes in
         through ``image=``; the reference reads it from ``input_id_images[0]``, CN :180, :255-258)."""
         if image is not None or mask_image is not None:
@@ -881,6 +942,7 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
             cn = self.controlnet
         null_e, aug_e, text_e = self._split(prompt_embeds)
         b_mask, b_init, b_noise = self._blend_inputs(extra, mask_latents, image_latents, noise)
+        variance_noise = self._variance_noise(eta, generator, variance_noise, latents, num_inference_steps, first_step)
         out = self._engine.run(latents, null_e, aug_e, text_e, num_inference_steps=num_inference_steps,
                                guidance_scale=guidance_scale, start_merge_step=start_merge_step,
                                down_residuals=down_block_res_samples, mid_residual=mid_block_res_sample,
@@ -888,7 +950,7 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
                                controlnet=cn, control_image=control_image, conditioning_scale=float(scale),
                                control_guidance_start=float(g0), control_guidance_end=float(g1),
                                callback=callback, callback_steps=callback_steps, first_step=first_step, scale_initial=scaled,
-                               unet_extra=extra)
+                               unet_extra=extra, eta=eta, variance_noise=variance_noise)
         out = self._postprocess(out, output_type)
         if not return_dict:
             return (out, None)

@@ -5,7 +5,14 @@ steps_offset 1, set_alpha_to_one False, eta 0; timestep spacing "leading" (the b
 "linspace" / "trailing" on request; ``from_config`` takes a diffusers scheduler config.
 
 Only tiny tables are computed here (float64 on the host, once); the per-element update runs
-in cid_cfg_ddim_step_f16 which reads the coefficients from device memory."""
+in cid_cfg_ddim_step_f16 which reads the coefficients from device memory.
+
+``PNDMScheduler`` (the sampler the Stable Diffusion 1.5 model directory names), ``DPMSolverMultistepScheduler``
+(DPM-Solver++ 2M) and DDIM with eta > 0 are linear multistep updates: a combination of the sample, the current model
+output, earlier model outputs and a noise tensor.  They run in cid_cfg_multistep_step_f16, and each class writes its
+per-step rows (include/cid.h, "multistep row") by simulating its own state machine over the schedule entries the loop
+will run: ``coefficient_rows(inpaint, first_step, dtype)``.  The three algorithms are restated from the published
+diffusers 0.23 schedulers, UNPINNED like oracle/ddim.py."""
 from __future__ import annotations
 
 from typing import List, Tuple
@@ -13,6 +20,35 @@ from typing import List, Tuple
 import numpy as np
 
 SPACINGS = ("leading", "linspace", "trailing")
+
+ROW_WORDS = 16          # cid_cfg_multistep_step_f16's device row: words 0..11 fp32, 12..15 int32
+C_IN, C_Z = 8, 11       # word of the model-input scale (16-byte aligned: conv_in reads it in place) / of z's coefficient
+_W, _FLAGS, _ZROW = 12, 13, 14
+FLAG_SAVE, FLAG_RESTORE = 1, 2
+
+
+def _row(a=0.0, b=1.0, c_x=0.0, c_m=0.0, c_hist=(0.0, 0.0, 0.0, 0.0), c_z=0.0, c_init=1.0, c_noise=0.0, c_in=1.0,
+         w=-1, flags=0, z_row=0) -> List[float]:
+    return [a, b, c_x, c_m, *c_hist, c_in, c_init, c_noise, c_z, float(w), float(flags), float(z_row), 0.0]
+
+
+def _idle_row() -> List[float]:
+    """a schedule entry before ``first_step``: never selected; it writes nothing and weighs nothing"""
+    return _row(c_x=1.0)
+
+
+def pack_step_rows(rows: np.ndarray) -> np.ndarray:
+    """rows [n, 16] as ``coefficient_rows`` returns them (every word a float, the integer words holding integer values)
+    -> int32 [n, 16], the bit pattern the kernel reads: words 0..11 fp32, words 12..15 int32"""
+    rows = np.asarray(rows)
+    out = np.ascontiguousarray(rows.astype(np.float32)).view(np.int32).copy()
+    out[:, _W:] = np.rint(rows[:, _W:]).astype(np.int32)
+    return out
+
+
+def _train_alphas_cumprod(beta_start: float, beta_end: float, T: int) -> np.ndarray:
+    betas = np.linspace(np.float32(beta_start) ** 0.5, np.float32(beta_end) ** 0.5, T, dtype=np.float32) ** 2
+    return np.cumprod((1.0 - betas).astype(np.float32), dtype=np.float32)
 
 
 def _config_args(config, accepted) -> dict:
@@ -41,9 +77,17 @@ def _spaced_timesteps(T: int, n: int, spacing: str, offset: int) -> np.ndarray:
     raise ValueError(f"timestep_spacing {spacing!r}: one of {SPACINGS}")
 
 
+def _next_blend(sch, inpaint: bool, i: int) -> Tuple[float, float]:
+    """(c_init, c_noise) of the inpaint blend after schedule entry i: add_noise at the NEXT entry, identity after the last"""
+    if inpaint and i < len(sch.timesteps) - 1:
+        return sch.add_noise_coefficients(sch.timesteps[i + 1])
+    return 1.0, 0.0
+
+
 class DDIMScheduler:
     order = 1
     init_noise_sigma = 1.0
+    multistep = False        # eta = 0 is cid_cfg_ddim_step_f16's two-coefficient update; eta > 0 takes coefficient_rows
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
                  steps_offset: int = 1, set_alpha_to_one: bool = False, timestep_spacing: str = "leading"):
@@ -108,6 +152,21 @@ class DDIMScheduler:
             rows.append([c_x, c_e, ci, cn, 1.0])          # last column: model-input scale (identity for DDIM)
         return np.asarray(rows, dtype=np.float32)
 
+    def coefficient_rows(self, inpaint: bool = False, first_step: int = 0, dtype=np.float32, eta: float = 0.0) -> np.ndarray:
+        """[len(timesteps), 16] multistep rows of DDIM with ``eta`` (diffusers' ``step(..., eta=, variance_noise=)``):
+        sigma_t = eta sqrt((1 - a_prev) / (1 - a_t) (1 - a_t / a_prev)),
+        x' = sqrt(a_prev) (x - sqrt(1 - a_t) e) / sqrt(a_t) + sqrt(1 - a_prev - sigma_t^2) e + sigma_t z[k],
+        k counting the executed steps from ``first_step``.  The engine takes this path for eta > 0 only."""
+        ts = self.timesteps
+        rows = [_idle_row() for _ in range(min(first_step, len(ts)))]
+        for i in range(first_step, len(ts)):
+            a_t, a_p = self.alphas(int(ts[i]))
+            sigma = float(eta) * ((1.0 - a_p) / (1.0 - a_t) * (1.0 - a_t / a_p)) ** 0.5
+            c_e = (1.0 - a_p - sigma * sigma) ** 0.5 - (a_p ** 0.5) * ((1.0 - a_t) ** 0.5) / (a_t ** 0.5)
+            ci, cn = _next_blend(self, inpaint, i)
+            rows.append(_row(c_x=(a_p / a_t) ** 0.5, c_m=c_e, c_z=sigma, c_init=ci, c_noise=cn, z_row=i - first_step))
+        return np.asarray(rows, dtype=np.float64).reshape(-1, ROW_WORDS).astype(dtype)
+
 
 class EulerDiscreteScheduler:
     """The scheduler of the reference's canonical scripts (infer.py:33, infer_SDXL.py:37:
@@ -116,6 +175,7 @@ class EulerDiscreteScheduler:
     update as DDIM with other coefficients -- x_prev = x + (sigma_next - sigma) * eps -- plus a model-input scale
     1 / sqrt(sigma^2 + 1) (applied inside conv_in) and an initial latent scale ``init_noise_sigma``."""
     order = 1
+    multistep = False
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
                  steps_offset: int = 1, timestep_spacing: str = "leading"):
@@ -175,3 +235,189 @@ class EulerDiscreteScheduler:
                 ci, cn = 1.0, nxt                           # add_noise at the NEXT timestep: init + sigma_next * noise
             rows.append([1.0, nxt - s, ci, cn, 1.0 / (s * s + 1.0) ** 0.5])
         return np.asarray(rows, dtype=np.float32)
+
+
+class PNDMScheduler:
+    """The scheduler Stable Diffusion 1.5's model directory names (``scheduler/scheduler_config.json``: PNDMScheduler,
+    skip_prk_steps true, steps_offset 1): ``pipe.scheduler = PNDMScheduler.from_config(pipe.scheduler.config)`` samples
+    with the model's own sampler.  Built: ``skip_prk_steps=True`` (the linear multistep part, no Runge-Kutta warm-up) and
+    epsilon prediction.  The timestep list has num_inference_steps + 1 entries -- the second timestep comes twice: the
+    first step is taken once with its own model output and redone from the remembered sample with the mean of two -- so
+    a generation is num_inference_steps + 1 UNet evaluations (one for a single step)."""
+    order = 1
+    init_noise_sigma = 1.0
+    multistep = True
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                 steps_offset: int = 1, set_alpha_to_one: bool = False, timestep_spacing: str = "leading",
+                 skip_prk_steps: bool = True):
+        if not skip_prk_steps:
+            raise NotImplementedError("skip_prk_steps=False: the Runge-Kutta warm-up steps are not built")
+        if timestep_spacing not in SPACINGS:
+            raise ValueError(f"timestep_spacing {timestep_spacing!r}: one of {SPACINGS}")
+        self.alphas_cumprod = _train_alphas_cumprod(beta_start, beta_end, num_train_timesteps)
+        self.final_alpha_cumprod = np.float32(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
+        self.num_train_timesteps = num_train_timesteps
+        self.steps_offset, self.timestep_spacing = steps_offset, timestep_spacing
+        self.timesteps: np.ndarray = np.zeros(0, dtype=np.int64)
+        self.num_inference_steps = 0
+        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                           beta_schedule="scaled_linear", trained_betas=None, steps_offset=steps_offset,
+                           set_alpha_to_one=set_alpha_to_one, timestep_spacing=timestep_spacing, prediction_type="epsilon",
+                           skip_prk_steps=True)
+
+    @classmethod
+    def from_config(cls, config) -> "PNDMScheduler":
+        """a config without ``skip_prk_steps`` (another scheduler class's) gets the built variant; an explicit false raises"""
+        return cls(**_config_args(config, ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "set_alpha_to_one",
+                                           "timestep_spacing", "skip_prk_steps")))
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        T, n = self.num_train_timesteps, num_inference_steps
+        self.num_inference_steps = n
+        if self.timestep_spacing == "leading":
+            t = np.arange(0, n) * (T // n) + self.steps_offset
+        elif self.timestep_spacing == "linspace":
+            t = np.linspace(0, T - 1, n).round()
+        else:
+            t = np.round(np.arange(T, 0, -T / n))[::-1] - 1
+        t = t.astype(np.int64)
+        self.timesteps = np.concatenate([t[:-1], t[-2:-1], t[-1:]])[::-1].copy()
+
+    def scale_model_input(self, sample, t=None):
+        return sample
+
+    def add_noise_coefficients(self, t) -> Tuple[float, float]:
+        a = float(self.alphas_cumprod[int(t)])
+        return a ** 0.5, (1.0 - a) ** 0.5
+
+    def coefficient_rows(self, inpaint: bool = False, first_step: int = 0, dtype=np.float32) -> np.ndarray:
+        """[len(timesteps), 16] multistep rows: ``step_plms`` over entries [first_step, len) with a counter and a history
+        that start empty at ``first_step``, as a fresh scheduler stepping over the truncated list does.  The kernel's m is
+        the model output itself (a = 0, b = 1); ring slot k mod 4 takes the k-th appended one."""
+        ts, T = self.timesteps, self.num_train_timesteps
+        ratio = T // self.num_inference_steps
+        rows = [_idle_row() for _ in range(min(first_step, len(ts)))]
+        counter = appended = 0
+        for i in range(first_step, len(ts)):
+            t = int(ts[i])
+            w, flags, c_hist = -1, 0, [0.0] * 4
+            if counter != 1:
+                w = appended % 4
+                appended += 1
+                prev = t - ratio
+            else:
+                prev, t = t, t + ratio
+            a_t = float(self.alphas_cumprod[t])
+            a_p = float(self.alphas_cumprod[prev]) if prev >= 0 else float(self.final_alpha_cumprod)
+            c_x = (a_p / a_t) ** 0.5
+            c_mo = -(a_p - a_t) / (a_t * (1.0 - a_p) ** 0.5 + (a_t * (1.0 - a_t) * a_p) ** 0.5)
+            held = min(appended, 4)
+            slot = lambda back: (appended - back) % 4          # ring slot of ets[-back]
+            if counter == 1:                                    # (e + ets[-1]) / 2 from the remembered sample
+                c_m, flags = 0.5 * c_mo, FLAG_RESTORE
+                c_hist[slot(1)] = 0.5 * c_mo
+            else:                                               # ets[-1] is this step's e, written after the reads
+                weights = {1: (1.0,), 2: (1.5, -0.5), 3: (23 / 12, -16 / 12, 5 / 12), 4: (55 / 24, -59 / 24, 37 / 24, -9 / 24)}[held]
+                c_m = weights[0] * c_mo
+                for back, wt in enumerate(weights[1:], start=2):
+                    c_hist[slot(back)] = wt * c_mo
+                if counter == 0:
+                    flags = FLAG_SAVE
+            ci, cn = _next_blend(self, inpaint, i)
+            rows.append(_row(a=0.0, b=1.0, c_x=c_x, c_m=c_m, c_hist=c_hist, c_init=ci, c_noise=cn, w=w, flags=flags))
+            counter += 1
+        return np.asarray(rows, dtype=np.float64).reshape(-1, ROW_WORDS).astype(dtype)
+
+
+class DPMSolverMultistepScheduler:
+    """DPM-Solver++ (2M): ``algorithm_type="dpmsolver++"``, ``solver_order=2``, ``solver_type="midpoint"``,
+    ``lower_order_final=True``, epsilon prediction -- what ``DPMSolverMultistepScheduler.from_config(pipe.scheduler.config)``
+    gives on the Stable Diffusion configs.  The kernel's m is the data prediction (x - sigma_i e) / alpha_i, kept in the
+    fp32 ring; the second-order step weighs m_i and m_(i-1).  The first executed step is first order, and so is the last
+    one of a schedule shorter than 15 (``lower_order_final``)."""
+    order = 1
+    init_noise_sigma = 1.0
+    multistep = True
+
+    _BUILT = dict(algorithm_type="dpmsolver++", solver_order=2, solver_type="midpoint", lower_order_final=True,
+                  use_karras_sigmas=False, thresholding=False, lambda_min_clipped=-float("inf"), variance_type=None,
+                  euler_at_final=False, use_lu_lambdas=False)
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                 steps_offset: int = 0, timestep_spacing: str = "linspace"):
+        if timestep_spacing not in SPACINGS:
+            raise ValueError(f"timestep_spacing {timestep_spacing!r}: one of {SPACINGS}")
+        self.alphas_cumprod = _train_alphas_cumprod(beta_start, beta_end, num_train_timesteps)
+        ac = self.alphas_cumprod.astype(np.float64)
+        self._train_sigmas = ((1.0 - ac) / ac) ** 0.5
+        self.num_train_timesteps, self.steps_offset, self.timestep_spacing = num_train_timesteps, steps_offset, timestep_spacing
+        self.timesteps: np.ndarray = np.zeros(0, dtype=np.int64)
+        self.sigmas: np.ndarray = np.zeros(0, dtype=np.float64)
+        self.num_inference_steps = 0
+        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                           beta_schedule="scaled_linear", trained_betas=None, steps_offset=steps_offset,
+                           timestep_spacing=timestep_spacing, prediction_type="epsilon", **self._BUILT)
+
+    @classmethod
+    def from_config(cls, config) -> "DPMSolverMultistepScheduler":
+        """a config without ``timestep_spacing`` belongs to a class whose default is "leading" (PNDM, DDIM; see
+        EulerDiscreteScheduler.from_config); diffusers' own default for this class, "linspace", is the constructor's"""
+        cfg = dict(config)
+        for key, built in cls._BUILT.items():
+            got = cfg.get(key, built)
+            if key == "lambda_min_clipped":
+                ok = got is None or float(got) == built
+            elif key == "variance_type":
+                ok = got is None or not str(got).startswith("learned")      # a learned variance doubles the UNet's channels
+            else:
+                ok = got == built
+            if not ok:
+                raise NotImplementedError(f"{key}={got!r}: DPMSolverMultistepScheduler is built for {key}={built!r} only")
+        args = _config_args(cfg, ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "timestep_spacing"))
+        args.setdefault("timestep_spacing", "leading")
+        return cls(**args)
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        T, n = self.num_train_timesteps, num_inference_steps
+        self.num_inference_steps = n
+        if self.timestep_spacing == "linspace":
+            ts = np.linspace(0, T - 1, n + 1).round()[::-1][:-1]
+        elif self.timestep_spacing == "leading":
+            ts = (np.arange(0, n + 1) * (T // (n + 1))).round()[::-1][:-1] + self.steps_offset
+        else:
+            ts = np.arange(T, 0, -T / n).round() - 1
+        self.timesteps = ts.astype(np.int64)
+        sig = np.interp(self.timesteps, np.arange(0, T), self._train_sigmas)
+        self.sigmas = np.concatenate([sig, self._train_sigmas[:1]])
+
+    def scale_model_input(self, sample, t=None):
+        return sample
+
+    def add_noise_coefficients(self, t) -> Tuple[float, float]:
+        a = float(self.alphas_cumprod[int(t)])
+        return a ** 0.5, (1.0 - a) ** 0.5
+
+    def coefficient_rows(self, inpaint: bool = False, first_step: int = 0, dtype=np.float32) -> np.ndarray:
+        """[len(timesteps), 16] multistep rows over entries [first_step, len); the history starts empty at ``first_step``.
+        With alpha = 1 / sqrt(sigma^2 + 1), s = sigma alpha, lambda = log alpha - log s, h = lambda_(i+1) - lambda_i,
+        D = -alpha_(i+1) (exp(-h) - 1):  x' = (s_(i+1) / s_i) x + D m_i  [+ D / (2 r) (m_i - m_(i-1)),
+        r = (lambda_i - lambda_(i-1)) / h]."""
+        n = len(self.timesteps)
+        alpha = 1.0 / (self.sigmas ** 2 + 1.0) ** 0.5
+        s = self.sigmas * alpha
+        lam = np.log(alpha) - np.log(s)
+        rows = [_idle_row() for _ in range(min(first_step, n))]
+        for i in range(first_step, n):
+            k = i - first_step
+            h = lam[i + 1] - lam[i]
+            D = -alpha[i + 1] * (np.exp(-h) - 1.0)
+            c_m, c_hist = D, [0.0] * 4
+            if k > 0 and not (i == n - 1 and n < 15):
+                r = (lam[i] - lam[i - 1]) / h
+                c_m = D + D / (2.0 * r)
+                c_hist[(k - 1) % 4] = -D / (2.0 * r)
+            ci, cn = _next_blend(self, inpaint, i)
+            rows.append(_row(a=1.0 / alpha[i], b=-s[i] / alpha[i], c_x=s[i + 1] / s[i], c_m=float(c_m), c_hist=c_hist,
+                             c_init=ci, c_noise=cn, w=k % 4))
+        return np.asarray(rows, dtype=np.float64).reshape(-1, ROW_WORDS).astype(dtype)

@@ -27,7 +27,7 @@ extern "C" {
 typedef void* cid_stream_t;      /* hipStream_t */
 typedef uint16_t cid_half;       /* IEEE binary16 bit pattern */
 
-int cid_version(void);          /* 104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
+int cid_version(void);          /* 105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
                                  * pointer (102: act, 101: pad_mode; set them or zero the struct) */
 const char* cid_last_error(void);
 
@@ -439,7 +439,31 @@ int cid_linear_small_f16(const cid_half* x, int32_t ldx, const cid_half* w, cons
 int cid_cfg_ddim_step_f16(const cid_half* eps, cid_half* latents, const float* coef, float guidance,
                           const cid_half* mask, const cid_half* init, const cid_half* noise,
                           int32_t B, int32_t per_sample, cid_stream_t stream);
-/* y[i] += a[i mod na]  (ControlNet residual adds, CN :418-425) */
+/* CFG + one step of a linear multistep sampler: PNDM (skip_prk_steps), DPM-Solver++ 2M, DDIM with eta > 0
+ * (consistentid_amd/scheduler.py computes the rows).  eps [2B][per_sample] (uncond first); latents [B][per_sample],
+ * updated in place; hist: fp32 ring [4][B * per_sample] of earlier model outputs; saved: fp16 [B * per_sample], the
+ * sample PNDM's second evaluation steps from again; z: fp16 [z_rows][B * per_sample] pre-drawn noise or NULL (z_rows 0).
+ * row: DEVICE, sixteen 4-byte words (cid_step_select fills it), the "multistep row":
+ *    f0 a   f1 b           m = a * x + b * e,  e = eps_u + g (eps_c - eps_u),  x = latents as they come in
+ *    f2 c_x f3 c_m         coefficient of the source sample / of m
+ *    f4..f7 c_hist[0..3]   coefficient of ring slot 0..3 as it is BEFORE this launch (absolute slots: the host permutes)
+ *    f8 c_in               model-input scale: conv_in reads this word through a 16-byte-aligned view, which is why it
+ *                          sits here; 1.0 for these samplers, not used by this kernel
+ *    f9 c_init f10 c_noise inpaint blend of the NEXT timestep, as in cid_cfg_ddim_step_f16
+ *    f11 c_z               coefficient of z[z_row]
+ *    i12 w                 ring slot that receives m (written after the reads), none unless 0 <= w < 4
+ *    i13 flags             bit0: copy x into `saved`;  bit1: the source sample is `saved` (as it is before this launch), else x
+ *    i14 z_row             clamped to [0, z_rows)        i15 0
+ *    x' = c_x * src + c_m * m + sum_s c_hist[s] * hist[s] + c_z * z[z_row];
+ *    latents = mask ? (1 - mask) * (c_init * init + c_noise * noise) + mask * x' : x'
+ * A ring slot with c_hist[s] == 0, z with c_z == 0 and `saved` with bit1 clear are NOT read (they may hold anything, NaN
+ * included).  fp32 arithmetic, one rounding to fp16 at the store of latents; hist keeps m in fp32.
+ * B * per_sample % 8 == 0; every buffer 16-byte aligned; mask/init/noise come together or not at all. */
+int cid_cfg_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
+                               const cid_half* z, int32_t z_rows, const void* row, float guidance,
+                               const cid_half* mask, const cid_half* init, const cid_half* noise,
+                               int32_t B, int32_t per_sample, cid_stream_t stream);
+/* y[i] += a[i mod na] (ControlNet residual adds, CN :418-425) */
 int cid_add_inplace_f16(cid_half* y, const cid_half* a, int64_t n, int64_t na, cid_stream_t stream);
 
 /* The reference's  `for i, t in enumerate(timesteps):`  (pipline_StableDiffusion_ConsistentID.py:535, SDXL :611, CN :375)
