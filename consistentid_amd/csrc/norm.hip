@@ -15,12 +15,12 @@ constexpr int LN_MAXCH = 3;
 __global__ void __launch_bounds__(256)
 layernorm_kernel(const half_t* __restrict__ x, half_t* __restrict__ out,
                  const half_t* __restrict__ gamma, const half_t* __restrict__ beta,
-                 int M, int C, float eps) {
+                 int M, int C, long ldx, long ldo, float eps) {
     const int lane = threadIdx.x & 63;
     const int row = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (row >= M) return;
     const int nch = C >> 3;
-    const half_t* xr = x + (long)row * C;
+    const half_t* xr = x + (long)row * ldx;
     float v[LN_MAXCH][8];
     float s = 0.f;
 #pragma unroll
@@ -46,7 +46,7 @@ layernorm_kernel(const half_t* __restrict__ x, half_t* __restrict__ out,
         }
     }
     const float rstd = rsqrtf(wave_sum(q) / (float)C + eps);
-    half_t* orow = out + (long)row * C;
+    half_t* orow = out + (long)row * ldo;
 #pragma unroll
     for (int k = 0; k < LN_MAXCH; ++k) {
         const int c = lane + k * 64;
@@ -69,14 +69,14 @@ template <int LPR>
 __global__ void __launch_bounds__(256)
 layernorm_rows_kernel(const half_t* __restrict__ x, half_t* __restrict__ out,
                       const half_t* __restrict__ gamma, const half_t* __restrict__ beta,
-                      int M, int C, float eps) {
+                      int M, int C, long ldx, long ldo, float eps) {
     constexpr int RPW = 64 / LPR;                       // rows per wave
     const int lane = threadIdx.x & 63;
     const int sub = lane % LPR;
     const int row = (blockIdx.x * 4 + (threadIdx.x >> 6)) * RPW + lane / LPR;
     const int nk = (C >> 3) / LPR;                      // chunks per lane (the host checked: exact, <= LNR_MAXCH)
     const bool live = row < M;
-    const half_t* xr = x + (long)(live ? row : 0) * C;
+    const half_t* xr = x + (long)(live ? row : 0) * ldx;
     half8 h[LNR_MAXCH], g[LNR_MAXCH], b[LNR_MAXCH];
 #pragma unroll
     for (int k = 0; k < LNR_MAXCH; ++k)
@@ -103,7 +103,7 @@ layernorm_rows_kernel(const half_t* __restrict__ x, half_t* __restrict__ out,
     for (int o = LPR / 2; o > 0; o >>= 1) q += __shfl_xor(q, o, 64);
     const float rstd = rsqrtf(q / (float)C + eps);
     if (!live) return;
-    half_t* orow = out + (long)row * C;
+    half_t* orow = out + (long)row * ldo;
 #pragma unroll
     for (int k = 0; k < LNR_MAXCH; ++k)
         if (k < nk) {
@@ -397,28 +397,36 @@ inline int gn_nblk(int HW) { return (HW + gn_rows(HW) - 1) / gn_rows(HW); }
 
 }  // namespace
 
-extern "C" int cid_layernorm_f16(const cid_half* x, cid_half* out, const cid_half* gamma, const cid_half* beta,
-                                 int32_t M, int32_t C, float eps, cid_stream_t stream) {
-    CID_CHECK_ARG(x && out && gamma && beta, "cid_layernorm_f16: null pointer");
-    CID_CHECK_ARG(M > 0 && C > 0 && C % 8 == 0 && C <= 8 * 64 * LN_MAXCH, "cid_layernorm_f16: bad shape M=%d C=%d", M, C);
+// ldx / ldo: row pitches of x and out in halfs (>= C, multiples of 8: every lane moves 16 bytes)
+extern "C" int cid_layernorm_ld_f16(const cid_half* x, int64_t ldx, cid_half* out, int64_t ldo, const cid_half* gamma,
+                                    const cid_half* beta, int32_t M, int32_t C, float eps, cid_stream_t stream) {
+    CID_CHECK_ARG(x && out && gamma && beta, "cid_layernorm_ld_f16: null pointer");
+    CID_CHECK_ARG(M > 0 && C > 0 && C % 8 == 0 && C <= 8 * 64 * LN_MAXCH, "cid_layernorm_ld_f16: bad shape M=%d C=%d", M, C);
+    CID_CHECK_ARG(ldx >= C && ldo >= C && ldx % 8 == 0 && ldo % 8 == 0, "cid_layernorm_ld_f16: bad pitch ldx=%lld ldo=%lld (C=%d)",
+                  (long long)ldx, (long long)ldo, C);
     const int nch = C >> 3;
     // several rows per wave only where the launch is large enough to fill the chip that way (measured: 12.2 -> 10.2 us at
     // 32768 x 320, but 8.2 -> 8.7 us at 8192 x 640 and 2048 x 1280, where one row per wave already is one round of waves)
     const bool big = (long)M * C >= (8L << 20);
     if (!big)
         hipLaunchKernelGGL(layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                           (const half_t*)x, (half_t*)out, (const half_t*)gamma, (const half_t*)beta, M, C, eps);
+                           (const half_t*)x, (half_t*)out, (const half_t*)gamma, (const half_t*)beta, M, C, (long)ldx, (long)ldo, eps);
     else if (nch % 8 == 0 && nch / 8 <= LNR_MAXCH)
         hipLaunchKernelGGL(layernorm_rows_kernel<8>, dim3((M + 31) / 32), dim3(256), 0, (hipStream_t)stream,
-                           (const half_t*)x, (half_t*)out, (const half_t*)gamma, (const half_t*)beta, M, C, eps);
+                           (const half_t*)x, (half_t*)out, (const half_t*)gamma, (const half_t*)beta, M, C, (long)ldx, (long)ldo, eps);
     else if (nch % 16 == 0 && nch / 16 <= LNR_MAXCH)
         hipLaunchKernelGGL(layernorm_rows_kernel<16>, dim3((M + 15) / 16), dim3(256), 0, (hipStream_t)stream,
-                           (const half_t*)x, (half_t*)out, (const half_t*)gamma, (const half_t*)beta, M, C, eps);
+                           (const half_t*)x, (half_t*)out, (const half_t*)gamma, (const half_t*)beta, M, C, (long)ldx, (long)ldo, eps);
     else
         hipLaunchKernelGGL(layernorm_kernel, dim3((M + 3) / 4), dim3(256), 0, (hipStream_t)stream,
-                           (const half_t*)x, (half_t*)out, (const half_t*)gamma, (const half_t*)beta, M, C, eps);
-    CID_CHECK_LAUNCH("cid_layernorm_f16");
+                           (const half_t*)x, (half_t*)out, (const half_t*)gamma, (const half_t*)beta, M, C, (long)ldx, (long)ldo, eps);
+    CID_CHECK_LAUNCH("cid_layernorm_ld_f16");
     return 0;
+}
+
+extern "C" int cid_layernorm_f16(const cid_half* x, cid_half* out, const cid_half* gamma, const cid_half* beta,
+                                 int32_t M, int32_t C, float eps, cid_stream_t stream) {
+    return cid_layernorm_ld_f16(x, C, out, C, gamma, beta, M, C, eps, stream);
 }
 
 

@@ -94,7 +94,7 @@ id_xattn3_kernel(const half_t* __restrict__ x, half_t* __restrict__ out,
                  const half_t* __restrict__ wqp, const float* q_rowsum, const float* q_bias,
                  const half_t* __restrict__ wop, const half_t* bo,
                  const half_t* kp, const half_t* vp, const int* __restrict__ kvrow,
-                 int N, int tiles_per_sample, int total_tiles, float ip_scale, float ln_eps, int flags) {
+                 int N, int tiles_per_sample, int total_tiles, float ip_scale, float ln_eps, int flags, int ldo) {
 #if defined(__HIP_DEVICE_COMPILE__)
     extern __shared__ __attribute__((aligned(16))) char smem[];
     typedef __attribute__((address_space(3))) void lds_void;
@@ -469,13 +469,13 @@ id_xattn3_kernel(const half_t* __restrict__ x, half_t* __restrict__ out,
             }
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
         X3_STAMP(11);
-        half_t* ob = out + tok0 * YC + wn * 80;
+        half_t* ob = out + tok0 * ldo + wn * 80;          // ldo: row pitch of out (YC, or wider: a column block of a shared buffer)
 #pragma unroll
         for (int k = 0; k < 10; ++k) {
             const int e = k * 64 + lane;
             const int r = e / 10, c = e - r * 10;
             const int ch = wn * 80 + c * 8;
-            *reinterpret_cast<half8*>(ob + (long)r * YC + c * 8) = *t_frag(0, ch >> 6, r, (ch >> 3) & 7);
+            *reinterpret_cast<half8*>(ob + (long)r * ldo + c * 8) = *t_frag(0, ch >> 6, r, (ch >> 3) & 7);
         }
         X3_STAMP(12);
 #ifdef CID_X3_TRACE
@@ -533,24 +533,25 @@ extern "C" int cid_gather_pack_f16(const cid_half* src_a, const cid_half* src_b,
     return 0;
 }
 
-extern "C" int cid_id_xattn3_f16(const cid_half* x, cid_half* out, const cid_half* wq_packed, const float* q_rowsum,
-                                 const float* q_bias, const cid_half* wo_packed, const cid_half* bo, const cid_half* kp,
-                                 const cid_half* vp, const int32_t* kvrow, int32_t B, int32_t N, int32_t C, int32_t heads,
-                                 int32_t n_txt, int32_t n_ip, float ip_scale, float ln_eps, int32_t flags,
-                                 cid_stream_t stream) {
-    CID_CHECK_ARG(x && out && wq_packed && q_rowsum && q_bias && wo_packed && kp && vp && kvrow, "cid_id_xattn3_f16: null pointer");
+extern "C" int cid_id_xattn3_ld_f16(const cid_half* x, cid_half* out, int64_t ldo, const cid_half* wq_packed,
+                                    const float* q_rowsum, const float* q_bias, const cid_half* wo_packed, const cid_half* bo,
+                                    const cid_half* kp, const cid_half* vp, const int32_t* kvrow, int32_t B, int32_t N,
+                                    int32_t C, int32_t heads, int32_t n_txt, int32_t n_ip, float ip_scale, float ln_eps,
+                                    int32_t flags, cid_stream_t stream) {
+    CID_CHECK_ARG(x && out && wq_packed && q_rowsum && q_bias && wo_packed && kp && vp && kvrow, "cid_id_xattn3_ld_f16: null pointer");
     CID_CHECK_ARG(cid_id_xattn3_supported(C, heads, n_txt, n_ip),
-                  "cid_id_xattn3_f16: built for C=%d, %d heads and a 77+4 or 81+0 context (got C=%d heads=%d context %d+%d)",
+                  "cid_id_xattn3_ld_f16: built for C=%d, %d heads and a 77+4 or 81+0 context (got C=%d heads=%d context %d+%d)",
                   YC, YNH, C, heads, n_txt, n_ip);
-    CID_CHECK_ARG(B > 0 && N > 0 && N % YBT == 0, "cid_id_xattn3_f16: N=%d must be a positive multiple of %d", N, YBT);
-    CID_CHECK_ARG(x != out, "cid_id_xattn3_f16: in-place operation is not supported");
+    CID_CHECK_ARG(B > 0 && N > 0 && N % YBT == 0, "cid_id_xattn3_ld_f16: N=%d must be a positive multiple of %d", N, YBT);
+    CID_CHECK_ARG(x != out, "cid_id_xattn3_ld_f16: in-place operation is not supported");
+    CID_CHECK_ARG(ldo >= YC && ldo % 8 == 0 && ldo < (1 << 24), "cid_id_xattn3_ld_f16: bad output pitch %lld", (long long)ldo);
     const int kind = (n_txt == 77 && n_ip == 4) ? 0 : 1;
     auto kern = kind == 0 ? id_xattn3_kernel<77, 4> : id_xattn3_kernel<81, 0>;
     static bool configured[2] = {false, false};
     if (!configured[kind]) {
         hipError_t herr = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, Y_SMEM);
         if (herr != hipSuccess) {
-            cid_set_error("cid_id_xattn3_f16: cannot reserve %d bytes of LDS (%s)", Y_SMEM, hipGetErrorString(herr));
+            cid_set_error("cid_id_xattn3_ld_f16: cannot reserve %d bytes of LDS (%s)", Y_SMEM, hipGetErrorString(herr));
             return -5;
         }
         configured[kind] = true;
@@ -558,7 +559,16 @@ extern "C" int cid_id_xattn3_f16(const cid_half* x, cid_half* out, const cid_hal
     const int tiles = N / YBT, total = tiles * B;
     hipLaunchKernelGGL(kern, dim3(total), dim3(256), Y_SMEM, (hipStream_t)stream, (const half_t*)x, (half_t*)out,
                        (const half_t*)wq_packed, q_rowsum, q_bias, (const half_t*)wo_packed, (const half_t*)bo,
-                       (const half_t*)kp, (const half_t*)vp, kvrow, N, tiles, total, ip_scale, ln_eps, flags);
-    CID_CHECK_LAUNCH("cid_id_xattn3_f16");
+                       (const half_t*)kp, (const half_t*)vp, kvrow, N, tiles, total, ip_scale, ln_eps, flags, (int)ldo);
+    CID_CHECK_LAUNCH("cid_id_xattn3_ld_f16");
     return 0;
+}
+
+extern "C" int cid_id_xattn3_f16(const cid_half* x, cid_half* out, const cid_half* wq_packed, const float* q_rowsum,
+                                 const float* q_bias, const cid_half* wo_packed, const cid_half* bo, const cid_half* kp,
+                                 const cid_half* vp, const int32_t* kvrow, int32_t B, int32_t N, int32_t C, int32_t heads,
+                                 int32_t n_txt, int32_t n_ip, float ip_scale, float ln_eps, int32_t flags,
+                                 cid_stream_t stream) {
+    return cid_id_xattn3_ld_f16(x, out, C, wq_packed, q_rowsum, q_bias, wo_packed, bo, kp, vp, kvrow, B, N, C, heads, n_txt,
+                                n_ip, ip_scale, ln_eps, flags, stream);
 }

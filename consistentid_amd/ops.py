@@ -221,6 +221,30 @@ def ln_fold_geglu(M: int, C_: int) -> bool:
     return M <= _GEGLU_FOLD_MAX and not _geglu_on_h32(M, C_)
 
 
+# ff2 + proj_out of a transformer's tail as ONE GEMM over the row [ff | h3] (weights [Wp W2 | Wp]): "auto"
+# (default) folds where the folded launch plans to the kernel family, tile, ring depth and split / unsplit class of the ff2
+# launch it replaces -- the launch variants the models reach then stay the ones tests/golden/gemm_calls.json lists; "0" never;
+# "1" wherever the library accepts the launch (tests at tiny shapes)
+_FF2_FOLD_MODE = os.environ.get("CID_FF2_FOLD", "auto")
+GEMM_WS_BYTES = 64 << 20     # the engine's split-K workspace (HipUNet._gemm_ws allocates this): part of what the planner decides on
+
+
+@functools.lru_cache(maxsize=None)
+def ff2_fold(M: int, C_: int, gn_hw: int = 0) -> bool:
+    """does the tail of a transformer with ``C_`` channels on ``M`` tokens run as one GEMM?  (``gn_hw``: what proj_out passes)"""
+    if _FF2_FOLD_MODE == "0":
+        return False
+    try:
+        folded = gemm_plan(M=M, N=C_, c1=5 * C_, bias=True, res=True, ldr=C_, ws=True, ws_bytes=GEMM_WS_BYTES, gn_hw=gn_hw)
+    except _lib.CidError:
+        return False
+    if _FF2_FOLD_MODE == "1":
+        return True
+    ff2 = gemm_plan(M=M, N=C_, c1=4 * C_, bias=True, res=True, ldr=C_, ws=True, ws_bytes=GEMM_WS_BYTES)
+    same = lambda p: (p["family"], p["bm"], p["bn"], p["nbuf"], p["splitk"] > 1)
+    return same(folded) == same(ff2)
+
+
 # the query projection of the cross-attention with the attention epilogue (gemm mode 3): folded up to 8192 tokens per launch
 # (SD1.5's 32 x 32 level at CFG batch 8: 43.1 -> 39.9 us with norm2 folded; SDXL's 4096-token level 58.4 vs 57.9; A/B switch)
 _QATTN_FOLD_MAX = int(os.environ.get("CID_QATTN_LNFOLD_MAX", "8192"))
@@ -344,9 +368,10 @@ def id_xattn3_supported(C_: int, heads: int, n_txt: int, n_ip: int) -> bool:
 def id_xattn3(x: torch.Tensor, out: torch.Tensor, *, wq_p: torch.Tensor, q_rowsum: torch.Tensor, q_bias: torch.Tensor,
               wo_p: torch.Tensor, bo: Optional[torch.Tensor], kp: torch.Tensor, vp: torch.Tensor, kvrow: torch.Tensor,
               B: int, N: int, C_: int, heads: int, n_txt: int, n_ip: int, ip_scale: float, has_ln: bool,
-              add_residual: bool, ln_eps: float = 1e-5):
+              add_residual: bool, ln_eps: float = 1e-5, ldo: Optional[int] = None):
     """third-generation fused identity cross-attention: ``wq_p`` / ``wo_p`` = xattn_pack.pack_w3 of the (LayerNorm-folded)
-    query and the output projection; K / V operands from kv_pack2(order="reg")"""
+    query and the output projection; K / V operands from kv_pack2(order="reg").  ``ldo``: row pitch of ``out`` in halfs
+    where it is a column block of a wider buffer (cid_id_xattn3_ld_f16); ``x`` is contiguous either way"""
     lib = _lib.load()
     for name, t in (("x", x), ("out", out), ("wq_p", wq_p), ("wo_p", wo_p), ("kp", kp), ("vp", vp)):
         _req(t, f"id_xattn3.{name}")
@@ -355,9 +380,15 @@ def id_xattn3(x: torch.Tensor, out: torch.Tensor, *, wq_p: torch.Tensor, q_rowsu
     _req(q_rowsum, "id_xattn3.q_rowsum", torch.float32)
     _req(q_bias, "id_xattn3.q_bias", torch.float32)
     _req(kvrow, "id_xattn3.kvrow", torch.int32)
-    check(lib.cid_id_xattn3_f16(_p(x), _p(out), _p(wq_p), _p(q_rowsum), _p(q_bias), _p(wo_p), _p(bo), _p(kp), _p(vp),
-                                _p(kvrow), B, N, C_, heads, n_txt, n_ip, float(ip_scale), float(ln_eps),
-                                (1 if has_ln else 0) | (2 if add_residual else 0), _stream()), "cid_id_xattn3_f16")
+    flags = (1 if has_ln else 0) | (2 if add_residual else 0)
+    if ldo is None:
+        check(lib.cid_id_xattn3_f16(_p(x), _p(out), _p(wq_p), _p(q_rowsum), _p(q_bias), _p(wo_p), _p(bo), _p(kp), _p(vp),
+                                    _p(kvrow), B, N, C_, heads, n_txt, n_ip, float(ip_scale), float(ln_eps), flags,
+                                    _stream()), "cid_id_xattn3_f16")
+    else:
+        check(lib.cid_id_xattn3_ld_f16(_p(x), _p(out), ldo, _p(wq_p), _p(q_rowsum), _p(q_bias), _p(wo_p), _p(bo), _p(kp),
+                                       _p(vp), _p(kvrow), B, N, C_, heads, n_txt, n_ip, float(ip_scale), float(ln_eps),
+                                       flags, _stream()), "cid_id_xattn3_ld_f16")
     return out
 
 
@@ -374,11 +405,16 @@ def id_xattn_core(q: torch.Tensor, out: torch.Tensor, *, kp: torch.Tensor, vp: t
 
 # --------------------------------------------------------------------------- norms
 def layernorm(x: torch.Tensor, out: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, *, M: int, C_: int,
-              eps: float = 1e-5):
+              eps: float = 1e-5, ldx: Optional[int] = None, ldo: Optional[int] = None):
+    """``ldx`` / ``ldo``: row pitches in halfs where ``x`` / ``out`` is a column block of a wider buffer (cid_layernorm_ld_f16)"""
     lib = _lib.load()
     for name, t in (("x", x), ("out", out), ("gamma", gamma), ("beta", beta)):
         _req(t, f"layernorm.{name}")
-    check(lib.cid_layernorm_f16(_p(x), _p(out), _p(gamma), _p(beta), M, C_, eps, _stream()), "cid_layernorm_f16")
+    if ldx is None and ldo is None:
+        check(lib.cid_layernorm_f16(_p(x), _p(out), _p(gamma), _p(beta), M, C_, eps, _stream()), "cid_layernorm_f16")
+    else:
+        check(lib.cid_layernorm_ld_f16(_p(x), C_ if ldx is None else ldx, _p(out), C_ if ldo is None else ldo, _p(gamma),
+                                       _p(beta), M, C_, eps, _stream()), "cid_layernorm_ld_f16")
     return out
 
 

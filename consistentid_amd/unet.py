@@ -53,6 +53,12 @@ class _Ctx:
         self.key_ref = None
 
 
+def fused_gen1(c: int, tokens: int, fused_max_c: int = 320) -> bool:
+    """one launch of the first-generation fused cross-attention kernel instead of LN + GEMM + core + GEMM, where the third
+    generation does not serve?  (HipUNet._fused_gen1 with the engine's CID_XATTN_FUSED_MAX_C; the measurements are there)"""
+    return c <= fused_max_c or (c <= 640 and tokens >= 16384 and fused_max_c >= 320)
+
+
 class HipUNet:
     def __init__(self, cfg: UNetConfig, unet_sd: Optional[Dict[str, torch.Tensor]] = None,
                  adapter_sd: Optional[Dict[str, torch.Tensor]] = None, device="cuda:0",
@@ -74,7 +80,7 @@ class HipUNet:
             self.ups = []
         self._ctx = _Ctx()
         self._gn_ws: Optional[torch.Tensor] = None
-        self._gemm_ws = torch.empty(64 << 20, dtype=torch.uint8, device=self.device)   # split-K partials
+        self._gemm_ws = torch.empty(ops.GEMM_WS_BYTES, dtype=torch.uint8, device=self.device)   # split-K partials
         # widest level that runs the one-launch fused ID cross-attention (wider levels: GEMMs around the core)
         self._xattn_fused_max_c = int(os.environ.get("CID_XATTN_FUSED_MAX_C", "320"))
         self._cfg_dedup = os.environ.get("CID_CFG_DEDUP", "1") != "0"
@@ -263,42 +269,62 @@ class HipUNet:
                 x = full if full is not None and full.shape[0] == rep * x.shape[0] else self._dup(x, rep)
                 Bc, M = B, B * N
             # --- identity cross attention (Consistent_IPAttProcessor, attention.py:207-294) inside x + attn2(LN(x), ehs)
-            h3 = self.cross_attention(b, h2, B, N, c, t.heads, kvrow)
+            gn_hw = N if N == N_real else 0
+            # the last block's ff2 and proj_out as one GEMM over the row [ff | h3]: both live in ONE
+            # [M, 5c] buffer, written at pitch 5c by their producers (the first-generation fused kernel has no pitched form)
+            fold = (k == t.n_layers - 1 and ops.ff2_fold(M, c, gn_hw)
+                    and (ctx.v2.get(b) == 3 or not self._fused_gen1(c, M)))
+            buf = self._empty(M, 5 * c) if fold else None
+            ldh = 5 * c if fold else c
+            h3 = self.cross_attention(b, h2, B, N, c, t.heads, kvrow, out=buf[:, 4 * c:] if fold else None)
             # --- feed forward (GEGLU)
-            ff = self._empty(M, 4 * c)
+            ff = buf if fold else self._empty(M, 4 * c)
             if ops.ln_fold_geglu(M, c):     # norm3 folded into the GEGLU projection
-                ops.gemm(h3, W[f"{b}.ff1.wl"], ff, M=M, N=8 * c, c1=c, mode=1, ln=self._ln(b, "ff1.ln"))
+                ops.gemm(h3, W[f"{b}.ff1.wl"], ff, M=M, N=8 * c, c1=c, ld1=ldh, ldo=ldh if fold else None, mode=1,
+                         ln=self._ln(b, "ff1.ln"))
             else:
                 ln3 = self._empty(M, c)
-                ops.layernorm(h3, ln3, W[f"{b}.norm3.g"], W[f"{b}.norm3.b"], M=M, C_=c)
-                ops.gemm(ln3, W[f"{b}.ff1.w"], ff, M=M, N=8 * c, c1=c, bias=W[f"{b}.ff1.b"], mode=1)
-            h = self._empty(M, c)
-            ops.gemm(ff, W[f"{b}.ff2.w"], h, M=M, N=c, c1=4 * c, bias=W[f"{b}.ff2.b"], res=h3, ldr=c,
-                     ws=self._gemm_ws)
-        out = self._empty(M, c)
-        ops.gemm(h, W[f"{n}.proj_out.w"], out, M=M, N=c, c1=c, bias=W[f"{n}.proj_out.b"], res=x, ldr=c,
-                 gn_hw=N if N == N_real else 0)      # (the next resnet's norm1 / a skip consumer reads it)
+                ops.layernorm(h3, ln3, W[f"{b}.norm3.g"], W[f"{b}.norm3.b"], M=M, C_=c, ldx=ldh if fold else None)
+                ops.gemm(ln3, W[f"{b}.ff1.w"], ff, M=M, N=8 * c, c1=c, ldo=ldh if fold else None, bias=W[f"{b}.ff1.b"], mode=1)
+            if fold:
+                out = self._empty(M, c)
+                ops.gemm(buf, W[f"{n}.ffpo.w"], out, M=M, N=c, c1=5 * c, bias=W[f"{n}.ffpo.b"], res=x, ldr=c,
+                         ws=self._gemm_ws, gn_hw=gn_hw)
+            else:
+                h = self._empty(M, c)
+                ops.gemm(ff, W[f"{b}.ff2.w"], h, M=M, N=c, c1=4 * c, bias=W[f"{b}.ff2.b"], res=h3, ldr=c,
+                         ws=self._gemm_ws)
+        if not fold:
+            out = self._empty(M, c)
+            ops.gemm(h, W[f"{n}.proj_out.w"], out, M=M, N=c, c1=c, bias=W[f"{n}.proj_out.b"], res=x, ldr=c,
+                     gn_hw=N if N == N_real else 0)      # (the next resnet's norm1 / a skip consumer reads it)
         if N != N_real:
             out = out.view(-1, N, c)[:, :N_real].reshape(-1, c)      # reshape of a sliced view: one copy
         return out
 
-    def cross_attention(self, b: str, h2: torch.Tensor, B: int, N: int, c: int, heads: int, kvrow: torch.Tensor) -> torch.Tensor:
+    def cross_attention(self, b: str, h2: torch.Tensor, B: int, N: int, c: int, heads: int, kvrow: torch.Tensor,
+                        out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """``h2 + attn2(LayerNorm(h2), context)`` of transformer block ``b`` on token-major ``h2`` [B * N, c]: the launch
         sequence the denoise step uses for this layer (bench.py times exactly this for the roofline block).
           * SD1.5 level 0 (C = 320, 8 heads): ONE launch of the third-generation fused kernel (csrc/xattn3.hip):
             LayerNorm folded into Wq, x read from HBM once;
           * C <= CID_XATTN_FUSED_MAX_C otherwise: one launch of the first-generation fused kernel;
           * wider levels: LayerNorm + q GEMM + two-stream attention core + out GEMM (+ bias + residual) -- a
-            [tokens x C] tile does not fit in LDS next to the weight slabs there."""
+            [tokens x C] tile does not fit in LDS next to the weight slabs there.
+        ``out``: a [B * N, c] column block of a wider buffer to write instead of a fresh contiguous tensor (its row stride is
+        the pitch; not with the first-generation fused kernel)."""
         W, ctx = self.W, self._ctx
         M = B * N
-        h3 = self._empty(M, c)
+        h3 = self._empty(M, c) if out is None else out
+        ldo = None if out is None else out.stride(0)
         if ctx.v2.get(b) == 3:
             ops.id_xattn3(h2, h3, wq_p=W[f"{b}.attn2.wq_p"], q_rowsum=W[f"{b}.attn2.qs"].view(torch.float32),
                           q_bias=W[f"{b}.attn2.qb"].view(torch.float32), wo_p=W[f"{b}.attn2.wo_p"], bo=W[f"{b}.attn2.bo"],
                           kp=ctx.kp[b], vp=ctx.vp[b], kvrow=kvrow, B=B, N=N, C_=c, heads=heads, n_txt=ctx.n_txt,
-                          n_ip=ctx.n_ip, ip_scale=self.packed.ip_scale[b], has_ln=True, add_residual=True, ln_eps=ops.LN_EPS)
+                          n_ip=ctx.n_ip, ip_scale=self.packed.ip_scale[b], has_ln=True, add_residual=True, ln_eps=ops.LN_EPS,
+                          ldo=ldo)
         elif self._fused_gen1(c, B * N):
+            assert out is None, "cross_attention: the first-generation fused kernel writes contiguous rows"
             ops.id_xattn(h2, h3, wq=W[f"{b}.attn2.wq"], wo=W[f"{b}.attn2.wo"], bo=W[f"{b}.attn2.bo"],
                          kp=ctx.kp[b], vp=ctx.vp[b], kvrow=kvrow, B=B, N=N, C_=c, heads=heads,
                          n_txt=ctx.n_txt, n_ip=ctx.n_ip, ip_scale=self.packed.ip_scale[b], residual=h2,
@@ -315,7 +341,7 @@ class HipUNet:
                 ln2 = self._empty(M, c)
                 ops.layernorm(h2, ln2, W[f"{b}.norm2.g"], W[f"{b}.norm2.b"], M=M, C_=c)
                 ops.gemm(ln2, W[f"{b}.attn2.wq"], o2, M=M, N=c, c1=c, mode=3, heads=heads, dhead=c // heads, ntok=N, att=att)
-            ops.gemm(o2, W[f"{b}.attn2.wo"], h3, M=M, N=c, c1=c, bias=W[f"{b}.attn2.bo"], res=h2, ldr=c)
+            ops.gemm(o2, W[f"{b}.attn2.wo"], h3, M=M, N=c, c1=c, ldo=ldo, bias=W[f"{b}.attn2.bo"], res=h2, ldr=c)
         else:
             q2 = self._empty(M, c)
             if ops.ln_fold(M):     # norm2 folded into the query projection
@@ -327,7 +353,7 @@ class HipUNet:
             o2 = self._empty(M, c)
             ops.id_xattn_core(q2, o2, kp=ctx.kp[b], vp=ctx.vp[b], kvrow=kvrow, B=B, N=N, C_=c, heads=heads,
                               n_txt=ctx.n_txt, n_ip=ctx.n_ip, ip_scale=self.packed.ip_scale[b])
-            ops.gemm(o2, W[f"{b}.attn2.wo"], h3, M=M, N=c, c1=c, bias=W[f"{b}.attn2.bo"], res=h2, ldr=c)
+            ops.gemm(o2, W[f"{b}.attn2.wo"], h3, M=M, N=c, c1=c, ldo=ldo, bias=W[f"{b}.attn2.bo"], res=h2, ldr=c)
         return h3
 
     def _fused_gen1(self, c: int, tokens: int) -> bool:
@@ -335,7 +361,7 @@ class HipUNet:
         (tools/xattn_levels.py, profiles/r02_xattn_levels.txt): always up to CID_XATTN_FUSED_MAX_C = 320 channels; at 640
         channels only with >= 16 k tokens in flight (SDXL's 64 x 64 level at CFG batch 4: 68.5 vs 78.2 us; SD1.5's
         32 x 32 level at CFG batch 8 has 8 k: 61.8 vs 53.3 us); never at 1280 (144-149 vs 54-67 us)."""
-        return c <= self._xattn_fused_max_c or (c <= 640 and tokens >= 16384 and self._xattn_fused_max_c >= 320)
+        return fused_gen1(c, tokens, self._xattn_fused_max_c)
 
     def cross_attention_path(self, b: str, c: int, B: int, N: int) -> str:
         """the launch sequence :meth:`cross_attention` runs for block ``b`` on B samples of N tokens, as text (bench.py's

@@ -51,6 +51,16 @@ def _geglu_interleave(t: torch.Tensor) -> torch.Tensor:
     return torch.stack([v, g], dim=1).reshape(n2, *t.shape[1:])
 
 
+def fold_ff2_proj_out(w2: torch.Tensor, b2: torch.Tensor, wp: torch.Tensor, bp: torch.Tensor):
+    """ff2 and proj_out of a transformer's tail as one linear map over the row [ff | h3] (nothing non-linear lies between:
+    out = Wp (W2 ff + b2 + h3) + bp + x):  W' = [Wp W2 | Wp]  [c, 5c],  b' = Wp b2 + bp.  The operands are the fp16-rounded
+    tensors the two-launch path uses; the products are taken in fp64 and rounded to fp16 once."""
+    wp64, w264 = wp.half().double(), w2.half().double()
+    w = torch.cat([wp64 @ w264, wp64], 1).half().contiguous()
+    b = (wp64 @ b2.half().double() + bp.half().double()).half().contiguous()
+    return w, b
+
+
 def fold_ln(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, bias: Optional[torch.Tensor] = None):
     """LayerNorm in front of a projection, folded (cid_gemm_desc.ln_s / ln_b):  LN(x) W^T + bias =
     rstd * (x W'^T - mean * s) + b'  with  W' = W diag(gamma) rounded to fp16, s = row sums of the ROUNDED W' (the mean
@@ -187,6 +197,9 @@ class PackedUNet:
                         _geglu_interleave(_f(sd[f"{b}.ff.net.0.proj.bias"], dev)))
                     W[f"{b}.ff2.w"] = _h(sd[f"{b}.ff.net.2.weight"], dev)
                     W[f"{b}.ff2.b"] = _h(sd[f"{b}.ff.net.2.bias"], dev)
+                # the last block's ff2 with proj_out as one GEMM (unet._transformer folds where ops.ff2_fold says so)
+                W[f"{n}.ffpo.w"], W[f"{n}.ffpo.b"] = fold_ff2_proj_out(W[f"{b}.ff2.w"], W[f"{b}.ff2.b"], W[f"{n}.proj_out.w"],
+                                                                       W[f"{n}.proj_out.b"])
 
     def _attention_weights(self, b: str, d: int, sd, adapter_sd, proc_index, lora_scale, ln2=None, ln1=None) -> Dict[str, torch.Tensor]:
         """packed projection weights of transformer block ``b`` (head dim ``d``): LoRA merged in fp32 (attention.py

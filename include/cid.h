@@ -239,6 +239,13 @@ int cid_id_xattn3_f16(const cid_half* x, cid_half* out, const cid_half* wq_packe
                       const cid_half* vp, const int32_t* kvrow, int32_t B, int32_t N, int32_t C, int32_t heads,
                       int32_t n_txt, int32_t n_ip, float ip_scale, float ln_eps, int32_t flags,
                       cid_stream_t stream);
+/* The same launch with a row pitch for out: ldo halfs (>= C, a multiple of 8); x stays contiguous.  out may be a column
+ * block of a wider buffer -- the [M, 5 C] row [ff | h3] that the folded ff2 + proj_out GEMM reads. */
+int cid_id_xattn3_ld_f16(const cid_half* x, cid_half* out, int64_t ldo, const cid_half* wq_packed,
+                         const float* q_rowsum, const float* q_bias, const cid_half* wo_packed, const cid_half* bo,
+                         const cid_half* kp, const cid_half* vp, const int32_t* kvrow, int32_t B, int32_t N,
+                         int32_t C, int32_t heads, int32_t n_txt, int32_t n_ip, float ip_scale, float ln_eps,
+                         int32_t flags, cid_stream_t stream);
 /* dst[r][e] = idx[e] < 0 ? 0 : (bit 30 of idx[e] ? src_b : src_a)[r * src_row_elems + (idx[e] & 0x3fffffff)]
  * for r < R, e < n_idx: the generic "put projected K / V rows into fragment order" step (idx on the device). */
 int cid_gather_pack_f16(const cid_half* src_a, const cid_half* src_b, const int32_t* idx, cid_half* dst,
@@ -251,6 +258,9 @@ int cid_gather_pack_f16(const cid_half* src_a, const cid_half* src_b, const int3
  */
 int cid_layernorm_f16(const cid_half* x, cid_half* out, const cid_half* gamma, const cid_half* beta,
                       int32_t M, int32_t C, float eps, cid_stream_t stream);
+/* The same with row pitches ldx / ldo in halfs (>= C, multiples of 8): x or out may be a column block of a wider buffer. */
+int cid_layernorm_ld_f16(const cid_half* x, int64_t ldx, cid_half* out, int64_t ldo, const cid_half* gamma,
+                         const cid_half* beta, int32_t M, int32_t C, float eps, cid_stream_t stream);
 /* In-place softmax over fp16 rows of BASE-2 logits (fp32 math): replaces the softmax of diffusers' default
  * attention in the VAE mid block (single head of width 512 over all latent pixels), which the reference reaches
  * through self.decode_latents / vae.decode (pipline_StableDiffusion_ConsistentID.py:587,:597).  cols % 8 == 0. */
