@@ -242,6 +242,19 @@ self_attn_kernel(const half_t* __restrict__ q, const half_t* __restrict__ k, con
     // mx_a / mx_b: row max of the score tile a step is about to consume, handed from step to step (taken beside the
     // previous step's P.V MFMAs); tile 0's comes from here
     float mx_a[QT], mx_b[QT];
+    // masked launches whose tile 0 already holds padding keys (n_keys < 64): the mask goes on before tile 0's max.  With BIAS
+    // that max is installed as the running max, which is only ever raised -- a padding K row that outscores the real keys
+    // would otherwise leave every real p at exp2(real - padding) (fp16 subnormal or zero: l = 0, O = NaN).  Key 0 is real,
+    // so the max stays finite.  (Without BIAS the max taken here is not used by masked launches: step takes its own.)
+    if (MASK && BIAS && n_keys < 64) {
+#pragma unroll
+        for (int kt = 0; kt < 2; ++kt)
+#pragma unroll
+            for (int t = 0; t < QT; ++t)
+#pragma unroll
+                for (int r = 0; r < 16; ++r)
+                    if (kt * 32 + crow(r, hi) >= n_keys) s_cur[kt][t][r] = -INFINITY;
+    }
 #pragma unroll
     for (int t = 0; t < QT; ++t) {
         const float mx = tile_max(s_cur, t);

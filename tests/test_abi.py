@@ -66,6 +66,27 @@ def test_argument_validation_without_gpu(lib):
     assert lib.cid_groupnorm_ws_bytes(8, 2560) > 0
 
 
+def test_attention_key_counts_refused_without_gpu(lib):
+    """the attention entry points refuse key counts outside their kernels' range before any launch: more than 96 context
+    rows or no text row for the first-generation cross-attention, n_keys outside (0, N], more than 1024 keys or a head width
+    other than 64 for cid_small_attn_f16"""
+    err = lib.cid_last_error
+    for n_txt, n_ip in ((93, 4), (97, 0), (0, 4)):
+        assert lib.cid_kv_pack_f16(1, 1, 1, 1, 2, 320, 8, n_txt, n_ip, None) == -22 and b"at most 96 context rows" in err()
+        assert lib.cid_id_xattn_core_f16(1, 1, 1, 1, 1, 2, 128, 320, 8, n_txt, n_ip, 1.0, None) == -22
+        assert b"cid_id_xattn_core_f16: at most 96 context rows" in err()
+        assert lib.cid_id_xattn_f16(1, 1, None, None, None, 1e-5, 1, 1, None, 1, 1, 1, 2, 128, 320, 8, n_txt, n_ip, 1.0, None) == -22
+        assert b"cid_id_xattn_f16: at most 96 context rows" in err()
+    for n_keys in (0, 129, -1):
+        assert lib.cid_self_attn_keys_f16(1, 1, 1, 1, 2, 128, 8, 40, 320, 320, 64, 320, n_keys, None) == -22
+        assert b"n_keys must be in (0, N]" in err()
+    small = lambda n1, n2, dim_head: lib.cid_small_attn_f16(1, 64, 1, n1, 1, n2, 128, 1, 64, 1, 1, 1, dim_head, 0.125, None)
+    assert small(1021, 4, 64) == -22 and b"at most 1024 keys" in err()
+    assert small(1025, 0, 64) == -22 and b"at most 1024 keys" in err()
+    assert small(0, 4, 64) == -22 and b"bad shape" in err()
+    assert small(257, 4, 32) == -22 and b"head width must be 64" in err()
+
+
 def test_python_front_end_refuses_cpu_tensors(lib):
     import torch
     from consistentid_amd import ops
