@@ -7,17 +7,19 @@ the reference's ``__call__`` keyword surface, running on the HIP engine.
   StableDiffusionControlNetInpaintConsistentIDPipeline pipelines/StableDIffusionControlNetInpaint_ConsistentID.py:94, :375-456
 
 Scope: the per-step path, the ControlNet encoder (row f-1), the VAE decode (row f-2) and the VAE
-encode of the inpaint pipelines (``image=`` / ``mask_image=`` with ``vae_encoder=HipVAEEncoder(...)``; the init image comes in
-through ``image=``, where the reference reads ``input_id_images[0]``).
+encode of the inpaint pipelines (``image=`` / ``mask_image=`` with ``vae_encoder=HipVAEEncoder(...)``; the init image is
+``image=`` when given, else ``input_id_images[0]``, where the reference reads it; PIL images go through image_prep.py).
 Prompt strings are encoded by ``encode_prompt`` / ``_encode_prompt`` / ``encode_prompt_with_trigger_word`` on the HIP
 text towers (``text_encoder=`` / ``text_encoder_2=``, clip_text.py; prompt_encode.py), the ID tokens by
-``prepare_prompt_embeds``.  The SD1.5 pipeline also runs the reference's whole pre-loop (``prepare_id_prompt_embeds``:
-the caller's FaceID app, HipBiSeNet face parsing, the facial crops, the CLIP vision tower) for ``prompt`` +
-``input_id_images``; every ``__call__`` also takes what the pre-loop produces:
+``prepare_prompt_embeds``.  The three SD1.5-family pipelines (SD1.5, inpaint, ControlNet-inpaint) also run the reference's
+whole pre-loop (``prepare_id_prompt_embeds``: the caller's FaceID app, HipBiSeNet face parsing, the facial crops, the
+CLIP vision tower) for ``prompt`` + ``input_id_images``; every ``__call__`` also takes what the pre-loop produces:
 ``prompt_embeds`` = cat([null, augmented, text_only]) of shape [3B, 77+4, Dc] exactly as the
 reference assembles it before ``.chunk(3)`` (ref :494-507, :527-531), and ``latents``.
-Elsewhere (SDXL, inpaint), and in SD1.5 without its pre-loop components, string prompts / ID images raise
-NotImplementedError naming what is missing instead of silently doing something else; ``output_type`` other than "latent" needs the pipeline to be built with ``vae=HipVAEDecoder(...)``.
+In SDXL (whose reference ``__call__`` reads names it never defines, so there is nothing sound to mirror), and in the SD1.5
+family without the pre-loop components, string prompts / ID images raise NotImplementedError naming what is missing
+instead of silently doing something else; ``output_type`` other than "latent" needs the pipeline to be built with
+``vae=HipVAEDecoder(...)``.
 
 B > 1 is this framework's extension (the reference is effectively B = 1 per call,
 SURVEY.md Appendix B): B independent samples, each with its own CFG pair.
@@ -311,6 +313,16 @@ class _BasePipeline:
                                  f"build the pipeline with from_pretrained(..., device={str(want)!r})")
         return self
 
+    def _nothing_to_do(self, *args, **kwargs) -> None:
+        """The memory and progress-bar switches the reference scripts call between load and generate
+        (demo/controlnet_demo.py ``pipe.enable_model_cpu_offload()``): accepted and ignored.  The engine's weights are packed
+        on the device at load time, so there is nothing to offload, slice or tile, the attention is the engine's own, and
+        the captured loop draws no progress bar."""
+        return None
+
+    enable_model_cpu_offload = enable_sequential_cpu_offload = enable_vae_slicing = enable_vae_tiling = _nothing_to_do
+    enable_xformers_memory_efficient_attention = set_progress_bar_config = _nothing_to_do
+
     @property
     def scheduler(self):
         """the reference scripts replace the scheduler AFTER construction (infer.py:33
@@ -500,6 +512,31 @@ class _IDPreLoop:
                 ("text encoder", self.text_encoder), ("tokenizer", self.tokenizer))
         return [name for name, v in need if v is None]
 
+    def _takes_id_pre_loop(self, prompt, input_id_images, prompt_embeds) -> bool:
+        """The argument checks the SD1.5-family ``__call__``s share: True when the call goes through the pre-loop (``prompt`` +
+        ``input_id_images``), False when it brings its own ``prompt_embeds``."""
+        if prompt is None and input_id_images is None:
+            return False
+        missing = self._missing_id_components()
+        if missing:
+            raise NotImplementedError("__call__(prompt=..., input_id_images=...) needs: " + ", ".join(missing)
+                                      + "; or build prompt_embeds with prepare_prompt_embeds and pass it with latents")
+        if prompt is None or input_id_images is None:
+            raise ValueError("prompt and input_id_images go together (ref :434-438)")
+        if prompt_embeds is not None:
+            raise ValueError("give either prompt + input_id_images or prompt_embeds, not both")
+        return True
+
+    def _id_call_prompt_embeds(self, prompt, input_id_images, negative_prompt, num_images_per_prompt) -> torch.Tensor:
+        """``prompt_embeds`` [3n, 77 + num_tokens, Dc] of a pre-loop call: the pre-loop runs once and each of its three row
+        groups is repeated ``num_images_per_prompt`` = n times, which is diffusers' meaning of the argument (the reference
+        itself breaks on n > 1)."""
+        n = 1 if num_images_per_prompt is None else int(num_images_per_prompt)
+        if n < 1:
+            raise ValueError(f"num_images_per_prompt must be at least 1, got {num_images_per_prompt}")
+        pe = self.prepare_id_prompt_embeds(prompt, input_id_images, negative_prompt)
+        return pe if n == 1 else torch.cat([rows.repeat(n, 1, 1) for rows in pe.chunk(3)])
+
     def get_prepare_faceid(self, face_image) -> torch.Tensor:
         """ref :216-226: the first face's ``normed_embedding`` [1, 512], zeros when the app finds no face"""
         faces = self.app.get(np.array(face_image))
@@ -613,25 +650,19 @@ class ConsistentIDStableDiffusionPipeline(_IDPreLoop, _SD15PromptEncoding, _Base
                  class_tokens_mask=None, prompt_embeds_text_only=None, variance_noise: Optional[torch.Tensor] = None):
         """``pipe(prompt, input_id_images=[face], ...)`` runs the reference's pre-loop (prepare_id_prompt_embeds) and, without
         ``latents``, draws them like diffusers' prepare_latents (randn_tensor on the generator's device); or pass
-        ``prompt_embeds`` (cat([null, augmented, text_only])) and ``latents`` directly."""
-        if prompt is not None or input_id_images is not None:
-            missing = self._missing_id_components()
-            if missing:
-                raise NotImplementedError("__call__(prompt=..., input_id_images=...) needs: " + ", ".join(missing)
-                                          + "; or build prompt_embeds with prepare_prompt_embeds and pass it with latents")
-            if prompt is None or input_id_images is None:
-                raise ValueError("prompt and input_id_images go together (ref :434-438)")
-            if prompt_embeds is not None:
-                raise ValueError("give either prompt + input_id_images or prompt_embeds, not both")
-            if num_images_per_prompt != 1:
-                raise NotImplementedError("num_images_per_prompt > 1 (the reference breaks on it, SURVEY.md Appendix B)")
-            prompt_embeds = self.prepare_id_prompt_embeds(prompt, input_id_images, negative_prompt)
+        ``prompt_embeds`` (cat([null, augmented, text_only])) and ``latents`` directly.  ``num_images_per_prompt`` = n on the
+        prompt path: n samples of the one identity -- the embeds repeated n times, the latents one draw of [n, C, h, w]."""
+        if self._takes_id_pre_loop(prompt, input_id_images, prompt_embeds):
+            prompt_embeds = self._id_call_prompt_embeds(prompt, input_id_images, negative_prompt, num_images_per_prompt)
+            n = prompt_embeds.shape[0] // 3
             if latents is None:
                 from .vae import randn_tensor
                 height = height or self.unet.config.sample_size * self.vae_scale_factor
                 width = width or self.unet.config.sample_size * self.vae_scale_factor
-                shape = (1, self.unet.in_channels, height // self.vae_scale_factor, width // self.vae_scale_factor)
+                shape = (n, self.unet.in_channels, height // self.vae_scale_factor, width // self.vae_scale_factor)
                 latents = randn_tensor(shape, generator=generator, device=self.device, dtype=torch.float16)   # ref :517-526
+            elif latents.shape[0] != n:
+                raise ValueError(f"latents of batch {latents.shape[0]} with num_images_per_prompt = {n}")
             prompt = input_id_images = None
         self._check_hot_path_inputs(prompt, input_id_images, prompt_embeds, latents, output_type)
         assert guidance_scale >= 1.0, "the reference asserts classifier-free guidance (ref :434,:441)"
@@ -740,8 +771,35 @@ class ConsistentIDStableDiffusionXLPipeline(_BasePipeline):
         return StableDiffusionXLPipelineOutput(images=out)
 
 
-class StableDiffusionInpaintConsistentIDPipeline(_SD15PromptEncoding, _BasePipeline):
+class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding, _BasePipeline):
     default_guidance = 7.5
+
+    def _call_inputs(self, prompt, input_id_images, prompt_embeds, negative_prompt, num_images_per_prompt, image, mask_image,
+                     height, width):
+        """What the reference does between its arguments and the VAE encode (inpaint ref :127-239, CN :180-265): the ID
+        pre-loop on ``input_id_images[0]`` for ``prompt`` + ``input_id_images``, and image_prep.py for PIL images.  The init
+        image is ``image`` when given, else ``input_id_images[0]`` (ref :157, :232-234); PIL inputs are brought to ``height``
+        x ``width`` -- by default the size of a tensor given beside them, else ``unet.config.sample_size * 8`` (ref
+        :127-128).  Float tensors pass through untouched.  Returns (prompt_embeds, image, mask_image, height, width,
+        normalize): ``normalize`` is False for an image that image_prep already put in [-1, 1], None for a tensor."""
+        from . import image_prep
+        id_call = self._takes_id_pre_loop(prompt, input_id_images, prompt_embeds)
+        if id_call and image is None and mask_image is not None:
+            image = input_id_images[0] if isinstance(input_id_images, (list, tuple)) else input_id_images
+        normalize = None
+        if image_prep.is_pil(image) or image_prep.is_pil(mask_image):
+            given = [t for t in (image, mask_image) if torch.is_tensor(t)]
+            side = self.unet.config.sample_size * self.vae_scale_factor
+            height = height or (given[0].shape[-2] if given else side)
+            width = width or (given[0].shape[-1] if given else side)
+            if image_prep.is_pil(image):
+                image, normalize = image_prep.preprocess_image(image, height, width), False
+            if image_prep.is_pil(mask_image):
+                mask_image = image_prep.preprocess_mask(mask_image, height, width)
+            height, width = (image if torch.is_tensor(image) else mask_image).shape[-2:]
+        if id_call:
+            prompt_embeds = self._id_call_prompt_embeds(prompt, input_id_images, negative_prompt, num_images_per_prompt)
+        return prompt_embeds, image, mask_image, height, width, normalize
 
     def _strength_window(self, strength: float, num_inference_steps: int, latents, image_latents, noise):
         """get_timesteps + prepare_latents of the inpaint pipelines (inpaint ref :246-252, :258-275; diffusers 0.23):
@@ -764,11 +822,12 @@ class StableDiffusionInpaintConsistentIDPipeline(_SD15PromptEncoding, _BasePipel
         ca, cn_ = self.scheduler.add_noise_coefficients(self.scheduler.timesteps[first])
         return first, ca * image_latents.float() + cn_ * noise.float(), False
 
-
-    def _encode_images(self, image, mask_image, height, width, latents, strength, generator, prompt_embeds, explicit):
+    def _encode_images(self, image, mask_image, height, width, latents, strength, generator, prompt_embeds, explicit,
+                       normalize=None):
         """``image=`` / ``mask_image=`` -> (image_latents, noise, mask_latents, masked_image_latents): the pre-loop of inpaint ref
         :231-295 (CN :254-356) on the HIP encoder.  The mask is binarised at 0.5, masked_image = image * (mask < 0.5); the
-        image is normalised (2x - 1) unless ``image.min() < 0`` (diffusers VaeImageProcessor); both images go through ONE
+        image is normalised (2x - 1) unless ``image.min() < 0`` (diffusers VaeImageProcessor) or ``normalize`` says whether
+        it still has to be (False for what image_prep.preprocess_image returns); both images go through ONE
         encoder pass; latents = scaling_factor * latent_dist.sample(generator) with the draws of ``inpaint_draws``; image /
         mask latents are repeated to the batch like diffusers does.  Given ``latents`` are also the blend noise (diffusers
         prepare_latents: ``noise = latents``)."""
@@ -778,8 +837,8 @@ class StableDiffusionInpaintConsistentIDPipeline(_SD15PromptEncoding, _BasePipel
         if image is None or mask_image is None:
             raise ValueError("image= (the init image) and mask_image= come together")
         if not (torch.is_tensor(image) and torch.is_tensor(mask_image)):
-            raise NotImplementedError("PIL / numpy images (image_processor / mask_processor pre-processing and resizing) are "
-                                      "not built: pass float tensors image [B, 3, H, W] and mask_image [B, 1, H, W]")
+            raise NotImplementedError("image / mask_image: PIL images (resized by image_prep.py) or float tensors image "
+                                      "[B, 3, H, W] and mask_image [B, 1, H, W]; numpy arrays are not taken")
         if self.vae_encoder is None:
             raise ValueError("image= / mask_image= need a VAE encoder: build the pipeline with vae_encoder=HipVAEEncoder(...) "
                              "(from_pretrained does when vae/ holds encoder weights)")
@@ -805,7 +864,8 @@ class StableDiffusionInpaintConsistentIDPipeline(_SD15PromptEncoding, _BasePipel
             raise ValueError(f"batch {B} is not a multiple of the image batch {Bi} / mask batch {msk.shape[0]}")
         cin = getattr(self.unet.config, "in_channels", 4)
         L = enc.config.latent_channels
-        normalize = not bool(img.min() < 0)                     # diffusers: "already in [-1, 1]" tensors are left alone
+        if normalize is None:
+            normalize = not bool(img.min() < 0)                 # diffusers: "already in [-1, 1]" tensors are left alone
         eps_img, noise, eps_msk = inpaint_draws(generator, image_batch=Bi, batch_size=B, latent_channels=L, h=H // 8,
                                                 w=W // 8, unet_channels=cin, latents_given=latents is not None,
                                                 strength=strength, device=self.device)
@@ -859,20 +919,27 @@ class StableDiffusionInpaintConsistentIDPipeline(_SD15PromptEncoding, _BasePipel
                  prompt_embeds_text_only=None, image_latents: Optional[torch.Tensor] = None,
                  noise: Optional[torch.Tensor] = None, mask_latents: Optional[torch.Tensor] = None,
                  down_block_res_samples=None, mid_block_res_sample=None, variance_noise: Optional[torch.Tensor] = None):
-        """Either ``image`` + ``mask_image`` (the pre-loop of ref :231-295 on ``vae_encoder``) or the pre-computed
-        ``image_latents`` (init latents), ``noise`` and ``mask_latents`` [B,1,h,w] (1 = repaint), ``masked_image_latents``.
-        ``image`` is the INIT image [B, 3, H, W] / [3, H, W] float in [0, 1] (or already in [-1, 1]): the reference reads
-        it from ``input_id_images[0]`` (ref :157, :232-235) and ignores its own ``image`` argument, but here
-        ``input_id_images`` belongs to the ID pre-loop, which is not built -- so the init image comes in through ``image=``.
-        ``mask_image`` [B, 1, H, W] / [1, H, W] / [H, W] float, binarised at 0.5 (1 = repaint); H, W = height, width
-        (no resizing).  ``generator`` seeds the posterior samples and the noise in diffusers' order."""
+        """The reference's call, ``pipe(prompt, input_id_images=face, mask_image=mask, height=, width=, ...)``, runs its whole
+        pre-loop: the ID pre-loop on ``input_id_images[0]`` (prepare_id_prompt_embeds; ref :157-229), image_prep.py on the
+        PIL init image and mask (ref :232-239), the VAE encode on ``vae_encoder`` (ref :255-291).  ``prompt_embeds``
+        (cat([null, augmented, text_only])) replaces the first part; the pre-computed ``image_latents`` (init latents),
+        ``noise``, ``mask_latents`` [B,1,h,w] (1 = repaint) and ``masked_image_latents`` replace the rest.
+        The INIT image is ``image`` when given, else ``input_id_images[0]``, where the reference reads it (ref :157,
+        :232-235; it ignores its own ``image`` argument).  PIL images (one, or a list) are converted to RGB / L and resized
+        to ``height`` x ``width`` (default ``unet.config.sample_size * 8``, each rounded down to a multiple of 8).  Float
+        tensors are taken as they are, without resizing: ``image`` [B, 3, H, W] / [3, H, W] in [0, 1] (or already in
+        [-1, 1]), ``mask_image`` [B, 1, H, W] / [1, H, W] / [H, W], binarised at 0.5 (1 = repaint), H, W = height, width.
+        ``generator`` seeds the posterior samples and the noise in diffusers' order.  ``num_images_per_prompt`` = n on the
+        prompt path: n samples of the one identity (embeds and image latents repeated, noise one draw of [n, C, h, w])."""
+        prompt_embeds, image, mask_image, height, width, normalize = self._call_inputs(
+            prompt, input_id_images, prompt_embeds, negative_prompt, num_images_per_prompt, image, mask_image, height, width)
         if image is not None or mask_image is not None:
             image_latents, noise, mask_latents, masked_image_latents = self._encode_images(
                 image, mask_image, height, width, latents, strength, generator, prompt_embeds,
                 dict(image_latents=image_latents, noise=noise, mask_latents=mask_latents,
-                     masked_image_latents=masked_image_latents))
+                     masked_image_latents=masked_image_latents), normalize)
         first, latents, scaled = self._strength_window(strength, num_inference_steps, latents, image_latents, noise)
-        self._check_hot_path_inputs(prompt, input_id_images, prompt_embeds, latents, output_type)
+        self._check_hot_path_inputs(None, None, prompt_embeds, latents, output_type)    # (_call_inputs took prompt / ID images)
         extra = self._unet_extra(latents, mask_latents, masked_image_latents)
         null_e, aug_e, text_e = self._split(prompt_embeds)
         b_mask, b_init, b_noise = self._blend_inputs(extra, mask_latents, image_latents, noise)
@@ -918,15 +985,19 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
                  image_latents: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                  mask_latents: Optional[torch.Tensor] = None, down_block_res_samples=None, mid_block_res_sample=None,
                  masked_image_latents: Optional[torch.Tensor] = None, variance_noise: Optional[torch.Tensor] = None):
-        """``image`` / ``mask_image``: as in StableDiffusionInpaintConsistentIDPipeline.__call__ (the init image comes in
-        through ``image=``; the reference reads it from ``input_id_images[0]``, CN :180, :255-258)."""
+        """``prompt`` / ``input_id_images`` / ``image`` / ``mask_image``: as in
+        StableDiffusionInpaintConsistentIDPipeline.__call__ (CN :180-265).  ``control_image``: a float tensor [B, 3, 8h, 8w]
+        in [0, 1], or one PIL image (or a list of one), converted to RGB and resized to the final height x width by
+        image_prep.preprocess_control (CN :267-280)."""
+        prompt_embeds, image, mask_image, height, width, normalize = self._call_inputs(
+            prompt, input_id_images, prompt_embeds, negative_prompt, num_images_per_prompt, image, mask_image, height, width)
         if image is not None or mask_image is not None:
             image_latents, noise, mask_latents, masked_image_latents = self._encode_images(
                 image, mask_image, height, width, latents, strength, generator, prompt_embeds,
                 dict(image_latents=image_latents, noise=noise, mask_latents=mask_latents,
-                     masked_image_latents=masked_image_latents))
+                     masked_image_latents=masked_image_latents), normalize)
         first_step, latents, scaled = self._strength_window(strength, num_inference_steps, latents, image_latents, noise)
-        self._check_hot_path_inputs(prompt, input_id_images, prompt_embeds, latents, output_type)
+        self._check_hot_path_inputs(None, None, prompt_embeds, latents, output_type)    # (_call_inputs took prompt / ID images)
         extra = self._unet_extra(latents, mask_latents, masked_image_latents)
         first = lambda v: v[0] if isinstance(v, (list, tuple)) else v        # single ControlNet (CN :352-358, :399-402)
         scale, g0, g1 = first(controlnet_conditioning_scale), first(control_guidance_start), first(control_guidance_end)
@@ -936,9 +1007,15 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
                 raise ValueError("control_image given but the pipeline was built without a controlnet")
             if down_block_res_samples is not None:
                 raise ValueError("pass either control_image (native ControlNet) or precomputed residuals")
+            if isinstance(control_image, (list, tuple)) and len(control_image) > 1:
+                raise NotImplementedError("MultiControlNet: a list of several control images")
+            from . import image_prep
+            if image_prep.is_pil(control_image):
+                control_image = image_prep.preprocess_control(control_image, latents.shape[-2] * self.vae_scale_factor,
+                                                              latents.shape[-1] * self.vae_scale_factor)
             if not torch.is_tensor(control_image):
-                raise NotImplementedError("PIL / numpy control images (prepare_control_image, CN :267-279, is image "
-                                          "pre-processing): pass a float tensor [B, 3, 8h, 8w] in [0, 1]")
+                raise NotImplementedError("control_image: one PIL image (resized by image_prep.py) or a float tensor "
+                                          "[B, 3, 8h, 8w] in [0, 1]; numpy arrays are not taken")
             cn = self.controlnet
         null_e, aug_e, text_e = self._split(prompt_embeds)
         b_mask, b_init, b_noise = self._blend_inputs(extra, mask_latents, image_latents, noise)
