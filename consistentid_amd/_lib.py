@@ -58,6 +58,14 @@ class StepSeg(C.Structure):
     _fields_ = [("dst", C.c_void_p), ("offset", C.c_int64), ("nbytes", C.c_int64)]
 
 
+MAX_CONTROLNETS = 4     # CID_MAX_CONTROLNETS (include/cid.h)
+
+
+class AccumSeg(C.Structure):
+    """struct cid_accum_seg (include/cid.h)."""
+    _fields_ = [("y", C.c_void_p), ("n", C.c_int64), ("nr", C.c_int64), ("r", C.c_void_p * MAX_CONTROLNETS)]
+
+
 # name -> (restype, argtypes); mirrors include/cid.h one to one
 SIGNATURES = {
     "cid_version": (C.c_int, []),
@@ -125,6 +133,7 @@ SIGNATURES = {
     "cid_cfg_multistep_step_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, c_half_p, c_half_p, C.c_int32, C.c_void_p,
                                              C.c_float, c_half_p, c_half_p, c_half_p, C.c_int32, C.c_int32, c_stream]),
     "cid_add_inplace_f16": (C.c_int, [c_half_p, c_half_p, C.c_int64, C.c_int64, c_stream]),
+    "cid_residual_accum_f16": (C.c_int, [C.POINTER(AccumSeg), C.c_int32, C.c_int32, C.c_void_p, c_stream]),
     "cid_step_select": (C.c_int, [C.c_void_p, C.c_int64, C.c_int32, C.c_void_p, C.POINTER(StepSeg), C.c_int32, c_stream]),
 }
 

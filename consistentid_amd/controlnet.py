@@ -11,16 +11,73 @@ ConsistentID processors on the UNet only): all 81 context tokens are keys of ONE
 fused cross-attention kernel runs as "n_txt = 81, n_ip = 0".  Everything reuses the UNet engine's
 kernels; new here are the condition embedding (small-channel direct convs, computed once per control
 image -- it does not depend on the latents or the timestep) and the 1x1 "zero convs" (plain GEMMs).
+
+``HipMultiControlNet`` is diffusers' ``MultiControlNetModel`` over 1..4 such engines (the reference keeps that class's
+branches: CN :139-149 guidance windows per net, :281-301 one control image per net, :363-370 a keep list per net and step,
+:397-398 ``cond_scale = [c * s for c, s in zip(controlnet_conditioning_scale, controlnet_keep[i])]``): the nets run
+one after another with UNSCALED zero convs and cid_residual_accum_f16 sums their residuals, scaled from a device vector.
+The window / scale bookkeeping of those reference lines is in the pure functions below (no GPU needed).
 """
 from __future__ import annotations
 
-from typing import Dict, List, Optional, Tuple
+from typing import Dict, List, Optional, Sequence, Tuple
 
 import torch
 
 from . import ops
+from ._lib import MAX_CONTROLNETS
 from .unet import HipUNet
 from .unet_spec import UNetConfig
+
+
+def check_controlnet_count(n: int) -> int:
+    """1..MAX_CONTROLNETS (CID_MAX_CONTROLNETS, include/cid.h): the nets one cid_residual_accum_f16 launch sums"""
+    if not 1 <= n <= MAX_CONTROLNETS:
+        raise ValueError(f"{n} ControlNets: a MultiControlNet takes 1..{MAX_CONTROLNETS}")
+    return n
+
+
+def broadcast_conditioning_scale(scale, n_nets: int) -> List[float]:
+    """``controlnet_conditioning_scale`` -> one float per net.  A float is repeated, as diffusers' own ControlNet pipelines
+    do (``[scale] * len(nets)``); the reference does not and would fail in its ``zip`` (CN :398) on a float."""
+    if isinstance(scale, (list, tuple)):
+        if len(scale) != n_nets:
+            raise ValueError(f"controlnet_conditioning_scale has {len(scale)} entries for {n_nets} ControlNets")
+        return [float(s) for s in scale]
+    return [float(scale)] * n_nets
+
+
+def align_control_guidance(start, end, n_nets: int) -> Tuple[List[float], List[float]]:
+    """``control_guidance_start`` / ``control_guidance_end`` -> two lists of ``n_nets`` floats, as CN :139-149 aligns them:
+    a float beside a list is repeated to the list's length, two floats to the number of nets.  (Tuples count as lists.)"""
+    start = list(start) if isinstance(start, tuple) else start
+    end = list(end) if isinstance(end, tuple) else end
+    if not isinstance(start, list) and isinstance(end, list):
+        start = len(end) * [start]
+    elif not isinstance(end, list) and isinstance(start, list):
+        end = len(start) * [end]
+    elif not isinstance(start, list) and not isinstance(end, list):
+        start, end = n_nets * [start], n_nets * [end]
+    if len(start) != len(end):
+        raise ValueError(f"control_guidance_start has {len(start)} entries, control_guidance_end has {len(end)}")
+    if len(start) != n_nets:
+        raise ValueError(f"control_guidance_start / control_guidance_end have {len(start)} entries for {n_nets} ControlNets")
+    return [float(s) for s in start], [float(e) for e in end]
+
+
+def controlnet_keep_table(n_steps: int, starts: Sequence[float], ends: Sequence[float], first_step: int = 0) -> List[List[float]]:
+    """CN :363-370: ``keep[i][k] = 1.0 - float(i / n < start_k or (i + 1) / n > end_k)`` over the ``n_steps`` executed
+    steps; ``first_step`` rows of zeros stand in front for the schedule entries a ``strength`` < 1 window skips (the
+    reference enumerates the truncated timestep list, so its i = 0 is schedule entry ``first_step``)."""
+    rows = [[0.0] * len(starts) for _ in range(first_step)]
+    for i in range(n_steps):
+        rows.append([1.0 - float(i / n_steps < s or (i + 1) / n_steps > e) for s, e in zip(starts, ends)])
+    return rows
+
+
+def active_nets(keep_row: Sequence[float]) -> Tuple[int, ...]:
+    """the nets that run in a step: keep > 0 (the others' residuals are scaled by 0 there, CN :397-398)"""
+    return tuple(k for k, v in enumerate(keep_row) if v > 0.0)
 
 
 class HipControlNet(HipUNet):
@@ -126,7 +183,7 @@ class HipControlNet(HipUNet):
         if return_dict:
             raise NotImplementedError("return_dict=True (the reference passes return_dict=False, CN :411)")
         if isinstance(conditioning_scale, (list, tuple)):
-            raise NotImplementedError("MultiControlNet")
+            raise NotImplementedError("MultiControlNet: a list of scales goes to HipMultiControlNet([...]), this is one net")
         sample = sample.to(device=self.device, dtype=torch.float16).contiguous()
         B = sample.shape[0]
         ehs = encoder_hidden_states
@@ -145,3 +202,69 @@ class HipControlNet(HipUNet):
 
         shapes = self._last_shapes
         return [nchw(t, s) for t, s in zip(down, shapes[:-1])], nchw(mid, shapes[-1])
+
+
+class HipMultiControlNet:
+    """diffusers' ``MultiControlNetModel`` over 1..4 ``HipControlNet``s of one geometry (same residual shapes, one device).
+    ``nets`` is the list; ``__call__`` follows ``MultiControlNetModel.forward``: every net sees the same sample, timestep and
+    encoder_hidden_states with its own control image and scale, and the residuals are summed."""
+
+    def __init__(self, nets):
+        nets = list(nets)
+        check_controlnet_count(len(nets))
+        for k, n in enumerate(nets):
+            if not isinstance(n, HipControlNet):
+                raise TypeError(f"HipMultiControlNet: entry {k} is {type(n).__name__}, expected HipControlNet")
+        geom = lambda n: (n.config.in_channels, tuple(n.config.block_out_channels), tuple(n.config.down_block_types),
+                          n.config.layers_per_block, n.config.cross_attention_dim, n.packed.n_zero, str(n.device))
+        for k, n in enumerate(nets[1:], 1):
+            if geom(n) != geom(nets[0]):
+                raise ValueError(f"HipMultiControlNet: net {k} has geometry {geom(n)}, net 0 has {geom(nets[0])} "
+                                 "(the residuals of all nets are summed element by element)")
+        self.nets = nets
+        self.config = nets[0].config
+        self.device = nets[0].device
+        self._scales = torch.zeros(MAX_CONTROLNETS, dtype=torch.float32, device=self.device)
+
+    @torch.no_grad()
+    def __call__(self, sample, timestep, encoder_hidden_states=None, controlnet_cond=None, conditioning_scale=None,
+                 guess_mode: bool = False, return_dict: bool = False):
+        """``controlnet_cond`` / ``conditioning_scale``: one control image [B or 1, 3, 8h, 8w] and one float per net.  Returns
+        the summed ``(down_block_res_samples, mid_block_res_sample)`` in ``HipControlNet.__call__``'s layout.  The zero
+        convs run unscaled and one cid_residual_accum_f16 launch per residual group forms sum_k scale_k * r_k in fp32 with
+        one rounding (diffusers rounds every scaled residual and every partial sum to fp16)."""
+        if guess_mode:
+            raise NotImplementedError("guess_mode residual scaling (the reference never forwards it, CN :405-412)")
+        if return_dict:
+            raise NotImplementedError("return_dict=True (the reference passes return_dict=False, CN :411)")
+        N = len(self.nets)
+        if not isinstance(controlnet_cond, (list, tuple)) or len(controlnet_cond) != N:
+            got = len(controlnet_cond) if isinstance(controlnet_cond, (list, tuple)) else 1
+            raise ValueError(f"controlnet_cond has {got} control images for {N} ControlNets")
+        scales = broadcast_conditioning_scale(1.0 if conditioning_scale is None else conditioning_scale, N)
+        sample = sample.to(device=self.device, dtype=torch.float16).contiguous()
+        B = sample.shape[0]
+        ehs = encoder_hidden_states
+        key = (ehs.data_ptr(), ehs._version, tuple(ehs.shape))
+        kvrow = torch.arange(B, dtype=torch.int32, device=self.device)
+        downs, mids = [], []
+        for net, cond in zip(self.nets, controlnet_cond):
+            if net._ctx.key != key or net._ctx.key_ref is not ehs:
+                net.set_context(ehs, num_tokens=0)
+                net._ctx.key, net._ctx.key_ref = key, ehs
+            net._t_buf.fill_(float(timestep))
+            d, m = net.forward_tokens(sample, net._t_buf, kvrow, B, net.cond_embedding(cond), 1.0)
+            downs.append(d)
+            mids.append(m)
+        self._scales.copy_(torch.tensor(scales + [0.0] * (MAX_CONTROLNETS - N), dtype=torch.float32))
+        out_d = [torch.zeros_like(t) for t in downs[0]]
+        out_m = torch.zeros_like(mids[0])
+        ops.residual_accum(out_d, downs, self._scales)
+        ops.residual_accum([out_m], [[m] for m in mids], self._scales)
+
+        def nchw(t, shp):
+            c, h, w = shp
+            return t.view(B, h, w, c).permute(0, 3, 1, 2)
+
+        shapes = self.nets[0]._last_shapes
+        return [nchw(t, s) for t, s in zip(out_d, shapes[:-1])], nchw(out_m, shapes[-1])

@@ -15,7 +15,7 @@ void cid_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* cid_last_error(void) { return g_err; }
-extern "C" int cid_version(void) { return 105; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4, 104: cid_gemm_plan, 105: cid_cfg_multistep_step_f16
+extern "C" int cid_version(void) { return 106; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4, 104: cid_gemm_plan, 105: cid_cfg_multistep_step_f16, 106: cid_residual_accum_f16
 
 namespace {
 
@@ -563,6 +563,51 @@ add_inplace_kernel(half_t* __restrict__ y, const half_t* __restrict__ a, long n,
     }
 }
 
+// Residuals of several ControlNets onto up to 16 tensors in one launch (cid_residual_accum_f16, cid.h).  The segments travel
+// by value; `first` holds the prefix sums of their 256-chunk tiles (a chunk = 8 halves = 16 bytes per lane), so a tile lies
+// in ONE segment and a workgroup finds it with a wave-uniform walk over at most 16 kernel-argument words.  The grid is capped:
+// a workgroup strides over the tiles.  The scales come from device memory (the launch is the same for every step of a captured
+// loop); a net whose scale is exactly 0 is skipped by a wave-uniform branch BEFORE its residual is loaded -- a net outside
+// its guidance window did not run, its buffers may hold anything, and 0 * NaN is NaN.
+constexpr int RA_MAX_SEGS = 16;
+constexpr int RA_TILE = 256;        // chunks per tile = lanes per workgroup
+struct AccumSegs {
+    cid_accum_seg s[RA_MAX_SEGS];
+    long first[RA_MAX_SEGS + 1];    // tiles before segment j; first[n] = all tiles
+    int n, n_nets;
+};
+__global__ void __launch_bounds__(256)
+residual_accum_kernel(AccumSegs segs, const float* __restrict__ scales) {
+    float sc[CID_MAX_CONTROLNETS];
+#pragma unroll
+    for (int k = 0; k < CID_MAX_CONTROLNETS; ++k) sc[k] = k < segs.n_nets ? scales[k] : 0.f;
+    const long tiles = segs.first[segs.n];
+    for (long tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
+        int j = 0;
+        while (j + 1 < segs.n && tile >= segs.first[j + 1]) ++j;
+        const long n = segs.s[j].n, nr = segs.s[j].nr;
+        const long q = ((tile - segs.first[j]) * RA_TILE + threadIdx.x) * 8;
+        if (q >= n) continue;                                   // the tail of a segment's last tile
+        const long qr = nr == n ? q : q % nr;                   // B-row residual under the 2B-row batch (CN :418-425)
+        half_t* yp = reinterpret_cast<half_t*>(segs.s[j].y) + q;
+        const half8 yv = ld_global_h8(yp);
+        float acc[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) acc[i] = 0.f;
+#pragma unroll
+        for (int k = 0; k < CID_MAX_CONTROLNETS; ++k)
+            if (sc[k] != 0.f) {
+                const half8 rv = ld_global_h8(reinterpret_cast<const half_t*>(segs.s[j].r[k]) + qr);
+#pragma unroll
+                for (int i = 0; i < 8; ++i) acc[i] += sc[k] * (float)rv[i];
+            }
+        half8 o;
+#pragma unroll
+        for (int i = 0; i < 8; ++i) o[i] = (half_t)((float)yv[i] + acc[i]);
+        *reinterpret_cast<half8*>(yp) = o;
+    }
+}
+
 // Upsample2D weight fold (cid_upconv_fold_f16): one thread per element of w4[parity][n][tap4][c].  Along an axis, parity p and
 // folded tap r take the source taps [lo, hi]: (p, r) = (0, 0): {0}, (0, 1): {1, 2}, (1, 0): {0, 1}, (1, 1): {2}.
 __global__ void __launch_bounds__(256)
@@ -774,6 +819,38 @@ extern "C" int cid_add_inplace_f16(cid_half* y, const cid_half* a, int64_t n, in
     hipLaunchKernelGGL(add_inplace_kernel, dim3(grid_for(n / 8, 256, 2048)), dim3(256), 0, (hipStream_t)stream,
                        (half_t*)y, (const half_t*)a, (long)n, (long)na);
     CID_CHECK_LAUNCH("cid_add_inplace_f16");
+    return 0;
+}
+
+extern "C" int cid_residual_accum_f16(const cid_accum_seg* segs, int32_t n_segs, int32_t n_nets, const float* scales,
+                                      cid_stream_t stream) {
+    CID_CHECK_ARG(segs && scales, "cid_residual_accum_f16: null pointer");
+    CID_CHECK_ARG(n_segs >= 1 && n_segs <= RA_MAX_SEGS, "cid_residual_accum_f16: %d segments (1..%d)", n_segs, RA_MAX_SEGS);
+    CID_CHECK_ARG(n_nets >= 1 && n_nets <= CID_MAX_CONTROLNETS, "cid_residual_accum_f16: %d nets (1..%d)", n_nets,
+                  CID_MAX_CONTROLNETS);
+    AccumSegs sg;
+    sg.n = n_segs;
+    sg.n_nets = n_nets;
+    long tiles = 0;
+    for (int j = 0; j < RA_MAX_SEGS; ++j) {
+        sg.first[j] = tiles;
+        if (j >= n_segs) { sg.s[j] = cid_accum_seg{}; continue; }
+        const cid_accum_seg& s = segs[j];
+        CID_CHECK_ARG(s.y && ((uintptr_t)s.y & 15) == 0, "cid_residual_accum_f16: segment %d: y is null or not 16-byte aligned", j);
+        CID_CHECK_ARG(s.n > 0 && s.nr > 0 && s.n % 8 == 0 && s.nr % 8 == 0 && s.n % s.nr == 0,
+                      "cid_residual_accum_f16: segment %d: n = %lld, nr = %lld (positive multiples of 8, n %% nr == 0)", j,
+                      (long long)s.n, (long long)s.nr);
+        for (int k = 0; k < n_nets; ++k)
+            CID_CHECK_ARG(s.r[k] && ((uintptr_t)s.r[k] & 15) == 0,
+                          "cid_residual_accum_f16: segment %d: residual of net %d is null or not 16-byte aligned", j, k);
+        sg.s[j] = s;
+        for (int k = n_nets; k < CID_MAX_CONTROLNETS; ++k) sg.s[j].r[k] = nullptr;
+        tiles += (s.n / 8 + RA_TILE - 1) / RA_TILE;
+    }
+    sg.first[RA_MAX_SEGS] = tiles;
+    for (int j = n_segs; j <= RA_MAX_SEGS; ++j) sg.first[j] = tiles;
+    hipLaunchKernelGGL(residual_accum_kernel, dim3(grid_for(tiles, 1, 2048)), dim3(256), 0, (hipStream_t)stream, sg, scales);
+    CID_CHECK_LAUNCH("cid_residual_accum_f16");
     return 0;
 }
 

@@ -126,8 +126,14 @@ def load_unet(root: Union[str, os.PathLike], device="cuda:0", subfolder: str = "
     return HipUNet(unet_config_from_diffusers(cfg), sd, None, device=device, keep_base=keep_base, **kw)
 
 
-def load_controlnet(folder: Union[str, os.PathLike], device="cuda:0"):
-    from .controlnet import HipControlNet
+def load_controlnet(folder, device="cuda:0"):
+    """a ControlNetModel folder -> HipControlNet; a list / tuple of folders and / or HipControlNets -> HipMultiControlNet
+    (diffusers wraps a list of ControlNets in a MultiControlNetModel in the same way)"""
+    from .controlnet import HipControlNet, HipMultiControlNet, check_controlnet_count
+    if isinstance(folder, (list, tuple)):
+        check_controlnet_count(len(folder))         # before anything is read
+        return HipMultiControlNet([load_controlnet(f, device=device) if isinstance(f, (str, os.PathLike)) else f
+                                   for f in folder])
     cfg, sd = read_component(folder)
     return HipControlNet(unet_config_from_diffusers(cfg), sd, device=device)
 
@@ -239,7 +245,7 @@ def from_pretrained(pipeline_cls, root: Union[str, os.PathLike], torch_dtype=tor
     """``Pipeline.from_pretrained(base_model_path, torch_dtype=torch.float16)`` of the reference scripts (infer.py:17-21;
     with ``controlnet=`` demo/controlnet_demo.py:44-47): UNet (required), VAE decoder, text encoders and tokenizers (when
     their folders exist) of a local diffusers model directory; ``controlnet`` = a HipControlNet or the folder of a
-    ControlNetModel.  ``text_encoder=`` / ``tokenizer=`` / ``text_encoder_2=`` / ``tokenizer_2=`` take a ready object, or
+    ControlNetModel, or a list of those for a HipMultiControlNet.  ``text_encoder=`` / ``tokenizer=`` / ``text_encoder_2=`` / ``tokenizer_2=`` take a ready object, or
     None to skip that component."""
     if torch_dtype not in (torch.float16, None):
         raise NotImplementedError("the engine computes in fp16 (the reference's own inference dtype, infer.py:19)")
@@ -278,6 +284,6 @@ def from_pretrained(pipeline_cls, root: Union[str, os.PathLike], torch_dtype=tor
         if base is not None:
             args["scheduler"] = base
     if controlnet is not None:
-        cn = load_controlnet(controlnet, device=device) if isinstance(controlnet, (str, os.PathLike)) else controlnet
+        cn = load_controlnet(controlnet, device=device) if isinstance(controlnet, (str, os.PathLike, list, tuple)) else controlnet
         return pipeline_cls(unet, controlnet=cn, **args)
     return pipeline_cls(unet, **args)

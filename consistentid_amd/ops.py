@@ -728,6 +728,45 @@ def add_inplace(y: torch.Tensor, a: torch.Tensor):
     return y
 
 
+def residual_accum(ys, rs, scales: torch.Tensor):
+    """cid_residual_accum_f16: ``ys[j] += sum_k scales[k] * rs[k][j]`` (fp32 sum in net order, one rounding) for up to 16
+    destinations and up to 4 nets in ONE launch.  ``rs[k]`` holds net k's residual of every destination -- ``rs[k][j]`` with
+    ``ys[j].numel() % rs[k][j].numel() == 0``, the B-row residual repeating under a 2B-row batch -- or is None for a net that
+    did not run: its ``scales[k]`` must then be 0 on the device; the kernel does not read the residuals of such a net, and its
+    slots carry the destination's own address only because the ABI takes no null.  ``scales``: DEVICE fp32, at least
+    ``len(rs)`` values (the launch reads the first ``len(rs)``), so a captured launch follows the step table."""
+    lib = _lib.load()
+    if not 1 <= len(ys) <= 16 or not 1 <= len(rs) <= _lib.MAX_CONTROLNETS:
+        raise _lib.CidError(f"residual_accum: {len(ys)} destinations (1..16), {len(rs)} nets (1..{_lib.MAX_CONTROLNETS})")
+    _req(scales, "residual_accum.scales", torch.float32)
+    if scales.numel() < len(rs) or not scales.is_contiguous():
+        raise _lib.CidError(f"residual_accum.scales: {scales.numel()} values for {len(rs)} nets")
+    segs = (_lib.AccumSeg * len(ys))()
+    for j, y in enumerate(ys):
+        _req(y, f"residual_accum.ys[{j}]")
+        if not y.is_contiguous():
+            raise _lib.CidError(f"residual_accum.ys[{j}]: not contiguous")
+        if hasattr(y, "_gn_stats"):
+            del y._gn_stats          # the epilogue statistics describe the tensor BEFORE this in-place update
+        segs[j].y, segs[j].n = y.data_ptr(), y.numel()
+        nr = None
+        for k, net in enumerate(rs):
+            if net is None:
+                segs[j].r[k] = y.data_ptr()
+                continue
+            if len(net) != len(ys):
+                raise _lib.CidError(f"residual_accum.rs[{k}]: {len(net)} residuals for {len(ys)} destinations")
+            r = net[j]
+            _req(r, f"residual_accum.rs[{k}][{j}]")
+            if not r.is_contiguous() or (nr is not None and r.numel() != nr):
+                raise _lib.CidError(f"residual_accum.rs[{k}][{j}]: {r.numel()} elements (contiguous, {nr} like the other nets')")
+            nr = r.numel()
+            segs[j].r[k] = r.data_ptr()
+        segs[j].nr = y.numel() if nr is None else nr
+    check(lib.cid_residual_accum_f16(segs, len(ys), len(rs), scales.data_ptr(), _stream()), "cid_residual_accum_f16")
+    return ys
+
+
 class StepTable:
     """Per-step values of one generation as ONE device table + the buffers the captured step reads (cid_step_select):
     ``columns`` = [(destination tensor, per-step values [S, ...] of the same dtype / trailing shape)].  ``select()`` is

@@ -60,8 +60,10 @@ class _DenoiseEngine:
         self.use_graph = use_graph
         self._graph = None           # truthy while the static buffers the captured graphs point at are unchanged
         self._graph_key = None
-        self._graphs: Dict[bool, Any] = {}      # captured step, without / with the ControlNet forward
+        # captured step, without / with the ControlNet forward; with a HipMultiControlNet keyed by the tuple of nets that run
+        self._graphs: Dict[Any, Any] = {}
         self._warm_keys = set()
+        self.captures: List[Any] = []           # key of every capture this engine ever made, in order (re-captures show twice)
         self._static: Dict[str, torch.Tensor] = {}
         self.step_path: Optional[str] = None    # the step launch of the last run: "cfg_ddim" or "cfg_multistep"
 
@@ -81,8 +83,9 @@ class _DenoiseEngine:
             guidance_scale: float, start_merge_step: int, null_embeds_post=None, first_step: int = 0,
             pooled: Optional[Sequence[torch.Tensor]] = None, time_ids: Optional[torch.Tensor] = None,
             down_residuals=None, mid_residual=None, inpaint_mask=None, inpaint_init=None, inpaint_noise=None,
-            controlnet=None, control_image=None, conditioning_scale: float = 1.0,
-            control_guidance_start: float = 0.0, control_guidance_end: float = 1.0,
+            controlnet=None, control_image=None, conditioning_scale: Union[float, Sequence[float]] = 1.0,
+            control_guidance_start: Union[float, Sequence[float]] = 0.0,
+            control_guidance_end: Union[float, Sequence[float]] = 1.0,
             callback: Optional[Callable[[int, int, torch.Tensor], None]] = None, callback_steps: int = 1,
             scale_initial: bool = True, unet_extra: Optional[torch.Tensor] = None, eta: float = 0.0,
             variance_noise: Optional[torch.Tensor] = None):
@@ -92,7 +95,9 @@ class _DenoiseEngine:
         window (get_timesteps, inpaint ref :246-252); the embed switch and the ControlNet keep window count steps from
         there, exactly like the reference's ``for i, t in enumerate(timesteps)`` over the truncated list.
         ``unet_extra`` [B, 5, h, w]: cat([mask, masked_image_latents]) of a 9-channel inpainting UNet (inpaint ref
-        :320-321, CN :415-416) -- conv_in reads it beside the (scaled) latents, the ControlNet does not see it."""
+        :320-321, CN :415-416) -- conv_in reads it beside the (scaled) latents, the ControlNet does not see it.
+        ``controlnet`` = a ``HipMultiControlNet``: ``control_image``, ``conditioning_scale``, ``control_guidance_start`` and
+        ``control_guidance_end`` are sequences with one entry per net."""
         unet, sch = self.unet, self.scheduler
         dev = unet.device
         B = latents.shape[0]
@@ -174,7 +179,32 @@ class _DenoiseEngine:
             mres = S("mres", mid_residual, torch.float16)
         cn_cond = cn_kvrow = None
         cn_keep = [0.0] * len(ts)
-        if controlnet is not None:
+        from .controlnet import HipMultiControlNet, active_nets, controlnet_keep_table
+        multi = isinstance(controlnet, HipMultiControlNet)
+        nets = controlnet.nets if multi else []
+        cn_scale_buf = cn_scale_tab = None
+        if multi:
+            # MultiControlNet (CN :281-301, :363-370, :397-398): every net has its own context, condition embedding and
+            # keep window; they share the embed-row selector.  The zero convs stay unscaled: scale_k * keep_k[i] is a
+            # column of the step table that cid_residual_accum_f16 reads, so a new scale needs no new weights or graph.
+            assert down_residuals is None, "pass either a ControlNet or precomputed residuals"
+            ehs_cn = torch.cat([text_embeds.to(dev), augmented_embeds.to(dev)], dim=0)
+            for net in nets:
+                cn_before = net.context_addresses()
+                net.set_context(ehs_cn, num_tokens=0)
+                if net.context_addresses() != cn_before:
+                    self._graphs.clear()
+                    self._warm_keys.clear()
+            cn_cond = [S(f"cn_cond{k}", net.cond_embedding(img), torch.float16) for k, (net, img) in
+                       enumerate(zip(nets, control_image))]
+            cn_kvrow = S("cn_kvrow", ar, torch.int32)
+            cn_keep = controlnet_keep_table(len(ts) - first_step, control_guidance_start, control_guidance_end, first_step)
+            cn_scale_buf = S("cn_scale", torch.zeros(4), torch.float32)      # 4 fp32 = one 16-byte column
+            cn_scale_tab = torch.zeros(len(ts), 4)
+            cn_scale_tab[:, :len(nets)] = torch.tensor(cn_keep, dtype=torch.float64).mul(
+                torch.tensor(list(conditioning_scale), dtype=torch.float64)).float()
+            cn_scale_tab = cn_scale_tab.to(dev)
+        elif controlnet is not None:
             # native ControlNet (CN :389-412): conditional latents + conditional embeds, residuals recomputed per step.
             # Its K/V cache holds rows [0,B) text-only and [B,2B) augmented, selected like the UNet's.
             assert down_residuals is None, "pass either a ControlNet or precomputed residuals"
@@ -191,10 +221,19 @@ class _DenoiseEngine:
         # time path: one table per generation instead of three weight-streaming GEMVs per step (not with SDXL's
         # text_time conditioning, whose rows also depend on the sample)
         temb_tab = cn_temb_tab = temb_buf = cn_temb_buf = None
+        cn_temb_views = [None] * len(nets)
         if unet.config.addition_embed_type is None and not os.environ.get("CID_NO_TEMB_TABLE"):
             temb_tab = unet.time_embed_table(tvals)
             temb_buf = S("temb", temb_tab[:1], torch.float16)
-            if controlnet is not None:
+            if multi:
+                # all nets' rows side by side in ONE buffer and ONE table column (the table has 8); per-net views into it
+                tabs = [net.time_embed_table(tvals) for net in nets]
+                cn_temb_tab = torch.cat(tabs, dim=1)
+                cn_temb_buf = S("cn_temb", cn_temb_tab[:1], torch.float16)
+                offs = np.cumsum([0] + [t.shape[1] for t in tabs])
+                assert all(o % 8 == 0 for o in offs), "time-embedding rows are 16-byte multiples"
+                cn_temb_views = [cn_temb_buf[:, offs[k]:offs[k + 1]] for k in range(len(nets))]
+            elif controlnet is not None:
                 cn_temb_tab = controlnet.time_embed_table(tvals)
                 cn_temb_buf = S("cn_temb", cn_temb_tab[:1], torch.float16)
         # every per-step host value of the reference's `for i, t in enumerate(timesteps)` as one device table: row i holds t,
@@ -211,6 +250,8 @@ class _DenoiseEngine:
             cols.append((temb_buf, temb_tab.view(n_ts, -1)))
             if cn_temb_buf is not None:
                 cols.append((cn_temb_buf, cn_temb_tab.view(n_ts, -1)))
+        if cn_scale_buf is not None:
+            cols.append((cn_scale_buf, cn_scale_tab))
         if pooled_post is not None:
             pre = torch.cat([p_null, p_text], 0)
             cols.append((added["text_embeds"], torch.where(merged_at[:, None, None], pooled_post[None], pre[None])))
@@ -220,19 +261,29 @@ class _DenoiseEngine:
         # every static buffer exists now: a new one (S() cleared _graph) or a new configuration invalidates the captured
         # graphs AND their eager warm-up (the first step after a shape change must run eagerly again)
         key = (B, tuple(lat.shape), float(guidance_scale), inpaint, time_ids is not None, dres is not None,
-               controlnet is not None, float(conditioning_scale), extra is not None, multistep, z_buf is not None)
+               controlnet is not None, ("multi", len(nets)) if multi else float(conditioning_scale), extra is not None,
+               multistep, z_buf is not None)      # (the multi path reads its scales from the step table: not part of the key)
         if key != self._graph_key or self._graph is None:
             self._graphs.clear()
             self._warm_keys.clear()
             self._graph, self._graph_key = True, key     # (_graph: "static buffers valid" marker, cleared by S())
 
-        def step(with_cn: bool):
+        def step(with_cn):
+            """``with_cn``: bool for one ControlNet; with a HipMultiControlNet the tuple of nets that run, () = none"""
             table.select()
-            d, m = dres, mres
-            if with_cn:
+            d, m, scales = dres, mres, None
+            if multi and with_cn:
+                # unscaled residuals of the nets that run, one forward after another on the current stream (no forked
+                # capture streams, no parallel graph branches); the UNet adds sum_k cn_scale[k] * r_k in two launches
+                d, m, scales = [None] * len(nets), [None] * len(nets), cn_scale_buf
+                for k in with_cn:
+                    d[k], m[k] = nets[k].forward_tokens(lat, t_buf, cn_kvrow, B, cn_cond[k], 1.0, temb=cn_temb_views[k],
+                                                        in_scale=in_scale)
+            elif with_cn:
                 d, m = controlnet.forward_tokens(lat, t_buf, cn_kvrow, B, cn_cond, conditioning_scale, temb=cn_temb_buf,
                                                  in_scale=in_scale)
-            eps = unet.forward_tokens(lat, t_buf, kvrow, 2 * B, added, d, m, temb=temb_buf, in_scale=in_scale, extra=extra)
+            eps = unet.forward_tokens(lat, t_buf, kvrow, 2 * B, added, d, m, temb=temb_buf, in_scale=in_scale, extra=extra,
+                                      residual_scales=scales)
             if multistep:
                 ops.cfg_multistep_step(eps, lat, hist, saved, row_f32, guidance_scale, B=B, per_sample=per_sample, z=z_buf,
                                        mask=mask, init=init, noise=noise)
@@ -241,7 +292,10 @@ class _DenoiseEngine:
                                   mask=mask, init=init, noise=noise)
 
         for i in range(first_step, len(ts)):
-            with_cn = controlnet is not None and cn_keep[i] > 0.0     # keep = 0: the residuals are zero (CN :397-403)
+            if multi:
+                with_cn = active_nets(cn_keep[i])        # only nets with keep > 0 run; their tuple keys warm-up and graph
+            else:
+                with_cn = controlnet is not None and cn_keep[i] > 0.0     # keep = 0: the residuals are zero (CN :397-403)
             if not self.use_graph:
                 step(with_cn)
             elif with_cn not in self._warm_keys:
@@ -254,6 +308,7 @@ class _DenoiseEngine:
                     with torch.cuda.graph(g):
                         step(with_cn)
                     self._graphs[with_cn] = g
+                    self.captures.append(with_cn)
                 g.replay()
             if callback is not None and (i - first_step) % callback_steps == 0:
                 callback(i - first_step, int(ts[i]), lat)
@@ -969,7 +1024,12 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
     y[i] += a[i mod len(a)]."""
 
     def __init__(self, unet: HipUNet, controlnet=None, scheduler: Optional[DDIMScheduler] = None, **kw):
+        """``controlnet``: a ``HipControlNet``, a ``HipMultiControlNet``, or a list / tuple of 1..4 ``HipControlNet``s, which
+        becomes a ``HipMultiControlNet`` (as diffusers wraps a list in a MultiControlNetModel)"""
         super().__init__(unet, scheduler, **kw)
+        if isinstance(controlnet, (list, tuple)):
+            from .controlnet import HipMultiControlNet
+            controlnet = HipMultiControlNet(controlnet)
         self.controlnet = controlnet
 
     def __call__(self, prompt=None, image=None, mask_image=None, control_image=None, height=None, width=None,
@@ -988,7 +1048,15 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
         """``prompt`` / ``input_id_images`` / ``image`` / ``mask_image``: as in
         StableDiffusionInpaintConsistentIDPipeline.__call__ (CN :180-265).  ``control_image``: a float tensor [B, 3, 8h, 8w]
         in [0, 1], or one PIL image (or a list of one), converted to RGB and resized to the final height x width by
-        image_prep.preprocess_control (CN :267-280)."""
+        image_prep.preprocess_control (CN :267-280).
+        Built with a list of ControlNets (``controlnet=HipMultiControlNet([...])``, or a list given to ``from_pretrained``),
+        the pipeline takes the reference's MultiControlNet arguments (CN :139-149, :281-301, :363-370, :397-398):
+        ``control_image`` is a list with one item per net, each a PIL image, a list of one PIL image or a float tensor
+        [B or 1, 3, 8h, 8w]; ``controlnet_conditioning_scale`` a list of N floats, or one float for all nets as in diffusers'
+        own ControlNet pipelines (the reference itself would fail on a float there: its ``zip`` at CN :398 needs a list);
+        ``control_guidance_start`` / ``control_guidance_end`` floats or lists of N, aligned as CN :139-149.  A net runs only in
+        the steps of its window.  Mismatched lengths raise ValueError.  A pipeline built with ONE ControlNet refuses several
+        control images (NotImplementedError).  ``guess_mode`` is not forwarded, as in the reference."""
         prompt_embeds, image, mask_image, height, width, normalize = self._call_inputs(
             prompt, input_id_images, prompt_embeds, negative_prompt, num_images_per_prompt, image, mask_image, height, width)
         if image is not None or mask_image is not None:
@@ -999,23 +1067,49 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
         first_step, latents, scaled = self._strength_window(strength, num_inference_steps, latents, image_latents, noise)
         self._check_hot_path_inputs(None, None, prompt_embeds, latents, output_type)    # (_call_inputs took prompt / ID images)
         extra = self._unet_extra(latents, mask_latents, masked_image_latents)
-        first = lambda v: v[0] if isinstance(v, (list, tuple)) else v        # single ControlNet (CN :352-358, :399-402)
-        scale, g0, g1 = first(controlnet_conditioning_scale), first(control_guidance_start), first(control_guidance_end)
+        from .controlnet import HipMultiControlNet, align_control_guidance, broadcast_conditioning_scale
+        multi = isinstance(self.controlnet, HipMultiControlNet)
+        if multi:
+            n_nets = len(self.controlnet.nets)
+            scale = broadcast_conditioning_scale(controlnet_conditioning_scale, n_nets)
+            g0, g1 = align_control_guidance(control_guidance_start, control_guidance_end, n_nets)
+        else:
+            first = lambda v: v[0] if isinstance(v, (list, tuple)) else v    # single ControlNet (CN :352-358, :399-402)
+            scale, g0, g1 = (float(first(v)) for v in (controlnet_conditioning_scale, control_guidance_start,
+                                                        control_guidance_end))
         cn = None
         if control_image is not None:
             if self.controlnet is None:
                 raise ValueError("control_image given but the pipeline was built without a controlnet")
             if down_block_res_samples is not None:
                 raise ValueError("pass either control_image (native ControlNet) or precomputed residuals")
-            if isinstance(control_image, (list, tuple)) and len(control_image) > 1:
-                raise NotImplementedError("MultiControlNet: a list of several control images")
             from . import image_prep
-            if image_prep.is_pil(control_image):
-                control_image = image_prep.preprocess_control(control_image, latents.shape[-2] * self.vae_scale_factor,
-                                                              latents.shape[-1] * self.vae_scale_factor)
-            if not torch.is_tensor(control_image):
-                raise NotImplementedError("control_image: one PIL image (resized by image_prep.py) or a float tensor "
-                                          "[B, 3, 8h, 8w] in [0, 1]; numpy arrays are not taken")
+            size = (latents.shape[-2] * self.vae_scale_factor, latents.shape[-1] * self.vae_scale_factor)
+            if multi:
+                if not isinstance(control_image, (list, tuple)):
+                    control_image = [control_image]
+                if len(control_image) != n_nets:
+                    raise ValueError(f"control_image has {len(control_image)} entries for {n_nets} ControlNets")
+                items = []
+                for k, item in enumerate(control_image):                                       # CN :281-301
+                    if image_prep.is_pil(item):
+                        if isinstance(item, (list, tuple)) and len(item) > 1:
+                            raise NotImplementedError(f"control_image[{k}]: one PIL image per ControlNet (got {len(item)})")
+                        item = image_prep.preprocess_control(item, *size)
+                    if not torch.is_tensor(item):
+                        raise NotImplementedError(f"control_image[{k}]: one PIL image (resized by image_prep.py) or a float "
+                                                  "tensor [B, 3, 8h, 8w] in [0, 1]; numpy arrays are not taken")
+                    items.append(item)
+                control_image = items
+            else:
+                if isinstance(control_image, (list, tuple)) and len(control_image) > 1:
+                    raise NotImplementedError("MultiControlNet: several control images need a pipeline built with a list of "
+                                              "ControlNets (controlnet=[...] / HipMultiControlNet), this one has a single one")
+                if image_prep.is_pil(control_image):
+                    control_image = image_prep.preprocess_control(control_image, *size)
+                if not torch.is_tensor(control_image):
+                    raise NotImplementedError("control_image: one PIL image (resized by image_prep.py) or a float tensor "
+                                              "[B, 3, 8h, 8w] in [0, 1]; numpy arrays are not taken")
             cn = self.controlnet
         null_e, aug_e, text_e = self._split(prompt_embeds)
         b_mask, b_init, b_noise = self._blend_inputs(extra, mask_latents, image_latents, noise)
@@ -1024,8 +1118,8 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
                                guidance_scale=guidance_scale, start_merge_step=start_merge_step,
                                down_residuals=down_block_res_samples, mid_residual=mid_block_res_sample,
                                inpaint_mask=b_mask, inpaint_init=b_init, inpaint_noise=b_noise,
-                               controlnet=cn, control_image=control_image, conditioning_scale=float(scale),
-                               control_guidance_start=float(g0), control_guidance_end=float(g1),
+                               controlnet=cn, control_image=control_image, conditioning_scale=scale,
+                               control_guidance_start=g0, control_guidance_end=g1,
                                callback=callback, callback_steps=callback_steps, first_step=first_step, scale_initial=scaled,
                                unet_extra=extra, eta=eta, variance_noise=variance_noise)
         out = self._postprocess(out, output_type)

@@ -443,9 +443,14 @@ class HipUNet:
     def forward_tokens(self, sample: torch.Tensor, t_dev: torch.Tensor, kvrow: torch.Tensor, B: int,
                        added_cond_kwargs=None, down_residuals: Optional[Sequence[torch.Tensor]] = None,
                        mid_residual: Optional[torch.Tensor] = None, temb: Optional[torch.Tensor] = None,
-                       in_scale: Optional[torch.Tensor] = None, extra: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       in_scale: Optional[torch.Tensor] = None, extra: Optional[torch.Tensor] = None,
+                       residual_scales: Optional[torch.Tensor] = None) -> torch.Tensor:
         """sample: NCHW fp16 [Bin, cin, H, W] with B % Bin == 0 (batch row b reads sample b % Bin,
         i.e. the CFG duplication of ref :537-539 costs no copy).  Returns NCHW fp16 [B, cout, H, W].
+        ``residual_scales`` (DEVICE fp32, one value per net) selects the multi-ControlNet form: ``down_residuals`` and
+        ``mid_residual`` are then lists with one entry per net -- that net's UNSCALED residuals (a list of skip-shaped
+        tensors / the mid tensor), or None for a net that did not run and whose scale is 0 -- and two cid_residual_accum_f16
+        launches add sum_k scale_k * r_k to the skip tensors and to the mid block's output, whatever the number of nets.
         ``extra`` [Bin, cin2, H, W]: the trailing input channels of a 9-channel inpainting UNet (cat([mask,
         masked_image_latents]), inpaint ref :320-321), read by conv_in beside the latents instead of a concatenated copy
         and not touched by ``in_scale``."""
@@ -491,7 +496,20 @@ class HipUNet:
                          Hi=H, Wi=Wd, Ho=Ho, Wo=Wo, stride=2, ws=self._gemm_ws, gn_hw=Ho * Wo)
                 x, H, Wd = y, Ho, Wo
                 skips.append((x, c, H, Wd))
-        if down_residuals is not None:
+        multi = residual_scales is not None
+        if multi:
+            # the same two exceptions as below get a copy; then ONE launch over all skip tensors
+            ran = [d for d in down_residuals if d is not None]
+            assert ran and all(len(d) == len(skips) for d in ran) and len(mid_residual) == len(down_residuals)
+            new, seen = [], set()
+            for (s, sc_, sh, sw) in skips:
+                if s is x or s.data_ptr() in seen:
+                    s = s.clone()
+                seen.add(s.data_ptr())
+                new.append((s, sc_, sh, sw))
+            skips = new
+            ops.residual_accum([s for s, _, _, _ in skips], down_residuals, residual_scales)
+        elif down_residuals is not None:
             # ControlNet residuals (CN :418-425), given token-major [B or B/2, HW, C]
             assert len(down_residuals) == len(skips)
             # The down path is complete: every skip tensor has been read by whatever followed it there, the up blocks are the
@@ -509,7 +527,9 @@ class HipUNet:
         x = self._resnet(self.mid.resnets[0], x, None, c, 0, B, H, Wd, temb, trows)
         x = self._transformer(self.mid.attentions[0], x, B, H, Wd, kvrow)
         x = self._resnet(self.mid.resnets[1], x, None, c, 0, B, H, Wd, temb, trows)
-        if mid_residual is not None:     # (x is the mid block's own output here: nobody else holds it)
+        if multi:
+            ops.residual_accum([x], [None if m is None else [m] for m in mid_residual], residual_scales)
+        elif mid_residual is not None:     # (x is the mid block's own output here: nobody else holds it)
             ops.add_inplace(x, mid_residual.to(device=self.device, dtype=torch.float16).contiguous())
         for blk in self.ups:
             for j, r in enumerate(blk.resnets):

@@ -478,6 +478,28 @@ int cid_cfg_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hi
 /* y[i] += a[i mod na] (ControlNet residual adds, CN :418-425) */
 int cid_add_inplace_f16(cid_half* y, const cid_half* a, int64_t n, int64_t na, cid_stream_t stream);
 
+/* The residuals of several ControlNets (diffusers MultiControlNetModel; CN :397-398 scales, :418-425 the hand-over to
+ * the UNet) added to up to 16 destination tensors in ONE launch:
+ *    y_j[i] = fp16( fp32(y_j[i]) + sum_k scales[k] * fp32(r_jk[i mod nr_j]) )        j < n_segs, k < n_nets
+ * scales: DEVICE, n_nets fp32 values (conditioning scale x keep of the step; cid_step_select fills it in a captured
+ * loop) -- no per-step host value enters the launch.  The sum runs in fp32 in net order and is rounded once, at the
+ * store.  A net whose scale is exactly 0 adds nothing AND its residuals are NOT read: a net outside its guidance window
+ * is not run, so r_jk may then point at anything readable or stale (NaN bit patterns included), but must not be NULL.
+ * `i mod nr` is the B-row residual under the 2B-row CFG batch, as in cid_add_inplace_f16.
+ * segs: HOST array, copied into the kernel arguments.  Refused before any launch (-22): NULL segs / scales / y / r[k]
+ * with k < n_nets; n_segs outside 1..16; n_nets outside 1..CID_MAX_CONTROLNETS; n or nr not a positive multiple of 8;
+ * n % nr != 0; y or r[k] not 16-byte aligned.  r[k] with k >= n_nets is ignored.  The y_j must not overlap each other
+ * or any r_jk. */
+#define CID_MAX_CONTROLNETS 4
+typedef struct cid_accum_seg {
+    cid_half* y;
+    int64_t n;                              /* elements of y */
+    int64_t nr;                             /* elements of every r[k] */
+    const cid_half* r[CID_MAX_CONTROLNETS];
+} cid_accum_seg;
+int cid_residual_accum_f16(const cid_accum_seg* segs, int32_t n_segs, int32_t n_nets, const float* scales,
+                           cid_stream_t stream);
+
 /* The reference's  `for i, t in enumerate(timesteps):`  (pipline_StableDiffusion_ConsistentID.py:535, SDXL :611, CN :375)
  * turns every per-step host value -- t, the scheduler coefficients of step i, the embed set selected by
  * `i <= start_merge_step` (:542-549), SDXL's pooled embeds (:620-631), the time-embedding row -- into a kernel argument.

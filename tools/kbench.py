@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Per-kernel micro-benchmarks at the shapes of the SD1.5 (or SDXL) UNet step: achieved
 TFLOP/s (MFMA-bound kernels) or GB/s (HBM-bound kernels) with HIP-event timing.
-Usage: python tools/kbench.py [--b2 8] [--family sd15] [--only gemm,attn,xattn,norm]"""
+Usage: python tools/kbench.py [--b2 8] [--family sd15] [--only gemm,attn,xattn,norm]   (also: xattn3, resid)"""
 import argparse
 import json
 import os
@@ -193,6 +193,31 @@ def main():
             out = torch.empty_like(x)
             t = timeit(lambda: ops.layernorm(x, out, gm, bt, M=M, C_=c))
             rows.append((label, f"M={M}", t * 1e6, 2.0 * M * c * 2 / t / 1e9, "GB/s", 10))
+
+    if "resid" in only:
+        # ControlNet residuals onto the 12 skip tensors + the mid block's output of the SD1.5 UNet (B2 rows; residuals of B2 / 2
+        # rows, repeating over the CFG halves): one net as 13 cid_add_inplace_f16 launches, N nets as 2 cid_residual_accum_f16
+        skips = [(64, 320)] * 3 + [(32, 320), (32, 640), (32, 640), (16, 640), (16, 1280), (16, 1280)] + [(8, 1280)] * 3
+        ys = [rnd(B2 * s_ * s_, c) for s_, c in skips + [(8, 1280)]]
+        nets = [[rnd(B2 // 2 * s_ * s_, c) for s_, c in skips + [(8, 1280)]] for _ in range(4)]
+        ybytes, rbytes = sum(2.0 * y.numel() for y in ys), sum(2.0 * r.numel() for r in nets[0])
+
+        def adds():
+            for y, r in zip(ys, nets[0]):
+                ops.add_inplace(y, r)
+
+        def accum(n):
+            ops.residual_accum(ys[:12], [net[:12] for net in nets[:n]], sc)
+            ops.residual_accum(ys[12:], [net[12:] for net in nets[:n]], sc)
+
+        sc = torch.full((4,), 0.5, device=dev)
+        for p_ in range(3):     # three alternating passes of 200 back-to-back repetitions each: the spread is part of the result
+            t = timeit(adds, iters=200)
+            rows.append((f"residuals 1 net: 13 add_inplace #{p_}", f"B2={B2}", t * 1e6, (2 * ybytes + rbytes) / t / 1e9, "GB/s", 0))
+            for n in (1, 2, 4):
+                t = timeit(lambda: accum(n), iters=200)
+                rows.append((f"residuals {n} net: 2 residual_accum #{p_}", f"B2={B2}", t * 1e6, (2 * ybytes + n * rbytes) / t / 1e9,
+                             "GB/s", 0))
 
     tot = 0.0
     print(f"{'kernel':40s} {'shape':14s} {'us':>9s} {'rate':>9s} unit  {'alg GB/s':>9s}  x/fwd  ms/fwd")
