@@ -80,6 +80,72 @@ def active_nets(keep_row: Sequence[float]) -> Tuple[int, ...]:
     return tuple(k for k, v in enumerate(keep_row) if v > 0.0)
 
 
+def prepare_control_arguments(controlnet, control_image, conditioning_scale, guidance_start, guidance_end, size) -> dict:
+    """The ControlNet arguments of the pipeline's ``__call__`` -> the denoise engine's ``controlnet``, ``control_image``,
+    ``conditioning_scale``, ``control_guidance_start`` and ``control_guidance_end``.  ``controlnet`` is the pipeline's: a
+    ``HipMultiControlNet`` takes one control image per net (CN :281-301), scales broadcast and windows aligned as CN
+    :139-149; a plain ``HipControlNet`` (or none) goes the same way as a list of one -- of a list it reads the first
+    scale and window (CN :352-358, :399-402) -- and is unwrapped at the end.  PIL images are resized to ``size`` =
+    (height, width).  Without a ``control_image`` no net runs (``controlnet`` None)."""
+    from . import image_prep
+    multi = isinstance(controlnet, HipMultiControlNet)
+    n_nets = len(controlnet.nets) if multi else 1
+    if multi:
+        scales = broadcast_conditioning_scale(conditioning_scale, n_nets)
+        starts, ends = align_control_guidance(guidance_start, guidance_end, n_nets)
+    else:
+        scales, starts, ends = ([float(v[0] if isinstance(v, (list, tuple)) else v)] for v in
+                                (conditioning_scale, guidance_start, guidance_end))
+    images = None
+    if control_image is not None:
+        if controlnet is None:
+            raise ValueError("control_image given but the pipeline was built without a controlnet")
+        several = isinstance(control_image, (list, tuple))
+        if not multi and several and len(control_image) > 1:
+            raise NotImplementedError("MultiControlNet: several control images need a pipeline built with a list of "
+                                      "ControlNets (controlnet=[...] / HipMultiControlNet), this one has a single one")
+        images = list(control_image) if multi and several else [control_image]
+        if len(images) != n_nets:
+            raise ValueError(f"control_image has {len(images)} entries for {n_nets} ControlNets")
+        for k, item in enumerate(images):                                                  # CN :281-301
+            what = f"control_image[{k}]" if multi else "control_image"
+            if image_prep.is_pil(item):
+                if isinstance(item, (list, tuple)) and len(item) > 1:
+                    raise NotImplementedError(f"{what}: one PIL image per ControlNet (got {len(item)})")
+                item = image_prep.preprocess_control(item, *size)
+            if not torch.is_tensor(item):
+                raise NotImplementedError(f"{what}: one PIL image (resized by image_prep.py) or a float tensor "
+                                          "[B, 3, 8h, 8w] in [0, 1]; numpy arrays are not taken")
+            images[k] = item
+    if not multi:
+        images, scales, starts, ends = (v[0] if v else None for v in (images, scales, starts, ends))
+    return dict(controlnet=None if images is None else controlnet, control_image=images, conditioning_scale=scales,
+                control_guidance_start=starts, control_guidance_end=ends)
+
+
+def _refuse_unbuilt(guess_mode: bool, return_dict: bool):
+    if guess_mode:
+        raise NotImplementedError("guess_mode residual scaling (the reference never forwards it, CN :405-412)")
+    if return_dict:
+        raise NotImplementedError("return_dict=True (the reference passes return_dict=False, CN :411)")
+
+
+def _refresh_context(net, ehs: torch.Tensor):
+    """K/V of ``encoder_hidden_states``, recomputed only when the tensor changed (kept alive in key_ref so that its address
+    cannot be recycled)"""
+    key = (ehs.data_ptr(), ehs._version, tuple(ehs.shape))
+    if net._ctx.key != key or net._ctx.key_ref is not ehs:
+        net.set_context(ehs, num_tokens=0)
+        net._ctx.key, net._ctx.key_ref = key, ehs
+
+
+def _nchw(down, mid, B: int, shapes):
+    """token-major residuals [B * h * w, c] -> (down, mid) as [B, c, h, w]-shaped (channels-last) views; ``shapes``: (c, h, w)
+    of every down residual, then of the mid one"""
+    view = lambda t, s: t.view(B, s[1], s[2], s[0]).permute(0, 3, 1, 2)
+    return [view(t, s) for t, s in zip(down, shapes[:-1])], view(mid, shapes[-1])
+
+
 class HipControlNet(HipUNet):
     def __init__(self, cfg: UNetConfig, controlnet_sd: Optional[Dict[str, torch.Tensor]] = None, device="cuda:0",
                  packed=None):
@@ -178,30 +244,17 @@ class HipControlNet(HipUNet):
                  guess_mode: bool = False, return_dict: bool = False):
         """Returns ``(down_block_res_samples, mid_block_res_sample)`` as [B, C, H, W]-shaped (channels-last) views,
         which ``HipUNet.__call__`` takes back without a copy."""
-        if guess_mode:
-            raise NotImplementedError("guess_mode residual scaling (the reference never forwards it, CN :405-412)")
-        if return_dict:
-            raise NotImplementedError("return_dict=True (the reference passes return_dict=False, CN :411)")
+        _refuse_unbuilt(guess_mode, return_dict)
         if isinstance(conditioning_scale, (list, tuple)):
             raise NotImplementedError("MultiControlNet: a list of scales goes to HipMultiControlNet([...]), this is one net")
         sample = sample.to(device=self.device, dtype=torch.float16).contiguous()
         B = sample.shape[0]
-        ehs = encoder_hidden_states
-        key = (ehs.data_ptr(), ehs._version, tuple(ehs.shape))
-        if self._ctx.key != key or self._ctx.key_ref is not ehs:
-            self.set_context(ehs, num_tokens=0)
-            self._ctx.key, self._ctx.key_ref = key, ehs
+        _refresh_context(self, encoder_hidden_states)
         kvrow = torch.arange(B, dtype=torch.int32, device=self.device)
         self._t_buf.fill_(float(timestep))
         cond = self.cond_embedding(controlnet_cond)
         down, mid = self.forward_tokens(sample, self._t_buf, kvrow, B, cond, conditioning_scale)
-
-        def nchw(t, shp):
-            c, h, w = shp
-            return t.view(B, h, w, c).permute(0, 3, 1, 2)
-
-        shapes = self._last_shapes
-        return [nchw(t, s) for t, s in zip(down, shapes[:-1])], nchw(mid, shapes[-1])
+        return _nchw(down, mid, B, self._last_shapes)
 
 
 class HipMultiControlNet:
@@ -233,10 +286,7 @@ class HipMultiControlNet:
         the summed ``(down_block_res_samples, mid_block_res_sample)`` in ``HipControlNet.__call__``'s layout.  The zero
         convs run unscaled and one cid_residual_accum_f16 launch per residual group forms sum_k scale_k * r_k in fp32 with
         one rounding (diffusers rounds every scaled residual and every partial sum to fp16)."""
-        if guess_mode:
-            raise NotImplementedError("guess_mode residual scaling (the reference never forwards it, CN :405-412)")
-        if return_dict:
-            raise NotImplementedError("return_dict=True (the reference passes return_dict=False, CN :411)")
+        _refuse_unbuilt(guess_mode, return_dict)
         N = len(self.nets)
         if not isinstance(controlnet_cond, (list, tuple)) or len(controlnet_cond) != N:
             got = len(controlnet_cond) if isinstance(controlnet_cond, (list, tuple)) else 1
@@ -244,14 +294,10 @@ class HipMultiControlNet:
         scales = broadcast_conditioning_scale(1.0 if conditioning_scale is None else conditioning_scale, N)
         sample = sample.to(device=self.device, dtype=torch.float16).contiguous()
         B = sample.shape[0]
-        ehs = encoder_hidden_states
-        key = (ehs.data_ptr(), ehs._version, tuple(ehs.shape))
         kvrow = torch.arange(B, dtype=torch.int32, device=self.device)
         downs, mids = [], []
         for net, cond in zip(self.nets, controlnet_cond):
-            if net._ctx.key != key or net._ctx.key_ref is not ehs:
-                net.set_context(ehs, num_tokens=0)
-                net._ctx.key, net._ctx.key_ref = key, ehs
+            _refresh_context(net, encoder_hidden_states)
             net._t_buf.fill_(float(timestep))
             d, m = net.forward_tokens(sample, net._t_buf, kvrow, B, net.cond_embedding(cond), 1.0)
             downs.append(d)
@@ -261,10 +307,4 @@ class HipMultiControlNet:
         out_m = torch.zeros_like(mids[0])
         ops.residual_accum(out_d, downs, self._scales)
         ops.residual_accum([out_m], [[m] for m in mids], self._scales)
-
-        def nchw(t, shp):
-            c, h, w = shp
-            return t.view(B, h, w, c).permute(0, 3, 1, 2)
-
-        shapes = self.nets[0]._last_shapes
-        return [nchw(t, s) for t, s in zip(out_d, shapes[:-1])], nchw(out_m, shapes[-1])
+        return _nchw(out_d, out_m, B, self.nets[0]._last_shapes)

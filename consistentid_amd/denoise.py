@@ -1,0 +1,326 @@
+"""The denoise engine of the four pipelines (pipeline.py): one generation = set_context (K/V of the embed sets) +
+S x [ControlNets + UNet(2B) + CFG + scheduler step].  The step is captured once into a hipGraph and replayed; every
+per-step host value of the reference's loops lives in one device table (ops.StepTable).
+
+``DenoiseEngine.run`` is a driver over phases that take and return named values: the static-buffer pool, the graph
+cache, the step coefficients (``_StepCoefficients``), the ControlNet plan (``_ControlPlan``), the embed-row selectors
+(``step_rows``), the step table and the step closure.
+"""
+from __future__ import annotations
+
+import os
+from collections import namedtuple
+from dataclasses import dataclass, field
+from typing import Any, Callable, Dict, List, Optional, Sequence, Union
+
+import numpy as np
+import torch
+
+from . import ops
+from .controlnet import HipMultiControlNet, active_nets, controlnet_keep_table
+from .scheduler import C_IN, DDIMScheduler, pack_step_rows
+from .unet import HipUNet
+
+
+def check_eta(scheduler, eta: float, variance_noise=None) -> float:
+    """``eta`` / ``variance_noise`` of the reference ``__call__``s (prepare_extra_step_kwargs -> DDIMScheduler.step(eta=,
+    variance_noise=)): only DDIM has the term, its eta is in [0, 1], and the noise needs a coefficient.  -> float(eta)"""
+    eta = float(eta)
+    if eta == 0.0:
+        if variance_noise is not None:
+            raise ValueError("variance_noise without eta: the noise term has the coefficient eta * sigma_t")
+        return eta
+    if not isinstance(scheduler, DDIMScheduler):
+        raise ValueError(f"eta = {eta}: only DDIMScheduler has an eta term ({type(scheduler).__name__} is deterministic); "
+                         "set pipe.scheduler = DDIMScheduler.from_config(pipe.scheduler.config) or pass eta = 0")
+    if eta < 0.0:
+        raise ValueError(f"eta = {eta}: DDIM's eta is in [0, 1]")
+    return eta
+
+
+# per schedule entry: the UNet's K/V rows [n_ts, 2B] int32, the ControlNets' [n_ts, B] int32 (or None), "merged" [n_ts] bool
+StepRows = namedtuple("StepRows", "unet controlnet merged")
+
+
+def step_rows(n_ts: int, first_step: int, start_merge_step: int, B: int, has_null_post: bool, device="cpu",
+              controlnet: bool = True) -> StepRows:
+    """The embed sets every schedule entry reads (ref :542-549: text-only while i <= start_merge_step, i counted from
+    ``first_step`` like the reference's enumerate over the truncated timestep list).  The UNet's K/V cache holds rows
+    [0,B) null, [B,2B) text-only, [2B,3B) augmented (ref :527-531) and, for SDXL's second unconditional set (ref SDXL
+    :586-590, :620-631), [3B,4B) null-post: a step selects (null, text) before the merge, (null or null-post, augmented)
+    after it.  A ControlNet's cache holds [0,B) text-only and [B,2B) augmented, selected the same way (CN :389-396)."""
+    ar = torch.arange(B, dtype=torch.int32, device=device)
+    merged = torch.tensor([(i - first_step) > start_merge_step for i in range(n_ts)], device=device)
+    pre = torch.cat([ar, ar + B])
+    post = torch.cat([ar + (3 * B if has_null_post else 0), ar + 2 * B])
+    cn = torch.where(merged[:, None], (ar + B)[None], ar[None]) if controlnet else None
+    return StepRows(torch.where(merged[:, None], post[None], pre[None]), cn, merged)
+
+
+@dataclass
+class _StepCoefficients:
+    """The scheduler's side of a step: cid_cfg_ddim_step_f16 for the two first-order updates (DDIM at eta = 0, Euler),
+    cid_cfg_multistep_step_f16 for PNDM, DPM-Solver++ and DDIM with eta > 0 (history ring, remembered sample, noise row)"""
+    buf: torch.Tensor                           # the row the step table fills: 5 fp32, or the 16-word multistep row (cid.h)
+    row: torch.Tensor                           # ``buf`` as the step kernel reads it (fp32)
+    in_scale: torch.Tensor                      # the model-input scale inside ``row``: conv_in reads it in place
+    table: torch.Tensor                         # [n_ts, ...] per-step rows, dtype of ``buf``
+    hist: Optional[torch.Tensor] = None         # multistep: fp32 ring of earlier model outputs
+    saved: Optional[torch.Tensor] = None        # multistep: the sample PNDM steps from twice
+    z: Optional[torch.Tensor] = None            # DDIM eta > 0: the variance noise of every executed step
+
+    def update(self, eps, lat, guidance_scale, **kw):
+        if self.hist is None:
+            ops.cfg_ddim_step(eps, lat, self.buf, guidance_scale, **kw)
+        else:
+            ops.cfg_multistep_step(eps, lat, self.hist, self.saved, self.row, guidance_scale, z=self.z, **kw)
+
+
+@dataclass
+class _ControlPlan:
+    """The ControlNets of one generation: a plain ``HipControlNet`` is a list of one whose scale is folded into its zero
+    convs (``fold``; the UNet adds with cid_add_inplace_f16); a ``HipMultiControlNet`` runs unscaled and scale_k * keep_k[i]
+    is a step-table column that cid_residual_accum_f16 reads (``scale_column``).  A column is (the static buffer the
+    step's kernels read, the [n_ts, ...] table whose row i fills it) and is that buffer's only holder.  No net: all lists empty."""
+    keep: List[List[float]]                     # [n_ts][nets]: the guidance windows (CN :363-370), 0 in skipped entries
+    nets: list = field(default_factory=list)
+    cond: List[torch.Tensor] = field(default_factory=list)      # per-net condition embedding
+    kvrow: Optional[torch.Tensor] = None
+    temb_column: Optional[tuple] = None         # (``cn_temb``, all nets' rows side by side): ONE table column (of 8)
+    temb: List[Optional[torch.Tensor]] = field(default_factory=list)    # net k's slice of ``temb_column[0]`` (a view)
+    fold: float = 1.0
+    scale_column: Optional[tuple] = None        # multi only: (``cn_scale``, [n_ts, 4] scale_k * keep_k[i])
+
+
+class DenoiseEngine:
+    """The state that outlives a generation: the static buffers, the captured graphs and their warm-up keys"""
+
+    def __init__(self, unet: HipUNet, scheduler: DDIMScheduler, use_graph: bool = True):
+        self.unet = unet
+        self.scheduler = scheduler
+        self.use_graph = use_graph
+        # captured step, keyed by the tuple of ControlNets that run in it (() = none); valid while no static buffer or context
+        # moved and the configuration key is the same: invalidate()
+        self._graphs: Dict[Any, Any] = {}
+        self._warm_keys = set()
+        self._config_key = None
+        self.captures: List[Any] = []           # key of every capture this engine ever made, in order (re-captures show twice)
+        self._static: Dict[str, torch.Tensor] = {}
+        self.step_path: Optional[str] = None    # the step launch of the last run: "cfg_ddim" or "cfg_multistep"
+
+    def invalidate(self):
+        """forget the captured graphs AND their eager warm-up (the first step after a change must run eagerly again)"""
+        self._graphs.clear()
+        self._warm_keys.clear()
+
+    def _launch(self, step, key):
+        """``step(key)``: eager without graphs and the first time a key occurs, captured the second time, replayed from then on"""
+        if not self.use_graph:
+            step(key)
+        elif key not in self._warm_keys:
+            step(key)   # eager warm-up: configures kernels, sizes the allocator pools
+            self._warm_keys.add(key)
+        else:
+            g = self._graphs.get(key)
+            if g is None:
+                g = torch.cuda.CUDAGraph()
+                with torch.cuda.graph(g):
+                    step(key)
+                self._graphs[key] = g
+                self.captures.append(key)
+            g.replay()
+
+    def _static_tensor(self, name: str, like: torch.Tensor, dtype=None) -> torch.Tensor:
+        """persistent device buffer (stable address across generations -> the captured graph stays valid)"""
+        dtype = dtype or like.dtype
+        cur = self._static.get(name)
+        if cur is None or cur.shape != like.shape or cur.dtype != dtype:
+            cur = torch.empty(like.shape, dtype=dtype, device=self.unet.device)
+            self._static[name] = cur
+            self.invalidate()   # an address changed: re-capture
+        cur.copy_(like.to(device=self.unet.device, dtype=dtype))
+        return cur
+
+    def _step_coefficients(self, lat, inpaint: bool, first_step: int, eta: float, variance_noise) -> _StepCoefficients:
+        sch, S, dev = self.scheduler, self._static_tensor, self.unet.device
+        n_ts = len(sch.timesteps)
+        multistep = bool(getattr(sch, "multistep", False)) or eta > 0.0
+        self.step_path = "cfg_multistep" if multistep else "cfg_ddim"
+        if not multistep:
+            table = torch.from_numpy(sch.coefficient_table(inpaint)).to(dev).view(n_ts, 5).float()
+            buf = S("coef", torch.zeros(5), torch.float32)      # c_x, c_eps, c_init, c_noise, model-input scale
+            return _StepCoefficients(buf, buf, buf[4:5], table)
+        rows = sch.coefficient_rows(inpaint, first_step, np.float32, **({"eta": eta} if eta > 0.0 else {}))
+        table = torch.from_numpy(pack_step_rows(rows)).to(dev).view(n_ts, 16)
+        z = None
+        if eta > 0.0:
+            n_run = n_ts - first_step
+            if variance_noise is None or tuple(variance_noise.shape) != (n_run, *lat.shape):
+                raise ValueError(f"eta = {eta} needs variance_noise of shape {(n_run, *lat.shape)} (one tensor per executed "
+                                 f"step), got {None if variance_noise is None else tuple(variance_noise.shape)}")
+            z = S("z", variance_noise, torch.float16)
+        buf = S("ms_row", torch.zeros(16), torch.int32)     # the multistep row (cid.h): 12 fp32 words, 4 int32 words
+        row = buf.view(torch.float32)
+        return _StepCoefficients(buf, row, row[C_IN:C_IN + 1], table,
+                                 hist=S("ms_hist", torch.zeros(4, lat.numel()), torch.float32),
+                                 saved=S("ms_saved", torch.zeros(lat.numel()), torch.float16), z=z)
+
+    def _control_plan(self, controlnet, control_image, conditioning_scale, starts, ends, text_embeds, augmented_embeds,
+                      rows: StepRows, tvals, first_step: int, temb_table: bool) -> _ControlPlan:
+        """native ControlNets (CN :389-412; MultiControlNet CN :281-301, :363-370, :397-398): conditional latents +
+        conditional embeds, residuals recomputed per step.  Every net has its own context, condition embedding and keep
+        window; they share the embed-row selector."""
+        S, dev, n_ts = self._static_tensor, self.unet.device, len(tvals)
+        if controlnet is None:
+            return _ControlPlan(keep=[[]] * n_ts)
+        multi = isinstance(controlnet, HipMultiControlNet)
+        if not multi:       # a plain net is a list of one
+            control_image, starts, ends = [control_image], [starts], [ends]
+        plan = _ControlPlan(keep=controlnet_keep_table(n_ts - first_step, starts, ends, first_step),
+                            nets=controlnet.nets if multi else [controlnet])
+        ehs = torch.cat([text_embeds.to(dev), augmented_embeds.to(dev)], dim=0)
+        for net in plan.nets:
+            before = net.context_addresses()
+            net.set_context(ehs, num_tokens=0)
+            if net.context_addresses() != before:
+                self.invalidate()
+        plan.cond = [S(f"cn_cond{k}", net.cond_embedding(img), torch.float16) for k, (net, img) in
+                     enumerate(zip(plan.nets, control_image))]
+        plan.kvrow = S("cn_kvrow", rows.controlnet[0], torch.int32)
+        plan.temb = [None] * len(plan.nets)
+        if temb_table:
+            tabs = [net.time_embed_table(tvals) for net in plan.nets]
+            assert all(t.shape[1] % 8 == 0 for t in tabs), "time-embedding rows are 16-byte multiples"
+            tab = torch.cat(tabs, dim=1) if len(tabs) > 1 else tabs[0]
+            plan.temb_column = (S("cn_temb", tab[:1], torch.float16), tab.view(n_ts, -1))
+            plan.temb = list(plan.temb_column[0].split([t.shape[1] for t in tabs], dim=1))
+        if multi:
+            # the zero convs stay unscaled: a new scale needs no new weights or graph
+            tab = torch.zeros(n_ts, 4)
+            tab[:, :len(plan.nets)] = torch.tensor(plan.keep, dtype=torch.float64).mul(
+                torch.tensor(list(conditioning_scale), dtype=torch.float64)).float()
+            plan.scale_column = (S("cn_scale", torch.zeros(4), torch.float32), tab.to(dev))    # 4 fp32 = one 16-byte column
+        else:
+            plan.fold = float(conditioning_scale)
+        return plan
+
+    @torch.no_grad()
+    def run(self, latents: torch.Tensor, null_embeds, augmented_embeds, text_embeds, *, num_inference_steps: int,
+            guidance_scale: float, start_merge_step: int, null_embeds_post=None, first_step: int = 0,
+            pooled: Optional[Sequence[torch.Tensor]] = None, time_ids: Optional[torch.Tensor] = None,
+            down_residuals=None, mid_residual=None, inpaint_mask=None, inpaint_init=None, inpaint_noise=None,
+            controlnet=None, control_image=None, conditioning_scale: Union[float, Sequence[float]] = 1.0,
+            control_guidance_start: Union[float, Sequence[float]] = 0.0,
+            control_guidance_end: Union[float, Sequence[float]] = 1.0,
+            callback: Optional[Callable[[int, int, torch.Tensor], None]] = None, callback_steps: int = 1,
+            scale_initial: bool = True, unet_extra: Optional[torch.Tensor] = None, eta: float = 0.0,
+            variance_noise: Optional[torch.Tensor] = None):
+        """``eta`` > 0 (DDIMScheduler only) with ``variance_noise`` [executed steps, B, C, h, w]: the noise diffusers' DDIM
+        ``step(..., eta=, variance_noise=)`` adds, one tensor per executed step in loop order.
+        ``first_step``: the loop runs schedule entries [first_step, S) -- the inpaint pipelines' ``strength`` < 1
+        window (get_timesteps, inpaint ref :246-252); the embed switch and the ControlNet keep window count steps from
+        there, exactly like the reference's ``for i, t in enumerate(timesteps)`` over the truncated list.
+        ``unet_extra`` [B, 5, h, w]: cat([mask, masked_image_latents]) of a 9-channel inpainting UNet (inpaint ref
+        :320-321, CN :415-416) -- conv_in reads it beside the (scaled) latents, the ControlNet does not see it.
+        ``controlnet`` = a ``HipMultiControlNet``: ``control_image``, ``conditioning_scale``, ``control_guidance_start`` and
+        ``control_guidance_end`` are sequences with one entry per net."""
+        unet, sch, S = self.unet, self.scheduler, self._static_tensor
+        eta = check_eta(sch, eta, variance_noise)
+        dev, B = unet.device, latents.shape[0]
+        sch.set_timesteps(num_inference_steps)                      # ref :510, before prepare_latents (:517)
+        # prepare_latents (diffusers; ref :517-526) scales the initial noise by the scheduler's init_noise_sigma
+        lat = S("lat", latents.to(dev).float() * (float(sch.init_noise_sigma) if scale_initial else 1.0), torch.float16)
+        # rows [0,B) null, [B,2B) text-only, [2B,3B) augmented   (ref :527-531 + :542-549); the SDXL pipeline has a
+        # second unconditional set for the steps after the merge (ref SDXL :586-590, :620-631): rows [3B,4B)
+        ctx_before = unet.context_addresses()
+        sets = [null_embeds.to(dev), text_embeds.to(dev), augmented_embeds.to(dev)]
+        if null_embeds_post is not None:
+            sets.append(null_embeds_post.to(dev))
+        unet.set_context(torch.cat(sets, dim=0))
+        if unet.context_addresses() != ctx_before:
+            self.invalidate()
+        ts = sch.timesteps
+        n_ts = len(ts)
+        inpaint = inpaint_mask is not None
+        coef = self._step_coefficients(lat, inpaint, first_step, eta, variance_noise)
+        tvals = torch.tensor(ts.astype(np.float32), device=dev)
+        rows = step_rows(n_ts, first_step, start_merge_step, B, null_embeds_post is not None, dev, controlnet is not None)
+        t_buf = S("t", torch.zeros(1), torch.float32)
+        kvrow = S("kvrow", rows.unet[0], torch.int32)
+        added = None
+        if time_ids is not None:
+            p_null, p_text, p_aug = [p.to(device=dev, dtype=torch.float16) for p in pooled]
+            added = {"text_embeds": S("pooled", torch.cat([p_null, p_text], 0), torch.float16),
+                     "time_ids": S("time_ids", time_ids, torch.float32)}
+        blend = dict(mask=None, init=None, noise=None)
+        if inpaint:
+            if unet_extra is not None:
+                raise ValueError("a 9-channel inpainting UNet is not blended: the reference guards the mask blend with "
+                                 "`if num_channels_unet == 4` (inpaint ref :340, CN :437)")
+            if inpaint_init is None or inpaint_noise is None:
+                raise ValueError("the mask blend of a 4-channel UNet needs image_latents and noise (inpaint ref :340-353)")
+            blend = dict(mask=S("mask", inpaint_mask.to(dev).expand_as(lat), torch.float16),
+                         init=S("init", inpaint_init, torch.float16), noise=S("noise", inpaint_noise, torch.float16))
+        extra = S("unet_extra", unet_extra, torch.float16) if unet_extra is not None else None
+        dres = mres = None
+        if down_residuals is not None:
+            assert controlnet is None, "pass either a ControlNet or precomputed residuals"
+            dres = [S(f"dres{j}", r, torch.float16) for j, r in enumerate(down_residuals)]
+            mres = S("mres", mid_residual, torch.float16)
+        # time path: one table per generation instead of three weight-streaming GEMVs per step (not with SDXL's
+        # text_time conditioning, whose rows also depend on the sample)
+        temb_tab = temb_buf = None
+        if unet.config.addition_embed_type is None and not os.environ.get("CID_NO_TEMB_TABLE"):
+            temb_tab = unet.time_embed_table(tvals)
+            temb_buf = S("temb", temb_tab[:1], torch.float16)
+        cn = self._control_plan(controlnet, control_image, conditioning_scale, control_guidance_start, control_guidance_end,
+                                text_embeds, augmented_embeds, rows, tvals, first_step, temb_buf is not None)
+        # every per-step host value of the reference's `for i, t in enumerate(timesteps)` as one device table: row i holds t,
+        # the scheduler coefficients, the embed-set rows, the time-embedding row and SDXL's pooled embeds (ref SDXL
+        # :620-631); cid_step_select, the first launch of the captured step, copies row `counter` into the buffers the
+        # step's kernels read and increments the counter
+        cols = [(t_buf, tvals.view(n_ts, 1)), (coef.buf, coef.table), (kvrow, rows.unet)]
+        if cn.nets:
+            cols.append((cn.kvrow, rows.controlnet))
+        if temb_buf is not None:
+            cols.append((temb_buf, temb_tab.view(n_ts, -1)))
+        cols += [c for c in (cn.temb_column, cn.scale_column) if c is not None]
+        if added is not None:
+            pre, post = torch.cat([p_null, p_text], 0), torch.cat([p_null, p_aug], 0)
+            cols.append((added["text_embeds"], torch.where(rows.merged[:, None, None], post[None], pre[None])))
+        table = ops.StepTable(cols, dev, alloc=S)     # table + counter are static buffers too
+        table.reset(first_step)
+
+        # every static buffer exists now (a new one has invalidated the graphs); so does a new configuration.  The multi
+        # path reads its scales from the step table: they are not part of the key
+        key = (B, tuple(lat.shape), float(guidance_scale), inpaint, time_ids is not None, dres is not None, bool(cn.nets),
+               ("multi", len(cn.nets)) if cn.scale_column else cn.fold, extra is not None, coef.hist is not None,
+               coef.z is not None)
+        if key != self._config_key:
+            self.invalidate()
+            self._config_key = key
+        per_sample = lat[0].numel()
+
+        def step(active):
+            """``active``: the nets that run, () = none -- one forward after another on the current stream (no forked
+            capture streams, no parallel graph branches)"""
+            table.select()
+            d, m, scales = dres, mres, None
+            res = {k: cn.nets[k].forward_tokens(lat, t_buf, cn.kvrow, B, cn.cond[k], cn.fold, temb=cn.temb[k],
+                                                in_scale=coef.in_scale) for k in active}
+            if res and cn.scale_column is None:
+                d, m = res[0]               # scale folded into the zero convs: the UNet adds the residuals as they are
+            elif res:
+                # unscaled residuals (None: the net did not run); the UNet adds sum_k cn_scale[k] * r_k in two launches
+                d, m = ([res[k][j] if k in res else None for k in range(len(cn.nets))] for j in (0, 1))
+                scales = cn.scale_column[0]
+            eps = unet.forward_tokens(lat, t_buf, kvrow, 2 * B, added, d, m, temb=temb_buf, in_scale=coef.in_scale,
+                                      extra=extra, residual_scales=scales)
+            coef.update(eps, lat, guidance_scale, B=B, per_sample=per_sample, **blend)
+
+        for i in range(first_step, n_ts):
+            active = active_nets(cn.keep[i])     # only nets with keep > 0 run (CN :397-403); their tuple keys warm-up and graph
+            self._launch(step, active)
+            if callback is not None and (i - first_step) % callback_steps == 0:
+                callback(i - first_step, int(ts[i]), lat)
+        return lat.clone()

@@ -28,14 +28,14 @@ from __future__ import annotations
 
 import os
 from dataclasses import dataclass
-from typing import Any, Callable, Dict, List, Optional, Sequence, Union
+from typing import Any, List, Optional, Union
 
 import numpy as np
 import torch
 
-from . import ops
-from .scheduler import (C_IN, DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler,  # noqa: F401
-                        PNDMScheduler, pack_step_rows)
+from .controlnet import HipMultiControlNet, prepare_control_arguments
+from .denoise import DenoiseEngine, check_eta
+from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler, PNDMScheduler  # noqa: F401
 from .unet import HipUNet
 
 
@@ -48,271 +48,6 @@ class StableDiffusionPipelineOutput:
 @dataclass
 class StableDiffusionXLPipelineOutput:
     images: Any
-
-
-class _DenoiseEngine:
-    """One generation = set_context (K/V of the 3 embed sets) + S x [UNet(2B) + CFG + DDIM].
-    The step is captured once into a hipGraph and replayed; per-step scalars live on device."""
-
-    def __init__(self, unet: HipUNet, scheduler: DDIMScheduler, use_graph: bool = True):
-        self.unet = unet
-        self.scheduler = scheduler
-        self.use_graph = use_graph
-        self._graph = None           # truthy while the static buffers the captured graphs point at are unchanged
-        self._graph_key = None
-        # captured step, without / with the ControlNet forward; with a HipMultiControlNet keyed by the tuple of nets that run
-        self._graphs: Dict[Any, Any] = {}
-        self._warm_keys = set()
-        self.captures: List[Any] = []           # key of every capture this engine ever made, in order (re-captures show twice)
-        self._static: Dict[str, torch.Tensor] = {}
-        self.step_path: Optional[str] = None    # the step launch of the last run: "cfg_ddim" or "cfg_multistep"
-
-    def _static_tensor(self, name: str, like: torch.Tensor, dtype=None) -> torch.Tensor:
-        """persistent device buffer (stable address across generations -> the captured graph stays valid)"""
-        dtype = dtype or like.dtype
-        cur = self._static.get(name)
-        if cur is None or cur.shape != like.shape or cur.dtype != dtype:
-            cur = torch.empty(like.shape, dtype=dtype, device=self.unet.device)
-            self._static[name] = cur
-            self._graph = None   # an address changed: re-capture
-        cur.copy_(like.to(device=self.unet.device, dtype=dtype))
-        return cur
-
-    @torch.no_grad()
-    def run(self, latents: torch.Tensor, null_embeds, augmented_embeds, text_embeds, *, num_inference_steps: int,
-            guidance_scale: float, start_merge_step: int, null_embeds_post=None, first_step: int = 0,
-            pooled: Optional[Sequence[torch.Tensor]] = None, time_ids: Optional[torch.Tensor] = None,
-            down_residuals=None, mid_residual=None, inpaint_mask=None, inpaint_init=None, inpaint_noise=None,
-            controlnet=None, control_image=None, conditioning_scale: Union[float, Sequence[float]] = 1.0,
-            control_guidance_start: Union[float, Sequence[float]] = 0.0,
-            control_guidance_end: Union[float, Sequence[float]] = 1.0,
-            callback: Optional[Callable[[int, int, torch.Tensor], None]] = None, callback_steps: int = 1,
-            scale_initial: bool = True, unet_extra: Optional[torch.Tensor] = None, eta: float = 0.0,
-            variance_noise: Optional[torch.Tensor] = None):
-        """``eta`` > 0 (DDIMScheduler only) with ``variance_noise`` [executed steps, B, C, h, w]: the noise diffusers' DDIM
-        ``step(..., eta=, variance_noise=)`` adds, one tensor per executed step in loop order.
-        ``first_step``: the loop runs schedule entries [first_step, S) -- the inpaint pipelines' ``strength`` < 1
-        window (get_timesteps, inpaint ref :246-252); the embed switch and the ControlNet keep window count steps from
-        there, exactly like the reference's ``for i, t in enumerate(timesteps)`` over the truncated list.
-        ``unet_extra`` [B, 5, h, w]: cat([mask, masked_image_latents]) of a 9-channel inpainting UNet (inpaint ref
-        :320-321, CN :415-416) -- conv_in reads it beside the (scaled) latents, the ControlNet does not see it.
-        ``controlnet`` = a ``HipMultiControlNet``: ``control_image``, ``conditioning_scale``, ``control_guidance_start`` and
-        ``control_guidance_end`` are sequences with one entry per net."""
-        unet, sch = self.unet, self.scheduler
-        dev = unet.device
-        B = latents.shape[0]
-        S = self._static_tensor
-        sch.set_timesteps(num_inference_steps)                      # ref :510, before prepare_latents (:517)
-        # prepare_latents (diffusers; ref :517-526) scales the initial noise by the scheduler's init_noise_sigma
-        lat = S("lat", latents.to(dev).float() * (float(sch.init_noise_sigma) if scale_initial else 1.0), torch.float16)
-        per_sample = lat[0].numel()
-        # rows [0,B) null, [B,2B) text-only, [2B,3B) augmented   (ref :527-531 + :542-549); the SDXL pipeline has a
-        # second unconditional set for the steps after the merge (ref SDXL :586-590, :620-631): rows [3B,4B)
-        ctx_before = unet.context_addresses()
-        sets = [null_embeds.to(dev), text_embeds.to(dev), augmented_embeds.to(dev)]
-        if null_embeds_post is not None:
-            sets.append(null_embeds_post.to(dev))
-        unet.set_context(torch.cat(sets, dim=0))
-        if unet.context_addresses() != ctx_before:
-            self._graph = None
-        sch.set_timesteps(num_inference_steps)
-        ts = sch.timesteps
-        inpaint = inpaint_mask is not None
-        # the step launch: cid_cfg_ddim_step_f16 for the two first-order updates (DDIM at eta = 0, Euler), cid_cfg_multistep_
-        # step_f16 for PNDM, DPM-Solver++ and DDIM with eta > 0 (history ring, remembered sample, noise row)
-        eta = float(eta)
-        if eta != 0.0 and not isinstance(sch, DDIMScheduler):
-            raise ValueError(f"eta = {eta}: only DDIMScheduler has an eta term ({type(sch).__name__} is deterministic); "
-                             "set pipe.scheduler = DDIMScheduler.from_config(pipe.scheduler.config) or pass eta = 0")
-        if eta < 0.0:
-            raise ValueError(f"eta = {eta}: DDIM's eta is in [0, 1]")
-        multistep = bool(getattr(sch, "multistep", False)) or eta > 0.0
-        self.step_path = "cfg_multistep" if multistep else "cfg_ddim"
-        z_buf = None
-        if multistep:
-            rows = sch.coefficient_rows(inpaint, first_step, np.float32, **({"eta": eta} if eta > 0.0 else {}))
-            coefs = torch.from_numpy(pack_step_rows(rows)).to(dev)
-            if eta > 0.0:
-                n_run = len(ts) - first_step
-                if variance_noise is None or tuple(variance_noise.shape) != (n_run, *lat.shape):
-                    raise ValueError(f"eta = {eta} needs variance_noise of shape {(n_run, *lat.shape)} (one tensor per executed "
-                                     f"step), got {None if variance_noise is None else tuple(variance_noise.shape)}")
-                z_buf = S("z", variance_noise, torch.float16)
-        else:
-            coefs = torch.from_numpy(sch.coefficient_table(inpaint)).to(dev)
-        tvals = torch.tensor(ts.astype(np.float32), device=dev)
-        ar = torch.arange(B, dtype=torch.int32, device=dev)
-        kv_pre = torch.cat([ar, ar + B]).contiguous()       # i <= start_merge_step: (null, text)
-        kv_post = torch.cat([ar + (3 * B if null_embeds_post is not None else 0), ar + 2 * B]).contiguous()  # afterwards
-        t_buf = S("t", torch.zeros(1), torch.float32)
-        if multistep:
-            coef_buf = S("ms_row", torch.zeros(16), torch.int32)     # the multistep row (cid.h): 12 fp32 words, 4 int32 words
-            row_f32 = coef_buf.view(torch.float32)
-            in_scale = row_f32[C_IN:C_IN + 1]
-            hist = S("ms_hist", torch.zeros(4, lat.numel()), torch.float32)      # fp32 ring of earlier model outputs
-            saved = S("ms_saved", torch.zeros(lat.numel()), torch.float16)       # the sample PNDM steps from twice
-        else:
-            coef_buf = S("coef", torch.zeros(5), torch.float32)      # c_x, c_eps, c_init, c_noise, model-input scale
-            in_scale = coef_buf[4:5]
-        kvrow = S("kvrow", kv_pre, torch.int32)
-        added = None
-        pooled_post = None
-        if time_ids is not None:
-            p_null, p_text, p_aug = [p.to(device=dev, dtype=torch.float16) for p in pooled]
-            pooled_buf = S("pooled", torch.cat([p_null, p_text], 0), torch.float16)
-            pooled_post = torch.cat([p_null, p_aug], 0).contiguous()
-            added = {"text_embeds": pooled_buf, "time_ids": S("time_ids", time_ids, torch.float32)}
-        mask = init = noise = None
-        if inpaint:
-            if unet_extra is not None:
-                raise ValueError("a 9-channel inpainting UNet is not blended: the reference guards the mask blend with "
-                                 "`if num_channels_unet == 4` (inpaint ref :340, CN :437)")
-            if inpaint_init is None or inpaint_noise is None:
-                raise ValueError("the mask blend of a 4-channel UNet needs image_latents and noise (inpaint ref :340-353)")
-            mask = S("mask", inpaint_mask.to(dev).expand_as(lat), torch.float16)
-            init = S("init", inpaint_init, torch.float16)
-            noise = S("noise", inpaint_noise, torch.float16)
-        extra = S("unet_extra", unet_extra, torch.float16) if unet_extra is not None else None
-        dres = mres = None
-        if down_residuals is not None:
-            dres = [S(f"dres{j}", r, torch.float16) for j, r in enumerate(down_residuals)]
-            mres = S("mres", mid_residual, torch.float16)
-        cn_cond = cn_kvrow = None
-        cn_keep = [0.0] * len(ts)
-        from .controlnet import HipMultiControlNet, active_nets, controlnet_keep_table
-        multi = isinstance(controlnet, HipMultiControlNet)
-        nets = controlnet.nets if multi else []
-        cn_scale_buf = cn_scale_tab = None
-        if multi:
-            # MultiControlNet (CN :281-301, :363-370, :397-398): every net has its own context, condition embedding and
-            # keep window; they share the embed-row selector.  The zero convs stay unscaled: scale_k * keep_k[i] is a
-            # column of the step table that cid_residual_accum_f16 reads, so a new scale needs no new weights or graph.
-            assert down_residuals is None, "pass either a ControlNet or precomputed residuals"
-            ehs_cn = torch.cat([text_embeds.to(dev), augmented_embeds.to(dev)], dim=0)
-            for net in nets:
-                cn_before = net.context_addresses()
-                net.set_context(ehs_cn, num_tokens=0)
-                if net.context_addresses() != cn_before:
-                    self._graphs.clear()
-                    self._warm_keys.clear()
-            cn_cond = [S(f"cn_cond{k}", net.cond_embedding(img), torch.float16) for k, (net, img) in
-                       enumerate(zip(nets, control_image))]
-            cn_kvrow = S("cn_kvrow", ar, torch.int32)
-            cn_keep = controlnet_keep_table(len(ts) - first_step, control_guidance_start, control_guidance_end, first_step)
-            cn_scale_buf = S("cn_scale", torch.zeros(4), torch.float32)      # 4 fp32 = one 16-byte column
-            cn_scale_tab = torch.zeros(len(ts), 4)
-            cn_scale_tab[:, :len(nets)] = torch.tensor(cn_keep, dtype=torch.float64).mul(
-                torch.tensor(list(conditioning_scale), dtype=torch.float64)).float()
-            cn_scale_tab = cn_scale_tab.to(dev)
-        elif controlnet is not None:
-            # native ControlNet (CN :389-412): conditional latents + conditional embeds, residuals recomputed per step.
-            # Its K/V cache holds rows [0,B) text-only and [B,2B) augmented, selected like the UNet's.
-            assert down_residuals is None, "pass either a ControlNet or precomputed residuals"
-            cn_before = controlnet.context_addresses()
-            controlnet.set_context(torch.cat([text_embeds.to(dev), augmented_embeds.to(dev)], dim=0), num_tokens=0)
-            if controlnet.context_addresses() != cn_before:
-                self._graphs.clear()
-                self._warm_keys.clear()
-            cn_cond = S("cn_cond", controlnet.cond_embedding(control_image), torch.float16)
-            cn_kvrow = S("cn_kvrow", ar, torch.int32)
-            n = len(ts) - first_step
-            cn_keep = [0.0] * first_step + [1.0 - float(i / n < control_guidance_start or (i + 1) / n > control_guidance_end)
-                                            for i in range(n)]                      # CN :364-371
-        # time path: one table per generation instead of three weight-streaming GEMVs per step (not with SDXL's
-        # text_time conditioning, whose rows also depend on the sample)
-        temb_tab = cn_temb_tab = temb_buf = cn_temb_buf = None
-        cn_temb_views = [None] * len(nets)
-        if unet.config.addition_embed_type is None and not os.environ.get("CID_NO_TEMB_TABLE"):
-            temb_tab = unet.time_embed_table(tvals)
-            temb_buf = S("temb", temb_tab[:1], torch.float16)
-            if multi:
-                # all nets' rows side by side in ONE buffer and ONE table column (the table has 8); per-net views into it
-                tabs = [net.time_embed_table(tvals) for net in nets]
-                cn_temb_tab = torch.cat(tabs, dim=1)
-                cn_temb_buf = S("cn_temb", cn_temb_tab[:1], torch.float16)
-                offs = np.cumsum([0] + [t.shape[1] for t in tabs])
-                assert all(o % 8 == 0 for o in offs), "time-embedding rows are 16-byte multiples"
-                cn_temb_views = [cn_temb_buf[:, offs[k]:offs[k + 1]] for k in range(len(nets))]
-            elif controlnet is not None:
-                cn_temb_tab = controlnet.time_embed_table(tvals)
-                cn_temb_buf = S("cn_temb", cn_temb_tab[:1], torch.float16)
-        # every per-step host value of the reference's `for i, t in enumerate(timesteps)` as one device table: row i holds t,
-        # the scheduler coefficients, the embed-set rows (ref :542-549: text-only while i <= start_merge_step), the time-
-        # embedding row and SDXL's pooled embeds (ref SDXL :620-631); cid_step_select, the first launch of the captured
-        # step, copies row `counter` into the buffers the step's kernels read and increments the counter
-        n_ts = len(ts)
-        merged_at = torch.tensor([(i - first_step) > start_merge_step for i in range(n_ts)], device=dev)
-        cols = [(t_buf, tvals.view(n_ts, 1)), (coef_buf, coefs.view(n_ts, 16) if multistep else coefs.view(n_ts, 5).float()),
-                (kvrow, torch.where(merged_at[:, None], kv_post[None], kv_pre[None]))]
-        if cn_kvrow is not None:
-            cols.append((cn_kvrow, torch.where(merged_at[:, None], (ar + B)[None], ar[None])))
-        if temb_buf is not None:
-            cols.append((temb_buf, temb_tab.view(n_ts, -1)))
-            if cn_temb_buf is not None:
-                cols.append((cn_temb_buf, cn_temb_tab.view(n_ts, -1)))
-        if cn_scale_buf is not None:
-            cols.append((cn_scale_buf, cn_scale_tab))
-        if pooled_post is not None:
-            pre = torch.cat([p_null, p_text], 0)
-            cols.append((added["text_embeds"], torch.where(merged_at[:, None, None], pooled_post[None], pre[None])))
-        table = ops.StepTable(cols, dev, alloc=S)     # table + counter are static buffers too
-        table.reset(first_step)
-
-        # every static buffer exists now: a new one (S() cleared _graph) or a new configuration invalidates the captured
-        # graphs AND their eager warm-up (the first step after a shape change must run eagerly again)
-        key = (B, tuple(lat.shape), float(guidance_scale), inpaint, time_ids is not None, dres is not None,
-               controlnet is not None, ("multi", len(nets)) if multi else float(conditioning_scale), extra is not None,
-               multistep, z_buf is not None)      # (the multi path reads its scales from the step table: not part of the key)
-        if key != self._graph_key or self._graph is None:
-            self._graphs.clear()
-            self._warm_keys.clear()
-            self._graph, self._graph_key = True, key     # (_graph: "static buffers valid" marker, cleared by S())
-
-        def step(with_cn):
-            """``with_cn``: bool for one ControlNet; with a HipMultiControlNet the tuple of nets that run, () = none"""
-            table.select()
-            d, m, scales = dres, mres, None
-            if multi and with_cn:
-                # unscaled residuals of the nets that run, one forward after another on the current stream (no forked
-                # capture streams, no parallel graph branches); the UNet adds sum_k cn_scale[k] * r_k in two launches
-                d, m, scales = [None] * len(nets), [None] * len(nets), cn_scale_buf
-                for k in with_cn:
-                    d[k], m[k] = nets[k].forward_tokens(lat, t_buf, cn_kvrow, B, cn_cond[k], 1.0, temb=cn_temb_views[k],
-                                                        in_scale=in_scale)
-            elif with_cn:
-                d, m = controlnet.forward_tokens(lat, t_buf, cn_kvrow, B, cn_cond, conditioning_scale, temb=cn_temb_buf,
-                                                 in_scale=in_scale)
-            eps = unet.forward_tokens(lat, t_buf, kvrow, 2 * B, added, d, m, temb=temb_buf, in_scale=in_scale, extra=extra,
-                                      residual_scales=scales)
-            if multistep:
-                ops.cfg_multistep_step(eps, lat, hist, saved, row_f32, guidance_scale, B=B, per_sample=per_sample, z=z_buf,
-                                       mask=mask, init=init, noise=noise)
-            else:
-                ops.cfg_ddim_step(eps, lat, coef_buf, guidance_scale, B=B, per_sample=per_sample,
-                                  mask=mask, init=init, noise=noise)
-
-        for i in range(first_step, len(ts)):
-            if multi:
-                with_cn = active_nets(cn_keep[i])        # only nets with keep > 0 run; their tuple keys warm-up and graph
-            else:
-                with_cn = controlnet is not None and cn_keep[i] > 0.0     # keep = 0: the residuals are zero (CN :397-403)
-            if not self.use_graph:
-                step(with_cn)
-            elif with_cn not in self._warm_keys:
-                step(with_cn)   # eager warm-up: configures kernels, sizes the allocator pools
-                self._warm_keys.add(with_cn)
-            else:
-                g = self._graphs.get(with_cn)
-                if g is None:
-                    g = torch.cuda.CUDAGraph()
-                    with torch.cuda.graph(g):
-                        step(with_cn)
-                    self._graphs[with_cn] = g
-                    self.captures.append(with_cn)
-                g.replay()
-            if callback is not None and (i - first_step) % callback_steps == 0:
-                callback(i - first_step, int(ts[i]), lat)
-        return lat.clone()
 
 
 def inpaint_draws(generator, *, image_batch: int, batch_size: int, latent_channels: int, h: int, w: int,
@@ -356,7 +91,7 @@ class _BasePipeline:
         self.num_tokens = num_tokens
         self.lora_rank = lora_rank
         self.device = unet.device
-        self._engine = _DenoiseEngine(unet, scheduler or DDIMScheduler(), use_graph)
+        self._engine = DenoiseEngine(unet, scheduler or DDIMScheduler(), use_graph)
 
     def to(self, device=None, *args, **kwargs):
         """``pipe.to(device)`` of the reference scripts (infer.py:21, demo/controlnet_demo.py:60): the engines are built on
@@ -399,19 +134,11 @@ class _BasePipeline:
         DDIM and eta > 0 every executed step adds sigma_t * randn.  The tensors are drawn here, before the loop, one
         ``randn_tensor`` [B, C, h, w] fp16 per executed step in loop order on ``generator`` -- after every pre-loop draw, so
         the generator's stream is consumed in diffusers' order -- or taken from ``variance_noise`` [steps, B, C, h, w]."""
-        if eta == 0.0:
-            if variance_noise is not None:
-                raise ValueError("variance_noise without eta: the noise term has the coefficient eta * sigma_t")
-            return None
-        if not isinstance(self.scheduler, DDIMScheduler):
-            raise ValueError(f"eta = {eta}: only DDIMScheduler has an eta term ({type(self.scheduler).__name__} is deterministic); "
-                             "set pipe.scheduler = DDIMScheduler.from_config(pipe.scheduler.config) or pass eta = 0")
-        if variance_noise is not None:
-            return variance_noise
+        if check_eta(self.scheduler, eta, variance_noise) == 0.0 or variance_noise is not None:
+            return variance_noise       # no noise term (None), or the caller's tensors
         from .vae import randn_tensor
         self.scheduler.set_timesteps(num_inference_steps)
-        shape = tuple(latents.shape)
-        return torch.stack([randn_tensor(shape, generator=generator, device=self.device, dtype=torch.float16)
+        return torch.stack([randn_tensor(tuple(latents.shape), generator=generator, device=self.device, dtype=torch.float16)
                             for _ in range(len(self.scheduler.timesteps) - first_step)])
 
     # -- surface kept from the reference ------------------------------------------------------
@@ -473,7 +200,7 @@ class _BasePipeline:
         if self.image_proj_state and self.facial_encoder_state:
             from .idstack import HipIDConditioner
             self.id_conditioner = HipIDConditioner(self.image_proj_state, self.facial_encoder_state, device=self.device)
-        self._engine._graphs.clear()
+        self._engine.invalidate()
         return self
 
     def prepare_prompt_embeds(self, **encoder_outputs) -> torch.Tensor:
@@ -510,6 +237,13 @@ class _BasePipeline:
             from PIL import Image
             return [Image.fromarray(a) for a in (arr * 255).round().astype("uint8")]
         return arr
+
+    @staticmethod
+    def _output(out, return_dict: bool):
+        """the SD1.5-family tail (ref :596-598); no safety checker: has_nsfw_concept = None"""
+        if not return_dict:
+            return (out, None)
+        return StableDiffusionPipelineOutput(images=out, nsfw_content_detected=None)
 
     def _split(self, prompt_embeds):
         assert prompt_embeds.shape[0] % 3 == 0
@@ -726,10 +460,7 @@ class ConsistentIDStableDiffusionPipeline(_IDPreLoop, _SD15PromptEncoding, _Base
         out = self._engine.run(latents, null_e, aug_e, text_e, num_inference_steps=num_inference_steps,
                                guidance_scale=guidance_scale, start_merge_step=start_merge_step,
                                callback=callback, callback_steps=callback_steps, eta=eta, variance_noise=variance_noise)
-        out = self._postprocess(out, output_type, legacy_numpy=True)   # no safety checker: has_nsfw_concept = None
-        if not return_dict:
-            return (out, None)
-        return StableDiffusionPipelineOutput(images=out, nsfw_content_detected=None)
+        return self._output(self._postprocess(out, output_type, legacy_numpy=True), return_dict)
 
 
 class ConsistentIDStableDiffusionXLPipeline(_BasePipeline):
@@ -986,6 +717,22 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
         [-1, 1]), ``mask_image`` [B, 1, H, W] / [1, H, W] / [H, W], binarised at 0.5 (1 = repaint), H, W = height, width.
         ``generator`` seeds the posterior samples and the noise in diffusers' order.  ``num_images_per_prompt`` = n on the
         prompt path: n samples of the one identity (embeds and image latents repeated, noise one draw of [n, C, h, w])."""
+        return self._inpaint(prompt=prompt, image=image, mask_image=mask_image, masked_image_latents=masked_image_latents,
+                             height=height, width=width, strength=strength, num_inference_steps=num_inference_steps,
+                             guidance_scale=guidance_scale, negative_prompt=negative_prompt,
+                             num_images_per_prompt=num_images_per_prompt, eta=eta, generator=generator, latents=latents,
+                             prompt_embeds=prompt_embeds, output_type=output_type, return_dict=return_dict,
+                             callback=callback, callback_steps=callback_steps, input_id_images=input_id_images,
+                             start_merge_step=start_merge_step, image_latents=image_latents, noise=noise,
+                             mask_latents=mask_latents, down_block_res_samples=down_block_res_samples,
+                             mid_block_res_sample=mid_block_res_sample, variance_noise=variance_noise)
+
+    def _inpaint(self, *, prompt, image, mask_image, masked_image_latents, height, width, strength, num_inference_steps,
+                 guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents, prompt_embeds,
+                 output_type, return_dict, callback, callback_steps, input_id_images, start_merge_step, image_latents,
+                 noise, mask_latents, down_block_res_samples, mid_block_res_sample, variance_noise, control=None):
+        """The body both inpaint ``__call__``s share (inpaint ref :127-359, CN :180-456).  ``control``: the ControlNet
+        pipeline's (control_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end)."""
         prompt_embeds, image, mask_image, height, width, normalize = self._call_inputs(
             prompt, input_id_images, prompt_embeds, negative_prompt, num_images_per_prompt, image, mask_image, height, width)
         if image is not None or mask_image is not None:
@@ -996,6 +743,11 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
         first, latents, scaled = self._strength_window(strength, num_inference_steps, latents, image_latents, noise)
         self._check_hot_path_inputs(None, None, prompt_embeds, latents, output_type)    # (_call_inputs took prompt / ID images)
         extra = self._unet_extra(latents, mask_latents, masked_image_latents)
+        cn_kw = {}
+        if control is not None:
+            if control[0] is not None and self.controlnet is not None and down_block_res_samples is not None:
+                raise ValueError("pass either control_image (native ControlNet) or precomputed residuals")
+            cn_kw = prepare_control_arguments(self.controlnet, *control, [n * self.vae_scale_factor for n in latents.shape[-2:]])
         null_e, aug_e, text_e = self._split(prompt_embeds)
         b_mask, b_init, b_noise = self._blend_inputs(extra, mask_latents, image_latents, noise)
         variance_noise = self._variance_noise(eta, generator, variance_noise, latents, num_inference_steps, first)
@@ -1004,11 +756,8 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                                down_residuals=down_block_res_samples, mid_residual=mid_block_res_sample,
                                inpaint_mask=b_mask, inpaint_init=b_init, inpaint_noise=b_noise,
                                callback=callback, callback_steps=callback_steps, first_step=first, scale_initial=scaled,
-                               unet_extra=extra, eta=eta, variance_noise=variance_noise)
-        out = self._postprocess(out, output_type)
-        if not return_dict:
-            return (out, None)
-        return StableDiffusionPipelineOutput(images=out, nsfw_content_detected=None)
+                               unet_extra=extra, eta=eta, variance_noise=variance_noise, **cn_kw)
+        return self._output(self._postprocess(out, output_type), return_dict)
 
 
 class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpaintConsistentIDPipeline):
@@ -1028,7 +777,6 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
         becomes a ``HipMultiControlNet`` (as diffusers wraps a list in a MultiControlNetModel)"""
         super().__init__(unet, scheduler, **kw)
         if isinstance(controlnet, (list, tuple)):
-            from .controlnet import HipMultiControlNet
             controlnet = HipMultiControlNet(controlnet)
         self.controlnet = controlnet
 
@@ -1057,72 +805,14 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
         ``control_guidance_start`` / ``control_guidance_end`` floats or lists of N, aligned as CN :139-149.  A net runs only in
         the steps of its window.  Mismatched lengths raise ValueError.  A pipeline built with ONE ControlNet refuses several
         control images (NotImplementedError).  ``guess_mode`` is not forwarded, as in the reference."""
-        prompt_embeds, image, mask_image, height, width, normalize = self._call_inputs(
-            prompt, input_id_images, prompt_embeds, negative_prompt, num_images_per_prompt, image, mask_image, height, width)
-        if image is not None or mask_image is not None:
-            image_latents, noise, mask_latents, masked_image_latents = self._encode_images(
-                image, mask_image, height, width, latents, strength, generator, prompt_embeds,
-                dict(image_latents=image_latents, noise=noise, mask_latents=mask_latents,
-                     masked_image_latents=masked_image_latents), normalize)
-        first_step, latents, scaled = self._strength_window(strength, num_inference_steps, latents, image_latents, noise)
-        self._check_hot_path_inputs(None, None, prompt_embeds, latents, output_type)    # (_call_inputs took prompt / ID images)
-        extra = self._unet_extra(latents, mask_latents, masked_image_latents)
-        from .controlnet import HipMultiControlNet, align_control_guidance, broadcast_conditioning_scale
-        multi = isinstance(self.controlnet, HipMultiControlNet)
-        if multi:
-            n_nets = len(self.controlnet.nets)
-            scale = broadcast_conditioning_scale(controlnet_conditioning_scale, n_nets)
-            g0, g1 = align_control_guidance(control_guidance_start, control_guidance_end, n_nets)
-        else:
-            first = lambda v: v[0] if isinstance(v, (list, tuple)) else v    # single ControlNet (CN :352-358, :399-402)
-            scale, g0, g1 = (float(first(v)) for v in (controlnet_conditioning_scale, control_guidance_start,
-                                                        control_guidance_end))
-        cn = None
-        if control_image is not None:
-            if self.controlnet is None:
-                raise ValueError("control_image given but the pipeline was built without a controlnet")
-            if down_block_res_samples is not None:
-                raise ValueError("pass either control_image (native ControlNet) or precomputed residuals")
-            from . import image_prep
-            size = (latents.shape[-2] * self.vae_scale_factor, latents.shape[-1] * self.vae_scale_factor)
-            if multi:
-                if not isinstance(control_image, (list, tuple)):
-                    control_image = [control_image]
-                if len(control_image) != n_nets:
-                    raise ValueError(f"control_image has {len(control_image)} entries for {n_nets} ControlNets")
-                items = []
-                for k, item in enumerate(control_image):                                       # CN :281-301
-                    if image_prep.is_pil(item):
-                        if isinstance(item, (list, tuple)) and len(item) > 1:
-                            raise NotImplementedError(f"control_image[{k}]: one PIL image per ControlNet (got {len(item)})")
-                        item = image_prep.preprocess_control(item, *size)
-                    if not torch.is_tensor(item):
-                        raise NotImplementedError(f"control_image[{k}]: one PIL image (resized by image_prep.py) or a float "
-                                                  "tensor [B, 3, 8h, 8w] in [0, 1]; numpy arrays are not taken")
-                    items.append(item)
-                control_image = items
-            else:
-                if isinstance(control_image, (list, tuple)) and len(control_image) > 1:
-                    raise NotImplementedError("MultiControlNet: several control images need a pipeline built with a list of "
-                                              "ControlNets (controlnet=[...] / HipMultiControlNet), this one has a single one")
-                if image_prep.is_pil(control_image):
-                    control_image = image_prep.preprocess_control(control_image, *size)
-                if not torch.is_tensor(control_image):
-                    raise NotImplementedError("control_image: one PIL image (resized by image_prep.py) or a float tensor "
-                                              "[B, 3, 8h, 8w] in [0, 1]; numpy arrays are not taken")
-            cn = self.controlnet
-        null_e, aug_e, text_e = self._split(prompt_embeds)
-        b_mask, b_init, b_noise = self._blend_inputs(extra, mask_latents, image_latents, noise)
-        variance_noise = self._variance_noise(eta, generator, variance_noise, latents, num_inference_steps, first_step)
-        out = self._engine.run(latents, null_e, aug_e, text_e, num_inference_steps=num_inference_steps,
-                               guidance_scale=guidance_scale, start_merge_step=start_merge_step,
-                               down_residuals=down_block_res_samples, mid_residual=mid_block_res_sample,
-                               inpaint_mask=b_mask, inpaint_init=b_init, inpaint_noise=b_noise,
-                               controlnet=cn, control_image=control_image, conditioning_scale=scale,
-                               control_guidance_start=g0, control_guidance_end=g1,
-                               callback=callback, callback_steps=callback_steps, first_step=first_step, scale_initial=scaled,
-                               unet_extra=extra, eta=eta, variance_noise=variance_noise)
-        out = self._postprocess(out, output_type)
-        if not return_dict:
-            return (out, None)
-        return StableDiffusionPipelineOutput(images=out, nsfw_content_detected=None)
+        return self._inpaint(prompt=prompt, image=image, mask_image=mask_image, masked_image_latents=masked_image_latents,
+                             height=height, width=width, strength=strength, num_inference_steps=num_inference_steps,
+                             guidance_scale=guidance_scale, negative_prompt=negative_prompt,
+                             num_images_per_prompt=num_images_per_prompt, eta=eta, generator=generator, latents=latents,
+                             prompt_embeds=prompt_embeds, output_type=output_type, return_dict=return_dict,
+                             callback=callback, callback_steps=callback_steps, input_id_images=input_id_images,
+                             start_merge_step=start_merge_step, image_latents=image_latents, noise=noise,
+                             mask_latents=mask_latents, down_block_res_samples=down_block_res_samples,
+                             mid_block_res_sample=mid_block_res_sample, variance_noise=variance_noise,
+                             control=(control_image, controlnet_conditioning_scale, control_guidance_start,
+                             control_guidance_end))
