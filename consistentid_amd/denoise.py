@@ -4,7 +4,11 @@ per-step host value of the reference's loops lives in one device table (ops.Step
 
 ``DenoiseEngine.run`` is a driver over phases that take and return named values: the static-buffer pool, the graph
 cache, the step coefficients (``_StepCoefficients``), the ControlNet plan (``_ControlPlan``), the embed-row selectors
-(``step_rows``), the step table and the step closure.
+(``step_rows``), what the step reads of objects the engine does not own (``captured_reads``), the step table and the
+step closure.
+
+The engine keeps the reference to the ``HipUNet`` it was built on: assigning ``pipe.unet`` afterwards does not reach it (out
+of scope; build a new pipeline).  ``pipe.controlnet = other`` and ``pipe.scheduler = other`` take effect on the next call.
 """
 from __future__ import annotations
 
@@ -57,6 +61,17 @@ def step_rows(n_ts: int, first_step: int, start_merge_step: int, B: int, has_nul
     return StepRows(torch.where(merged[:, None], post[None], pre[None]), cn, merged)
 
 
+def captured_reads(unet, nets: Sequence[Any]) -> tuple:
+    """What a captured step bakes in of the objects the engine does not own -- the UNet, then the ControlNets in the order
+    they run -- as they are AFTER this generation's ``set_context`` calls: per object (its serial, its epoch, its
+    ``context_addresses()``).  The serial tells two objects at the same addresses and shapes apart, and [A, B] from [B, A]; the
+    epoch counts the changes of launch arguments kept on the host (``load_adapter_modules``: ip_scale) and the moves of the
+    K/V buffers, so an address that went away and came back while another engine used the object is not taken for the old
+    one.  A graph is valid only for the value it was captured under; nothing the step table carries (scales, merge step,
+    ``first_step``) is in it."""
+    return tuple((o.serial, o.epoch, tuple(o.context_addresses())) for o in (unet, *nets))
+
+
 @dataclass
 class _StepCoefficients:
     """The scheduler's side of a step: cid_cfg_ddim_step_f16 for the two first-order updates (DDIM at eta = 0, Euler),
@@ -99,8 +114,8 @@ class DenoiseEngine:
         self.unet = unet
         self.scheduler = scheduler
         self.use_graph = use_graph
-        # captured step, keyed by the tuple of ControlNets that run in it (() = none); valid while no static buffer or context
-        # moved and the configuration key is the same: invalidate()
+        # captured step, keyed by the tuple of ControlNets that run in it (() = none); valid while no static buffer moved
+        # and the configuration key (which holds captured_reads) is the same: invalidate()
         self._graphs: Dict[Any, Any] = {}
         self._warm_keys = set()
         self._config_key = None
@@ -180,10 +195,7 @@ class DenoiseEngine:
                             nets=controlnet.nets if multi else [controlnet])
         ehs = torch.cat([text_embeds.to(dev), augmented_embeds.to(dev)], dim=0)
         for net in plan.nets:
-            before = net.context_addresses()
             net.set_context(ehs, num_tokens=0)
-            if net.context_addresses() != before:
-                self.invalidate()
         plan.cond = [S(f"cn_cond{k}", net.cond_embedding(img), torch.float16) for k, (net, img) in
                      enumerate(zip(plan.nets, control_image))]
         plan.kvrow = S("cn_kvrow", rows.controlnet[0], torch.int32)
@@ -232,13 +244,10 @@ class DenoiseEngine:
         lat = S("lat", latents.to(dev).float() * (float(sch.init_noise_sigma) if scale_initial else 1.0), torch.float16)
         # rows [0,B) null, [B,2B) text-only, [2B,3B) augmented   (ref :527-531 + :542-549); the SDXL pipeline has a
         # second unconditional set for the steps after the merge (ref SDXL :586-590, :620-631): rows [3B,4B)
-        ctx_before = unet.context_addresses()
         sets = [null_embeds.to(dev), text_embeds.to(dev), augmented_embeds.to(dev)]
         if null_embeds_post is not None:
             sets.append(null_embeds_post.to(dev))
         unet.set_context(torch.cat(sets, dim=0))
-        if unet.context_addresses() != ctx_before:
-            self.invalidate()
         ts = sch.timesteps
         n_ts = len(ts)
         inpaint = inpaint_mask is not None
@@ -291,11 +300,16 @@ class DenoiseEngine:
         table = ops.StepTable(cols, dev, alloc=S)     # table + counter are static buffers too
         table.reset(first_step)
 
-        # every static buffer exists now (a new one has invalidated the graphs); so does a new configuration.  The multi
-        # path reads its scales from the step table: they are not part of the key
-        key = (B, tuple(lat.shape), float(guidance_scale), inpaint, time_ids is not None, dres is not None, bool(cn.nets),
-               ("multi", len(cn.nets)) if cn.scale_column else cn.fold, extra is not None, coef.hist is not None,
-               coef.z is not None)
+        # every static buffer exists now (a new one has invalidated the graphs); so does a new configuration, and so does
+        # anything else than what the graphs were captured under in the UNet or the nets (another object, moved K/V or
+        # workspace, a new epoch) -- whoever changed it, this engine or another one that shares the object.  The multi path
+        # reads its scales from the step table: they are not part of the key
+        unet.reserve_workspace(2 * B)
+        for net in cn.nets:
+            net.reserve_workspace(B)
+        key = (captured_reads(unet, cn.nets), B, tuple(lat.shape), float(guidance_scale), inpaint, time_ids is not None,
+               dres is not None, bool(cn.nets), ("multi", len(cn.nets)) if cn.scale_column else cn.fold, extra is not None,
+               coef.hist is not None, coef.z is not None)
         if key != self._config_key:
             self.invalidate()
             self._config_key = key

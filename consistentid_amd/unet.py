@@ -19,6 +19,7 @@ Design (MI355X-first, not a module tree):
 """
 from __future__ import annotations
 
+import itertools
 import os
 
 from dataclasses import dataclass
@@ -60,6 +61,8 @@ def fused_gen1(c: int, tokens: int, fused_max_c: int = 320) -> bool:
 
 
 class HipUNet:
+    _serials = itertools.count(1)       # one number per object ever built (id() is recycled after garbage collection)
+
     def __init__(self, cfg: UNetConfig, unet_sd: Optional[Dict[str, torch.Tensor]] = None,
                  adapter_sd: Optional[Dict[str, torch.Tensor]] = None, device="cuda:0",
                  num_tokens: int = 4, lora_scale: float = 1.0, packed: Optional[PackedUNet] = None,
@@ -79,6 +82,10 @@ class HipUNet:
         if self.packed.encoder_only:
             self.ups = []
         self._ctx = _Ctx()
+        # what a captured denoise step bakes in of this object (denoise.captured_reads): which object it is, and an epoch
+        # that counts every change of a host-side launch argument (ip_scale) and every move of the K/V buffers
+        self.serial = next(HipUNet._serials)
+        self.epoch = 0
         self._gn_ws: Optional[torch.Tensor] = None
         self._gemm_ws = torch.empty(ops.GEMM_WS_BYTES, dtype=torch.uint8, device=self.device)   # split-K partials
         # widest level that runs the one-launch fused ID cross-attention (wider levels: GEMMs around the core)
@@ -96,6 +103,7 @@ class HipUNet:
         with torch.cuda.device(self.device):
             self.packed.load_adapter_modules(adapter_sd, lora_scale)
         self._ctx.key = self._ctx.key_ref = None
+        self.epoch += 1         # ip_scale is a launch argument kept on the host: captured steps hold its old value
         return self
 
     # -- attributes the reference pipelines read
@@ -117,6 +125,7 @@ class HipUNet:
         ctx.rows, ctx.n_txt, ctx.n_ip = R, L - nt, nt
         M = R * L
         cache: Dict[int, torch.Tensor] = {}
+        moved = False
         for b in self.packed.xattn_layers:
             wt = self.W[f"{b}.attn2.kv_txt.w"]
             C2 = wt.shape[0]
@@ -133,6 +142,7 @@ class HipUNet:
             if kp is None or kp.numel() != R * ke:   # keep addresses stable across generations
                 kp = torch.empty(R * ke, dtype=torch.float16, device=self.device)
                 vp = torch.empty(R * ve, dtype=torch.float16, device=self.device)
+                moved = True
             if v3:      # fragment order of the third-generation fused kernel (SD1.5 level 0)
                 ops.kv_pack2(kv_txt, kv_ip, kp, vp, R=R, L=L, C_=C_, heads=heads, n_txt=ctx.n_txt, n_ip=ctx.n_ip, order="reg")
             else:
@@ -140,10 +150,20 @@ class HipUNet:
             ctx.kp[b], ctx.vp[b] = kp, vp
             ctx.v2[b] = 3 if v3 else 0
         ctx.key, ctx.key_ref = (ehs.data_ptr(), ehs._version, tuple(ehs.shape)), ehs
+        if moved:       # the allocator may hand an old address out again: the addresses alone do not tell
+            self.epoch += 1
         return self
 
     def context_addresses(self):
-        return tuple(t.data_ptr() for t in self._ctx.kp.values()) + (self._ctx.n_txt, self._ctx.n_ip)
+        """the device addresses and scalar launch arguments a captured step reads from this object besides its weights: the
+        packed K/V of every cross-attention layer, the GroupNorm workspace (``reserve_workspace``) and the context lengths"""
+        ws = 0 if self._gn_ws is None else self._gn_ws.data_ptr()
+        return (tuple(t.data_ptr() for t in self._ctx.kp.values()) + tuple(t.data_ptr() for t in self._ctx.vp.values())
+                + (ws, self._ctx.n_txt, self._ctx.n_ip))
+
+    def reserve_workspace(self, B: int):
+        """size the GroupNorm workspace for a forward of batch ``B`` now, so that its address is known before the first step"""
+        self._ws(B)
 
     def _heads_of(self, block_name: str) -> int:
         for blk in self.downs + [self.mid] + self.ups:

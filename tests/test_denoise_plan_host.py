@@ -1,5 +1,6 @@
 """The denoise engine's host-side phases without a GPU or the library: the embed-row selectors of every schedule entry,
-the ControlNet argument preparation of the pipeline call, the keep table of a plain net and the ``eta`` refusals."""
+the ControlNet argument preparation of the pipeline call, the keep table of a plain net, the ``eta`` refusals and the key
+of what a captured step reads of the UNet and the ControlNets."""
 from types import SimpleNamespace
 
 import numpy as np
@@ -143,3 +144,79 @@ def test_eta_refusals_are_the_same_from_pipeline_and_engine():
     assert _messages(scheduler.DDIMScheduler(), -0.5, noise) == "eta = -0.5: DDIM's eta is in [0, 1]"
     for sch in (scheduler.DDIMScheduler(), scheduler.PNDMScheduler()):
         assert _messages(sch, 0.0, noise) == "variance_noise without eta: the noise term has the coefficient eta * sigma_t"
+
+
+# --------------------------------------------------------------------------- what a captured step reads
+class _Obj:
+    """stands in for a HipUNet / HipControlNet: a serial from one counter, an epoch, K/V buffers that ``set_context`` moves when
+    the row count changes (and then counts in the epoch), as unet.py does.  ``pool`` plays the caching allocator: a freed
+    address is handed out again for the next request of the same size."""
+    _serials = iter(range(1, 1000))
+
+    def __init__(self, pool, addresses=None):
+        self.serial, self.epoch, self.pool, self.rows = next(self._serials), 0, pool, None
+        self.addr = addresses
+
+    def set_context(self, rows):
+        if rows != self.rows:
+            if self.rows is not None:
+                self.pool.setdefault(self.rows, []).append(self.addr)
+            free = self.pool.get(rows)
+            self.addr = free.pop() if free else (0x1000 * self.serial + rows,)
+            self.rows, self.epoch = rows, self.epoch + 1
+
+    def load_adapter_modules(self):
+        self.epoch += 1
+
+    def context_addresses(self):
+        return (*self.addr, 77, 4)
+
+
+def test_captured_reads_tell_objects_orders_moves_and_epochs_apart():
+    from consistentid_amd.denoise import captured_reads
+    unet, a, b = _Obj({}, (0x100,)), _Obj({}, (0x200,)), _Obj({}, (0x200,))
+    assert a.context_addresses() == b.context_addresses()
+    assert captured_reads(unet, [a]) == captured_reads(unet, [a]) == captured_reads(unet, (a,))
+    assert captured_reads(unet, [a, b]) == captured_reads(unet, [a, b])
+    assert captured_reads(unet, [a]) != captured_reads(unet, [b])             # A against B at identical addresses and shapes
+    assert captured_reads(unet, [a, b]) != captured_reads(unet, [b, a])
+    assert captured_reads(unet, []) != captured_reads(unet, [a]) != captured_reads(unet, [a, b])
+    before = captured_reads(unet, [a])
+    a.load_adapter_modules()                                                  # a host-side launch argument changed
+    assert captured_reads(unet, [a]) != before and captured_reads(unet, [a])[0] == before[0]
+    before = captured_reads(unet, [a])
+    unet.load_adapter_modules()
+    assert captured_reads(unet, [a]) != before and captured_reads(unet, [a])[1] == before[1]
+
+
+def test_captured_reads_after_a_shared_unet_moved_and_moved_back():
+    """One UNet under two engines: engine 1 captures at 6 rows (B = 2); engine 2 sets 3 rows, then 6 again, and the
+    allocator hands the first address out a second time.  The addresses are those engine 1 captured with, the key is not."""
+    from consistentid_amd.denoise import captured_reads
+    unet = _Obj({})
+    unet.set_context(6)
+    engine1 = captured_reads(unet, [])
+    unet.set_context(6)                                     # engine 1 again, same shapes: nothing moved
+    assert captured_reads(unet, []) == engine1
+    unet.set_context(3)                                     # engine 2 at B = 1
+    engine2 = captured_reads(unet, [])
+    assert engine2 != engine1
+    unet.set_context(6)                                     # engine 2 at B = 2
+    assert unet.context_addresses() == engine1[0][2]        # (moved back)
+    assert captured_reads(unet, []) not in (engine1, engine2)
+    unet.set_context(6)                                     # engine 1 at B = 2: ``set_context`` keeps the buffers
+    assert unet.context_addresses() == engine1[0][2] and captured_reads(unet, []) != engine1
+
+
+def test_captured_reads_hold_nothing_the_step_table_carries():
+    """the function sees the objects only: scales, merge step, ``first_step`` and the guidance windows cannot reach it, and
+    the key is (serial, epoch, addresses) per object and nothing else"""
+    import inspect
+    from consistentid_amd.denoise import captured_reads
+    assert list(inspect.signature(captured_reads).parameters) == ["unet", "nets"]
+    unet, a = _Obj({}, (0x100, 0x180)), _Obj({}, (0x200,))
+    assert captured_reads(unet, [a]) == ((unet.serial, 0, (0x100, 0x180, 77, 4)), (a.serial, 0, (0x200, 77, 4)))
+    for name in ("conditioning_scale", "fold", "start_merge_step", "first_step", "keep", "guidance_scale"):
+        setattr(a, name, 0.25)
+        setattr(unet, name, 3)
+    assert captured_reads(unet, [a]) == ((unet.serial, 0, (0x100, 0x180, 77, 4)), (a.serial, 0, (0x200, 77, 4)))

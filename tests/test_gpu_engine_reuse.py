@@ -1,0 +1,190 @@
+"""One denoise engine across differing generations.  A scenario is a list of generations (engine_cases.Spec) run on one live
+pipeline with use_graph=True; after every generation the latents (and with a callback every per-step clone) must equal, bit
+for bit, the same spec run eagerly on objects nothing else has touched (engine_cases.fresh_eager): a replay issues the same
+launches on the same values, so a difference means the graph read something that was not this generation's.  The first and
+the last generation and every one that follows a change of net or UNet are also held to the fp32 oracle within the fp16 arm
+(conftest.check_vs_fp16_arm, defaults), so two engines that are wrong in the same way cannot agree their way through.  Where
+the engine promises to keep its graphs ``len(eng.captures)`` must not grow; elsewhere the count is printed
+as an ``[engine]`` line.  Every generation has at least 3 steps on one set of active nets: eager, capture, replay."""
+from dataclasses import dataclass
+from typing import Any, Callable, Optional
+
+import pytest
+import torch
+
+from conftest import check_vs_fp16_arm
+from engine_cases import (Spec, call_pipeline, controlnet_of, executed_steps, fresh_eager, new_net, new_unet, oracle_pair,
+                          pipeline_class, product_scheduler, unet_models)
+
+pytestmark = pytest.mark.gpu
+
+
+@dataclass
+class Gen:
+    what: str                       # the one thing that differs from the generation before
+    spec: Spec
+    oracle: bool = False            # follows a change of net or UNet (the first and last generation are checked anyway)
+    same_graphs: bool = False       # a transition the engine promises not to re-capture for
+    pipe: Any = None                # scenarios over several pipelines: the one this generation runs on
+    before: Optional[Callable[[], None]] = None     # runs first (e.g. loads an adapter)
+
+
+def _run(dev, scenario, gens, pipe=None, net_objects=None):
+    """-> the latents of every generation"""
+    assert all(executed_steps(g.spec) >= 3 for g in gens)
+    outs, held, multis, last = [], [], {}, {}
+    for n, g in enumerate(gens):
+        p, spec = g.pipe or pipe, g.spec
+        eng = p._engine
+        if g.before is not None:
+            g.before()
+        if last.get(id(p), spec).scheduler != spec.scheduler or id(p) not in last:
+            p.scheduler = product_scheduler(spec)
+        if spec.nets and (id(p) not in last or (last[id(p)].nets, last[id(p)].multi) != (spec.nets, spec.multi)):
+            key = (spec.nets, spec.multi)
+            if key not in multis:
+                multis[key] = controlnet_of(spec, net_objects)
+            p.controlnet = multis[key]
+            held.append(p.controlnet)
+        last[id(p)] = spec
+        before = len(eng.captures)
+        got, steps = call_pipeline(p, spec, dev)
+        got = got.clone()
+        print(f"[engine] {scenario}: generation {n} ({g.what}): captures {before} -> {len(eng.captures)}"
+              f"{' (promised: none)' if g.same_graphs else ''}; graphs now {sorted(eng._graphs)}")
+        want, want_steps = fresh_eager(spec, str(dev))
+        assert torch.isfinite(got.float()).all(), f"{scenario}, generation {n} ({g.what}): not finite"
+        assert torch.equal(got, want), (f"{scenario}, generation {n} ({g.what}): differs from the fresh eager run, max |diff| = "
+                                        f"{(got.float() - want.float()).abs().max():.3e}")
+        if spec.callback:
+            assert len(steps) == len(want_steps) == executed_steps(spec)
+            for i, (a, b) in enumerate(zip(steps, want_steps)):
+                assert torch.equal(a, b), f"{scenario}, generation {n} ({g.what}): step {i} differs from the fresh eager run"
+        if g.oracle or n in (0, len(gens) - 1):
+            check_vs_fp16_arm(got, *oracle_pair(spec.but(callback=False), str(dev)), f"{scenario}, generation {n} ({g.what})")
+        if g.same_graphs:
+            assert len(eng.captures) == before, f"{scenario}, generation {n} ({g.what}): re-captured {eng.captures[before:]}"
+        outs.append(got)
+    for p in {id(g.pipe or pipe): g.pipe or pipe for g in gens}.values():
+        assert p._engine.captures, f"{scenario}: nothing was ever captured, so nothing was replayed"
+    return outs
+
+
+# --------------------------------------------------------------------------- 1. txt2img
+def test_txt2img_one_change_at_a_time(dev):
+    base = Spec(steps=4, merge=1, guidance=5.0)
+    cfg = unet_models(str(dev))[0]
+    assert (24, 40) != (cfg.sample_size, cfg.sample_size)
+    s = base
+    gens = [Gen("base", s)]
+    for what, change, promised in (
+            ("merge 2", dict(merge=2), True), ("6 steps", dict(steps=6), False), ("4 steps", dict(steps=4), False),
+            ("guidance 7.5", dict(guidance=7.5), False), ("B = 1", dict(B=1), False), ("B = 2", dict(B=2), False),
+            ("24 x 40 latents", dict(hw=(24, 40)), False), ("square latents", dict(hw=None), False),     # (test_tiny_unet_odd_resolution)
+            ("32 text tokens", dict(text_len=32), False), ("77 text tokens", dict(text_len=77), False),  # (32, 4): attention edges
+            ("new values", dict(seed=5), True), ("callback", dict(callback=True), False)):
+        s = s.but(**change)
+        gens.append(Gen(what, s, same_graphs=promised, oracle=what in ("24 x 40 latents", "32 text tokens")))
+    pipe = pipeline_class(base)(new_unet(str(dev)), use_graph=True)
+    _run(dev, "txt2img", gens, pipe)
+
+
+# --------------------------------------------------------------------------- 2. schedulers
+def test_schedulers_on_one_pipeline(dev):
+    base = Spec(steps=4, merge=1)
+    gens = [Gen("DDIM", base), Gen("Euler", base.but(scheduler="euler"), same_graphs=True),
+            Gen("DPM-Solver++ 2M", base.but(scheduler="dpm")), Gen("PNDM", base.but(scheduler="pndm")),
+            Gen("DDIM eta 1", base.but(eta=1.0)), Gen("DDIM eta 0", base)]
+    pipe = pipeline_class(base)(new_unet(str(dev)), use_graph=True)
+    outs = _run(dev, "schedulers", gens, pipe)
+    assert torch.equal(outs[-1], outs[0]), "DDIM at eta 0 after five other step kernels is not the DDIM it started with"
+    assert pipe._engine.step_path == "cfg_ddim"
+
+
+# --------------------------------------------------------------------------- 3. inpaint
+def test_inpaint_strength_windows(dev):
+    """strength 1.0 -> 0.6 -> 1.0 at 5 steps (first_step 0 -> 2 -> 0), DDIM then DPM-Solver++: the solver's history starts
+    empty at ``first_step`` every time, or the bits (and the oracle, which every generation here is held to) differ"""
+    base = Spec(pipe="inpaint", steps=5, merge=1, guidance=7.5)
+    gens = []
+    for sch in ("ddim", "dpm"):
+        s = base.but(scheduler=sch)
+        gens += [Gen(f"{sch}, strength 1.0", s, oracle=True, same_graphs=False),
+                 Gen(f"{sch}, strength 0.6", s.but(strength=0.6), oracle=True, same_graphs=True),
+                 Gen(f"{sch}, strength 1.0 again", s, oracle=True, same_graphs=True)]
+    pipe = pipeline_class(base)(new_unet(str(dev)), use_graph=True)
+    _run(dev, "inpaint", gens, pipe)
+
+
+# --------------------------------------------------------------------------- 4. ControlNet identity
+CN = Spec(pipe="controlnet", steps=4, merge=1, guidance=5.0)
+
+
+def _one(label, scale=0.5):
+    return CN.but(nets=(label,), scales=(scale,), windows=((0.0, 1.0),))
+
+
+def test_controlnet_identity_plain(dev):
+    """net A -> a fresh net B -> A again -> no control image -> A.  The graphs are keyed by the INDEX of the nets that run,
+    (0,) for either net; A's buffers do not move when it comes back."""
+    nets = {k: new_net(str(dev), k) for k in "AB"}                          # held for the whole test
+    gens = [Gen("net A", _one("A")), Gen("fresh net B", _one("B"), oracle=True), Gen("net A again", _one("A"), oracle=True),
+            Gen("no control image", CN, oracle=True), Gen("net A", _one("A"), oracle=True)]
+    pipe = pipeline_class(CN)(new_unet(str(dev)), controlnet=nets["A"], use_graph=True)
+    _run(dev, "plain ControlNet", gens, pipe, nets)
+
+
+def test_controlnet_identity_multi(dev):
+    """[A, B] -> a new HipMultiControlNet([B, A]) with images and scales swapped to match -> [A] -> [A, B]; the engine's key
+    says ("multi", 2) for both orders.  Then the two transitions of a MultiControlNet that keep the graphs: new scales, and
+    guidance windows that leave the sets of active nets as they were.  Precomputed residuals beside control images are
+    refused as before."""
+    nets = {k: new_net(str(dev), k) for k in "AB"}
+    two = lambda a, b, sa, sb: CN.but(nets=(a, b), multi=True, scales=(sa, sb), windows=((0.0, 1.0), (0.0, 1.0)))
+    ab = two("A", "B", 0.5, 0.8)
+    gens = [Gen("[A, B]", ab), Gen("[B, A]", two("B", "A", 0.8, 0.5), oracle=True),
+            Gen("[A]", CN.but(nets=("A",), multi=True, scales=(0.5,), windows=((0.0, 1.0),)), oracle=True),
+            Gen("[A, B]", ab, oracle=True), Gen("[A, B], new scales", ab.but(scales=(0.3, 0.9)), same_graphs=True),
+            # 5 steps: (0, 1) three times, then (0,) twice, so both are captured within the generation
+            Gen("5 steps, B's window ends at 0.6", ab.but(steps=5, windows=((0.0, 1.0), (0.0, 0.6)))),
+            Gen("B's window ends at 0.7: the same active sets", ab.but(steps=5, windows=((0.0, 1.0), (0.0, 0.7))), same_graphs=True)]
+    pipe = pipeline_class(CN)(new_unet(str(dev)), controlnet=[nets["A"], nets["B"]], use_graph=True)
+    _run(dev, "MultiControlNet", gens, pipe, nets)
+    with pytest.raises(ValueError, match="pass either control_image"):
+        pipe(prompt_embeds=torch.zeros(6, 81, 8), latents=torch.zeros(2, 4, 8, 8), control_image=[torch.zeros(2, 3, 64, 64)] * 2,
+             image_latents=torch.zeros(2, 4, 8, 8), noise=torch.zeros(2, 4, 8, 8), mask_latents=torch.zeros(2, 1, 8, 8),
+             num_inference_steps=4, output_type="latent", down_block_res_samples=[torch.zeros(2, 64, 8)],
+             mid_block_res_sample=torch.zeros(2, 64, 8))
+
+
+# --------------------------------------------------------------------------- 5. one UNet under two pipelines
+def test_shared_unet_under_two_pipelines(dev):
+    """P1 (txt2img) at B = 2, P2 (inpaint) at B = 1 and B = 2 -- the UNet's K/V buffers move twice -- then P1 at B = 2 again:
+    ``set_context`` keeps the buffers it finds, which are not the ones P1's graph was captured with.  Then P2 loads a second
+    adapter into the shared UNet and P1 runs: it must see the new weights (a fresh UNet built with that adapter, and its
+    oracle)."""
+    unet = new_unet(str(dev), keep_base=True)
+    t2i, inp = Spec(steps=4, merge=1), Spec(pipe="inpaint", steps=4, merge=1)
+    p1 = pipeline_class(t2i)(unet, use_graph=True)
+    p2 = pipeline_class(inp)(unet, use_graph=True)
+    ad2 = unet_models(str(dev), "tiny", 1)[2]
+    gens = [Gen("P1, B = 2", t2i, pipe=p1), Gen("P2, B = 1", inp.but(B=1), pipe=p2, oracle=True),
+            Gen("P2, B = 2", inp, pipe=p2, oracle=True), Gen("P1, B = 2 again", t2i, pipe=p1, oracle=True),
+            Gen("P1 after P2 loaded a second adapter", t2i.but(adapter=1), pipe=p1, oracle=True,
+                before=lambda: p2.load_ConsistentID_model({"adapter_modules": ad2}, lora_rank=8)),
+            Gen("P2 with the second adapter", inp.but(adapter=1), pipe=p2, oracle=True)]
+    _run(dev, "shared UNet", gens)
+
+
+# --------------------------------------------------------------------------- 6. SDXL
+def test_sdxl_one_change_at_a_time(dev):
+    base = Spec(pipe="sdxl", steps=4, merge=1, guidance=7.5)
+    s = base
+    gens = [Gen("base", s)]
+    for what, change, promised in (
+            ("second unconditional set", dict(null_post=True), False), ("one unconditional set", dict(null_post=False), False),
+            ("new time_ids", dict(time_ids=(8, 16)), True), ("new values", dict(seed=3), True), ("3 steps", dict(steps=3), False)):
+        s = s.but(**change)
+        gens.append(Gen(what, s, same_graphs=promised, oracle="unconditional" in what))
+    pipe = pipeline_class(base)(new_unet(str(dev), "tinyxl"), use_graph=True)
+    _run(dev, "SDXL", gens, pipe)

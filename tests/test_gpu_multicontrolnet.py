@@ -7,8 +7,8 @@ import numpy as np
 import pytest
 import torch
 
-from conftest import check_vs_fp16_arm, half_arm
-from oracle_utils import build_oracle, make_weights, product_cfg
+from conftest import check_vs_fp16_arm
+from engine_cases import OracleMulti as _OracleMulti, loop_inputs as _loop_inputs, models as _models
 
 pytestmark = pytest.mark.gpu
 
@@ -123,42 +123,6 @@ def test_residual_accum_drops_stale_groupnorm_statistics(dev):
     assert not hasattr(y, "_gn_stats") and float(y.sum()) == 64.0
 
 
-# --------------------------------------------------------------------------- models (built once)
-@functools.lru_cache(maxsize=None)
-def _models(dev_str):
-    from consistentid_amd import synth
-    from consistentid_amd.controlnet import HipControlNet
-    from consistentid_amd.unet import HipUNet
-    from oracle import unet as ounet
-    from oracle.controlnet import ControlNetModel
-    dev = torch.device(dev_str)
-    cfg = product_cfg("tiny")
-    o_cns, sds = [], []
-    for seed in (3, 4):
-        sd = synth.random_controlnet_state_dict(cfg, seed=seed)
-        o = ControlNetModel(ounet.tiny_config("sd15"))
-        o.load_state_dict({k: v.float() for k, v in sd.items()}, strict=True)
-        o_cns.append(o.eval())
-        sds.append(sd)
-    _, sd, ad = make_weights("tiny", rank=8)
-    o_unet = build_oracle("tiny", sd, ad, rank=8)
-    return dict(cfg=cfg, o_cns=o_cns, cn_sds=sds, o_unet=o_unet, unet_sd=(sd, ad),
-                a_cns=[half_arm(o, dev) for o in o_cns], a_unet=half_arm(o_unet, dev),
-                new_cn=lambda k: HipControlNet(cfg, sds[k], device=dev), new_unet=lambda: HipUNet(cfg, sd, ad, device=dev))
-
-
-def _loop_inputs(cfg, B=2):
-    from consistentid_amd import synth
-    side = cfg.sample_size * 8
-    inp = synth.random_inputs(cfg, B, side, side)
-    gen = torch.Generator().manual_seed(21)
-    imgs = [torch.rand(B, 3, side, side, generator=gen).half() for _ in range(2)]
-    init = torch.randn(B, 4, side // 8, side // 8, generator=gen).half()
-    noise = torch.randn(B, 4, side // 8, side // 8, generator=gen).half()
-    mask = (torch.rand(B, 1, side // 8, side // 8, generator=gen) > 0.5).half()
-    return inp, imgs, init, noise, mask
-
-
 # --------------------------------------------------------------------------- forward
 def test_multi_controlnet_forward(dev):
     """HipMultiControlNet.__call__ of two tiny nets: the 6 + 1 summed residuals against the fp32 oracle nets scaled and
@@ -204,25 +168,6 @@ STEPS, MERGE, GUIDANCE = 4, 1, 5.0
 WINDOWS = {"overlap": [(0.0, 0.75), (0.25, 1.0)],       # active sets {0}, {0,1}, {0,1}, {1}
            "gap": [(0.0, 0.5), (0.75, 1.0)]}             # active sets {0}, {0}, {}, {1}
 ACTIVE = {"overlap": [(0,), (0, 1), (0, 1), (1,)], "gap": [(0,), (0,), (), (1,)]}
-
-
-class _OracleMulti:
-    """What the reference's loop does around ``self.controlnet(...)`` with a MultiControlNetModel, for oracle.loop.denoise:
-    counts its calls (= the step index), applies scale_k * keep_k[i] itself (CN :363-370, :397-398) and sums the nets'
-    residuals as diffusers does.  The loop's own window stays (0, 1) and its scale 1."""
-
-    def __init__(self, nets, scales, windows, n_steps):
-        self.nets, self.scales, self.calls = nets, scales, 0
-        self.keep = [[1.0 - float(i / n_steps < s or (i + 1) / n_steps > e) for s, e in windows] for i in range(n_steps)]
-
-    def __call__(self, sample, t, cond, control_images, conditioning_scale=1.0):
-        assert conditioning_scale == 1.0
-        i, self.calls = self.calls, self.calls + 1
-        down = mid = None
-        for k, net in enumerate(self.nets):
-            d, m = net(sample, t, cond, control_images[k], conditioning_scale=self.scales[k] * self.keep[i][k])
-            down, mid = (d, m) if down is None else ([a + b for a, b in zip(down, d)], mid + m)
-        return down, mid
 
 
 @functools.lru_cache(maxsize=None)
