@@ -145,3 +145,93 @@ def test_ln_fold_geglu_matches_its_old_predicate(lib, tmp_path):
         got = gemm_plan_grid.run_child("fold", tmp_path / "shapes.json", setting)
         wrong = [(M, c, bool(g)) for (M, c), g in zip(shapes, got) if bool(g) != _ln_fold_geglu_spec(M, c, on)]
         assert not wrong, f"ops.ln_fold_geglu under {setting or 'the defaults'} differs from its old predicate at (M, C_, now): {wrong}"
+
+
+# ----------------------------------------------------------------------------- the fast 3x3 convolutions on non-square images
+FAST_CONV = ("igemm_halo", "conv_h32", "conv_h32_phase")
+
+
+def test_rect_table_covers_every_fast_conv_key(lib):
+    """tests/test_gpu_conv_rect.py: every 3x3 variant key of the census outside the gather kernel has at least one tall and one
+    wide case, and every case still plans to its key.  A fast key added later fails here until it gets rectangular cases."""
+    import test_gpu_conv_rect as rect
+    fast = {k for k, (r, p) in KEYS.items() if r["taps"] == 9 and gemm_census.families()[p["family"]] != "igemm"}
+    assert fast and {gemm_census.families()[KEYS[k][1]["family"]] for k in fast} == set(FAST_CONV)
+    assert set(rect.RECT) == fast, f"without rectangular cases: {sorted(fast - set(rect.RECT))}; not in the census: {sorted(set(rect.RECT) - fast)}"
+    moved = []
+    for key, (tall, wide) in rect.RECT.items():
+        assert tall and all(h > w for _, h, w in tall), f"{key}: no tall case / a tall case that is not tall: {tall}"
+        assert wide and all(w > h for _, h, w in wide), f"{key}: no wide case / a wide case that is not wide: {wide}"
+        base = KEYS[key][0]
+        for shape in tall + wide:
+            rec, plan, now = rect.rect_plan(key, shape)
+            if now != key:
+                moved.append(f"{key} {shape}: {now}")
+            # only the geometry differs from the census record
+            same = set(rec) - {"Hi", "Wi", "Ho", "Wo", "M", "gn_hw", "rows_per_sample"}
+            assert all(rec[f] == base[f] for f in same) and rec["M"] == shape[0] * rec["Ho"] * rec["Wo"]
+            assert max(shape[1], shape[2]) <= 4 * min(shape[1], shape[2])
+    assert not moved, "rectangular cases that left their variant:\n  " + "\n  ".join(moved)
+    assert len(rect.CASES) == sum(len(t) + len(w) for t, w in rect.RECT.values())
+
+
+def _tile_geometry_faults(fam, bm, B, Hi, Wi, up):
+    """What the kernels need of a planned tile, restated from their index arithmetic (csrc/gemm.hip igemm_halo_kernel,
+    csrc/conv3x3.hip conv_h32_kernel): a list of violated conditions.  A tile is ``bm`` consecutive pixels of the tile image:
+    the output image for the halo kernel and conv_h32, the input image (one output parity) for the phase mode."""
+    Ho, Wo = Hi << up, Wi << up
+    H, W = (Hi, Wi) if fam == "conv_h32_phase" else (Ho, Wo)
+    P, M = H * W, B * Ho * Wo
+    bad = []
+    if M % bm:
+        bad.append("M % bm != 0")
+    if fam == "igemm_halo" and (bm != 256 or up):
+        bad.append("the halo kernel has 256-token tiles and no upsampling")
+    if P % bm and bm % P:
+        bad.append("a tile is neither inside one image nor a whole number of whole images")
+    if fam == "conv_h32_phase" and P % bm:
+        bad.append("a phase tile is not inside one image (tiles per image and parity = P / bm)")
+    seg = min(bm, P)                                  # pixels a tile takes from one image
+    if seg % W:
+        bad.append("a tile is not made of whole rows")
+    rows = seg // W
+    if up and fam == "conv_h32":
+        if bm > P or rows % 2:
+            bad.append("up = 1 on nine taps: a tile is not an even number of output rows of one image")
+    # halo rows as the kernels count them: per image of the tile, its rows (input rows under up = 1) and columns plus a frame
+    ups = up if fam == "conv_h32" else 0
+    nh = (bm // seg) * ((rows >> ups) + 2) * ((W >> ups) + 2)
+    cap = 448 if fam == "igemm_halo" else 400         # HPW * NW * 8 halo rows (gemm.hip); three weight stages next to two halo
+    if nh > cap:                                      # buffers in 160 KB (conv3x3.hip)
+        bad.append(f"{nh} halo rows exceed the buffer's {cap}")
+    return bad
+
+
+def test_fast_conv_tiles_on_a_rectangle_grid(lib):
+    """Whatever route_halo / route_conv3x3 send to a fast kernel on a non-square image is a tiling that kernel can index."""
+    from consistentid_amd import ops
+    sides = (4, 8, 12, 16, 24, 32, 48, 64, 96, 128)
+    seen, faults = {}, []
+    for Hi in sides:
+        for Wi in sides:
+            if Hi == Wi:
+                continue
+            for B in (1, 2, 4, 8):
+                for C_ in (320, 640, 1280):
+                    for up, w4 in ((0, None), (1, True), (1, None)):
+                        Ho, Wo = Hi << up, Wi << up
+                        p = ops.gemm_plan(M=B * Ho * Wo, N=C_, c1=C_, taps=9, Hi=Hi, Wi=Wi, Ho=Ho, Wo=Wo, stride=1, up=up, bias=True,
+                                          ws=True, ws_bytes=64 << 20, gn_hw=Ho * Wo, w_up4=w4)
+                        fam = p["family"]
+                        if fam not in FAST_CONV:
+                            continue
+                        assert fam != "conv_h32_phase" or w4, "the phase mode without folded weights"
+                        orient = "tall" if Hi > Wi else "wide"
+                        seen[fam, up, orient] = seen.get((fam, up, orient), 0) + 1
+                        faults += [f"B={B} {Hi}x{Wi} C={C_} up={up} w_up4={bool(w4)} -> {fam} bm={p['bm']}: {why}"
+                                   for why in _tile_geometry_faults(fam, p["bm"], B, Hi, Wi, up)]
+    print(f"[rect grid] fast plans: {seen}")
+    # the grid reaches every family in both orientations (and conv_h32's nine-tap up = 1 path), or it checks nothing
+    for want in [(f, u, o) for o in ("tall", "wide") for f, u in (("igemm_halo", 0), ("conv_h32", 0), ("conv_h32", 1), ("conv_h32_phase", 1))]:
+        assert seen.get(want, 0) >= 4, f"the grid hardly reaches {want}: {seen}"
+    assert not faults, f"{len(faults)} planned tilings a kernel cannot index:\n  " + "\n  ".join(faults[:30])

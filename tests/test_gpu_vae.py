@@ -36,11 +36,19 @@ def test_softmax_rows(dev):
     del ref
 
 
-@pytest.mark.parametrize("side", [16, 24])
-def test_tiny_vae_decode(dev, side):
+def _hw_id(v):
+    """ids of the (h, w) parameters: a square keeps the id it had as a single side"""
+    if isinstance(v, tuple):
+        return str(v[0]) if v[0] == v[1] else f"{v[0]}x{v[1]}"
+    return None
+
+
+@pytest.mark.parametrize("hw", [(16, 16), (24, 24), (16, 24), (24, 16)], ids=_hw_id)
+def test_tiny_vae_decode(dev, hw):
     from oracle.vae import decode_latents
     cfg, oracle, hip = _pair(dev, "tiny")
-    lat = (torch.randn(2, 4, side, side, generator=torch.Generator().manual_seed(7)) * 0.18215 * 4).half()
+    h, w = hw
+    lat = (torch.randn(2, 4, h, w, generator=torch.Generator().manual_seed(7)) * 0.18215 * 4).half()
     with torch.no_grad():
         ref_raw = oracle.decode(lat.float() / cfg.scaling_factor)
         ref_img = decode_latents(oracle, lat.float())
@@ -48,7 +56,7 @@ def test_tiny_vae_decode(dev, side):
     out_img = hip.decode_latents(lat.to(dev))
     (dec,) = hip.decode(lat.to(dev) / cfg.scaling_factor, return_dict=False)
     torch.cuda.synchronize()
-    assert out_raw.shape == ref_raw.shape == (2, 3, side * 2, side * 2)
+    assert out_raw.shape == ref_raw.shape == (2, 3, h * 2, w * 2)
     arm_m = half_arm(oracle, dev)
     with torch.no_grad():
         arm_raw = arm_m.decode(lat.to(dev) / cfg.scaling_factor)
@@ -116,31 +124,36 @@ def test_pipeline_pixel_outputs(dev):
 TOL32 = dict(tol_l2=5e-5, tol_max=5e-4)      # fp32 kernels against the fp32 oracle: summation order and exp2 / exp ulps only
 
 
-@pytest.mark.parametrize("B,H,cin,cout,taps,up,res", [
-    (2, 16, 64, 96, 9, 0, True), (1, 12, 32, 64, 9, 1, False), (2, 8, 4, 100, 9, 0, False),    # cin % 4 != ... 4 -> vector path, N ragged
-    (1, 10, 6, 40, 9, 0, True),                                                               # scalar gather path (c % 4 != 0)
-    (3, 7, 128, 3, 9, 0, False),                                                              # conv_out: N = 3
-    (1, 33, 160, 72, 1, 0, True),                                                             # linear / 1x1, ragged M
-])
-def test_gemm_f32(dev, B, H, cin, cout, taps, up, res):
+@pytest.mark.parametrize("B,hw,cin,cout,taps,up,res", [
+    (2, (16, 16), 64, 96, 9, 0, True), (1, (12, 12), 32, 64, 9, 1, False), (2, (8, 8), 4, 100, 9, 0, False),    # cin % 4 != ... 4 -> vector path, N ragged
+    (1, (10, 10), 6, 40, 9, 0, True),                                                         # scalar gather path (c % 4 != 0)
+    (3, (7, 7), 128, 3, 9, 0, False),                                                         # conv_out: N = 3
+    (1, (33, 33), 160, 72, 1, 0, True),                                                       # linear / 1x1, ragged M
+    # non-square images: the gather derives (image, y, x) of a token from Hi and Wi, which a square cannot tell apart
+    (2, (12, 20), 64, 96, 9, 0, True), (2, (20, 12), 64, 96, 9, 0, True),
+    (1, (10, 6), 32, 64, 9, 1, False), (1, (6, 10), 32, 64, 9, 1, False),                     # nearest-2x upsample in the gather
+    (1, (7, 11), 6, 40, 9, 0, True),                                                          # scalar gather path
+], ids=_hw_id)
+def test_gemm_f32(dev, B, hw, cin, cout, taps, up, res):
     from consistentid_amd import ops
+    H, W = hw
     g = torch.Generator().manual_seed(cin + cout)
-    x = torch.randn(B, cin, H, H, generator=g)
+    x = torch.randn(B, cin, H, W, generator=g)
     k = 3 if taps == 9 else 1
     w = torch.randn(cout, cin, k, k, generator=g) * (cin * taps) ** -0.5
     b = torch.randn(cout, generator=g)
     xin = torch.nn.functional.interpolate(x, scale_factor=2, mode="nearest") if up else x
     ref = torch.nn.functional.conv2d(xin.double(), w.double(), b.double(), padding=1 if taps == 9 else 0)
-    Ho = H << up
-    r = torch.randn(B, cout, Ho, Ho, generator=g) if res else None
+    Ho, Wo = H << up, W << up
+    r = torch.randn(B, cout, Ho, Wo, generator=g) if res else None
     if res:
         ref = ref + r.double()
     tok = lambda t: t.permute(0, 2, 3, 1).reshape(-1, t.shape[1]).contiguous()
-    out = torch.empty(B * Ho * Ho, cout, dtype=torch.float32, device=dev)
-    ops.gemm_f32(tok(x).to(dev), w.permute(0, 2, 3, 1).reshape(cout, -1).contiguous().to(dev), out, M=B * Ho * Ho, N=cout,
-                 c=cin, bias=b.to(dev), res=tok(r).to(dev) if res else None, taps=taps, Hi=H, Wi=H, up=up)
+    out = torch.empty(B * Ho * Wo, cout, dtype=torch.float32, device=dev)
+    ops.gemm_f32(tok(x).to(dev), w.permute(0, 2, 3, 1).reshape(cout, -1).contiguous().to(dev), out, M=B * Ho * Wo, N=cout,
+                 c=cin, bias=b.to(dev), res=tok(r).to(dev) if res else None, taps=taps, Hi=H, Wi=W, up=up)
     torch.cuda.synchronize()
-    check_close(out, tok(ref), f"gemm_f32 {cin}->{cout} taps={taps} up={up}", **TOL32)
+    check_close(out, tok(ref), f"gemm_f32 {H}x{W} {cin}->{cout} taps={taps} up={up}", **TOL32)
 
 
 def test_groupnorm_and_softmax_f32(dev):
@@ -176,10 +189,11 @@ def _pair32(dev, name):
     return cfg, oracle.eval(), hip
 
 
-def test_tiny_vae_decode_fp32(dev):
+@pytest.mark.parametrize("hw", [(20, 20), (20, 12), (12, 20)], ids=_hw_id)
+def test_tiny_vae_decode_fp32(dev, hw):
     """force_upcast VAE (the SDXL convention): fp32 decode (SDXL :670-676) against the fp32 oracle at fp32 tolerance"""
     cfg, oracle, hip = _pair32(dev, "tiny")
-    lat = torch.randn(2, 4, 20, 20, generator=torch.Generator().manual_seed(7)) * cfg.scaling_factor * 4
+    lat = torch.randn(2, 4, *hw, generator=torch.Generator().manual_seed(7)) * cfg.scaling_factor * 4
     with torch.no_grad():
         ref = oracle.decode(lat / cfg.scaling_factor)
     out = hip.decode_tokens(lat.to(dev))
