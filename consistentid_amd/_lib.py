@@ -111,6 +111,9 @@ SIGNATURES = {
     "cid_conv3x3_small_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 7 + [c_stream]),
     "cid_gelu_f16": (C.c_int, [c_half_p, C.c_int64, c_stream]),
     "cid_quick_gelu_f16": (C.c_int, [c_half_p, C.c_int64, c_stream]),
+    "cid_clip_head_f16": (C.c_int, [c_half_p, C.c_int64, c_half_p, c_half_p, C.c_float, c_half_p, C.c_void_p, C.c_void_p]
+                          + [C.c_int32] * 5 + [c_half_p, C.c_void_p, C.c_void_p, C.c_void_p, c_stream]),
+    "cid_blackout_f16": (C.c_int, [c_half_p, C.c_void_p, C.c_int32, C.c_int64, c_stream]),
     "cid_text_embed_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_int32, C.c_int32, c_half_p, c_half_p, c_half_p, C.c_int32,
                                      C.c_int32, c_stream]),
     "cid_small_attn_f16": (C.c_int, [c_half_p, C.c_int32, c_half_p, C.c_int32, c_half_p, C.c_int32, C.c_int32, c_half_p,

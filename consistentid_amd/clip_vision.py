@@ -8,7 +8,10 @@ i.e. the token states [B, 257, 1280] after all but the last encoder layer.  Weig
 (``vision_model.*``).  The 14x14/14 patch embedding is an unfold (index plumbing) + ``cid_gemm_f16`` (K padded 588 -> 640),
 every encoder layer is LayerNorm -> fused QKV GEMM (V written transposed) -> ``cid_self_attn_keys_f16`` (257 real keys on a
 320-token padded axis) -> out-proj GEMM (+residual) -> LayerNorm -> fc1 GEMM -> ``cid_gelu_f16`` -> fc2 GEMM (+residual).
-The pooled / projected image embedding (post_layernorm, visual_projection) is never read by the reference and is not computed.
+
+The safety checker (safety.py) runs the same tower at the ViT-L/14 geometry with ``hidden_act="quick_gelu"``
+(``cid_quick_gelu_f16``) and reads what follows the last layer: ``image_embeds`` = visual_projection(post_layernorm(CLS)),
+one ``cid_clip_head_f16`` launch on token 0 of the padded state.  The ConsistentID pre-loop never reads that embedding.
 """
 from __future__ import annotations
 
@@ -20,6 +23,9 @@ from . import ops
 from .weights import LOG2E
 
 
+ACTIVATIONS = ("gelu", "quick_gelu")
+
+
 def _h(t, dev):
     return t.to(device=dev, dtype=torch.float16).contiguous()
 
@@ -27,8 +33,10 @@ def _h(t, dev):
 class HipCLIPVision:
     def __init__(self, state_dict: Dict[str, torch.Tensor], num_heads: int, patch_size: int = 14, device="cuda:0",
                  hidden_act: str = "gelu", layer_norm_eps: float = 1e-5):
-        if hidden_act != "gelu":
-            raise NotImplementedError(f"hidden_act {hidden_act!r}: the ViT-H tower of the reference uses exact GELU")
+        if hidden_act not in ACTIVATIONS:
+            raise NotImplementedError(f"hidden_act {hidden_act!r}: the vision towers are built for {ACTIVATIONS} (exact GELU: "
+                                      "the ViT-H tower of the reference; quick GELU: the safety checker's ViT-L)")
+        self._act = ops.quick_gelu_ if hidden_act == "quick_gelu" else ops.gelu_
         self.device = dev = torch.device(device)
         sd = {k[len("vision_model."):]: v for k, v in state_dict.items() if k.startswith("vision_model.")}
         pw = sd["embeddings.patch_embedding.weight"]                     # [C, 3, P, P], no bias
@@ -58,6 +66,11 @@ class HipCLIPVision:
                 W[f"{i}.{ln}.g"], W[f"{i}.{ln}.b"] = _h(sd[p + ln + ".weight"], dev), _h(sd[p + ln + ".bias"], dev)
             for fc in ("fc1", "fc2"):
                 W[f"{i}.{fc}.w"], W[f"{i}.{fc}.b"] = _h(sd[p + f"mlp.{fc}.weight"], dev), _h(sd[p + f"mlp.{fc}.bias"], dev)
+        # what follows the last layer (CLIPVisionTransformer.post_layernorm, CLIPVisionModelWithProjection.visual_projection):
+        # read by image_embeds only; checkpoints of the bare CLIPVisionModel have no projection
+        self.post_ln = (_h(sd["post_layernorm.weight"], dev), _h(sd["post_layernorm.bias"], dev)) if "post_layernorm.weight" in sd else None
+        vp = state_dict.get("visual_projection.weight")
+        self.visual_projection = None if vp is None else _h(vp, dev)                      # [P, C], no bias
         self.W = W
 
     def _empty(self, *shape):
@@ -66,6 +79,12 @@ class HipCLIPVision:
     @torch.no_grad()
     def hidden_states(self, pixel_values: torch.Tensor, index: int = -2) -> torch.Tensor:
         """``image_encoder(pixel_values, output_hidden_states=True).hidden_states[index]`` -> [B, 1 + n_patches, C]"""
+        x, ntok = self._padded_states(pixel_values, index)
+        return x[:, :ntok].contiguous()
+
+    @torch.no_grad()
+    def _padded_states(self,pixel_values: torch.Tensor, index: int):
+        """(hidden_states[index] on the padded token axis [B, Np, C], number of real tokens)"""
         W, C, P, dev = self.W, self.C, self.P, self.device
         n_run = self.n_layers + 1 + index if index < 0 else index      # hidden_states[k] = state after k layers
         assert 0 <= n_run <= self.n_layers
@@ -105,11 +124,30 @@ class HipCLIPVision:
             ops.layernorm(x2, ln2, W[f"{i}.layer_norm2.g"], W[f"{i}.layer_norm2.b"], M=M, C_=C, eps=self.eps)
             f = self._empty(M, W[f"{i}.fc1.w"].shape[0])
             ops.gemm(ln2, W[f"{i}.fc1.w"], f, M=M, N=f.shape[1], c1=C, bias=W[f"{i}.fc1.b"])
-            ops.gelu_(f)
+            self._act(f)
             x = self._empty(M, C)
             ops.gemm(f, W[f"{i}.fc2.w"], x, M=M, N=C, c1=f.shape[1], bias=W[f"{i}.fc2.b"], res=x2, ldr=C)
-        return x.view(B, Np, C)[:, :ntok].contiguous()
+        return x.view(B, Np, C), ntok
+
+    def head_inputs(self, pixel_values: torch.Tensor):
+        """The operands of ``ops.clip_head`` for these images: (last hidden state on its padded axis [B, Np, C] -- row b of
+        the head is its token 0, pitch Np * C --, post_layernorm gain, bias, visual_projection weight)"""
+        if self.post_ln is None or self.visual_projection is None:
+            raise ValueError("this state dict has no post_layernorm / visual_projection.weight: image_embeds needs a "
+                             "CLIPVisionModelWithProjection checkpoint")
+        x, _ = self._padded_states(pixel_values, -1)
+        return x, self.post_ln[0], self.post_ln[1], self.visual_projection
+
+    @torch.no_grad()
+    def image_embeds(self, pixel_values: torch.Tensor) -> torch.Tensor:
+        """``image_encoder(pixel_values).image_embeds`` -> [B, projection_dim] fp16: every layer, then post_layernorm of
+        the CLS token and visual_projection in one launch"""
+        x, g, b, w = self.head_inputs(pixel_values)
+        B, Np, C = x.shape
+        out = self._empty(B, w.shape[0])
+        return ops.clip_head(x, g, b, w, B=B, ldx=Np * C, eps=self.eps, embeds=out)
 
     def __call__(self, pixel_values, output_hidden_states: bool = True):
-        raise NotImplementedError("only hidden_states(pixel_values, -2) is implemented: the reference reads nothing else "
-                                  "from the image encoder (ref :182-183, :200-201)")
+        raise NotImplementedError("hidden_states(pixel_values, index) and image_embeds(pixel_values) are implemented: the "
+                                  "reference reads hidden_states[-2] from the image encoder (ref :182-183, :200-201) and its "
+                                  "safety checker the projected embedding")

@@ -12,9 +12,12 @@ sub-folder per component.  This module reads the components the hot path needs, 
     <root>/text_encoder{,_2}/config.json + model{.fp16,}.safetensors | pytorch_model{.fp16,}.bin
                                                                           -> HipCLIPTextModel (optional; transformers names)
     <root>/tokenizer{,_2}/                                                -> transformers.CLIPTokenizer (optional)
+    <root>/safety_checker/config.json + model{.fp16,}.safetensors | pytorch_model{.fp16,}.bin
+                                                                          -> HipSafetyChecker (optional; SD1.5 family only)
+    <root>/feature_extractor/preprocessor_config.json                     -> settings of face_prep.clip_preprocess (optional)
 
 Local files only (there is no hub access in the engine), ``.fp16`` variants are picked up, sharded checkpoints are
-not.  Safety checker / feature extractor folders are left alone.
+not.
 ``scheduler/scheduler_config.json`` is read for its betas / steps_offset / timestep spacing (the engine carries its own
 DDIM / Euler coefficient tables, scheduler.py; the base model's sampler class itself is not built).
 
@@ -189,6 +192,94 @@ def read_text_components(root: Union[str, os.PathLike], device="cuda:0", given: 
     return out
 
 
+SAFETY_COMPONENTS = ("safety_checker", "feature_extractor")
+
+
+def _edge(v, keys, what: str) -> int:
+    """an image-processor size: an int, [h, w] or a dict ({"shortest_edge": n} / {"height": n, "width": n}) -> n"""
+    if isinstance(v, dict):
+        vals = [v[k] for k in keys if k in v]
+        if not vals:
+            raise NotImplementedError(f"{what}={v!r}: expected one of {keys}")
+    else:
+        vals = list(v) if isinstance(v, (list, tuple)) else [v]
+    if len(set(int(x) for x in vals)) != 1:
+        raise NotImplementedError(f"{what}={v!r}: clip_preprocess crops a square")
+    return int(vals[0])
+
+
+def preprocessor_settings(cfg: Dict) -> Dict:
+    """A CLIPImageProcessor / CLIPFeatureExtractor config (``preprocessor_config.json``) -> {"size": n}, the one setting
+    ``face_prep.clip_preprocess`` takes.  Everything else has to BE what clip_preprocess does -- shortest edge to n with
+    bicubic resampling, centre crop n x n, rescale by 1 / 255, OpenAI CLIP mean / std -- or the key is named in a
+    NotImplementedError.  Absent keys take transformers' CLIPImageProcessor defaults, which are exactly that (an absent
+    crop_size follows size, so that the settings this function returns pass through it unchanged)."""
+    from .face_prep import CLIP_MEAN, CLIP_SIZE, CLIP_STD
+    for key in ("do_resize", "do_center_crop", "do_rescale", "do_normalize"):
+        if not cfg.get(key, True):
+            raise NotImplementedError(f"preprocessor {key}={cfg[key]!r}: clip_preprocess always resizes, centre-crops, "
+                                      "rescales and normalises")
+    if cfg.get("resample", 3) != 3:
+        raise NotImplementedError(f"preprocessor resample={cfg['resample']!r}: clip_preprocess resamples bicubic (3)")
+    if abs(float(cfg.get("rescale_factor", 1 / 255)) - 1 / 255) > 1e-9:
+        raise NotImplementedError(f"preprocessor rescale_factor={cfg['rescale_factor']!r}: clip_preprocess rescales by 1 / 255")
+    for key, want in (("image_mean", CLIP_MEAN), ("image_std", CLIP_STD)):
+        got = cfg.get(key, want)
+        if len(got) != 3 or any(abs(float(a) - b) > 1e-6 for a, b in zip(got, want)):
+            raise NotImplementedError(f"preprocessor {key}={got!r}: clip_preprocess normalises with the CLIP values {want}")
+    size = _edge(cfg.get("size", CLIP_SIZE), ("shortest_edge", "height", "width"), "preprocessor size")
+    crop = size if "crop_size" not in cfg else _edge(cfg["crop_size"], ("height", "width"), "preprocessor crop_size")
+    if size != crop:
+        raise NotImplementedError(f"preprocessor size={cfg.get('size')!r} with crop_size={cfg.get('crop_size')!r}: "
+                                  "clip_preprocess crops to the size it resized the shorter edge to")
+    return {"size": size}
+
+
+def feature_extractor_settings(fe) -> Dict:
+    """a ready ``feature_extractor=``: settings ({"size": n}), a preprocessor config dict, or a transformers image
+    processor (anything with ``to_dict()``) -> ``preprocessor_settings``"""
+    return preprocessor_settings(fe.to_dict() if hasattr(fe, "to_dict") else dict(fe))
+
+
+def read_feature_extractor(folder: Union[str, os.PathLike]) -> Dict:
+    """``feature_extractor/preprocessor_config.json`` -> ``preprocessor_settings`` (settings only: no processor is built)"""
+    path = os.path.join(os.fspath(folder), "preprocessor_config.json")
+    if not os.path.isfile(path):
+        raise FileNotFoundError(f"{path}: not a feature extractor folder")
+    with open(path) as f:
+        return preprocessor_settings(json.load(f))
+
+
+def load_safety_checker(folder: Union[str, os.PathLike], device="cuda:0"):
+    """``safety_checker/`` (diffusers StableDiffusionSafetyChecker, saved by transformers) -> HipSafetyChecker"""
+    from .safety import HipSafetyChecker
+    cfg, sd = read_component(folder, TEXT_WEIGHT_NAMES)
+    return HipSafetyChecker(cfg, sd, device=device)
+
+
+def read_safety_components(root: Union[str, os.PathLike], device="cuda:0", given: Optional[Dict] = None) -> Dict:
+    """The safety checker and its pre-processing settings with diffusers' meaning of the keywords: a component passed in
+    ``given`` is kept (None: not loaded, which is how the reference's SDXL script switches the checker off); otherwise it
+    is read when its folder exists.  Without a checker the feature extractor is not read either.  A ready
+    ``feature_extractor`` may be settings ({"size": n}), a preprocessor config dict, or a transformers image processor."""
+    given = given or {}
+    out = {}
+    folder = os.path.join(os.fspath(root), "safety_checker")
+    if "safety_checker" in given:
+        out["safety_checker"] = given["safety_checker"]
+    elif os.path.isdir(folder):
+        out["safety_checker"] = load_safety_checker(folder, device=device)
+    if out.get("safety_checker") is None:
+        return {}
+    fe = given.get("feature_extractor")
+    folder = os.path.join(os.fspath(root), "feature_extractor")
+    if fe is not None:
+        out["feature_extractor"] = feature_extractor_settings(fe)
+    elif "feature_extractor" not in given and os.path.isdir(folder):
+        out["feature_extractor"] = read_feature_extractor(folder)
+    return out
+
+
 def _has_encoder(sd) -> bool:
     return any(k.startswith("encoder.") for k in sd)
 
@@ -246,15 +337,18 @@ def from_pretrained(pipeline_cls, root: Union[str, os.PathLike], torch_dtype=tor
     with ``controlnet=`` demo/controlnet_demo.py:44-47): UNet (required), VAE decoder, text encoders and tokenizers (when
     their folders exist) of a local diffusers model directory; ``controlnet`` = a HipControlNet or the folder of a
     ControlNetModel, or a list of those for a HipMultiControlNet.  ``text_encoder=`` / ``tokenizer=`` / ``text_encoder_2=`` / ``tokenizer_2=`` take a ready object, or
-    None to skip that component."""
+    None to skip that component.  ``safety_checker=`` / ``feature_extractor=`` likewise, for the SD1.5-family pipelines: the
+    checker is loaded when ``safety_checker/`` exists and the caller did not pass ``safety_checker=None``; the SDXL pipeline
+    never has one (the reference's has none)."""
     if torch_dtype not in (torch.float16, None):
         raise NotImplementedError("the engine computes in fp16 (the reference's own inference dtype, infer.py:19)")
-    # diffusers loader keywords the reference scripts pass (infer.py:17-21 variant="fp16"; infer_SDXL.py safety_checker=None;
-    # demo/controlnet_demo.py use_safetensors=True): they select files / components the engine does not read -- the
-    # .fp16 weight files are preferred anyway, there is no safety checker and no hub access
-    for name in ("variant", "use_safetensors", "safety_checker", "feature_extractor", "requires_safety_checker",
+    # diffusers loader keywords the reference scripts pass (infer.py:17-21 variant="fp16"; demo/controlnet_demo.py
+    # use_safetensors=True): they select files the engine does not read -- the .fp16 weight files are preferred anyway and
+    # there is no hub access.  safety_checker= / feature_extractor= (infer_SDXL.py safety_checker=None) are components
+    for name in ("variant", "use_safetensors", "requires_safety_checker",
                  "local_files_only", "cache_dir", "revision", "low_cpu_mem_usage", "add_watermarker"):
         kw.pop(name, None)
+    safety_given = {k: kw.pop(k) for k in SAFETY_COMPONENTS if k in kw}
     unknown = [k for k in kw if k not in ("scheduler", "num_tokens", "lora_rank") + TEXT_COMPONENTS]
     if unknown:
         raise TypeError(f"from_pretrained: unexpected keyword(s) {unknown}")
@@ -277,6 +371,8 @@ def from_pretrained(pipeline_cls, root: Union[str, os.PathLike], torch_dtype=tor
     from .pipeline import ConsistentIDStableDiffusionXLPipeline
     if issubclass(pipeline_cls, ConsistentIDStableDiffusionXLPipeline):
         args["force_zeros_for_empty_prompt"] = read_force_zeros(root)
+    else:
+        args.update(read_safety_components(root, device=device, given=safety_given))
     if vae_encoder is not None:
         args["vae_encoder"] = vae_encoder
     if "scheduler" not in args:

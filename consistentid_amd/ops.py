@@ -491,6 +491,51 @@ def quick_gelu_(x: torch.Tensor):
     return x
 
 
+def clip_head(x: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, w_proj: torch.Tensor, *, B: int, ldx: int,
+              eps: float = 1e-5, concepts: Optional[torch.Tensor] = None, thresholds: Optional[torch.Tensor] = None,
+              n_special: int = 0, embeds: Optional[torch.Tensor] = None):
+    """The tail of the CLIP vision tower and of the safety checker in one launch (cid_clip_head_f16): post_layernorm of the
+    CLS row of each of ``B`` images (row b at ``x`` + b * ``ldx``), ``w_proj`` [P, C], then -- with ``concepts`` fp32 [K, P]
+    (L2-normalised rows, the ``n_special`` special-care rows first) and ``thresholds`` fp32 [K] -- the cosines and the
+    decision.  Returns (cos [B, K] fp32, scores [B, K] fp32, flags [B] int32), or ``embeds`` when there are no concepts."""
+    lib = _lib.load()
+    for name, t in (("x", x), ("gamma", gamma), ("beta", beta), ("w_proj", w_proj)) + ((("embeds", embeds),) if embeds is not None else ()):
+        _req(t, f"clip_head.{name}")
+    P, C_ = w_proj.shape
+    if x.numel() < (B - 1) * ldx + C_ or gamma.numel() != C_ or beta.numel() != C_ or not w_proj.is_contiguous():
+        raise _lib.CidError(f"clip_head: x of {x.numel()} elements / gamma / beta do not hold B = {B} rows of C = {C_} at pitch {ldx}")
+    if embeds is not None and (embeds.numel() != B * P or not embeds.is_contiguous()):
+        raise _lib.CidError(f"clip_head: embeds must be contiguous [{B}, {P}]")
+    K = 0
+    cos = scores = flags = None
+    if concepts is not None:
+        _req(concepts, "clip_head.concepts", torch.float32)
+        _req(thresholds, "clip_head.thresholds", torch.float32)
+        K = concepts.shape[0]
+        if tuple(concepts.shape) != (K, P) or thresholds.numel() != K or not concepts.is_contiguous():
+            raise _lib.CidError(f"clip_head: concepts {tuple(concepts.shape)} / thresholds {tuple(thresholds.shape)} against P = {P}")
+        cos = torch.empty(B, K, dtype=torch.float32, device=x.device)
+        scores = torch.empty(B, K, dtype=torch.float32, device=x.device)
+        flags = torch.empty(B, dtype=torch.int32, device=x.device)
+    check(lib.cid_clip_head_f16(_p(x), ldx, _p(gamma), _p(beta), eps, _p(w_proj), _p(concepts), _p(thresholds), B, C_, P, K,
+                                n_special, _p(embeds), _p(cos), _p(scores), _p(flags), _stream()), "cid_clip_head_f16")
+    return (cos, scores, flags) if K else embeds
+
+
+def blackout_(images: torch.Tensor, flags: torch.Tensor):
+    """in place: image b of fp16 ``images`` [B, ...] becomes zero where ``flags`` [B] (int32, on the GPU) is non-zero; nothing
+    is read back"""
+    lib = _lib.load()
+    if not images.is_cuda or images.dtype != torch.float16 or not images.is_contiguous():
+        raise _lib.CidError(f"blackout.images: a contiguous fp16 GPU tensor is expected (got {images.dtype} on {images.device})")
+    _req(flags, "blackout.flags", torch.int32)
+    B = images.shape[0]
+    if flags.numel() != B:
+        raise _lib.CidError(f"blackout: {flags.numel()} flags for {B} images")
+    check(lib.cid_blackout_f16(_p(images), _p(flags), B, images.numel() // B, _stream()), "cid_blackout_f16")
+    return images
+
+
 def text_embed(ids: torch.Tensor, tok: torch.Tensor, pos: torch.Tensor, out: torch.Tensor, *, B: int, T: int, Tp: int):
     """CLIPTextEmbeddings: ``out`` [B, Tp, C] = tok[ids] + pos[:T], zero rows for t >= T.  ``ids`` int32 [B, T] on the GPU,
     already range-checked by the caller (clip_text.check_ids)"""

@@ -11,8 +11,9 @@ encode of the inpaint pipelines (``image=`` / ``mask_image=`` with ``vae_encoder
 ``image=`` when given, else ``input_id_images[0]``, where the reference reads it; PIL images go through image_prep.py).
 Prompt strings are encoded by ``encode_prompt`` / ``_encode_prompt`` / ``encode_prompt_with_trigger_word`` on the HIP
 text towers (``text_encoder=`` / ``text_encoder_2=``, clip_text.py; prompt_encode.py), the ID tokens by
-``prepare_prompt_embeds``.  The three SD1.5-family pipelines (SD1.5, inpaint, ControlNet-inpaint) also run the reference's
-whole pre-loop (``prepare_id_prompt_embeds``: the caller's FaceID app, HipBiSeNet face parsing, the facial crops, the
+``prepare_prompt_embeds``.  With ``safety_checker=`` (safety.py; ``from_pretrained`` reads ``safety_checker/``) the three
+SD1.5-family pipelines (SD1.5, inpaint, ControlNet-inpaint) run the reference's ``run_safety_checker`` after the VAE
+decode.  They also run the reference's whole pre-loop (``prepare_id_prompt_embeds``: the caller's FaceID app, HipBiSeNet face parsing, the facial crops, the
 CLIP vision tower) for ``prompt`` + ``input_id_images``; every ``__call__`` also takes what the pre-loop produces:
 ``prompt_embeds`` = cat([null, augmented, text_only]) of shape [3B, 77+4, Dc] exactly as the
 reference assembles it before ``.chunk(3)`` (ref :494-507, :527-531), and ``latents``.
@@ -77,17 +78,27 @@ class _BasePipeline:
 
     def __init__(self, unet: HipUNet, scheduler: Optional[DDIMScheduler] = None, use_graph: bool = True,
                  num_tokens: int = 4, lora_rank: int = 128, vae=None, vae_encoder=None, text_encoder=None, tokenizer=None,
-                 text_encoder_2=None, tokenizer_2=None):
+                 text_encoder_2=None, tokenizer_2=None, safety_checker=None, feature_extractor=None):
         """``vae``: a ``consistentid_amd.vae.HipVAEDecoder`` -- enables every ``output_type`` besides "latent".
         ``vae_encoder``: a ``consistentid_amd.vae.HipVAEEncoder`` -- lets the inpaint pipelines take ``image=`` and
         ``mask_image=`` (the reference's pre-loop VAE encode) instead of pre-computed latents.
         ``text_encoder`` / ``text_encoder_2``: ``consistentid_amd.clip_text.HipCLIPTextModel`` (CLIP-L; SDXL's bigG with
-        projection), ``tokenizer`` / ``tokenizer_2``: ``transformers.CLIPTokenizer`` -- let ``encode_prompt`` take strings."""
+        projection), ``tokenizer`` / ``tokenizer_2``: ``transformers.CLIPTokenizer`` -- let ``encode_prompt`` take strings.
+        ``safety_checker``: a ``consistentid_amd.safety.HipSafetyChecker`` (or any callable with diffusers' ``(images=,
+        clip_input=) -> (images, [bool])``) -- the SD1.5-family pipelines then fill ``nsfw_content_detected`` and black out
+        flagged images; ``feature_extractor``: its pre-processing settings ``{"size": n}``, a preprocessor config dict or a
+        transformers image processor (loader.feature_extractor_settings refuses what clip_preprocess does not do; default:
+        the checker's own ``image_size``, 224 for ViT-L/14)."""
         self.unet = unet
         self.text_encoder, self.tokenizer = text_encoder, tokenizer
         self.text_encoder_2, self.tokenizer_2 = text_encoder_2, tokenizer_2
         self.vae = vae
         self.vae_encoder = vae_encoder
+        self.safety_checker = safety_checker
+        self.feature_extractor = None
+        if feature_extractor is not None:
+            from .loader import feature_extractor_settings
+            self.feature_extractor = feature_extractor_settings(feature_extractor)
         self.num_tokens = num_tokens
         self.lora_rank = lora_rank
         self.device = unet.device
@@ -223,27 +234,57 @@ class _BasePipeline:
             raise ValueError("output_type other than 'latent' needs a VAE decoder: build the pipeline with "
                              "vae=HipVAEDecoder(...)")
 
+    @staticmethod
+    def _numpy_to_pil(arr: np.ndarray):
+        """NHWC float in [0, 1] -> PIL images (diffusers numpy_to_pil)"""
+        from PIL import Image
+        return [Image.fromarray(a) for a in (arr * 255).round().astype("uint8")]
+
+    def run_safety_checker(self, image, device=None, dtype=None):
+        """D: StableDiffusionPipeline.run_safety_checker (ref :589-602, inpaint :371, CN :468) -> (image, has_nsfw_concept).
+        ``image``: NHWC numpy in [0, 1] (the SD1.5 pipeline checks after decode_latents) or the decoded [B, 3, H, W] device
+        tensor in [0, 1] (the inpaint pipelines check the tensor).  Either becomes PIL images as ``_postprocess`` builds
+        them, those go through ``face_prep.clip_preprocess`` (the feature extractor) and the checker; flagged images come
+        back black -- a tensor is zeroed in place on the device.  Without a checker: (image, None), as in diffusers.
+        ``device`` / ``dtype`` are the reference's arguments; the engine has one device and computes in fp16."""
+        if self.safety_checker is None:
+            return image, None
+        from .face_prep import clip_preprocess
+        arr = image.float().permute(0, 2, 3, 1).cpu().numpy() if torch.is_tensor(image) else image
+        size = (self.feature_extractor or {}).get("size") or getattr(self.safety_checker, "image_size", 224)
+        clip_input = torch.from_numpy(np.stack([clip_preprocess(im, size) for im in self._numpy_to_pil(arr)]))
+        return self.safety_checker(images=image, clip_input=clip_input)
+
     def _postprocess(self, latents: torch.Tensor, output_type: str, legacy_numpy: bool = False):
-        """SD1.5 (ref :581-598): decode_latents -> NHWC float32 numpy in [0, 1] (-> PIL for "pil"); any other
-        non-latent output_type also yields numpy there (``legacy_numpy``).  The image_processor-based pipelines
-        (SDXL :676-684, inpaint) additionally know "pt" (the [B, 3, H, W] tensor in [0, 1])."""
+        """``_postprocess_checked`` without the safety checker: the images only (SDXL :676-684 has no checker)"""
+        return self._postprocess_checked(latents, output_type, legacy_numpy, check=False)[0]
+
+    def _postprocess_checked(self, latents: torch.Tensor, output_type: str, legacy_numpy: bool = False, check: bool = True):
+        """-> (images, has_nsfw_concept).  SD1.5 (ref :581-602): decode_latents -> NHWC float32 numpy in [0, 1] ->
+        run_safety_checker on the numpy array (-> PIL for "pil"); any other non-latent output_type also yields numpy there
+        (``legacy_numpy``).  The image_processor-based pipelines (SDXL :676-684, inpaint :367-381) check the decoded tensor
+        and additionally know "pt" (the [B, 3, H, W] tensor in [0, 1]).  "latent" is never checked."""
         if output_type == "latent":
-            return latents
+            return latents, None
         img = self.vae.decode_latents(latents)
+        nsfw = None
+        if check and not legacy_numpy:
+            img, nsfw = self.run_safety_checker(img)
         if output_type == "pt" and not legacy_numpy:
-            return img
+            return img, nsfw
         arr = img.float().permute(0, 2, 3, 1).cpu().numpy()
+        if check and legacy_numpy:
+            arr, nsfw = self.run_safety_checker(arr)
         if output_type == "pil":
-            from PIL import Image
-            return [Image.fromarray(a) for a in (arr * 255).round().astype("uint8")]
-        return arr
+            return self._numpy_to_pil(arr), nsfw
+        return arr, nsfw
 
     @staticmethod
-    def _output(out, return_dict: bool):
-        """the SD1.5-family tail (ref :596-598); no safety checker: has_nsfw_concept = None"""
+    def _output(out, return_dict: bool, has_nsfw_concept: Optional[List[bool]] = None):
+        """the SD1.5-family tail (ref :608-613); ``has_nsfw_concept`` is None without a safety checker and for latents"""
         if not return_dict:
-            return (out, None)
-        return StableDiffusionPipelineOutput(images=out, nsfw_content_detected=None)
+            return (out, has_nsfw_concept)
+        return StableDiffusionPipelineOutput(images=out, nsfw_content_detected=has_nsfw_concept)
 
     def _split(self, prompt_embeds):
         assert prompt_embeds.shape[0] % 3 == 0
@@ -460,7 +501,8 @@ class ConsistentIDStableDiffusionPipeline(_IDPreLoop, _SD15PromptEncoding, _Base
         out = self._engine.run(latents, null_e, aug_e, text_e, num_inference_steps=num_inference_steps,
                                guidance_scale=guidance_scale, start_merge_step=start_merge_step,
                                callback=callback, callback_steps=callback_steps, eta=eta, variance_noise=variance_noise)
-        return self._output(self._postprocess(out, output_type, legacy_numpy=True), return_dict)
+        out, has_nsfw_concept = self._postprocess_checked(out, output_type, legacy_numpy=True)
+        return self._output(out, return_dict, has_nsfw_concept)
 
 
 class ConsistentIDStableDiffusionXLPipeline(_BasePipeline):
@@ -757,7 +799,8 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                                inpaint_mask=b_mask, inpaint_init=b_init, inpaint_noise=b_noise,
                                callback=callback, callback_steps=callback_steps, first_step=first, scale_initial=scaled,
                                unet_extra=extra, eta=eta, variance_noise=variance_noise, **cn_kw)
-        return self._output(self._postprocess(out, output_type), return_dict)
+        out, has_nsfw_concept = self._postprocess_checked(out, output_type)
+        return self._output(out, return_dict, has_nsfw_concept)
 
 
 class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpaintConsistentIDPipeline):

@@ -27,7 +27,7 @@ extern "C" {
 typedef void* cid_stream_t;      /* hipStream_t */
 typedef uint16_t cid_half;       /* IEEE binary16 bit pattern */
 
-int cid_version(void);          /* 105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
+int cid_version(void);          /* 107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
                                  * pointer (102: act, 101: pad_mode; set them or zero the struct) */
 const char* cid_last_error(void);
 
@@ -361,6 +361,33 @@ int cid_conv_out_f16(const cid_half* x, cid_half* out, const cid_half* w, const 
 int cid_quick_gelu_f16(cid_half* x, int64_t n, cid_stream_t stream);
 int cid_text_embed_f16(const int32_t* ids, int32_t B, int32_t T, int32_t Tp, const cid_half* tok, const cid_half* pos,
                        cid_half* out, int32_t V, int32_t C, cid_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Safety checker tail (csrc/safety.hip).  The three SD1.5-family pipelines call run_safety_checker between the VAE decode and
+ * the PIL conversion (pipline_StableDiffusion_ConsistentID.py:584-602, pipelines/StableDIffusionInpaint_ConsistentID.py:371-381,
+ * pipelines/StableDIffusionControlNetInpaint_ConsistentID.py:468-478) -> D: StableDiffusionSafetyChecker.forward.  The CLIP
+ * ViT-L/14 tower runs on the vision engine's launches (quick GELU); these two are what follows its last encoder layer.
+ * cid_clip_head_f16: D: CLIPVisionTransformer.post_layernorm on the CLS token, CLIPVisionModelWithProjection.visual_projection,
+ *   D: cosine_distance against the concept tables and the threshold loop of the checker, for B images in ONE launch (one
+ *   256-thread workgroup per image).  All arithmetic fp32:
+ *     ln = LayerNorm(x[b]) (gain / bias ln_gamma / ln_beta fp16 [C], ln_eps);  e = w_proj ln  (w_proj fp16 [P][C], no bias);
+ *     embeds[b] = fp16(e)  (image_embeds, not normalised; the one rounding);  cos[b][k] = (e / max(|e|, 1e-12)) . concepts[k];
+ *     adj = 0;  for k in index order:  scores[b][k] = (cos[b][k] - thresholds[k]) + adj;  hit = rintf(scores * 1000.f) >= 1.f
+ *     (Python's round(np.float32, 3) > 0, half to even);  a hit at k < n_special sets adj = 0.01f for every LATER k and does
+ *     not flag;  flags[b] = any hit at k >= n_special.
+ *   x: row b at x + b * ldx halfs -- token 0 of a padded [B][Np][C] state with ldx = Np * C.  concepts: fp32 [K][P], rows
+ *   L2-normalised by the caller, the n_special special-care rows FIRST; thresholds fp32 [K] in the same order.  cos / scores fp32
+ *   [B][K], flags int32 [B]; embeds fp16 [B][P] or NULL.  K == 0 (concepts, thresholds, cos, scores, flags NULL) writes only
+ *   embeds.  Refused (-22): a NULL required pointer; C, P or ldx not a multiple of 8; C or P > 4096; ldx < C; K outside [0, 64];
+ *   n_special outside [0, K]; B <= 0; x / ln_gamma / ln_beta / w_proj not 16-byte aligned.
+ * cid_blackout_f16: `images[idx] = torch.zeros_like(images[idx])` of the checker for every flagged image, reading the flags on
+ *   the device: images fp16 [B][per_image], image b zeroed where flags[b] != 0, the others not written.  Any per_image >= 1
+ *   (16-byte stores when per_image % 8 == 0 and the base is 16-byte aligned, 2-byte stores otherwise); B <= 65535. */
+int cid_clip_head_f16(const cid_half* x, int64_t ldx, const cid_half* ln_gamma, const cid_half* ln_beta, float ln_eps,
+                      const cid_half* w_proj, const float* concepts, const float* thresholds, int32_t B, int32_t C, int32_t P,
+                      int32_t K, int32_t n_special, cid_half* embeds, float* cos, float* scores, int32_t* flags,
+                      cid_stream_t stream);
+int cid_blackout_f16(cid_half* images, const int32_t* flags, int32_t B, int64_t per_image, cid_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * VAE encoder ends (csrc/vae_enc.hip).  The inpaint pipelines encode the init image and the masked image before the loop
