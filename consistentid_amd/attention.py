@@ -170,7 +170,7 @@ class Consistent_IPAttProcessor(nn.Module):
         heads = attn.heads
         w = self._weights(attn)
         ehs = encoder_hidden_states.contiguous()
-        R, L, Dc = ehs.shape
+        R, L, _ = ehs.shape
         assert R == B
         n_ip = self.num_tokens
         n_txt = L - n_ip                                         # attention.py:241
@@ -181,19 +181,9 @@ class Consistent_IPAttProcessor(nn.Module):
         # (the keyed tensor is kept in _kv[3]: a live tensor's address cannot be recycled for another prompt's embeddings;
         # a caller that passes a fresh temporary every step simply recomputes K/V every step, like the reference does)
         if kvk != self._kv_key or self._kv[3] is not ehs:
-            dev = x.device
-            kv_txt = torch.empty(R * L, 2 * c, dtype=torch.float16, device=dev)
-            kv_ip = torch.empty(R * L, 2 * c, dtype=torch.float16, device=dev)
-            ops.gemm(ehs, w["kv_txt"], kv_txt, M=R * L, N=2 * c, c1=Dc)       # :249-250
-            ops.gemm(ehs, w["kv_ip"], kv_ip, M=R * L, N=2 * c, c1=Dc)         # :266-267
-            ke, ve = ops.kv_pack2_elems(c, heads) if v3 else ops.kv_pack_elems(c, heads)
-            kp = torch.empty(R * ke, dtype=torch.float16, device=dev)
-            vp = torch.empty(R * ve, dtype=torch.float16, device=dev)
-            if v3:
-                ops.kv_pack2(kv_txt, kv_ip, kp, vp, R=R, L=L, C_=c, heads=heads, n_txt=n_txt, n_ip=n_ip, order="reg")
-            else:
-                ops.kv_pack(kv_txt, kv_ip, kp, vp, R=R, C_=c, heads=heads, n_txt=n_txt, n_ip=n_ip)
-            self._kv = (kp, vp, torch.arange(R, dtype=torch.int32, device=dev), ehs)   # (ehs: see _kv_key below)
+            kp, vp, _ = ops.context_kv(ehs, w["kv_txt"], w["kv_ip"], R=R, L=L, C_=c, heads=heads, n_txt=n_txt, n_ip=n_ip,
+                                       v3=v3)                                  # :249-250, :266-267
+            self._kv = (kp, vp, torch.arange(R, dtype=torch.int32, device=x.device), ehs)   # (ehs: see _kv_key below)
             self._kv_key = kvk
         kp, vp, kvrow = self._kv[:3]
         out = torch.empty_like(x)

@@ -8,9 +8,8 @@
 ``HipCLIPTextModel`` stands in for transformers' ``CLIPTextModel`` (SD1.5's CLIP-L, SDXL's first tower) and
 ``CLIPTextModelWithProjection`` (SDXL's OpenCLIP bigG, ``text_projection.weight`` present).  Weights: the transformers
 state_dict (``text_model.*`` + ``text_projection.weight``; keys without the ``text_model.`` prefix are read as well).
-Every layer is LayerNorm -> fused QKV GEMM (V written transposed, softmax scale x log2 e folded into Wq) ->
-``cid_self_attn_causal_f16`` (T real tokens on a token axis padded to a multiple of 64) -> out-proj GEMM (+residual) ->
-LayerNorm -> fc1 GEMM -> ``cid_quick_gelu_f16`` / ``cid_gelu_f16`` -> fc2 GEMM (+residual); the embedding is
+Every layer is the encoder layer of clip_layers.py (weights packed and launched there) around
+``cid_self_attn_causal_f16`` (T real tokens on a token axis padded to a multiple of 64); the embedding is
 ``cid_text_embed_f16``, the projection ``cid_linear_small_f16``.  Pad rows of the token axis start at zero and stay
 row-local.  The host-side rules (config mapping, the id check, the EOS pooling index) are plain functions below, so that
 they can be tested without a GPU.
@@ -22,9 +21,8 @@ from typing import Dict, Optional
 
 import torch
 
-from .weights import LOG2E
-
-ACTIVATIONS = ("quick_gelu", "gelu")
+from .clip_layers import ACTIVATIONS, pack_layers, run_layer
+from .weights import _h
 
 
 @dataclass(frozen=True)
@@ -51,7 +49,7 @@ def text_config(config) -> TextTowerConfig:
     get = (lambda k, d=None: config.get(k, d)) if isinstance(config, dict) else (lambda k, d=None: getattr(config, k, d))
     act = get("hidden_act", "quick_gelu")
     if act not in ACTIVATIONS:
-        raise NotImplementedError(f"hidden_act {act!r}: the text towers are built with {ACTIVATIONS}")
+        raise NotImplementedError(f"hidden_act {act!r}: the text towers are built with {tuple(ACTIVATIONS)}")
     cfg = TextTowerConfig(
         hidden_size=int(get("hidden_size", 512)), intermediate_size=int(get("intermediate_size", 2048)),
         num_hidden_layers=int(get("num_hidden_layers", 12)), num_attention_heads=int(get("num_attention_heads", 8)),
@@ -108,10 +106,6 @@ class TextEncoderOutput:
         return self._tuple
 
 
-def _h(t, dev):
-    return t.to(device=dev, dtype=torch.float16).contiguous()
-
-
 class HipCLIPTextModel:
     def __init__(self, state_dict: Dict[str, torch.Tensor], config, device="cuda:0"):
         self.config = config
@@ -132,21 +126,10 @@ class HipCLIPTextModel:
         if n_layers != cfg.num_hidden_layers:
             raise ValueError(f"{n_layers} encoder layers in the weights, {cfg.num_hidden_layers} in the config")
         self.n_layers = n_layers
-        qs = (self.d ** -0.5) * LOG2E                                    # CLIPAttention.scale and log2 e
+        self._act = ACTIVATIONS[cfg.hidden_act]
         W: Dict[str, torch.Tensor] = {"final.g": _h(sd["final_layer_norm.weight"], dev),
                                       "final.b": _h(sd["final_layer_norm.bias"], dev)}
-        for i in range(n_layers):
-            p = f"encoder.layers.{i}."
-            a = p + "self_attn."
-            W[f"{i}.qkv.w"] = _h(torch.cat([sd[a + "q_proj.weight"].float() * qs, sd[a + "k_proj.weight"].float(),
-                                            sd[a + "v_proj.weight"].float()], 0), dev)
-            W[f"{i}.qkv.b"] = _h(torch.cat([sd[a + "q_proj.bias"].float() * qs, sd[a + "k_proj.bias"].float(),
-                                            sd[a + "v_proj.bias"].float()], 0), dev)
-            W[f"{i}.o.w"], W[f"{i}.o.b"] = _h(sd[a + "out_proj.weight"], dev), _h(sd[a + "out_proj.bias"], dev)
-            for ln in ("layer_norm1", "layer_norm2"):
-                W[f"{i}.{ln}.g"], W[f"{i}.{ln}.b"] = _h(sd[p + ln + ".weight"], dev), _h(sd[p + ln + ".bias"], dev)
-            for fc in ("fc1", "fc2"):
-                W[f"{i}.{fc}.w"], W[f"{i}.{fc}.b"] = _h(sd[p + f"mlp.{fc}.weight"], dev), _h(sd[p + f"mlp.{fc}.bias"], dev)
+        pack_layers(W, sd, n_layers, self.d, dev)
         if self.with_projection:
             W["proj.w"] = _h(sd["text_projection.weight"], dev)                # [projection_dim, C], no bias
         self.W = W
@@ -177,24 +160,8 @@ class HipCLIPTextModel:
         ops.text_embed(ids.to(device=dev, dtype=torch.int32).contiguous(), self.tok, self.pos, x, B=B, T=T, Tp=Tp)
         states = [x]
         for i in range(self.n_layers):
-            ln = self._empty(M, C)
-            ops.layernorm(x, ln, W[f"{i}.layer_norm1.g"], W[f"{i}.layer_norm1.b"], M=M, C_=C, eps=self.eps)
-            qk = self._empty(M, 2 * C)
-            vt = self._empty(B * self.heads * ops.dvp_of(self.d) * Tp)
-            ops.gemm(ln, W[f"{i}.qkv.w"], qk, M=M, N=3 * C, c1=C, bias=W[f"{i}.qkv.b"], mode=2, vt=vt, n_vt0=2 * C,
-                     heads=self.heads, dhead=self.d, ntok=Tp)
-            ao = self._empty(M, C)
-            ops.self_attn_causal(qk, qk[:, C:], vt, ao, B=B, N=Tp, heads=self.heads, d=self.d, ldq=2 * C, ldk=2 * C, ldo=C,
-                                 n_keys=T)
-            x2 = self._empty(M, C)
-            ops.gemm(ao, W[f"{i}.o.w"], x2, M=M, N=C, c1=C, bias=W[f"{i}.o.b"], res=x, ldr=C)
-            ln2 = self._empty(M, C)
-            ops.layernorm(x2, ln2, W[f"{i}.layer_norm2.g"], W[f"{i}.layer_norm2.b"], M=M, C_=C, eps=self.eps)
-            f = self._empty(M, W[f"{i}.fc1.w"].shape[0])
-            ops.gemm(ln2, W[f"{i}.fc1.w"], f, M=M, N=f.shape[1], c1=C, bias=W[f"{i}.fc1.b"])
-            (ops.quick_gelu_ if cfg.hidden_act == "quick_gelu" else ops.gelu_)(f)
-            x = self._empty(M, C)
-            ops.gemm(f, W[f"{i}.fc2.w"], x, M=M, N=C, c1=f.shape[1], bias=W[f"{i}.fc2.b"], res=x2, ldr=C)
+            x = run_layer(W, i, x, B=B, Np=Tp, heads=self.heads, d=self.d, eps=self.eps, attn=ops.self_attn_causal,
+                          n_keys=T, act=self._act)
             states.append(x)
         last = self._empty(M, C)
         ops.layernorm(x, last, W["final.g"], W["final.b"], M=M, C_=C, eps=self.eps)

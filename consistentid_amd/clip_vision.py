@@ -6,8 +6,8 @@
 
 i.e. the token states [B, 257, 1280] after all but the last encoder layer.  Weights: the ``transformers`` state_dict
 (``vision_model.*``).  The 14x14/14 patch embedding is an unfold (index plumbing) + ``cid_gemm_f16`` (K padded 588 -> 640),
-every encoder layer is LayerNorm -> fused QKV GEMM (V written transposed) -> ``cid_self_attn_keys_f16`` (257 real keys on a
-320-token padded axis) -> out-proj GEMM (+residual) -> LayerNorm -> fc1 GEMM -> ``cid_gelu_f16`` -> fc2 GEMM (+residual).
+every encoder layer is the encoder layer of clip_layers.py (weights packed and launched there) around
+``cid_self_attn_keys_f16`` (257 real keys on a 320-token padded axis), with ``cid_gelu_f16``.
 
 The safety checker (safety.py) runs the same tower at the ViT-L/14 geometry with ``hidden_act="quick_gelu"``
 (``cid_quick_gelu_f16``) and reads what follows the last layer: ``image_embeds`` = visual_projection(post_layernorm(CLS)),
@@ -20,23 +20,17 @@ from typing import Dict
 import torch
 
 from . import ops
-from .weights import LOG2E
-
-
-ACTIVATIONS = ("gelu", "quick_gelu")
-
-
-def _h(t, dev):
-    return t.to(device=dev, dtype=torch.float16).contiguous()
+from .clip_layers import ACTIVATIONS, pack_layers, run_layer
+from .weights import _h
 
 
 class HipCLIPVision:
     def __init__(self, state_dict: Dict[str, torch.Tensor], num_heads: int, patch_size: int = 14, device="cuda:0",
                  hidden_act: str = "gelu", layer_norm_eps: float = 1e-5):
         if hidden_act not in ACTIVATIONS:
-            raise NotImplementedError(f"hidden_act {hidden_act!r}: the vision towers are built for {ACTIVATIONS} (exact GELU: "
+            raise NotImplementedError(f"hidden_act {hidden_act!r}: the vision towers are built for {tuple(ACTIVATIONS)} (exact GELU: "
                                       "the ViT-H tower of the reference; quick GELU: the safety checker's ViT-L)")
-        self._act = ops.quick_gelu_ if hidden_act == "quick_gelu" else ops.gelu_
+        self._act = ACTIVATIONS[hidden_act]
         self.device = dev = torch.device(device)
         sd = {k[len("vision_model."):]: v for k, v in state_dict.items() if k.startswith("vision_model.")}
         pw = sd["embeddings.patch_embedding.weight"]                     # [C, 3, P, P], no bias
@@ -53,19 +47,7 @@ class HipCLIPVision:
         for n in ("pre_layrnorm",):
             W[f"{n}.g"], W[f"{n}.b"] = _h(sd[f"{n}.weight"], dev), _h(sd[f"{n}.bias"], dev)
         self.n_layers = 1 + max(int(k.split(".")[2]) for k in sd if k.startswith("encoder.layers."))
-        qs = (self.d ** -0.5) * LOG2E                                    # softmax scale (CLIPAttention.scale) and log2 e
-        for i in range(self.n_layers):
-            p = f"encoder.layers.{i}."
-            a = p + "self_attn."
-            W[f"{i}.qkv.w"] = _h(torch.cat([sd[a + "q_proj.weight"].float() * qs, sd[a + "k_proj.weight"].float(),
-                                            sd[a + "v_proj.weight"].float()], 0), dev)
-            W[f"{i}.qkv.b"] = _h(torch.cat([sd[a + "q_proj.bias"].float() * qs, sd[a + "k_proj.bias"].float(),
-                                            sd[a + "v_proj.bias"].float()], 0), dev)
-            W[f"{i}.o.w"], W[f"{i}.o.b"] = _h(sd[a + "out_proj.weight"], dev), _h(sd[a + "out_proj.bias"], dev)
-            for ln in ("layer_norm1", "layer_norm2"):
-                W[f"{i}.{ln}.g"], W[f"{i}.{ln}.b"] = _h(sd[p + ln + ".weight"], dev), _h(sd[p + ln + ".bias"], dev)
-            for fc in ("fc1", "fc2"):
-                W[f"{i}.{fc}.w"], W[f"{i}.{fc}.b"] = _h(sd[p + f"mlp.{fc}.weight"], dev), _h(sd[p + f"mlp.{fc}.bias"], dev)
+        pack_layers(W, sd, self.n_layers, self.d, dev)
         # what follows the last layer (CLIPVisionTransformer.post_layernorm, CLIPVisionModelWithProjection.visual_projection):
         # read by image_embeds only; checkpoints of the bare CLIPVisionModel have no projection
         self.post_ln = (_h(sd["post_layernorm.weight"], dev), _h(sd["post_layernorm.bias"], dev)) if "post_layernorm.weight" in sd else None
@@ -109,24 +91,8 @@ class HipCLIPVision:
         x = self._empty(M, C)
         ops.layernorm(h, x, W["pre_layrnorm.g"], W["pre_layrnorm.b"], M=M, C_=C, eps=self.eps)
         for i in range(n_run):
-            ln = self._empty(M, C)
-            ops.layernorm(x, ln, W[f"{i}.layer_norm1.g"], W[f"{i}.layer_norm1.b"], M=M, C_=C, eps=self.eps)
-            qk = self._empty(M, 2 * C)
-            vt = self._empty(B * self.heads * ops.dvp_of(self.d) * Np)
-            ops.gemm(ln, W[f"{i}.qkv.w"], qk, M=M, N=3 * C, c1=C, bias=W[f"{i}.qkv.b"], mode=2, vt=vt, n_vt0=2 * C,
-                     heads=self.heads, dhead=self.d, ntok=Np)
-            ao = self._empty(M, C)
-            ops.self_attn(qk, qk[:, C:], vt, ao, B=B, N=Np, heads=self.heads, d=self.d, ldq=2 * C, ldk=2 * C, ldo=C,
-                          n_keys=ntok)
-            x2 = self._empty(M, C)
-            ops.gemm(ao, W[f"{i}.o.w"], x2, M=M, N=C, c1=C, bias=W[f"{i}.o.b"], res=x, ldr=C)
-            ln2 = self._empty(M, C)
-            ops.layernorm(x2, ln2, W[f"{i}.layer_norm2.g"], W[f"{i}.layer_norm2.b"], M=M, C_=C, eps=self.eps)
-            f = self._empty(M, W[f"{i}.fc1.w"].shape[0])
-            ops.gemm(ln2, W[f"{i}.fc1.w"], f, M=M, N=f.shape[1], c1=C, bias=W[f"{i}.fc1.b"])
-            self._act(f)
-            x = self._empty(M, C)
-            ops.gemm(f, W[f"{i}.fc2.w"], x, M=M, N=C, c1=f.shape[1], bias=W[f"{i}.fc2.b"], res=x2, ldr=C)
+            x = run_layer(W, i, x, B=B, Np=Np, heads=self.heads, d=self.d, eps=self.eps, attn=ops.self_attn, n_keys=ntok,
+                          act=self._act)
         return x.view(B, Np, C), ntok
 
     def head_inputs(self, pixel_values: torch.Tensor):

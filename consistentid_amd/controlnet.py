@@ -130,15 +130,6 @@ def _refuse_unbuilt(guess_mode: bool, return_dict: bool):
         raise NotImplementedError("return_dict=True (the reference passes return_dict=False, CN :411)")
 
 
-def _refresh_context(net, ehs: torch.Tensor):
-    """K/V of ``encoder_hidden_states``, recomputed only when the tensor changed (kept alive in key_ref so that its address
-    cannot be recycled)"""
-    key = (ehs.data_ptr(), ehs._version, tuple(ehs.shape))
-    if net._ctx.key != key or net._ctx.key_ref is not ehs:
-        net.set_context(ehs, num_tokens=0)
-        net._ctx.key, net._ctx.key_ref = key, ehs
-
-
 def _nchw(down, mid, B: int, shapes):
     """token-major residuals [B * h * w, c] -> (down, mid) as [B, c, h, w]-shaped (channels-last) views; ``shapes``: (c, h, w)
     of every down residual, then of the mid one"""
@@ -249,7 +240,7 @@ class HipControlNet(HipUNet):
             raise NotImplementedError("MultiControlNet: a list of scales goes to HipMultiControlNet([...]), this is one net")
         sample = sample.to(device=self.device, dtype=torch.float16).contiguous()
         B = sample.shape[0]
-        _refresh_context(self, encoder_hidden_states)
+        self.refresh_context(encoder_hidden_states, num_tokens=0)
         kvrow = torch.arange(B, dtype=torch.int32, device=self.device)
         self._t_buf.fill_(float(timestep))
         cond = self.cond_embedding(controlnet_cond)
@@ -297,7 +288,7 @@ class HipMultiControlNet:
         kvrow = torch.arange(B, dtype=torch.int32, device=self.device)
         downs, mids = [], []
         for net, cond in zip(self.nets, controlnet_cond):
-            _refresh_context(net, encoder_hidden_states)
+            net.refresh_context(encoder_hidden_states, num_tokens=0)
             net._t_buf.fill_(float(timestep))
             d, m = net.forward_tokens(sample, net._t_buf, kvrow, B, net.cond_embedding(cond), 1.0)
             downs.append(d)

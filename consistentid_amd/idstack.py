@@ -19,10 +19,7 @@ from typing import Dict, Optional
 import torch
 
 from . import ops
-
-
-def _h(t: torch.Tensor, dev) -> torch.Tensor:
-    return t.to(device=dev, dtype=torch.float16).contiguous()
+from .weights import _h
 
 
 class _Mod:

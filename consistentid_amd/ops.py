@@ -330,7 +330,7 @@ _KV_IDX_CACHE = {}
 
 
 def kv_pack2(kv_txt: torch.Tensor, kv_ip: torch.Tensor, kp: torch.Tensor, vp: torch.Tensor, *, R: int, L: int, C_: int,
-             heads: int, n_txt: int, n_ip: int, order: str = "slot"):
+             heads: int, n_txt: int, n_ip: int, order: str):
     """projected [K | V] rows of R context rows ([R, L, 2C], text and ID projections) -> the fragment-ordered
     operands of cid_id_xattn3_f16 (order "reg": register-major keys, xattn_pack.slot_key; order "slot" is the
     key order of the retired second generation, kept for the layout tests); index tables from xattn_pack, cached on the device"""
@@ -347,6 +347,29 @@ def kv_pack2(kv_txt: torch.Tensor, kv_ip: torch.Tensor, kp: torch.Tensor, vp: to
     for idx, dst in ((ki, kp), (vi, vp)):
         check(lib.cid_gather_pack_f16(_p(kv_txt), _p(kv_ip), idx.data_ptr(), _p(dst), R, L * 2 * C_, idx.numel(), _stream()),
               "cid_gather_pack_f16")
+
+
+def context_kv(ehs: torch.Tensor, w_txt: torch.Tensor, w_ip: torch.Tensor, *, R: int, L: int, C_: int, heads: int,
+               n_txt: int, n_ip: int, v3: bool, kp: Optional[torch.Tensor] = None, vp: Optional[torch.Tensor] = None):
+    """The packed K/V of one cross-attention layer for context rows ``ehs`` [R, L, Dc]: both [K | V] projections
+    (``w_txt`` / ``w_ip`` [2 C, Dc]), then the operand layout of the third-generation fused kernel (``v3``) or of the
+    first-generation kernels.  ``kp`` / ``vp`` are written in place where their size fits (a captured step keeps their
+    addresses).  Returns (kp, vp, whether they are new tensors)."""
+    M, Dc = R * L, ehs.shape[-1]
+    kv_txt = torch.empty(M, 2 * C_, dtype=torch.float16, device=ehs.device)
+    kv_ip = torch.empty(M, 2 * C_, dtype=torch.float16, device=ehs.device)
+    gemm(ehs, w_txt, kv_txt, M=M, N=2 * C_, c1=Dc)
+    gemm(ehs, w_ip, kv_ip, M=M, N=2 * C_, c1=Dc)
+    ke, ve = kv_pack2_elems(C_, heads) if v3 else kv_pack_elems(C_, heads)
+    moved = kp is None or kp.numel() != R * ke
+    if moved:
+        kp = torch.empty(R * ke, dtype=torch.float16, device=ehs.device)
+        vp = torch.empty(R * ve, dtype=torch.float16, device=ehs.device)
+    if v3:
+        kv_pack2(kv_txt, kv_ip, kp, vp, R=R, L=L, C_=C_, heads=heads, n_txt=n_txt, n_ip=n_ip, order="reg")
+    else:
+        kv_pack(kv_txt, kv_ip, kp, vp, R=R, C_=C_, heads=heads, n_txt=n_txt, n_ip=n_ip)
+    return kp, vp, moved
 
 
 XATTN_GEN_DEFAULT = 3

@@ -54,6 +54,10 @@ class _Ctx:
         self.key_ref = None
 
 
+def _tensor_key(t: torch.Tensor):
+    return t.data_ptr(), t._version, tuple(t.shape)
+
+
 def fused_gen1(c: int, tokens: int, fused_max_c: int = 320) -> bool:
     """one launch of the first-generation fused cross-attention kernel instead of LN + GEMM + core + GEMM, where the third
     generation does not serve?  (HipUNet._fused_gen1 with the engine's CID_XATTN_FUSED_MAX_C; the measurements are there)"""
@@ -119,40 +123,34 @@ class HipUNet:
         """Project + pack cross-attention K/V for ``ehs`` [R, L, Dc] (L = text + ID tokens).
         Replaces the per-step to_k/to_v/to_k_ip/to_v_ip GEMMs of attention.py:249-250,266-269."""
         nt = self.num_tokens if num_tokens is None else num_tokens
-        ehs = ehs.to(device=self.device, dtype=torch.float16).contiguous()
-        R, L, Dc = ehs.shape
+        given, ehs = ehs, ehs.to(device=self.device, dtype=torch.float16).contiguous()
+        R, L, _ = ehs.shape
         ctx = self._ctx
         ctx.rows, ctx.n_txt, ctx.n_ip = R, L - nt, nt
-        M = R * L
-        cache: Dict[int, torch.Tensor] = {}
         moved = False
         for b in self.packed.xattn_layers:
             wt = self.W[f"{b}.attn2.kv_txt.w"]
-            C2 = wt.shape[0]
-            C_ = C2 // 2
+            C_ = wt.shape[0] // 2
             heads = self._heads_of(b)
-            kv_txt = torch.empty(M, C2, dtype=torch.float16, device=self.device)
-            kv_ip = torch.empty(M, C2, dtype=torch.float16, device=self.device)
-            ops.gemm(ehs, wt, kv_txt, M=M, N=C2, c1=Dc)
-            ops.gemm(ehs, self.W[f"{b}.attn2.kv_ip.w"], kv_ip, M=M, N=C2, c1=Dc)
+            # fragment order of the third-generation fused kernel (SD1.5 level 0) where it serves
             v3 = (self._xattn_gen >= 3 and f"{b}.attn2.wq_p" in self.W
                   and ops.id_xattn3_supported(C_, heads, ctx.n_txt, ctx.n_ip))
-            ke, ve = ops.kv_pack2_elems(C_, heads) if v3 else ops.kv_pack_elems(C_, heads)
-            kp, vp = ctx.kp.get(b), ctx.vp.get(b)
-            if kp is None or kp.numel() != R * ke:   # keep addresses stable across generations
-                kp = torch.empty(R * ke, dtype=torch.float16, device=self.device)
-                vp = torch.empty(R * ve, dtype=torch.float16, device=self.device)
-                moved = True
-            if v3:      # fragment order of the third-generation fused kernel (SD1.5 level 0)
-                ops.kv_pack2(kv_txt, kv_ip, kp, vp, R=R, L=L, C_=C_, heads=heads, n_txt=ctx.n_txt, n_ip=ctx.n_ip, order="reg")
-            else:
-                ops.kv_pack(kv_txt, kv_ip, kp, vp, R=R, C_=C_, heads=heads, n_txt=ctx.n_txt, n_ip=ctx.n_ip)
-            ctx.kp[b], ctx.vp[b] = kp, vp
+            # (the buffers of the last context are reused: addresses stay stable across generations)
+            ctx.kp[b], ctx.vp[b], new = ops.context_kv(ehs, wt, self.W[f"{b}.attn2.kv_ip.w"], R=R, L=L, C_=C_, heads=heads,
+                                                       n_txt=ctx.n_txt, n_ip=ctx.n_ip, v3=v3, kp=ctx.kp.get(b),
+                                                       vp=ctx.vp.get(b))
+            moved |= new
             ctx.v2[b] = 3 if v3 else 0
-        ctx.key, ctx.key_ref = (ehs.data_ptr(), ehs._version, tuple(ehs.shape)), ehs
+        ctx.key, ctx.key_ref = _tensor_key(given), given
         if moved:       # the allocator may hand an old address out again: the addresses alone do not tell
             self.epoch += 1
         return self
+
+    def refresh_context(self, ehs: torch.Tensor, num_tokens: Optional[int] = None):
+        """:meth:`set_context` unless ``ehs`` is the tensor the kept K/V were computed from: the same object, unchanged
+        (address, version, shape)"""
+        if self._ctx.key != _tensor_key(ehs) or self._ctx.key_ref is not ehs:
+            self.set_context(ehs, num_tokens)
 
     def context_addresses(self):
         """the device addresses and scalar launch arguments a captured step reads from this object besides its weights: the
@@ -578,11 +576,7 @@ class HipUNet:
                  mid_block_additional_residual=None, return_dict=True):
         sample = sample.to(device=self.device, dtype=torch.float16).contiguous()
         B = sample.shape[0]
-        ehs = encoder_hidden_states
-        key = (ehs.data_ptr(), ehs._version, tuple(ehs.shape))
-        if self._ctx.key != key or self._ctx.key_ref is not ehs:
-            self.set_context(ehs)
-            self._ctx.key, self._ctx.key_ref = key, ehs
+        self.refresh_context(encoder_hidden_states)
         kvrow = torch.arange(B, dtype=torch.int32, device=self.device)
         self._t_buf.fill_(float(timestep))
 

@@ -15,8 +15,9 @@ moves through the softmax (rows of P sum to 1) into the output projection's bias
 
 SDXL's VAE sets ``force_upcast``: the reference decodes it in float32 (``upcast_vae()``,
 pipline_StableDiffusionXL_ConsistentID.py:670-676).  ``HipVAEDecoderF32`` below is that decoder on the fp32 kernels
-(``cid_gemm_f32`` / ``cid_groupnorm_f32`` / ``cid_softmax_rows_f32``, csrc/f32.hip); ``make_vae_decoder`` picks the
-engine from the config like the reference's ``needs_upcasting`` test does.
+(``cid_gemm_f32`` / ``cid_groupnorm_f32`` / ``cid_softmax_rows_f32``, csrc/f32.hip): the same weight loading, blocks and
+decode walk (``_HipVAEBlocks``, ``_HipVAEDecoderWalk``) with its own primitives, weight converters, head and tail;
+``make_vae_decoder`` picks the engine from the config like the reference's ``needs_upcasting`` test does.
 """
 from __future__ import annotations
 
@@ -30,44 +31,28 @@ from .vae_spec import VAEConfig, decoder_blocks, encoder_blocks
 from .weights import LOG2E, _conv3, _f, _h
 
 
-def _load_resnet(W: Dict[str, torch.Tensor], sd: Dict[str, torch.Tensor], n: str, dev):
-    """fp16 weights of one ResnetBlock2D (temb-less, as in the VAE) into W under ``n``"""
-    for k in ("norm1", "norm2"):
-        W[f"{n}.{k}.g"], W[f"{n}.{k}.b"] = _h(sd[f"{n}.{k}.weight"], dev), _h(sd[f"{n}.{k}.bias"], dev)
-    for k in ("conv1", "conv2"):
-        W[f"{n}.{k}.w"], W[f"{n}.{k}.b"] = _conv3(sd[f"{n}.{k}.weight"], dev), _h(sd[f"{n}.{k}.bias"], dev)
-    if f"{n}.conv_shortcut.weight" in sd:
-        sw = sd[f"{n}.conv_shortcut.weight"]
-        W[f"{n}.short.w"] = _h(sw.reshape(sw.shape[0], sw.shape[1]), dev)
-        W[f"{n}.short.b"] = _h(sd[f"{n}.conv_shortcut.bias"], dev)
-
-
-def _load_attention(W: Dict[str, torch.Tensor], sd: Dict[str, torch.Tensor], a: str, c: int, dev):
-    """the mid block's single-head attention ``a`` into W["attn.*"], with the folds described in the module docstring"""
-    W["attn.gn.g"], W["attn.gn.b"] = _h(sd[f"{a}.group_norm.weight"], dev), _h(sd[f"{a}.group_norm.bias"], dev)
-    qs = (c ** -0.5) * LOG2E
-    W["attn.q.w"] = _h(_f(sd[f"{a}.to_q.weight"], dev) * qs, dev)
-    W["attn.q.b"] = _h(_f(sd[f"{a}.to_q.bias"], dev) * qs, dev)
-    W["attn.k.w"] = _h(sd[f"{a}.to_k.weight"], dev)                     # bias dropped: constant per score row
-    W["attn.v.w"] = _h(sd[f"{a}.to_v.weight"], dev)
-    wo = _f(sd[f"{a}.to_out.0.weight"], dev)
-    W["attn.o.w"] = _h(wo, dev)
-    W["attn.o.b"] = _h(_f(sd[f"{a}.to_out.0.bias"], dev) + wo @ _f(sd[f"{a}.to_v.bias"], dev), dev)
-
-
 class _HipVAEBlocks:
-    """The fp16 building blocks the decoder and the encoder share: GroupNorm(+SiLU), 3x3 convolution, ResnetBlock2D and
-    the mid block's single-head attention, all on token-major activations.  Subclasses fill ``W``, ``config`` and
-    ``device``."""
+    """The building blocks the decoders and the encoder share, on token-major activations: ResnetBlock2D, the mid block's
+    single-head attention and their weight loading, written on four primitives (``_gn``: GroupNorm(+SiLU), ``_conv``: 3x3
+    convolution, ``_linear``, ``_softmax``) and two weight converters (``_t``: a plain tensor, ``_t3``: a 3x3 kernel,
+    tap-major [Cout, 9 * Cin]).  The primitives and converters here are the fp16 ones; ``HipVAEDecoderF32`` replaces them.
+    Subclasses fill ``W``, ``config`` and ``device``."""
     config: VAEConfig
     device: torch.device
+    dtype = torch.float16
     W: Dict[str, torch.Tensor]
     _gn_ws: Optional[torch.Tensor]
     _gemm_ws: torch.Tensor
 
-    # ------------------------------------------------------------------ helpers
+    # ------------------------------------------------------------------ fp16 primitives and converters
+    def _t(self, t):
+        return _h(t, self.device)
+
+    def _t3(self, w):
+        return _conv3(w, self.device)
+
     def _empty(self, *shape):
-        return torch.empty(*shape, dtype=torch.float16, device=self.device)
+        return torch.empty(*shape, dtype=self.dtype, device=self.device)
 
     def _gn(self, x, c, B, HW, g, b, silu):
         need = ops.groupnorm_ws_bytes(B, c)
@@ -84,105 +69,106 @@ class _HipVAEBlocks:
                  ldr=cout if res is not None else 0, taps=9, Hi=H, Wi=Wd, Ho=Ho, Wo=Wo, stride=1, up=up, ws=self._gemm_ws)
         return out
 
+    def _linear(self, x, w, b, M, N, c, res=None, out=None, ws=False):
+        """x [M, c] @ w [N, c]^T (+ b) (+ res) -> ``out`` (a fresh [M, N] by default); ``ws``: with the split-K workspace"""
+        out = self._empty(M, N) if out is None else out
+        ops.gemm(x, w, out, M=M, N=N, c1=c, bias=b, res=res, ws=self._gemm_ws if ws else None)      # (res at pitch N)
+        return out
+
+    def _softmax(self, s, n):
+        ops.softmax_rows(s, rows=n, cols=n, ld=n)
+
+    # ------------------------------------------------------------------ weights
+    def _load_resnet(self, sd: Dict[str, torch.Tensor], n: str):
+        """weights of one ResnetBlock2D (temb-less, as in the VAE) into W under ``n``"""
+        W, t = self.W, self._t
+        for k in ("norm1", "norm2"):
+            W[f"{n}.{k}.g"], W[f"{n}.{k}.b"] = t(sd[f"{n}.{k}.weight"]), t(sd[f"{n}.{k}.bias"])
+        for k in ("conv1", "conv2"):
+            W[f"{n}.{k}.w"], W[f"{n}.{k}.b"] = self._t3(sd[f"{n}.{k}.weight"]), t(sd[f"{n}.{k}.bias"])
+        if f"{n}.conv_shortcut.weight" in sd:
+            sw = sd[f"{n}.conv_shortcut.weight"]
+            W[f"{n}.short.w"] = t(sw.reshape(sw.shape[0], sw.shape[1]))
+            W[f"{n}.short.b"] = t(sd[f"{n}.conv_shortcut.bias"])
+
+    def _load_attention(self, sd: Dict[str, torch.Tensor], a: str, c: int):
+        """the mid block's single-head attention ``a`` into W["attn.*"], with the folds described in the module docstring"""
+        W, t, dev = self.W, self._t, self.device
+        W["attn.gn.g"], W["attn.gn.b"] = t(sd[f"{a}.group_norm.weight"]), t(sd[f"{a}.group_norm.bias"])
+        qs = (c ** -0.5) * LOG2E
+        W["attn.q.w"] = t(_f(sd[f"{a}.to_q.weight"], dev) * qs)
+        W["attn.q.b"] = t(_f(sd[f"{a}.to_q.bias"], dev) * qs)
+        W["attn.k.w"] = t(sd[f"{a}.to_k.weight"])                           # bias dropped: constant per score row
+        W["attn.v.w"] = t(sd[f"{a}.to_v.weight"])
+        wo = _f(sd[f"{a}.to_out.0.weight"], dev)
+        W["attn.o.w"] = t(wo)
+        W["attn.o.b"] = t(_f(sd[f"{a}.to_out.0.bias"], dev) + wo @ _f(sd[f"{a}.to_v.bias"], dev))
+
+    # ------------------------------------------------------------------ blocks
     def _resnet(self, n, x, cin, cout, B, H, Wd):
         W, HW = self.W, H * Wd
         h = self._gn(x, cin, B, HW, W[f"{n}.norm1.g"], W[f"{n}.norm1.b"], True)
         h = self._conv(h, f"{n}.conv1", cin, cout, B, H, Wd)
         h = self._gn(h, cout, B, HW, W[f"{n}.norm2.g"], W[f"{n}.norm2.b"], True)
-        if cin != cout:
-            sc = self._empty(B * HW, cout)
-            ops.gemm(x, W[f"{n}.short.w"], sc, M=B * HW, N=cout, c1=cin, bias=W[f"{n}.short.b"], ws=self._gemm_ws)
-        else:
-            sc = x
+        sc = x if cin == cout else self._linear(x, W[f"{n}.short.w"], W[f"{n}.short.b"], B * HW, cout, cin, ws=True)
         return self._conv(h, f"{n}.conv2", cout, cout, B, H, Wd, res=sc)
 
     def _attention(self, x, c, B, HW):
         """single-head attention over all HW positions of each sample (diffusers Attention, residual_connection)"""
-        W = self.W
-        M = B * HW
+        W, M = self.W, B * HW
         t = self._gn(x, c, B, HW, W["attn.gn.g"], W["attn.gn.b"], False)
-        q, k = self._empty(M, c), self._empty(M, c)
-        ops.gemm(t, W["attn.q.w"], q, M=M, N=c, c1=c, bias=W["attn.q.b"])
-        ops.gemm(t, W["attn.k.w"], k, M=M, N=c, c1=c)
+        q = self._linear(t, W["attn.q.w"], W["attn.q.b"], M, c, c)
+        k = self._linear(t, W["attn.k.w"], None, M, c, c)
         o = self._empty(M, c)
-        s = self._empty(HW, HW)
-        vt = self._empty(c, HW)
+        s, vt = self._empty(HW, HW), self._empty(c, HW)
         for b in range(B):
             rows = slice(b * HW, (b + 1) * HW)
-            ops.gemm(q[rows], k[rows], s, M=HW, N=HW, c1=c)                      # S = Q K^T      [HW, HW]
-            ops.softmax_rows(s, rows=HW, cols=HW, ld=HW)
-            ops.gemm(W["attn.v.w"], t[rows], vt, M=c, N=HW, c1=c)                # V^T = Wv T^T   [C, HW]
-            ops.gemm(s, vt, o[rows], M=HW, N=c, c1=HW, ws=self._gemm_ws)         # O = P V        [HW, C]
-        out = self._empty(M, c)
-        ops.gemm(o, W["attn.o.w"], out, M=M, N=c, c1=c, bias=W["attn.o.b"], res=x, ldr=c)
-        return out
+            self._linear(q[rows], k[rows], None, HW, HW, c, out=s)               # S = Q K^T      [HW, HW]
+            self._softmax(s, HW)
+            self._linear(W["attn.v.w"], t[rows], None, c, HW, c, out=vt)         # V^T = Wv T^T   [C, HW]
+            self._linear(s, vt, None, HW, c, HW, out=o[rows], ws=True)           # O = P V        [HW, C]
+        return self._linear(o, W["attn.o.w"], W["attn.o.b"], M, c, c, res=x)
 
 
-class HipVAEDecoder(_HipVAEBlocks):
+class _HipVAEDecoderWalk(_HipVAEBlocks):
+    """What the two decoders share: the weight loading and the decode walk (mid block, up blocks, ``conv_norm_out``)
+    between a head (``post_quant_conv`` + ``conv_in``: ``_load_head`` / ``_head``) and a tail (``conv_out`` to NCHW:
+    ``_tail``) that each precision writes itself."""
+
     def __init__(self, cfg: VAEConfig, vae_sd: Dict[str, torch.Tensor], device="cuda:0"):
-        if cfg.force_upcast:
-            raise NotImplementedError("force_upcast VAEs (SDXL) decode in fp32 in the reference: use HipVAEDecoderF32 "
-                                      "(make_vae_decoder picks it)")
         self.config = cfg
         self.device = torch.device(device)
-        self.dtype = torch.float16
-        dev, sd = self.device, vae_sd
+        sd = vae_sd
         W: Dict[str, torch.Tensor] = {}
         self.W = W
-        L, boc = cfg.latent_channels, cfg.block_out_channels
-        c_mid = boc[-1]
         with torch.cuda.device(self.device):
-            # post_quant_conv (1x1, L -> L) with the latent scale folded in, carried as the centre tap of a 3x3 conv
-            # whose output is padded to 8 channels (the small-conv kernel's granule); conv_in reads those 8 channels
-            pq = _f(sd["post_quant_conv.weight"], dev).reshape(L, L) / cfg.scaling_factor
-            w = torch.zeros(8, 9, L, device=dev)
-            w[:L, 4, :] = pq
-            W["pq.w"] = _h(w.reshape(8, 9 * L), dev)
-            b = torch.zeros(8, device=dev)
-            b[:L] = _f(sd["post_quant_conv.bias"], dev)
-            W["pq.b"] = _h(b, dev)
-            ci = _f(sd["decoder.conv_in.weight"], dev)                         # [C, L, 3, 3]
-            w = torch.zeros(c_mid, 9, 8, device=dev)
-            w[:, :, :L] = ci.permute(0, 2, 3, 1).reshape(c_mid, 9, L)
-            W["conv_in.w"] = _h(w.reshape(c_mid, 72), dev)
-            W["conv_in.b"] = _h(sd["decoder.conv_in.bias"], dev)
-
-            def resnet(n):
-                _load_resnet(W, sd, n, dev)
-
+            self._load_head(sd)
             m = "decoder.mid_block"
-            resnet(f"{m}.resnets.0")
-            resnet(f"{m}.resnets.1")
-            _load_attention(W, sd, f"{m}.attentions.0", c_mid, dev)
+            self._load_resnet(sd, f"{m}.resnets.0")
+            self._load_resnet(sd, f"{m}.resnets.1")
+            self._load_attention(sd, f"{m}.attentions.0", cfg.block_out_channels[-1])
             self.blocks = decoder_blocks(cfg)
             for name, cin, cout, n, up in self.blocks:
                 for j in range(n):
-                    resnet(f"{name}.resnets.{j}")
+                    self._load_resnet(sd, f"{name}.resnets.{j}")
                 if up:
                     u = f"{name}.upsamplers.0.conv"
-                    W[f"{u}.w"], W[f"{u}.b"] = _conv3(sd[f"{u}.weight"], dev), _h(sd[f"{u}.bias"], dev)
-            W["norm_out.g"], W["norm_out.b"] = _h(sd["decoder.conv_norm_out.weight"], dev), _h(sd["decoder.conv_norm_out.bias"], dev)
-            co = sd["decoder.conv_out.weight"]
-            W["conv_out.w"] = _h(co.permute(0, 2, 3, 1).reshape(co.shape[0], -1), dev)
-            W["conv_out.b"] = _h(sd["decoder.conv_out.bias"], dev)
+                    W[f"{u}.w"], W[f"{u}.b"] = self._t3(sd[f"{u}.weight"]), self._t(sd[f"{u}.bias"])
+            W["norm_out.g"], W["norm_out.b"] = self._t(sd["decoder.conv_norm_out.weight"]), self._t(sd["decoder.conv_norm_out.bias"])
+            W["conv_out.w"], W["conv_out.b"] = self._t3(sd["decoder.conv_out.weight"]), self._t(sd["decoder.conv_out.bias"])
         self._gn_ws: Optional[torch.Tensor] = None
-        self._gemm_ws = torch.empty(64 << 20, dtype=torch.uint8, device=self.device)
 
-    # ------------------------------------------------------------------ decode
     @torch.no_grad()
     def decode_tokens(self, latents: torch.Tensor):
         """latents [B, L, h, w] (UNSCALED, as the denoise loop leaves them) -> image token-major is internal; returns
-        the decoded image [B, 3, 8h, 8w] fp16 NCHW in the VAE's [-1, 1] range."""
+        the decoded image [B, 3, 8h, 8w] NCHW in the VAE's [-1, 1] range, in the engine's dtype."""
         cfg, W = self.config, self.W
-        lat = latents.to(device=self.device, dtype=torch.float16)
+        lat = latents.to(device=self.device, dtype=self.dtype)
         B, L, H, Wd = lat.shape
         assert L == cfg.latent_channels
-        x = lat.permute(0, 2, 3, 1).reshape(B * H * Wd, L).contiguous()        # 32 KB per image: host-side plumbing
-        z = self._empty(B * H * Wd, 8)
-        ops.conv3x3_small(x, z, W["pq.w"], W["pq.b"], B=B, Hi=H, Wi=Wd, cin=L, cout=8)
         c = cfg.block_out_channels[-1]
-        x = self._empty(B * H * Wd, c)
-        ops.conv3x3_small(z, x, W["conv_in.w"], W["conv_in.b"], B=B, Hi=H, Wi=Wd, cin=8, cout=c)
+        x = lat.permute(0, 2, 3, 1).reshape(B * H * Wd, L).contiguous()        # 32 KB per image: host-side plumbing
+        x = self._head(x, c, B, H, Wd)
         m = "decoder.mid_block"
         x = self._resnet(f"{m}.resnets.0", x, c, c, B, H, Wd)
         x = self._attention(x, c, B, H * Wd)
@@ -195,9 +181,7 @@ class HipVAEDecoder(_HipVAEBlocks):
                 H, Wd = 2 * H, 2 * Wd
             c = cout
         g = self._gn(x, c, B, H * Wd, W["norm_out.g"], W["norm_out.b"], True)
-        out = self._empty(B, cfg.out_channels, H, Wd)
-        ops.conv_out(g, out, W["conv_out.w"], W["conv_out.b"], B=B, H=H, W=Wd, cin=c, cout=cfg.out_channels)
-        return out
+        return self._tail(g, c, B, H, Wd)
 
     def decode(self, z: torch.Tensor, return_dict: bool = False):
         """diffusers ``vae.decode(z)`` protocol: ``z`` is ALREADY divided by scaling_factor by the caller
@@ -207,9 +191,46 @@ class HipVAEDecoder(_HipVAEBlocks):
         return (self.decode_tokens(z * self.config.scaling_factor),)
 
     def decode_latents(self, latents: torch.Tensor) -> torch.Tensor:
-        """``StableDiffusionPipeline.decode_latents`` up to the device tensor: [B, 3, H, W] fp16 in [0, 1]."""
+        """``StableDiffusionPipeline.decode_latents`` up to the device tensor: [B, 3, H, W] in [0, 1]."""
         return (self.decode_tokens(latents) / 2 + 0.5).clamp(0, 1)
 
+
+class HipVAEDecoder(_HipVAEDecoderWalk):
+    def __init__(self, cfg: VAEConfig, vae_sd: Dict[str, torch.Tensor], device="cuda:0"):
+        if cfg.force_upcast:
+            raise NotImplementedError("force_upcast VAEs (SDXL) decode in fp32 in the reference: use HipVAEDecoderF32 "
+                                      "(make_vae_decoder picks it)")
+        super().__init__(cfg, vae_sd, device)
+        self._gemm_ws = torch.empty(64 << 20, dtype=torch.uint8, device=self.device)
+
+    def _load_head(self, sd):
+        # post_quant_conv (1x1, L -> L) with the latent scale folded in, carried as the centre tap of a 3x3 conv
+        # whose output is padded to 8 channels (the small-conv kernel's granule); conv_in reads those 8 channels
+        cfg, W, dev = self.config, self.W, self.device
+        L, c_mid = cfg.latent_channels, cfg.block_out_channels[-1]
+        pq = _f(sd["post_quant_conv.weight"], dev).reshape(L, L) / cfg.scaling_factor
+        w = torch.zeros(8, 9, L, device=dev)
+        w[:L, 4, :] = pq
+        W["pq.w"] = _h(w.reshape(8, 9 * L), dev)
+        b = torch.zeros(8, device=dev)
+        b[:L] = _f(sd["post_quant_conv.bias"], dev)
+        W["pq.b"] = _h(b, dev)
+        ci = _f(sd["decoder.conv_in.weight"], dev)                         # [C, L, 3, 3]
+        w = torch.zeros(c_mid, 9, 8, device=dev)
+        w[:, :, :L] = ci.permute(0, 2, 3, 1).reshape(c_mid, 9, L)
+        W["conv_in.w"] = _h(w.reshape(c_mid, 72), dev)
+        W["conv_in.b"] = _h(sd["decoder.conv_in.bias"], dev)
+
+    def _head(self, x, c, B, H, Wd):
+        W, L = self.W, self.config.latent_channels
+        z = self._empty(B * H * Wd, 8)
+        ops.conv3x3_small(x, z, W["pq.w"], W["pq.b"], B=B, Hi=H, Wi=Wd, cin=L, cout=8)
+        x = self._empty(B * H * Wd, c)
+        return ops.conv3x3_small(z, x, W["conv_in.w"], W["conv_in.b"], B=B, Hi=H, Wi=Wd, cin=8, cout=c)
+
+    def _tail(self, g, c, B, H, Wd):
+        W, co = self.W, self.config.out_channels
+        return ops.conv_out(g, self._empty(B, co, H, Wd), W["conv_out.w"], W["conv_out.b"], B=B, H=H, W=Wd, cin=c, cout=co)
 
 
 # ---------------------------------------------------------------------------------------------------------------- encoder
@@ -283,7 +304,6 @@ class HipVAEEncoder(_HipVAEBlocks):
                                       "(there is no SDXL inpaint pipeline)")
         self.config = cfg
         self.device = torch.device(device)
-        self.dtype = torch.float16
         dev, sd = self.device, vae_sd
         W: Dict[str, torch.Tensor] = {}
         self.W = W
@@ -295,14 +315,14 @@ class HipVAEEncoder(_HipVAEBlocks):
             self.blocks = encoder_blocks(cfg)
             for name, cin, cout, n, down in self.blocks:
                 for j in range(n):
-                    _load_resnet(W, sd, f"{name}.resnets.{j}", dev)
+                    self._load_resnet(sd, f"{name}.resnets.{j}")
                 if down:
                     d = f"{name}.downsamplers.0.conv"
                     W[f"{d}.w"], W[f"{d}.b"] = _conv3(sd[f"{d}.weight"], dev), _h(sd[f"{d}.bias"], dev)
             m = "encoder.mid_block"
-            _load_resnet(W, sd, f"{m}.resnets.0", dev)
-            _load_resnet(W, sd, f"{m}.resnets.1", dev)
-            _load_attention(W, sd, f"{m}.attentions.0", boc[-1], dev)
+            self._load_resnet(sd, f"{m}.resnets.0")
+            self._load_resnet(sd, f"{m}.resnets.1")
+            self._load_attention(sd, f"{m}.attentions.0", boc[-1])
             W["norm_out.g"], W["norm_out.b"] = _h(sd["encoder.conv_norm_out.weight"], dev), _h(sd["encoder.conv_norm_out.bias"], dev)
             w, b = fold_quant_conv(_f(sd["encoder.conv_out.weight"], dev), _f(sd["encoder.conv_out.bias"], dev),
                                    _f(sd["quant_conv.weight"], dev), _f(sd["quant_conv.bias"], dev))
@@ -411,60 +431,18 @@ class HipVAEEncoder(_HipVAEBlocks):
         return {"image_latents": img, "masked_image_latents": msk, "mask_latents": mask_lat}
 
 
-class HipVAEDecoderF32:
+class HipVAEDecoderF32(_HipVAEDecoderWalk):
     """The same decoder in float32, for VAEs with ``force_upcast`` (SDXL): what the reference runs after
     ``upcast_vae()`` (pipline_StableDiffusionXL_ConsistentID.py:670-676).  Token-major fp32 activations, every op one of
     the three fp32 kernels of csrc/f32.hip; the weight folds (latent scale into post_quant_conv, attention scale and
     log2 e into to_q, K bias dropped, V bias through the softmax into the output bias) are the fp16 engine's."""
+    dtype = torch.float32
 
-    def __init__(self, cfg: VAEConfig, vae_sd: Dict[str, torch.Tensor], device="cuda:0"):
-        self.config = cfg
-        self.device = torch.device(device)
-        self.dtype = torch.float32
-        dev, sd = self.device, vae_sd
-        W: Dict[str, torch.Tensor] = {}
-        self.W = W
-        L, c_mid = cfg.latent_channels, cfg.block_out_channels[-1]
-        f = lambda t: _f(t, dev).contiguous()
-        conv = lambda w: f(w).permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()       # [Cout, 9 * Cin], tap-major
-        with torch.cuda.device(self.device):
-            W["pq.w"] = (f(sd["post_quant_conv.weight"]).reshape(L, L) / cfg.scaling_factor).contiguous()
-            W["pq.b"] = f(sd["post_quant_conv.bias"])
-            W["conv_in.w"], W["conv_in.b"] = conv(sd["decoder.conv_in.weight"]), f(sd["decoder.conv_in.bias"])
+    def _t(self, t):
+        return _f(t, self.device).contiguous()
 
-            def resnet(n):
-                for k in ("norm1", "norm2"):
-                    W[f"{n}.{k}.g"], W[f"{n}.{k}.b"] = f(sd[f"{n}.{k}.weight"]), f(sd[f"{n}.{k}.bias"])
-                for k in ("conv1", "conv2"):
-                    W[f"{n}.{k}.w"], W[f"{n}.{k}.b"] = conv(sd[f"{n}.{k}.weight"]), f(sd[f"{n}.{k}.bias"])
-                if f"{n}.conv_shortcut.weight" in sd:
-                    sw = sd[f"{n}.conv_shortcut.weight"]
-                    W[f"{n}.short.w"], W[f"{n}.short.b"] = f(sw).reshape(sw.shape[0], sw.shape[1]).contiguous(), f(sd[f"{n}.conv_shortcut.bias"])
-
-            m = "decoder.mid_block"
-            resnet(f"{m}.resnets.0")
-            resnet(f"{m}.resnets.1")
-            a = f"{m}.attentions.0"
-            W["attn.gn.g"], W["attn.gn.b"] = f(sd[f"{a}.group_norm.weight"]), f(sd[f"{a}.group_norm.bias"])
-            qs = (c_mid ** -0.5) * LOG2E
-            W["attn.q.w"], W["attn.q.b"] = (f(sd[f"{a}.to_q.weight"]) * qs).contiguous(), (f(sd[f"{a}.to_q.bias"]) * qs).contiguous()
-            W["attn.k.w"], W["attn.v.w"] = f(sd[f"{a}.to_k.weight"]), f(sd[f"{a}.to_v.weight"])
-            wo = f(sd[f"{a}.to_out.0.weight"])
-            W["attn.o.w"] = wo
-            W["attn.o.b"] = (f(sd[f"{a}.to_out.0.bias"]) + wo @ f(sd[f"{a}.to_v.bias"])).contiguous()
-            self.blocks = decoder_blocks(cfg)
-            for name, cin, cout, n, up in self.blocks:
-                for j in range(n):
-                    resnet(f"{name}.resnets.{j}")
-                if up:
-                    u = f"{name}.upsamplers.0.conv"
-                    W[f"{u}.w"], W[f"{u}.b"] = conv(sd[f"{u}.weight"]), f(sd[f"{u}.bias"])
-            W["norm_out.g"], W["norm_out.b"] = f(sd["decoder.conv_norm_out.weight"]), f(sd["decoder.conv_norm_out.bias"])
-            W["conv_out.w"], W["conv_out.b"] = conv(sd["decoder.conv_out.weight"]), f(sd["decoder.conv_out.bias"])
-        self._gn_ws: Optional[torch.Tensor] = None
-
-    def _empty(self, *shape):
-        return torch.empty(*shape, dtype=torch.float32, device=self.device)
+    def _t3(self, w):
+        return self._t(w).permute(0, 2, 3, 1).reshape(w.shape[0], -1).contiguous()       # [Cout, 9 * Cin], tap-major
 
     def _gn(self, x, c, B, HW, g, b, silu):
         need = ops.groupnorm_f32_ws_bytes(B, HW, c)
@@ -479,67 +457,29 @@ class HipVAEDecoderF32:
         ops.gemm_f32(x, self.W[f"{n}.w"], out, M=out.shape[0], N=cout, c=cin, bias=self.W[f"{n}.b"], res=res, taps=9, Hi=H, Wi=Wd, up=up)
         return out
 
-    def _linear(self, x, w, b, M, N, c, res=None):
-        out = self._empty(M, N)
+    def _linear(self, x, w, b, M, N, c, res=None, out=None, ws=False):
+        out = self._empty(M, N) if out is None else out
         ops.gemm_f32(x, w, out, M=M, N=N, c=c, bias=b, res=res)
         return out
 
-    def _resnet(self, n, x, cin, cout, B, H, Wd):
-        W, HW = self.W, H * Wd
-        h = self._gn(x, cin, B, HW, W[f"{n}.norm1.g"], W[f"{n}.norm1.b"], True)
-        h = self._conv(h, f"{n}.conv1", cin, cout, B, H, Wd)
-        h = self._gn(h, cout, B, HW, W[f"{n}.norm2.g"], W[f"{n}.norm2.b"], True)
-        sc = x if cin == cout else self._linear(x, W[f"{n}.short.w"], W[f"{n}.short.b"], B * HW, cout, cin)
-        return self._conv(h, f"{n}.conv2", cout, cout, B, H, Wd, res=sc)
+    def _softmax(self, s, n):
+        ops.softmax_rows_f32(s, rows=n, cols=n, ld=n)
 
-    def _attention(self, x, c, B, HW):
-        W, M = self.W, B * HW
-        t = self._gn(x, c, B, HW, W["attn.gn.g"], W["attn.gn.b"], False)
-        q = self._linear(t, W["attn.q.w"], W["attn.q.b"], M, c, c)
-        k = self._linear(t, W["attn.k.w"], None, M, c, c)
-        o = self._empty(M, c)
-        s, vt = self._empty(HW, HW), self._empty(c, HW)
-        for b in range(B):
-            rows = slice(b * HW, (b + 1) * HW)
-            ops.gemm_f32(q[rows], k[rows], s, M=HW, N=HW, c=c)                   # S = Q K^T    [HW, HW]
-            ops.softmax_rows_f32(s, rows=HW, cols=HW, ld=HW)
-            ops.gemm_f32(W["attn.v.w"], t[rows], vt, M=c, N=HW, c=c)             # V^T = Wv T^T [C, HW]
-            ops.gemm_f32(s, vt, o[rows], M=HW, N=c, c=HW)                        # O = P V      [HW, C]
-        return self._linear(o, W["attn.o.w"], W["attn.o.b"], M, c, c, res=x)
+    def _load_head(self, sd):
+        cfg, W, L = self.config, self.W, self.config.latent_channels
+        W["pq.w"] = (self._t(sd["post_quant_conv.weight"]).reshape(L, L) / cfg.scaling_factor).contiguous()
+        W["pq.b"] = self._t(sd["post_quant_conv.bias"])
+        W["conv_in.w"], W["conv_in.b"] = self._t3(sd["decoder.conv_in.weight"]), self._t(sd["decoder.conv_in.bias"])
 
-    @torch.no_grad()
-    def decode_tokens(self, latents: torch.Tensor):
-        """latents [B, L, h, w] (UNSCALED) -> decoded image [B, 3, 8h, 8w] fp32 NCHW in the VAE's [-1, 1] range"""
-        cfg, W = self.config, self.W
-        lat = latents.to(device=self.device, dtype=torch.float32)
-        B, L, H, Wd = lat.shape
-        assert L == cfg.latent_channels
-        x = lat.permute(0, 2, 3, 1).reshape(B * H * Wd, L).contiguous()
-        z = self._linear(x, W["pq.w"], W["pq.b"], B * H * Wd, L, L)
-        c = cfg.block_out_channels[-1]
-        x = self._conv(z, "conv_in", L, c, B, H, Wd)
-        m = "decoder.mid_block"
-        x = self._resnet(f"{m}.resnets.0", x, c, c, B, H, Wd)
-        x = self._attention(x, c, B, H * Wd)
-        x = self._resnet(f"{m}.resnets.1", x, c, c, B, H, Wd)
-        for name, cin, cout, n, up in self.blocks:
-            for j in range(n):
-                x = self._resnet(f"{name}.resnets.{j}", x, cin if j == 0 else cout, cout, B, H, Wd)
-            if up:
-                x = self._conv(x, f"{name}.upsamplers.0.conv", cout, cout, B, H, Wd, up=1)
-                H, Wd = 2 * H, 2 * Wd
-            c = cout
-        g = self._gn(x, c, B, H * Wd, W["norm_out.g"], W["norm_out.b"], True)
-        img = self._conv(g, "conv_out", c, cfg.out_channels, B, H, Wd)              # [B * H * W, 3]
-        return img.view(B, H, Wd, cfg.out_channels).permute(0, 3, 1, 2).contiguous()   # NCHW for the caller (plumbing)
+    def _head(self, x, c, B, H, Wd):
+        L = self.config.latent_channels
+        z = self._linear(x, self.W["pq.w"], self.W["pq.b"], B * H * Wd, L, L)
+        return self._conv(z, "conv_in", L, c, B, H, Wd)
 
-    def decode(self, z: torch.Tensor, return_dict: bool = False):
-        if return_dict:
-            raise NotImplementedError("return_dict=True (the reference passes return_dict=False)")
-        return (self.decode_tokens(z * self.config.scaling_factor),)
-
-    def decode_latents(self, latents: torch.Tensor) -> torch.Tensor:
-        return (self.decode_tokens(latents) / 2 + 0.5).clamp(0, 1)
+    def _tail(self, g, c, B, H, Wd):
+        co = self.config.out_channels
+        img = self._conv(g, "conv_out", c, co, B, H, Wd)                           # [B * H * W, 3]
+        return img.view(B, H, Wd, co).permute(0, 3, 1, 2).contiguous()             # NCHW for the caller (plumbing)
 
 
 def make_vae_decoder(cfg: VAEConfig, vae_sd: Dict[str, torch.Tensor], device="cuda:0"):
