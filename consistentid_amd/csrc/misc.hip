@@ -740,6 +740,10 @@ extern "C" int cid_small_attn_f16(const cid_half* q, int32_t ldq, const cid_half
     CID_CHECK_ARG(dim_head == 64, "cid_small_attn_f16: head width must be 64 (got %d)", dim_head);
     CID_CHECK_ARG(B > 0 && Lq > 0 && heads > 0 && n1 > 0 && n2 >= 0 && n1 + n2 <= 64 * SA_MAXK && ldq % 8 == 0 && ldkv % 8 == 0,
                   "cid_small_attn_f16: bad shape (at most %d keys)", 64 * SA_MAXK);
+    // a q / out row holds `heads` heads of 64, a key row [K | V]: the kernel reads V at row + heads * 64
+    CID_CHECK_ARG(ldq >= heads * 64 && ldkv >= 2 * heads * 64 && ldo >= heads * 64,
+                  "cid_small_attn_f16: bad pitch ldq=%d ldkv=%d ldo=%d (ldq, ldo >= heads * 64 = %d, ldkv >= twice that)", ldq, ldkv, ldo,
+                  heads * 64);
     const int total = B * heads * Lq;
     hipLaunchKernelGGL(small_attn_kernel, dim3((total + 3) / 4), dim3(256), 0, (hipStream_t)stream, (const half_t*)q, ldq,
                        (const half_t*)kv1, n1, (const half_t*)kv2, n2, ldkv, (half_t*)out, ldo, Lq, heads, scale2, total);
@@ -774,6 +778,8 @@ extern "C" int cid_linear_small_f16(const cid_half* x, int32_t ldx, const cid_ha
                                     cid_stream_t stream) {
     CID_CHECK_ARG(x && w && out, "cid_linear_small_f16: null pointer");
     CID_CHECK_ARG(M > 0 && M <= 64 && N > 0 && K > 0 && K % 8 == 0 && ldx % 8 == 0, "cid_linear_small_f16: bad shape (M <= 64, K %% 8)");
+    CID_CHECK_ARG(ldx >= K && ldo >= N && (ldadd == 0 || ldadd >= N),
+                  "cid_linear_small_f16: bad pitch ldx=%d ldo=%d ldadd=%d (ldx >= K = %d, ldo >= N = %d, ldadd 0 or >= N)", ldx, ldo, ldadd, K, N);
     const int waves = (N + LS_NPW - 1) / LS_NPW;
     hipLaunchKernelGGL(linear_small_kernel, dim3((waves + 3) / 4), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)x, ldx, (const half_t*)w, (const half_t*)b, (const half_t*)add, ldadd,

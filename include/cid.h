@@ -339,7 +339,8 @@ int cid_conv3x3_small_f16(const cid_half* x, cid_half* out, const cid_half* w, c
  *   cid_small_attn_f16  PerceiverAttention core (functions.py:439-447): Lq latent queries per sample attend to the keys of
  *                       two row blocks (n1 image tokens, n2 latents: the torch.cat of :433 without the copy); a key row is
  *                       [K | V] as produced by to_kv (:434); out = softmax(scale2 * q k^T) v, head width 64,
- *                       n1 + n2 <= 1024.  q [B*Lq][ldq], kv* [B*n*][ldkv], out [B*Lq][ldo]. */
+ *                       n1 + n2 <= 1024.  q [B*Lq][ldq], kv* [B*n*][ldkv], out [B*Lq][ldo].
+ *                       Refused (-EINVAL): ldq or ldo < heads * 64, ldkv < 2 * heads * 64 (V is read at row + heads * 64). */
 int cid_gelu_f16(cid_half* x, int64_t n, cid_stream_t stream);
 int cid_small_attn_f16(const cid_half* q, int32_t ldq, const cid_half* kv1, int32_t n1, const cid_half* kv2, int32_t n2,
                        int32_t ldkv, cid_half* out, int32_t ldo, int32_t B, int32_t Lq, int32_t heads, int32_t dim_head,
@@ -457,6 +458,7 @@ int cid_parse_head_f16(const cid_half* logits, int32_t ld, int32_t ncls, int32_t
  *                   f_i = exp(-ln(10000) * i / (dim/2)); v is a DEVICE fp32 array.
  * cid_linear_small: out[m][n] = act_out( sum_k act_in(x[m][k]) W[n][k] + b[n] (+ add[m][n]) )
  *                   for M <= 32 rows; act: 0 none, 1 SiLU.
+ *                   Refused (-EINVAL): ldx < K, ldo < N, ldadd neither 0 (one row for every m) nor >= N.
  */
 int cid_sincos_embed_f16(const float* v, cid_half* out, int32_t rows, int32_t dim, cid_stream_t stream);
 int cid_linear_small_f16(const cid_half* x, int32_t ldx, const cid_half* w, const cid_half* b,
