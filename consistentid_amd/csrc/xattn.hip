@@ -467,6 +467,7 @@ kv_pack_kernel(const half_t* __restrict__ kv_txt, const half_t* __restrict__ kv_
     }
 }
 
+// wp[((rt * (K / 16) + kk) * 64 + lane) * 8 + i] = w[(rt * 32 + (lane & 31)) * K + kk * 16 + (lane >> 5) * 8 + i], i < 8
 __global__ void __launch_bounds__(256)
 pack_wfrag_kernel(const half_t* __restrict__ w, half_t* __restrict__ wp, int rows, int K) {
     const long total = (long)rows * K / 8;
