@@ -26,15 +26,27 @@ def pack_layers(W: Dict[str, torch.Tensor], sd: Dict[str, torch.Tensor], n_layer
     for i in range(n_layers):
         p = f"encoder.layers.{i}."
         a = p + "self_attn."
-        W[f"{i}.qkv.w"] = _h(torch.cat([sd[a + "q_proj.weight"].float() * qs, sd[a + "k_proj.weight"].float(),
-                                        sd[a + "v_proj.weight"].float()], 0), dev)
+        W.update(pack_layer_weights(lambda k: sd[k].float(), i, d, dev))
         W[f"{i}.qkv.b"] = _h(torch.cat([sd[a + "q_proj.bias"].float() * qs, sd[a + "k_proj.bias"].float(),
                                         sd[a + "v_proj.bias"].float()], 0), dev)
-        W[f"{i}.o.w"], W[f"{i}.o.b"] = _h(sd[a + "out_proj.weight"], dev), _h(sd[a + "out_proj.bias"], dev)
+        W[f"{i}.o.b"] = _h(sd[a + "out_proj.bias"], dev)
         for ln in ("layer_norm1", "layer_norm2"):
             W[f"{i}.{ln}.g"], W[f"{i}.{ln}.b"] = _h(sd[p + ln + ".weight"], dev), _h(sd[p + ln + ".bias"], dev)
         for fc in ("fc1", "fc2"):
-            W[f"{i}.{fc}.w"], W[f"{i}.{fc}.b"] = _h(sd[p + f"mlp.{fc}.weight"], dev), _h(sd[p + f"mlp.{fc}.bias"], dev)
+            W[f"{i}.{fc}.b"] = _h(sd[p + f"mlp.{fc}.bias"], dev)
+
+
+def pack_layer_weights(get, i: int, d: int, dev) -> Dict[str, torch.Tensor]:
+    """the four weight matrices of layer ``i`` -- ``{i}.qkv.w`` (scale folded into the Q rows), ``{i}.o.w``, ``{i}.fc1.w``,
+    ``{i}.fc2.w`` -- from ``get(key)``, which returns the fp32 weight of ``encoder.layers.{i}.<linear>.weight`` on the host
+    (the state dict's own, or with LoRA deltas merged: ``HipCLIPTextModel.set_lora``)"""
+    qs = (d ** -0.5) * LOG2E
+    p = f"encoder.layers.{i}."
+    a = p + "self_attn."
+    return {f"{i}.qkv.w": _h(torch.cat([get(a + "q_proj.weight") * qs, get(a + "k_proj.weight"), get(a + "v_proj.weight")], 0),
+                             dev),
+            f"{i}.o.w": _h(get(a + "out_proj.weight"), dev), f"{i}.fc1.w": _h(get(p + "mlp.fc1.weight"), dev),
+            f"{i}.fc2.w": _h(get(p + "mlp.fc2.weight"), dev)}
 
 
 def run_layer(W: Dict[str, torch.Tensor], i: int, x: torch.Tensor, *, B: int, Np: int, heads: int, d: int, eps: float,

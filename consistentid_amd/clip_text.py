@@ -21,7 +21,8 @@ from typing import Dict, Optional
 
 import torch
 
-from .clip_layers import ACTIVATIONS, pack_layers, run_layer
+from .clip_layers import ACTIVATIONS, pack_layer_weights, pack_layers, run_layer
+from .lora import TOWER_MODULES, merged_delta
 from .weights import _h
 
 
@@ -107,7 +108,9 @@ class TextEncoderOutput:
 
 
 class HipCLIPTextModel:
-    def __init__(self, state_dict: Dict[str, torch.Tensor], config, device="cuda:0"):
+    def __init__(self, state_dict: Dict[str, torch.Tensor], config, device="cuda:0", keep_base: bool = False):
+        """``keep_base``: keep references to the state dict's six LoRA-able weights per layer on the HOST (no device
+        memory), so that ``set_lora`` can merge community LoRA files later, in place"""
         self.config = config
         self.spec = cfg = text_config(config)
         self.device = dev = torch.device(device)
@@ -133,6 +136,34 @@ class HipCLIPTextModel:
         if self.with_projection:
             W["proj.w"] = _h(sd["text_projection.weight"], dev)                # [projection_dim, C], no bias
         self.W = W
+        self._base: Dict[str, torch.Tensor] = {}
+        if keep_base:
+            for i in range(n_layers):
+                for m in TOWER_MODULES:
+                    self._base[f"encoder.layers.{i}.{m}.weight"] = sd[f"encoder.layers.{i}.{m}.weight"].detach().cpu()
+
+    def require_base(self):
+        """raise the RuntimeError of :meth:`set_lora` now, before a caller changes anything else"""
+        if not self._base:
+            raise RuntimeError("LoRA weights need the text tower's base weights: construct HipCLIPTextModel with keep_base=True")
+
+    def set_lora(self, entries):
+        """the active community LoRA entries ``[(modules, weight), ...]`` (lora.parse_lora's part for this tower; module
+        paths ``text_model.encoder.layers.{i}.<linear>``) -> ``{i}.qkv.w`` (scale folded into the Q rows), ``{i}.o.w``,
+        ``{i}.fc1.w`` and ``{i}.fc2.w``, recomputed in fp32 on the host as base + sum_a weight_a * delta_a and copied into the
+        existing device tensors.  ``[]`` restores the base bit for bit; an entry of weight 0 counts as absent."""
+        self.require_base()
+        entries = [(modules, float(weight)) for modules, weight in entries if float(weight) != 0.0]
+
+        def get(key: str) -> torch.Tensor:
+            w = self._base[key].float()
+            d = merged_delta(entries, "text_model." + key[:-len(".weight")])
+            return w if d is None else w + d
+
+        for i in range(self.n_layers):
+            for name, val in pack_layer_weights(get, i, self.d, self.device).items():
+                self.W[name].copy_(val)
+        return self
 
     def _empty(self, *shape):
         return torch.empty(*shape, dtype=torch.float16, device=self.device)

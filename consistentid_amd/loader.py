@@ -155,10 +155,11 @@ def load_vae_encoder(root: Union[str, os.PathLike], device="cuda:0", subfolder: 
 
 
 def load_text_encoder(folder: Union[str, os.PathLike], device="cuda:0"):
-    """``text_encoder/`` or ``text_encoder_2/`` (transformers CLIPTextModel / CLIPTextModelWithProjection) -> HipCLIPTextModel"""
+    """``text_encoder/`` or ``text_encoder_2/`` (transformers CLIPTextModel / CLIPTextModelWithProjection) -> HipCLIPTextModel,
+    with the base weights kept on the host so that ``load_lora_weights`` can merge text-encoder LoRA later"""
     from .clip_text import HipCLIPTextModel
     cfg, sd = read_component(folder, TEXT_WEIGHT_NAMES)
-    return HipCLIPTextModel(sd, cfg, device=device)
+    return HipCLIPTextModel(sd, cfg, device=device, keep_base=True)
 
 
 def load_tokenizer(folder: Union[str, os.PathLike]):

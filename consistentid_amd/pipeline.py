@@ -22,6 +22,10 @@ family without the pre-loop components, string prompts / ID images raise NotImpl
 instead of silently doing something else; ``output_type`` other than "latent" needs the pipeline to be built with
 ``vae=HipVAEDecoder(...)``.
 
+Community LoRA files (the reference scripts' ``load_lora_weights`` / ``set_adapters`` / ``fuse_lora`` block) are merged into
+the packed weights of the UNet and the text towers in place (lora.py; ``_BasePipeline.load_lora_weights`` and the methods
+after it).
+
 B > 1 is this framework's extension (the reference is effectively B = 1 per call,
 SURVEY.md Appendix B): B independent samples, each with its own CFG pair.
 """
@@ -103,6 +107,9 @@ class _BasePipeline:
         self.lora_rank = lora_rank
         self.device = unet.device
         self._engine = DenoiseEngine(unet, scheduler or DDIMScheduler(), use_graph)
+        # community LoRA files: adapters by name in load order ({target: modules}), active name -> weight, the multiplier of
+        # fuse_lora, and the targets whose packed weights currently hold a LoRA
+        self._lora_adapters, self._lora_active, self._lora_fuse, self._lora_merged = {}, {}, 1.0, set()
 
     def to(self, device=None, *args, **kwargs):
         """``pipe.to(device)`` of the reference scripts (infer.py:21, demo/controlnet_demo.py:60): the engines are built on
@@ -213,6 +220,95 @@ class _BasePipeline:
             self.id_conditioner = HipIDConditioner(self.image_proj_state, self.facial_encoder_state, device=self.device)
         self._engine.invalidate()
         return self
+
+    # -- community LoRA files (lora.py): infer.py's "using LoRA modules in community" block -------------------
+    def _lora_engines(self):
+        return {"unet": self.unet, "text_encoder": self.text_encoder, "text_encoder_2": self.text_encoder_2}
+
+    def _apply_lora(self):
+        """hand every engine its active ``(modules, weight x fuse multiplier)`` entries, in load order; engines no adapter
+        ever touched are left alone.  The step graphs are forgotten as after ``load_ConsistentID_model`` (addresses do not
+        change)."""
+        adapters, active = self._lora_adapters, self._lora_active
+        for target, engine in self._lora_engines().items():
+            entries = [(adapters[n][target], active[n] * self._lora_fuse) for n in adapters if n in active and adapters[n][target]]
+            if engine is not None and (entries or target in self._lora_merged):
+                engine.set_lora(entries)
+                if entries:
+                    self._lora_merged.add(target)
+                else:
+                    self._lora_merged.discard(target)
+        self._engine.invalidate()
+
+    def load_lora_weights(self, pretrained_model_name_or_path_or_dict, weight_name: Optional[str] = None,
+                          adapter_name: Optional[str] = None, **ignored):
+        """``pipe.load_lora_weights(os.path.dirname(lora_path), weight_name=lora_model_name)`` (infer.py, infer_SDXL.py): a
+        kohya or diffusers LoRA file (dict, ``.safetensors``, ``.bin`` / ``.pt``, or folder + ``weight_name``; local files
+        only) is parsed and validated as a whole (lora.parse_lora), stored under ``adapter_name`` (default ``default_0``,
+        ``default_1``, ...), activated at weight 1.0 and merged into the packed weights of the UNet and the text towers in
+        place.  The UNet (and a tower the file addresses) must have been built with ``keep_base=True``, as ``from_pretrained``
+        does.  Nothing is touched when anything is refused."""
+        from . import lora
+        adapters, active = self._lora_adapters, self._lora_active
+        if adapter_name is None:
+            adapter_name = next(f"default_{i}" for i in range(len(adapters) + 1) if f"default_{i}" not in adapters)
+        if adapter_name in adapters:
+            raise ValueError(f"adapter {adapter_name!r} is already loaded: pick another adapter_name or unload_lora_weights()")
+        flat = lora.read_lora(pretrained_model_name_or_path_or_dict, weight_name)
+        engines = self._lora_engines()
+        parsed = lora.parse_lora(flat, self.unet.config, {t: getattr(e, "spec", None) for t, e in engines.items() if t != "unet"})
+        for target, modules in parsed.items():
+            if modules:
+                engines[target].require_base()
+        adapters[adapter_name] = parsed
+        active[adapter_name] = 1.0
+        self._apply_lora()
+        return self
+
+    def set_adapters(self, adapter_names, adapter_weights=None):
+        """``pipe.set_adapters([...], adapter_weights=[...])``: the listed adapters become active with those weights (a float
+        for all, a list, or None = 1.0), every other adapter inactive"""
+        adapters, active = self._lora_adapters, self._lora_active
+        names = [adapter_names] if isinstance(adapter_names, str) else list(adapter_names)
+        if adapter_weights is None or isinstance(adapter_weights, (int, float)):
+            weights = [1.0 if adapter_weights is None else float(adapter_weights)] * len(names)
+        else:
+            weights = [1.0 if w is None else float(w) for w in adapter_weights]
+        if len(weights) != len(names):
+            raise ValueError(f"{len(names)} adapter names with {len(weights)} adapter weights")
+        unknown = [n for n in names if n not in adapters]
+        if unknown or len(set(names)) != len(names):
+            raise ValueError(f"set_adapters: unknown or repeated adapter name(s) {unknown or names}; loaded: {list(adapters)}")
+        active.clear()
+        active.update(zip(names, weights))
+        self._apply_lora()
+        return self
+
+    def fuse_lora(self, lora_scale: float = 1.0, **ignored):
+        """``pipe.fuse_lora()``: the engine's weights are always merged, so this only sets one multiplier on all active
+        adapters; ``unfuse_lora`` resets it and the adapters are active at their own weights again, as in diffusers"""
+        self._lora_fuse = float(lora_scale)
+        self._apply_lora()
+        return self
+
+    def unfuse_lora(self, **ignored):
+        return self.fuse_lora(1.0)
+
+    def unload_lora_weights(self):
+        """drop every adapter; the packed weights return to the base (with the ConsistentID adapter, if loaded) bit for bit"""
+        adapters, active = self._lora_adapters, self._lora_active
+        adapters.clear()
+        active.clear()
+        self._lora_fuse = 1.0
+        self._apply_lora()
+        return self
+
+    def get_active_adapters(self) -> List[str]:
+        adapters, active = self._lora_adapters, self._lora_active
+        return [n for n in adapters if n in active]
+
+    def get_list_adapters(self) -> List[str]:
+        return list(self._lora_adapters)
 
     def prepare_prompt_embeds(self, **encoder_outputs) -> torch.Tensor:
         """``prompt_embeds`` = cat([null, augmented, text_only]) from the upstream encoders' outputs (what ref :479-507

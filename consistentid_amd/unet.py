@@ -110,6 +110,20 @@ class HipUNet:
         self.epoch += 1         # ip_scale is a launch argument kept on the host: captured steps hold its old value
         return self
 
+    def require_base(self):
+        """raise the RuntimeError of :meth:`set_lora` now, before a caller changes anything else"""
+        self.packed.require_base()
+
+    def set_lora(self, entries):
+        """the active community LoRA entries ``[(modules, weight), ...]`` (lora.parse_lora's ``unet`` part) -> packed weights,
+        in place (``PackedUNet.set_lora``; needs ``keep_base=True``); ``[]`` restores the base.  The cached cross-attention
+        K/V are dropped because the K/V projections changed.  No address and no host-side launch argument changes, so the
+        epoch stays."""
+        with torch.cuda.device(self.device):
+            self.packed.set_lora(entries)
+        self._ctx.key = self._ctx.key_ref = None
+        return self
+
     # -- attributes the reference pipelines read (SURVEY.md 8b.3)
     @property
     def in_channels(self) -> int:

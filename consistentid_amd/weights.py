@@ -20,6 +20,7 @@ from typing import Dict, List, Optional
 import torch
 
 from . import ops
+from .lora import merged_delta
 from .unet_spec import UNetConfig, attn_processor_names, walk
 
 LOG2E = 1.4426950408889634
@@ -82,13 +83,18 @@ class PackedUNet:
                  adapter_sd: Optional[Dict[str, torch.Tensor]], device, lora_scale: float = 1.0,
                  encoder_only: bool = False, keep_base: bool = False):
         """``keep_base``: keep the un-merged attention projection weights (fp16, ~10 % of the model) so that
-        ``load_adapter_modules`` can merge a ConsistentID checkpoint's LoRA / ID projections later, in place.
+        ``load_adapter_modules`` can merge a ConsistentID checkpoint's LoRA / ID projections later, in place -- and, on the
+        HOST, references to the source tensors of the other LoRA-able weights (``ff.net.0.proj``, ``ff.net.2``, ``proj_in``,
+        ``proj_out``) for ``set_lora``: no device memory, but the state dict's tensors stay alive.
         ``encoder_only``: ``unet_sd`` is a diffusers ControlNetModel state_dict -- the UNet's encoder half plus
         ``controlnet_cond_embedding.*`` / ``controlnet_down_blocks.*`` / ``controlnet_mid_block.*``."""
         self.cfg = cfg
         self.encoder_only = encoder_only
         self._base_attn: Dict[str, torch.Tensor] = {}
+        self._base_host: Dict[str, torch.Tensor] = {}       # ff / proj_in / proj_out sources for set_lora (host tensors)
+        self._lora: list = []                               # active (modules, weight) entries of set_lora
         self._lora_scale = lora_scale
+        self._adapter_sd, self._adapter_scale = (adapter_sd, lora_scale) if keep_base else (None, lora_scale)
         self.device = device
         self.w: Dict[str, torch.Tensor] = {}
         self.temb_offsets: Dict[str, int] = {}
@@ -187,36 +193,54 @@ class PackedUNet:
                         for a in ("attn1", "attn2"):
                             for w_ in ("to_q", "to_k", "to_v", "to_out.0"):
                                 self._base_attn[f"{b}.{a}.{w_}.weight"] = _h(sd[f"{b}.{a}.{w_}.weight"], dev)
+                        for k_ in (f"{b}.ff.net.0.proj.weight", f"{b}.ff.net.0.proj.bias", f"{b}.ff.net.2.weight"):
+                            self._base_host[k_] = sd[k_].detach().cpu()
                     self.xattn_layers.append(b)
                     # feed forward
-                    W[f"{b}.ff1.w"] = _h(_geglu_interleave(_f(sd[f"{b}.ff.net.0.proj.weight"], dev)), dev)
+                    for k_, v_ in self._ff_weights(b, _f(sd[f"{b}.ff.net.0.proj.weight"], dev),
+                                                   _f(sd[f"{b}.ff.net.0.proj.bias"], dev), _f(sd[f"{b}.ff.net.2.weight"], dev)).items():
+                        W[k_] = v_
                     W[f"{b}.ff1.b"] = _h(_geglu_interleave(_f(sd[f"{b}.ff.net.0.proj.bias"], dev)), dev)
-                    # norm3 folded into the GEGLU projection (same row interleave for W', s and b')
-                    W[f"{b}.ff1.wl"], W[f"{b}.ff1.lns"], W[f"{b}.ff1.lnb"] = fold_ln(
-                        _geglu_interleave(_f(sd[f"{b}.ff.net.0.proj.weight"], dev)), W[f"{b}.norm3.g"], W[f"{b}.norm3.b"],
-                        _geglu_interleave(_f(sd[f"{b}.ff.net.0.proj.bias"], dev)))
-                    W[f"{b}.ff2.w"] = _h(sd[f"{b}.ff.net.2.weight"], dev)
                     W[f"{b}.ff2.b"] = _h(sd[f"{b}.ff.net.2.bias"], dev)
+                if keep_base:
+                    for p in ("proj_in", "proj_out"):
+                        self._base_host[f"{n}.{p}.weight"] = sd[f"{n}.{p}.weight"].detach().cpu()
                 # the last block's ff2 with proj_out as one GEMM (unet._transformer folds where ops.ff2_fold says so)
                 W[f"{n}.ffpo.w"], W[f"{n}.ffpo.b"] = fold_ff2_proj_out(W[f"{b}.ff2.w"], W[f"{b}.ff2.b"], W[f"{n}.proj_out.w"],
                                                                        W[f"{n}.proj_out.b"])
 
-    def _attention_weights(self, b: str, d: int, sd, adapter_sd, proc_index, lora_scale, ln2=None, ln1=None) -> Dict[str, torch.Tensor]:
+    def _ff_weights(self, b: str, w1: torch.Tensor, b1: torch.Tensor, w2: torch.Tensor) -> Dict[str, torch.Tensor]:
+        """packed feed-forward weights of transformer block ``b`` from fp32 ``ff.net.0.proj`` (weight, bias) and ``ff.net.2``:
+        the GEGLU rows interleaved, norm3 folded into the GEGLU projection (same row interleave for W', s and b')"""
+        dev = self.device
+        out: Dict[str, torch.Tensor] = {}
+        w1i, b1i = _geglu_interleave(w1), _geglu_interleave(b1)
+        out[f"{b}.ff1.w"] = _h(w1i, dev)
+        out[f"{b}.ff1.wl"], out[f"{b}.ff1.lns"], out[f"{b}.ff1.lnb"] = fold_ln(w1i, self.w[f"{b}.norm3.g"],
+                                                                                 self.w[f"{b}.norm3.b"], b1i)
+        out[f"{b}.ff2.w"] = _h(w2, dev)
+        return out
+
+    def _attention_weights(self, b: str, d: int, sd, adapter_sd, proc_index, lora_scale, ln2=None, ln1=None,
+                           extra=None) -> Dict[str, torch.Tensor]:
         """packed projection weights of transformer block ``b`` (head dim ``d``): LoRA merged in fp32 (attention.py
         :139-162 / :236-282), softmax scale and log2(e) folded into to_q, q/k/v and K/V pairs concatenated.
         ``ln2`` = (gamma, beta) of the block's norm2: where the second-generation fused cross-attention applies
         (cid_id_xattn3_supported), LayerNorm is folded into the query projection (xattn_pack.fold_layernorm); the two
-        fp32 fold vectors are stored as raw bits in fp16-typed tensors so that the weight arena stays one dtype."""
+        fp32 fold vectors are stored as raw bits in fp16-typed tensors so that the weight arena stays one dtype.
+        ``extra``: module path -> a further fp32 delta or None (``set_lora``), added after the adapter's own LoRA."""
         dev = self.device
         out: Dict[str, torch.Tensor] = {}
 
         def merged(base: str, idx: int, which: str) -> torch.Tensor:
-            w = _f(sd[f"{base}.to_{which}.weight" if which != "out" else f"{base}.to_out.0.weight"], dev)
-            if adapter_sd is None:
-                return w
-            up = _f(adapter_sd[f"{idx}.to_{which}_lora.up.weight"], dev)
-            down = _f(adapter_sd[f"{idx}.to_{which}_lora.down.weight"], dev)
-            return w + lora_scale * (up @ down)
+            path = f"{base}.to_{which}" if which != "out" else f"{base}.to_out.0"
+            w = _f(sd[f"{path}.weight"], dev)
+            if adapter_sd is not None:
+                up = _f(adapter_sd[f"{idx}.to_{which}_lora.up.weight"], dev)
+                down = _f(adapter_sd[f"{idx}.to_{which}_lora.down.weight"], dev)
+                w = w + lora_scale * (up @ down)
+            more = extra(path) if extra is not None else None
+            return w if more is None else w + more
 
         qscale = (d ** -0.5) * LOG2E
         i1 = proc_index[f"{b}.attn1.processor"]
@@ -263,20 +287,77 @@ class PackedUNet:
         bad = [k for k in want if k in adapter_sd and tuple(adapter_sd[k].shape) != tuple(want[k])]
         if missing or unexpected or bad:     # the reference loads strict=True
             raise RuntimeError(f"adapter_modules mismatch: missing {missing[:3]} unexpected {unexpected[:3]} shape {bad[:3]}")
-        scale = self._lora_scale if lora_scale is None else lora_scale
+        # (kept, so that set_lora can combine both kinds of delta in either load order)
+        self._adapter_sd, self._adapter_scale = adapter_sd, self._lora_scale if lora_scale is None else lora_scale
+        self._repack_attention(with_ip=True)
+        return self
+
+    def _repack_attention(self, with_ip: bool):
+        """every packed attention tensor again, in place, from the fp16 base, the kept ConsistentID adapter and the active
+        LoRA entries; ``with_ip``: also the ID stream's ``kv_ip`` and ``ip_scale`` (the adapter's part alone)"""
         downs, mid, ups = walk(self.cfg)
         proc_index = {n: i for i, n in enumerate(attn_processor_names(self.cfg))}
+        extra = (lambda path: merged_delta(self._lora, path, self.device)) if self._lora else None
         for blk in downs + [mid] + ups:
             for t in blk.attentions:
                 for k in range(t.n_layers):
                     b = f"{t.name}.transformer_blocks.{k}"
-                    for name, val in self._attention_weights(b, t.channels // t.heads, self._base_attn, adapter_sd,
-                                                             proc_index, scale,
+                    for name, val in self._attention_weights(b, t.channels // t.heads, self._base_attn, self._adapter_sd,
+                                                             proc_index, self._adapter_scale,
                                                              ln2=(self.w[f"{b}.norm2.g"], self.w[f"{b}.norm2.b"]),
-                                                             ln1=(self.w[f"{b}.norm1.g"], self.w[f"{b}.norm1.b"])).items():
-                        self.w[name].copy_(val)
-                    self.ip_scale[b] = 1.0
+                                                             ln1=(self.w[f"{b}.norm1.g"], self.w[f"{b}.norm1.b"]),
+                                                             extra=extra).items():
+                        if with_ip or not name.endswith(".kv_ip.w"):
+                            self.w[name].copy_(val)
+                    if with_ip:
+                        self.ip_scale[b] = 1.0
+
+    def require_base(self):
+        """raise the RuntimeError of :meth:`set_lora` now, before a caller changes anything else"""
+        if not self._base_attn or not self._base_host:
+            raise RuntimeError("set_lora needs the UNet's base weights: construct with keep_base=True (engines built from the "
+                               "broadcast arena do not carry them)")
+
+    def set_lora(self, entries):
+        """Merge community LoRA deltas IN PLACE (lora.py): ``entries`` is the list of active ``(modules, weight)`` with
+        ``modules`` = {module path: (down, up, alpha)}.  Every LoRA-able weight is recomputed in fp32 as
+        base + lora_scale * up_cid @ down_cid + sum_a weight_a * delta_a (entries summed in their order), pushed through the
+        packing of the constructor and copied into the existing tensors: ``attn1.qkv.{w,wl,lns,lnb}``, ``attn1.out.w``,
+        ``attn2.{wq,wql,wq_lns,wq_lnb,wq_f,wq_p,qs,qb,wo,wo_p,kv_txt.w}``, ``ff1.{w,wl,lns,lnb}``, ``ff2.w``, ``proj_in.w``,
+        ``proj_out.w`` and ``ffpo.{w,b}``.  Biases and ``kv_ip`` do not change, and no address does.  ``set_lora([])``
+        restores the base (with the ConsistentID adapter, if one is loaded) bit for bit; an entry of weight 0 counts as
+        absent, so that -0.0 + 0.0 cannot flip a sign bit.  Needs ``keep_base=True`` at construction."""
+        self.require_base()
+        self._lora = [(modules, float(weight)) for modules, weight in entries if float(weight) != 0.0]
+        dev, W = self.device, self.w
+
+        def more(path: str, w: torch.Tensor) -> torch.Tensor:
+            d = merged_delta(self._lora, path, dev)
+            return w if d is None else w + d
+
+        self._repack_attention(with_ip=False)
+        downs, mid, ups = walk(self.cfg)
+        for blk in downs + [mid] + ups:
+            for t in blk.attentions:
+                n, c = t.name, t.channels
+                for p in ("proj_in", "proj_out"):
+                    W[f"{n}.{p}.w"].copy_(_h(more(f"{n}.{p}", _f(self._base_host[f"{n}.{p}.weight"], dev).reshape(c, c)), dev))
+                for k in range(t.n_layers):
+                    b = f"{n}.transformer_blocks.{k}"
+                    ff = self._ff_weights(b, more(f"{b}.ff.net.0.proj", _f(self._base_host[f"{b}.ff.net.0.proj.weight"], dev)),
+                                          _f(self._base_host[f"{b}.ff.net.0.proj.bias"], dev),
+                                          more(f"{b}.ff.net.2", _f(self._base_host[f"{b}.ff.net.2.weight"], dev)))
+                    for name, val in ff.items():
+                        W[name].copy_(val)
+                w, bias = fold_ff2_proj_out(W[f"{b}.ff2.w"], W[f"{b}.ff2.b"], W[f"{n}.proj_out.w"], W[f"{n}.proj_out.b"])
+                W[f"{n}.ffpo.w"].copy_(w)
+                W[f"{n}.ffpo.b"].copy_(bias)
         return self
+
+    def retained_device_bytes(self) -> int:
+        """device bytes kept beside the packed tensors for later merges (the fp16 attention base of ``keep_base``)"""
+        kept = list(self._base_attn.values()) + list(self._base_host.values()) + list((self._adapter_sd or {}).values())
+        return sum(t.numel() * t.element_size() for t in kept if t.is_cuda)
 
     def nbytes(self) -> int:
         return sum(t.numel() * t.element_size() for t in self.w.values())
@@ -294,6 +375,7 @@ class PackedUNet:
         self = cls.__new__(cls)
         self.cfg, self.device, self.w = cfg, device, w
         self._base_attn, self._lora_scale = {}, meta.get("lora_scale", 1.0)   # (un-merged weights are not broadcast)
+        self._base_host, self._lora, self._adapter_sd, self._adapter_scale = {}, [], None, self._lora_scale
         self.temb_offsets, self.temb_total = meta["temb_offsets"], meta["temb_total"]
         self.ip_scale, self.xattn_layers = meta["ip_scale"], meta["xattn_layers"]
         self.encoder_only = meta.get("encoder_only", False)
