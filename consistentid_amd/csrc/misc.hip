@@ -15,7 +15,7 @@ void cid_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* cid_last_error(void) { return g_err; }
-extern "C" int cid_version(void) { return 107; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4, 104: cid_gemm_plan, 105: cid_cfg_multistep_step_f16, 106: cid_residual_accum_f16, 107: cid_clip_head_f16 / cid_blackout_f16
+extern "C" int cid_version(void) { return 108; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4, 104: cid_gemm_plan, 105: cid_cfg_multistep_step_f16, 106: cid_residual_accum_f16, 107: cid_clip_head_f16 / cid_blackout_f16, 108: cid_cfg_rescale_f16 / cid_cfg_*_step_scaled_f16
 
 namespace {
 
@@ -463,21 +463,29 @@ linear_small_kernel(const half_t* __restrict__ x, int ldx, const half_t* __restr
 }
 
 // ---------------------------------------------------------------- loop glue
+// SCALED (the *_scaled_f16 entries, guidance_rescale): e is multiplied by escale[sample], the factor cfg_rescale_kernel wrote;
+// per_sample % 8 == 0 there, so an 8-half item lies inside one sample.  The trailing two arguments are not read without it:
+// the unscaled instantiation is the kernel as it was.
+template <bool SCALED>
 __global__ void __launch_bounds__(256)
 cfg_ddim_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, const float* __restrict__ coef,
                 float g, const half_t* __restrict__ mask, const half_t* __restrict__ init,
-                const half_t* __restrict__ noise, long n /* B * per_sample, multiple of 8 */) {
+                const half_t* __restrict__ noise, long n /* B * per_sample, multiple of 8 */,
+                const float* __restrict__ escale, int sample_items /* 8-half items per sample */) {
     const float cx = coef[0], ce = coef[1];
     const float ci = mask ? coef[2] : 0.f, cn = mask ? coef[3] : 0.f;
     for (long q = ((long)blockIdx.x * 256 + threadIdx.x) * 8; q < n; q += (long)gridDim.x * 256 * 8) {
         const half8 eu = ld_global_h8(eps + q), ec = ld_global_h8(eps + n + q), xl = ld_global_h8(lat + q);
         half8 mk, in0, nz;
         if (mask) { mk = ld_global_h8(mask + q); in0 = ld_global_h8(init + q); nz = ld_global_h8(noise + q); }
+        float es = 1.f;
+        if constexpr (SCALED) es = escale[(unsigned)(q >> 3) / (unsigned)sample_items];   // fewer than 2^31 items: the entry checks
         half8 o;
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const float u = (float)eu[i], c = (float)ec[i];
-            const float e = u + g * (c - u);
+            float e = u + g * (c - u);
+            if constexpr (SCALED) e *= es;
             float v = cx * (float)xl[i] + ce * e;
             if (mask) {
                 const float m = (float)mk[i];
@@ -493,11 +501,12 @@ cfg_ddim_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, const 
 // per-step value -- coefficients, the ring slot that receives m, the save / restore flags, the noise row -- is read from the
 // 16-word device row, so the launch is the same for every step.  A ring slot, `saved` and `z` are loaded only where the
 // row gives them a non-zero coefficient (wave-uniform branches): an unwritten buffer may hold NaN, and 0 * NaN is NaN.
+template <bool SCALED>      // as cfg_ddim_kernel's
 __global__ void __launch_bounds__(256)
 cfg_multistep_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, float* hist, half_t* saved,
                      const half_t* __restrict__ z, int z_rows, const float* __restrict__ row, float g,
                      const half_t* __restrict__ mask, const half_t* __restrict__ init, const half_t* __restrict__ noise,
-                     long n /* B * per_sample, multiple of 8 */) {
+                     long n /* B * per_sample, multiple of 8 */, const float* __restrict__ escale, int sample_items /* 8-half items per sample */) {
     const float a = row[0], b = row[1], cx = row[2], cm = row[3], cz = z ? row[11] : 0.f;
     const float ch[4] = {row[4], row[5], row[6], row[7]};
     const float ci = mask ? row[9] : 0.f, cn = mask ? row[10] : 0.f;
@@ -508,11 +517,14 @@ cfg_multistep_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, f
     for (long q = ((long)blockIdx.x * 256 + threadIdx.x) * 8; q < n; q += (long)gridDim.x * 256 * 8) {
         const half8 eu = ld_global_h8(eps + q), ec = ld_global_h8(eps + n + q), xl = ld_global_h8(lat + q);
         const half8 src = restore ? ld_global_h8(saved + q) : xl;
+        float es = 1.f;
+        if constexpr (SCALED) es = escale[(unsigned)(q >> 3) / (unsigned)sample_items];   // fewer than 2^31 items: the entry checks
         float m[8], v[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
             const float u = (float)eu[i], c = (float)ec[i];
-            const float e = u + g * (c - u);
+            float e = u + g * (c - u);
+            if constexpr (SCALED) e *= es;
             m[i] = a * (float)xl[i] + b * e;
             v[i] = cx * (float)src[i] + cm * m[i];
         }
@@ -549,6 +561,74 @@ cfg_multistep_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, f
             o[i] = (half_t)r;
         }
         *reinterpret_cast<half8*>(lat + q) = o;
+    }
+}
+
+// guidance_rescale's factor (cid.h, cid_cfg_rescale_f16): one 1024-thread workgroup per sample walks the sample's conditional
+// half c and the guided e = u + g (c - u) once and keeps, for both, a running (count, mean, M2 = sum of squared deviations).
+// An 8-half item enters as its own (8, mean, M2) -- the mean taken relative to the item's first value, so that a constant
+// item has M2 == 0 exactly -- and every merge, thread-local, across the lanes of a wave and across the 16 waves through LDS, is
+// Chan's pairwise update in its delta form: a zero delta leaves the mean untouched, so a constant sample ends at M2 == 0.
+// No sum / sum of squares (it cancels at a non-zero mean), no atomics, a fixed merge order: the same input gives the same bits.
+struct Moments { float n, mc, sc, me, se; };     // count, mean and M2 of c, mean and M2 of e
+
+CID_DEVINL void moments_merge(Moments& a, const Moments& b) {
+    const float n = a.n + b.n;
+    if (n > 0.f) {                               // both empty (a thread past a short sample's end): nothing to merge
+        const float fb = b.n / n, w = a.n * fb;
+        const float dc = b.mc - a.mc, de = b.me - a.me;
+        a.mc += dc * fb;  a.sc += b.sc + dc * dc * w;
+        a.me += de * fb;  a.se += b.se + de * de * w;
+        a.n = n;
+    }
+}
+CID_DEVINL Moments moments_shfl_xor(const Moments& a, int o) {
+    Moments b;
+    b.n = __shfl_xor(a.n, o, 64);   b.mc = __shfl_xor(a.mc, o, 64); b.sc = __shfl_xor(a.sc, o, 64);
+    b.me = __shfl_xor(a.me, o, 64); b.se = __shfl_xor(a.se, o, 64);
+    return b;
+}
+
+__global__ void __launch_bounds__(1024)
+cfg_rescale_kernel(const half_t* __restrict__ eps, float g, float phi, float* __restrict__ escale, long n /* B * per_sample */,
+                   int per_sample /* multiple of 8 */) {
+    __shared__ Moments part[16];
+    const int b = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const half_t* pu = eps + (long)b * per_sample;
+    const half_t* pc = pu + n;
+    Moments acc = {0.f, 0.f, 0.f, 0.f, 0.f};
+    for (int q = tid * 8; q < per_sample; q += 1024 * 8) {
+        const half8 eu = ld_global_h8(pu + q), ec = ld_global_h8(pc + q);
+        float c[8], e[8];
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float u = (float)eu[i];
+            c[i] = (float)ec[i];
+            e[i] = u + g * (c[i] - u);
+        }
+        float dc = 0.f, de = 0.f;
+#pragma unroll
+        for (int i = 1; i < 8; ++i) { dc += c[i] - c[0]; de += e[i] - e[0]; }
+        Moments it = {8.f, c[0] + dc * 0.125f, 0.f, e[0] + de * 0.125f, 0.f};
+#pragma unroll
+        for (int i = 0; i < 8; ++i) {
+            const float rc = c[i] - it.mc, re = e[i] - it.me;
+            it.sc += rc * rc;
+            it.se += re * re;
+        }
+        moments_merge(acc, it);
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) moments_merge(acc, moments_shfl_xor(acc, o));
+    if (lane == 0) part[wave] = acc;
+    __syncthreads();
+    if (wave == 0) {
+        Moments t = {0.f, 0.f, 0.f, 0.f, 0.f};
+        if (lane < 16) t = part[lane];
+#pragma unroll
+        for (int o = 8; o > 0; o >>= 1) moments_merge(t, moments_shfl_xor(t, o));
+        // std(c) / std(e): the two share N - 1.  std(e) == 0 (a constant prediction) -> 1.0, where diffusers divides by zero
+        if (lane == 0) escale[b] = t.se == 0.f ? 1.f : 1.f - phi + phi * sqrtf(t.sc / t.se);
     }
 }
 
@@ -796,10 +876,42 @@ extern "C" int cid_cfg_ddim_step_f16(const cid_half* eps, cid_half* latents, con
                   "cid_cfg_ddim_step_f16: mask/init/noise must come together");
     const long n = (long)B * per_sample;
     CID_CHECK_ARG(B > 0 && per_sample > 0 && n % 8 == 0, "cid_cfg_ddim_step_f16: B * per_sample must be a multiple of 8");
-    hipLaunchKernelGGL(cfg_ddim_kernel, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(cfg_ddim_kernel<false>, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)eps, (half_t*)latents, coef, guidance, (const half_t*)mask, (const half_t*)init,
-                       (const half_t*)noise, n);
+                       (const half_t*)noise, n, (const float*)nullptr, 0);
     CID_CHECK_LAUNCH("cid_cfg_ddim_step_f16");
+    return 0;
+}
+
+extern "C" int cid_cfg_ddim_step_scaled_f16(const cid_half* eps, cid_half* latents, const float* coef, float guidance,
+                                            const cid_half* mask, const cid_half* init, const cid_half* noise,
+                                            int32_t B, int32_t per_sample, const float* escale, cid_stream_t stream) {
+    CID_CHECK_ARG(eps && latents && coef && escale, "cid_cfg_ddim_step_scaled_f16: null pointer");
+    CID_CHECK_ARG((mask == nullptr) == (init == nullptr) && (mask == nullptr) == (noise == nullptr),
+                  "cid_cfg_ddim_step_scaled_f16: mask/init/noise must come together");
+    CID_CHECK_ARG(B > 0 && per_sample > 0 && per_sample % 8 == 0,
+                  "cid_cfg_ddim_step_scaled_f16: per_sample must be a multiple of 8 (an 8-half item lies inside one sample)");
+    const long n = (long)B * per_sample;
+    CID_CHECK_ARG(n / 8 <= 0x7fffffffL, "cid_cfg_ddim_step_scaled_f16: B * per_sample must be below 2^34");
+    hipLaunchKernelGGL(cfg_ddim_kernel<true>, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)eps, (half_t*)latents, coef, guidance, (const half_t*)mask, (const half_t*)init,
+                       (const half_t*)noise, n, escale, (int)(per_sample / 8));
+    CID_CHECK_LAUNCH("cid_cfg_ddim_step_scaled_f16");
+    return 0;
+}
+
+extern "C" int cid_cfg_rescale_f16(const cid_half* eps, float guidance, float rescale, float* escale, int32_t B,
+                                   int32_t per_sample, cid_stream_t stream) {
+    CID_CHECK_ARG(eps && escale, "cid_cfg_rescale_f16: null pointer");
+    CID_CHECK_ARG(B > 0, "cid_cfg_rescale_f16: B must be positive");
+    CID_CHECK_ARG(per_sample > 0 && per_sample % 8 == 0, "cid_cfg_rescale_f16: per_sample must be a positive multiple of 8");
+    // the element counts are kept in fp32 (exact up to 2^24) and a sample is indexed with an int
+    CID_CHECK_ARG(per_sample <= (1 << 24), "cid_cfg_rescale_f16: per_sample must be at most 2^24 (16777216)");
+    CID_CHECK_ARG((uintptr_t)eps % 16 == 0 && (uintptr_t)escale % 4 == 0, "cid_cfg_rescale_f16: eps must be 16-byte aligned");
+    CID_CHECK_ARG(rescale >= 0.f && rescale <= 3.402823466e+38f, "cid_cfg_rescale_f16: rescale must be finite and not negative");
+    hipLaunchKernelGGL(cfg_rescale_kernel, dim3(B), dim3(1024), 0, (hipStream_t)stream, (const half_t*)eps, guidance, rescale,
+                       escale, (long)B * per_sample, (int)per_sample);
+    CID_CHECK_LAUNCH("cid_cfg_rescale_f16");
     return 0;
 }
 
@@ -813,10 +925,32 @@ extern "C" int cid_cfg_multistep_step_f16(const cid_half* eps, cid_half* latents
                   "cid_cfg_multistep_step_f16: mask/init/noise must come together");
     const long n = (long)B * per_sample;
     CID_CHECK_ARG(B > 0 && per_sample > 0 && n % 8 == 0, "cid_cfg_multistep_step_f16: B * per_sample must be a multiple of 8");
-    hipLaunchKernelGGL(cfg_multistep_kernel, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
+    hipLaunchKernelGGL(cfg_multistep_kernel<false>, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z, (int)z_rows,
-                       (const float*)row, guidance, (const half_t*)mask, (const half_t*)init, (const half_t*)noise, n);
+                       (const float*)row, guidance, (const half_t*)mask, (const half_t*)init, (const half_t*)noise, n,
+                       (const float*)nullptr, 0);
     CID_CHECK_LAUNCH("cid_cfg_multistep_step_f16");
+    return 0;
+}
+
+extern "C" int cid_cfg_multistep_step_scaled_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
+                                                 const cid_half* z, int32_t z_rows, const void* row, float guidance,
+                                                 const cid_half* mask, const cid_half* init, const cid_half* noise,
+                                                 int32_t B, int32_t per_sample, const float* escale, cid_stream_t stream) {
+    CID_CHECK_ARG(eps && latents && hist && saved && row && escale, "cid_cfg_multistep_step_scaled_f16: null pointer");
+    CID_CHECK_ARG((z == nullptr) == (z_rows == 0) && z_rows >= 0,
+                  "cid_cfg_multistep_step_scaled_f16: z and z_rows must come together");
+    CID_CHECK_ARG((mask == nullptr) == (init == nullptr) && (mask == nullptr) == (noise == nullptr),
+                  "cid_cfg_multistep_step_scaled_f16: mask/init/noise must come together");
+    CID_CHECK_ARG(B > 0 && per_sample > 0 && per_sample % 8 == 0,
+                  "cid_cfg_multistep_step_scaled_f16: per_sample must be a multiple of 8 (an 8-half item lies inside one sample)");
+    const long n = (long)B * per_sample;
+    CID_CHECK_ARG(n / 8 <= 0x7fffffffL, "cid_cfg_multistep_step_scaled_f16: B * per_sample must be below 2^34");
+    hipLaunchKernelGGL(cfg_multistep_kernel<true>, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z, (int)z_rows,
+                       (const float*)row, guidance, (const half_t*)mask, (const half_t*)init, (const half_t*)noise, n,
+                       escale, (int)(per_sample / 8));
+    CID_CHECK_LAUNCH("cid_cfg_multistep_step_scaled_f16");
     return 0;
 }
 

@@ -26,6 +26,15 @@ from .scheduler import C_IN, DDIMScheduler, pack_step_rows
 from .unet import HipUNet
 
 
+def check_guidance_rescale(guidance_rescale) -> float:
+    """``guidance_rescale`` of the reference ``__call__``s (diffusers 0.23 rescale_noise_cfg's phi) -> float; negative or
+    non-finite values are refused"""
+    phi = float(guidance_rescale)
+    if not np.isfinite(phi) or phi < 0.0:
+        raise ValueError(f"guidance_rescale = {guidance_rescale!r}: a finite value >= 0 (0 = off, the paper suggests 0.7)")
+    return phi
+
+
 def check_eta(scheduler, eta: float, variance_noise=None) -> float:
     """``eta`` / ``variance_noise`` of the reference ``__call__``s (prepare_extra_step_kwargs -> DDIMScheduler.step(eta=,
     variance_noise=)): only DDIM has the term, its eta is in [0, 1], and the noise needs a coefficient.  -> float(eta)"""
@@ -83,8 +92,13 @@ class _StepCoefficients:
     hist: Optional[torch.Tensor] = None         # multistep: fp32 ring of earlier model outputs
     saved: Optional[torch.Tensor] = None        # multistep: the sample PNDM steps from twice
     z: Optional[torch.Tensor] = None            # DDIM eta > 0: the variance noise of every executed step
+    escale: Optional[torch.Tensor] = None       # guidance_rescale: fp32 [B], the factor cid_cfg_rescale_f16 writes every step
+    rescale: float = 0.0
 
     def update(self, eps, lat, guidance_scale, **kw):
+        if self.escale is not None:             # UNet -> factor -> scaled step; the scaled entries of the same two kernels
+            ops.cfg_rescale(eps, guidance_scale, self.rescale, self.escale, B=kw["B"], per_sample=kw["per_sample"])
+            kw["escale"] = self.escale
         if self.hist is None:
             ops.cfg_ddim_step(eps, lat, self.buf, guidance_scale, **kw)
         else:
@@ -121,7 +135,7 @@ class DenoiseEngine:
         self._config_key = None
         self.captures: List[Any] = []           # key of every capture this engine ever made, in order (re-captures show twice)
         self._static: Dict[str, torch.Tensor] = {}
-        self.step_path: Optional[str] = None    # the step launch of the last run: "cfg_ddim" or "cfg_multistep"
+        self.step_path: Optional[str] = None    # the step launch of the last run: "cfg_ddim" or "cfg_multistep", "+rescale" with guidance_rescale
 
     def invalidate(self):
         """forget the captured graphs AND their eager warm-up (the first step after a change must run eagerly again)"""
@@ -226,8 +240,11 @@ class DenoiseEngine:
             control_guidance_end: Union[float, Sequence[float]] = 1.0,
             callback: Optional[Callable[[int, int, torch.Tensor], None]] = None, callback_steps: int = 1,
             scale_initial: bool = True, unet_extra: Optional[torch.Tensor] = None, eta: float = 0.0,
-            variance_noise: Optional[torch.Tensor] = None):
-        """``eta`` > 0 (DDIMScheduler only) with ``variance_noise`` [executed steps, B, C, h, w]: the noise diffusers' DDIM
+            variance_noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0):
+        """``guidance_rescale`` > 0 with ``guidance_scale`` > 1 (diffusers' condition): every step runs UNet ->
+        cid_cfg_rescale_f16 (the per-sample factor, into a static buffer) -> the scaled step entry; at 0 the step is the
+        one it always was.
+        ``eta`` > 0 (DDIMScheduler only) with ``variance_noise`` [executed steps, B, C, h, w]: the noise diffusers' DDIM
         ``step(..., eta=, variance_noise=)`` adds, one tensor per executed step in loop order.
         ``first_step``: the loop runs schedule entries [first_step, S) -- the inpaint pipelines' ``strength`` < 1
         window (get_timesteps, inpaint ref :246-252); the embed switch and the ControlNet keep window count steps from
@@ -238,6 +255,7 @@ class DenoiseEngine:
         ``control_guidance_end`` are sequences with one entry per net."""
         unet, sch, S = self.unet, self.scheduler, self._static_tensor
         eta = check_eta(sch, eta, variance_noise)
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
         dev, B = unet.device, latents.shape[0]
         sch.set_timesteps(num_inference_steps)                      # ref :510, before prepare_latents (:517)
         # prepare_latents (diffusers; ref :517-526) scales the initial noise by the scheduler's init_noise_sigma
@@ -252,6 +270,9 @@ class DenoiseEngine:
         n_ts = len(ts)
         inpaint = inpaint_mask is not None
         coef = self._step_coefficients(lat, inpaint, first_step, eta, variance_noise)
+        if guidance_rescale > 0.0 and guidance_scale > 1.0:
+            coef.escale, coef.rescale = S("escale", torch.ones(B), torch.float32), guidance_rescale
+            self.step_path += "+rescale"
         tvals = torch.tensor(ts.astype(np.float32), device=dev)
         rows = step_rows(n_ts, first_step, start_merge_step, B, null_embeds_post is not None, dev, controlnet is not None)
         t_buf = S("t", torch.zeros(1), torch.float32)
@@ -309,7 +330,7 @@ class DenoiseEngine:
             net.reserve_workspace(B)
         key = (captured_reads(unet, cn.nets), B, tuple(lat.shape), float(guidance_scale), inpaint, time_ids is not None,
                dres is not None, bool(cn.nets), ("multi", len(cn.nets)) if cn.scale_column else cn.fold, extra is not None,
-               coef.hist is not None, coef.z is not None)
+               coef.hist is not None, coef.z is not None, coef.rescale)
         if key != self._config_key:
             self.invalidate()
             self._config_key = key

@@ -303,8 +303,18 @@ def read_scheduler(root: Union[str, os.PathLike]):
     if name not in ("EulerDiscreteScheduler", "DDIMScheduler"):
         warnings.warn(f"{name} is not built: the engine samples with DDIM on its config until pipe.scheduler is replaced "
                       "(infer.py:33 / demo/controlnet_demo.py:67 do that on the next line)")
+    def make(c):
+        # a v-prediction model: the saved prediction type goes on as the explicit keyword from_config asks for (a raw
+        # config alone is refused there); said once, because X.from_config(<this json>) elsewhere needs the same keyword
+        if c.get("prediction_type") == "v_prediction":
+            sch = cls.from_config(c, prediction_type="v_prediction")
+            warnings.warn(f"{spath}: a v-prediction model; {cls.__name__} samples with v-prediction coefficients, and "
+                          "`Other.from_config(pipe.scheduler.config)` keeps that")
+            return sch
+        return cls.from_config(c)
+
     try:
-        return cls.from_config(cfg)
+        return make(cfg)
     except NotImplementedError as e:     # e.g. clip_sample=true of a saved DDIM default: must not block the load
         # drop ONLY the sampling modifiers the engine does not build and keep the rest of the saved config (betas,
         # steps_offset, timestep spacing); defaults only if the schedule itself (beta schedule / prediction type) is foreign
@@ -316,14 +326,15 @@ def read_scheduler(root: Union[str, os.PathLike]):
         schedule = ("use_karras_sigmas", "interpolation_type", "rescale_betas_zero_snr")
         changed = sorted(k for k in schedule if cfg.get(k) not in (None, False, "linear"))
         if changed:
-            raise NotImplementedError(f"{spath}: {changed} change the noise schedule and are not built; the engine would not "
+            raise NotImplementedError(f"{spath}: {changed} change the noise schedule and are not built from a saved config; the engine would not "
                                       f"reproduce the reference's samples -- pass the scheduler to use explicitly, "
-                                      f"`from_pretrained(..., scheduler=DDIMScheduler(...))` (the saved config is then not "
+                                      f"`from_pretrained(..., scheduler=DDIMScheduler(...))` (DDIMScheduler takes "
+                                      f"rescale_betas_zero_snr and prediction_type as arguments; the saved config is then not "
                                       f"read; infer.py:33 replaces the loaded scheduler in the same way)") from e
         kept = {k: v for k, v in cfg.items() if k not in harmless}
         dropped = sorted(k for k in harmless if cfg.get(k) not in (None, False))
         try:
-            sch = cls.from_config(kept)
+            sch = make(kept)
             warnings.warn(f"{spath}: {e}; the engine does not build {dropped} and IGNORES them (samples differ from a "
                           "scheduler that applies them); the rest of the saved scheduler config is kept")
             return sch

@@ -739,13 +739,40 @@ def linear_small(x: torch.Tensor, w: torch.Tensor, b: Optional[torch.Tensor], ou
     return out
 
 
+def cfg_rescale(eps: torch.Tensor, guidance: float, rescale: float, escale: torch.Tensor, *, B: int, per_sample: int):
+    """guidance_rescale's per-sample factor (cid.h, cid_cfg_rescale_f16): ``eps`` fp16 [2B, per_sample] (uncond first) ->
+    ``escale`` fp32 [B] = 1 - rescale + rescale * std(cond) / std(guided); one launch, deterministic"""
+    lib = _lib.load()
+    _req(eps, "cfg_rescale.eps")
+    _req(escale, "cfg_rescale.escale", torch.float32)
+    if eps.numel() != 2 * B * per_sample or escale.numel() != B:
+        raise _lib.CidError(f"cfg_rescale: eps / escale hold {eps.numel()} / {escale.numel()} elements; B = {B}, per_sample = "
+                            f"{per_sample} need {2 * B * per_sample} / {B}")
+    check(lib.cid_cfg_rescale_f16(_p(eps), float(guidance), float(rescale), _p(escale), B, per_sample, _stream()),
+          "cid_cfg_rescale_f16")
+    return escale
+
+
+def _req_escale(escale: torch.Tensor, B: int, what: str):
+    _req(escale, f"{what}.escale", torch.float32)
+    if escale.numel() != B:
+        raise _lib.CidError(f"{what}.escale: {escale.numel()} elements, B = {B}")
+
+
 def cfg_ddim_step(eps: torch.Tensor, latents: torch.Tensor, coef: torch.Tensor, guidance: float, *, B: int,
                   per_sample: int, mask: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None,
-                  noise: Optional[torch.Tensor] = None):
+                  noise: Optional[torch.Tensor] = None, escale: Optional[torch.Tensor] = None):
+    """``escale`` fp32 [B] (``cfg_rescale``): the guided prediction of sample b is multiplied by escale[b]
+    (cid_cfg_ddim_step_scaled_f16); None is the unscaled entry"""
     lib = _lib.load()
     _req(eps, "cfg_ddim_step.eps")
     _req(latents, "cfg_ddim_step.latents")
     _req(coef, "cfg_ddim_step.coef", torch.float32)
+    if escale is not None:
+        _req_escale(escale, B, "cfg_ddim_step")
+        check(lib.cid_cfg_ddim_step_scaled_f16(_p(eps), _p(latents), _p(coef), float(guidance), _p(mask), _p(init), _p(noise),
+                                               B, per_sample, _p(escale), _stream()), "cid_cfg_ddim_step_scaled_f16")
+        return latents
     check(lib.cid_cfg_ddim_step_f16(_p(eps), _p(latents), _p(coef), float(guidance), _p(mask), _p(init), _p(noise),
                                     B, per_sample, _stream()), "cid_cfg_ddim_step_f16")
     return latents
@@ -754,10 +781,10 @@ def cfg_ddim_step(eps: torch.Tensor, latents: torch.Tensor, coef: torch.Tensor, 
 def cfg_multistep_step(eps: torch.Tensor, latents: torch.Tensor, hist: torch.Tensor, saved: torch.Tensor, row: torch.Tensor,
                        guidance: float, *, B: int, per_sample: int, z: Optional[torch.Tensor] = None,
                        mask: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None,
-                       noise: Optional[torch.Tensor] = None):
+                       noise: Optional[torch.Tensor] = None, escale: Optional[torch.Tensor] = None):
     """CFG + one step of PNDM / DPM-Solver++ 2M / DDIM with eta (cid.h, "multistep row").  ``row``: 16 fp32 words on the
     device (the integer words bit-cast), ``hist`` fp32 [4, B * per_sample], ``saved`` fp16 [B * per_sample], ``z`` fp16
-    [rows, B * per_sample] or None."""
+    [rows, B * per_sample] or None; ``escale`` fp32 [B] or None as in ``cfg_ddim_step``."""
     lib = _lib.load()
     n = B * per_sample
     _req(eps, "cfg_multistep_step.eps")
@@ -780,6 +807,12 @@ def cfg_multistep_step(eps: torch.Tensor, latents: torch.Tensor, hist: torch.Ten
             _req(t, f"cfg_multistep_step.{name}")
             if t.numel() != n:
                 raise _lib.CidError(f"cfg_multistep_step.{name}: {t.numel()} elements, B * per_sample = {n}")
+    if escale is not None:
+        _req_escale(escale, B, "cfg_multistep_step")
+        check(lib.cid_cfg_multistep_step_scaled_f16(_p(eps), _p(latents), _p(hist), _p(saved), _p(z), z_rows, _p(row),
+                                                    float(guidance), _p(mask), _p(init), _p(noise), B, per_sample,
+                                                    _p(escale), _stream()), "cid_cfg_multistep_step_scaled_f16")
+        return latents
     check(lib.cid_cfg_multistep_step_f16(_p(eps), _p(latents), _p(hist), _p(saved), _p(z), z_rows, _p(row), float(guidance),
                                          _p(mask), _p(init), _p(noise), B, per_sample, _stream()),
           "cid_cfg_multistep_step_f16")

@@ -39,7 +39,7 @@ import numpy as np
 import torch
 
 from .controlnet import HipMultiControlNet, prepare_control_arguments
-from .denoise import DenoiseEngine, check_eta
+from .denoise import DenoiseEngine, check_eta, check_guidance_rescale
 from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler, PNDMScheduler  # noqa: F401
 from .unet import HipUNet
 
@@ -573,11 +573,15 @@ class ConsistentIDStableDiffusionPipeline(_IDPreLoop, _SD15PromptEncoding, _Base
                  negative_prompt_embeds=None, output_type: Optional[str] = "pil", return_dict: bool = True,
                  cross_attention_kwargs=None, original_size=None, target_size=None, callback=None,
                  callback_steps: int = 1, input_id_images=None, start_merge_step: int = 0,
-                 class_tokens_mask=None, prompt_embeds_text_only=None, variance_noise: Optional[torch.Tensor] = None):
-        """``pipe(prompt, input_id_images=[face], ...)`` runs the reference's pre-loop (prepare_id_prompt_embeds) and, without
+                 class_tokens_mask=None, prompt_embeds_text_only=None, variance_noise: Optional[torch.Tensor] = None,
+                 guidance_rescale: float = 0.0):
+        """``guidance_rescale`` (diffusers 0.23 StableDiffusionPipeline; rescale_noise_cfg's phi): > 0 rescales the guided
+        prediction to the conditional one's standard deviation, per sample and step.
+        ``pipe(prompt, input_id_images=[face], ...)`` runs the reference's pre-loop (prepare_id_prompt_embeds) and, without
         ``latents``, draws them like diffusers' prepare_latents (randn_tensor on the generator's device); or pass
         ``prompt_embeds`` (cat([null, augmented, text_only])) and ``latents`` directly.  ``num_images_per_prompt`` = n on the
         prompt path: n samples of the one identity -- the embeds repeated n times, the latents one draw of [n, C, h, w]."""
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
         if self._takes_id_pre_loop(prompt, input_id_images, prompt_embeds):
             prompt_embeds = self._id_call_prompt_embeds(prompt, input_id_images, negative_prompt, num_images_per_prompt)
             n = prompt_embeds.shape[0] // 3
@@ -596,7 +600,8 @@ class ConsistentIDStableDiffusionPipeline(_IDPreLoop, _SD15PromptEncoding, _Base
         null_e, aug_e, text_e = self._split(prompt_embeds)
         out = self._engine.run(latents, null_e, aug_e, text_e, num_inference_steps=num_inference_steps,
                                guidance_scale=guidance_scale, start_merge_step=start_merge_step,
-                               callback=callback, callback_steps=callback_steps, eta=eta, variance_noise=variance_noise)
+                               callback=callback, callback_steps=callback_steps, eta=eta, variance_noise=variance_noise,
+                               guidance_rescale=guidance_rescale)
         out, has_nsfw_concept = self._postprocess_checked(out, output_type, legacy_numpy=True)
         return self._output(out, return_dict, has_nsfw_concept)
 
@@ -652,7 +657,9 @@ class ConsistentIDStableDiffusionXLPipeline(_BasePipeline):
                  variance_noise: Optional[torch.Tensor] = None):
         """pooled_prompt_embeds = pooled embeds used AFTER the merge step, pooled_prompt_embeds_text_only
         BEFORE it, negative_pooled_prompt_embeds for the unconditional half (ref SDXL :620-631);
-        add_time_ids [2B, 6] (ref :531-539)."""
+        add_time_ids [2B, 6] (ref :531-539).  ``guidance_rescale``: diffusers' rescale_noise_cfg, which the reference's loop
+        has commented out (ref SDXL :652-654); honoured here, 0 = the reference's behaviour."""
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
         self._check_hot_path_inputs(prompt, input_id_images, prompt_embeds, latents, output_type)
         assert guidance_scale >= 1.0
         variance_noise = self._variance_noise(eta, generator, variance_noise, latents, num_inference_steps)
@@ -688,7 +695,8 @@ class ConsistentIDStableDiffusionXLPipeline(_BasePipeline):
                                guidance_scale=guidance_scale, start_merge_step=start_merge_step, null_embeds_post=null_post,
                                pooled=(negative_pooled_prompt_embeds, pooled_prompt_embeds_text_only,
                                        pooled_prompt_embeds), time_ids=add_time_ids,
-                               callback=callback, callback_steps=callback_steps, eta=eta, variance_noise=variance_noise)
+                               callback=callback, callback_steps=callback_steps, eta=eta, variance_noise=variance_noise,
+                               guidance_rescale=guidance_rescale)
         out = self._postprocess(out, output_type)
         if not return_dict:
             return (out,)
@@ -842,8 +850,10 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                  input_id_images=None, start_merge_step: int = 0, class_tokens_mask=None,
                  prompt_embeds_text_only=None, image_latents: Optional[torch.Tensor] = None,
                  noise: Optional[torch.Tensor] = None, mask_latents: Optional[torch.Tensor] = None,
-                 down_block_res_samples=None, mid_block_res_sample=None, variance_noise: Optional[torch.Tensor] = None):
-        """The reference's call, ``pipe(prompt, input_id_images=face, mask_image=mask, height=, width=, ...)``, runs its whole
+                 down_block_res_samples=None, mid_block_res_sample=None, variance_noise: Optional[torch.Tensor] = None,
+                 guidance_rescale: float = 0.0):
+        """``guidance_rescale``: an engine extension here (diffusers' inpaint pipelines do not take it), as in
+        ConsistentIDStableDiffusionPipeline.__call__.  The reference's call, ``pipe(prompt, input_id_images=face, mask_image=mask, height=, width=, ...)``, runs its whole
         pre-loop: the ID pre-loop on ``input_id_images[0]`` (prepare_id_prompt_embeds; ref :157-229), image_prep.py on the
         PIL init image and mask (ref :232-239), the VAE encode on ``vae_encoder`` (ref :255-291).  ``prompt_embeds``
         (cat([null, augmented, text_only])) replaces the first part; the pre-computed ``image_latents`` (init latents),
@@ -863,14 +873,17 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                              callback=callback, callback_steps=callback_steps, input_id_images=input_id_images,
                              start_merge_step=start_merge_step, image_latents=image_latents, noise=noise,
                              mask_latents=mask_latents, down_block_res_samples=down_block_res_samples,
-                             mid_block_res_sample=mid_block_res_sample, variance_noise=variance_noise)
+                             mid_block_res_sample=mid_block_res_sample, variance_noise=variance_noise,
+                             guidance_rescale=guidance_rescale)
 
     def _inpaint(self, *, prompt, image, mask_image, masked_image_latents, height, width, strength, num_inference_steps,
                  guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents, prompt_embeds,
                  output_type, return_dict, callback, callback_steps, input_id_images, start_merge_step, image_latents,
-                 noise, mask_latents, down_block_res_samples, mid_block_res_sample, variance_noise, control=None):
+                 noise, mask_latents, down_block_res_samples, mid_block_res_sample, variance_noise, control=None,
+                 guidance_rescale: float = 0.0):
         """The body both inpaint ``__call__``s share (inpaint ref :127-359, CN :180-456).  ``control``: the ControlNet
         pipeline's (control_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end)."""
+        guidance_rescale = check_guidance_rescale(guidance_rescale)
         prompt_embeds, image, mask_image, height, width, normalize = self._call_inputs(
             prompt, input_id_images, prompt_embeds, negative_prompt, num_images_per_prompt, image, mask_image, height, width)
         if image is not None or mask_image is not None:
@@ -894,7 +907,8 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                                down_residuals=down_block_res_samples, mid_residual=mid_block_res_sample,
                                inpaint_mask=b_mask, inpaint_init=b_init, inpaint_noise=b_noise,
                                callback=callback, callback_steps=callback_steps, first_step=first, scale_initial=scaled,
-                               unet_extra=extra, eta=eta, variance_noise=variance_noise, **cn_kw)
+                               unet_extra=extra, eta=eta, variance_noise=variance_noise, guidance_rescale=guidance_rescale,
+                               **cn_kw)
         out, has_nsfw_concept = self._postprocess_checked(out, output_type)
         return self._output(out, return_dict, has_nsfw_concept)
 
@@ -931,8 +945,9 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
                  input_id_images=None, start_merge_step: int = 0, class_tokens_mask=None, prompt_embeds_text_only=None,
                  image_latents: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                  mask_latents: Optional[torch.Tensor] = None, down_block_res_samples=None, mid_block_res_sample=None,
-                 masked_image_latents: Optional[torch.Tensor] = None, variance_noise: Optional[torch.Tensor] = None):
-        """``prompt`` / ``input_id_images`` / ``image`` / ``mask_image``: as in
+                 masked_image_latents: Optional[torch.Tensor] = None, variance_noise: Optional[torch.Tensor] = None,
+                 guidance_rescale: float = 0.0):
+        """``prompt`` / ``input_id_images`` / ``image`` / ``mask_image`` / ``guidance_rescale``: as in
         StableDiffusionInpaintConsistentIDPipeline.__call__ (CN :180-265).  ``control_image``: a float tensor [B, 3, 8h, 8w]
         in [0, 1], or one PIL image (or a list of one), converted to RGB and resized to the final height x width by
         image_prep.preprocess_control (CN :267-280).
@@ -954,4 +969,4 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
                              mask_latents=mask_latents, down_block_res_samples=down_block_res_samples,
                              mid_block_res_sample=mid_block_res_sample, variance_noise=variance_noise,
                              control=(control_image, controlnet_conditioning_scale, control_guidance_start,
-                             control_guidance_end))
+                             control_guidance_end), guidance_rescale=guidance_rescale)

@@ -12,7 +12,12 @@ in cid_cfg_ddim_step_f16 which reads the coefficients from device memory.
 output, earlier model outputs and a noise tensor.  They run in cid_cfg_multistep_step_f16, and each class writes its
 per-step rows (include/cid.h, "multistep row") by simulating its own state machine over the schedule entries the loop
 will run: ``coefficient_rows(inpaint, first_step, dtype)``.  The three algorithms are restated from the published
-diffusers 0.23 schedulers, UNPINNED like oracle/ddim.py."""
+diffusers 0.23 schedulers, UNPINNED like oracle/ddim.py.
+
+``prediction_type="v_prediction"`` (all four classes) and ``DDIMScheduler(rescale_betas_zero_snr=True)`` -- constructor
+arguments, or keywords of ``from_config(config, **kwargs)`` -- are other coefficients in the same tables: the update stays linear in the sample and the model output.  A
+schedule entry whose coefficients are not finite -- epsilon prediction at a timestep whose alphas_cumprod is 0, the terminal
+step of a zero-SNR schedule -- raises ValueError when the table is built."""
 from __future__ import annotations
 
 from typing import List, Tuple
@@ -20,6 +25,7 @@ from typing import List, Tuple
 import numpy as np
 
 SPACINGS = ("leading", "linspace", "trailing")
+PREDICTION_TYPES = ("epsilon", "v_prediction")
 
 ROW_WORDS = 16          # cid_cfg_multistep_step_f16's device row: words 0..11 fp32, 12..15 int32
 C_IN, C_Z = 8, 11       # word of the model-input scale (16-byte aligned: conv_in reads it in place) / of z's coefficient
@@ -51,18 +57,74 @@ def _train_alphas_cumprod(beta_start: float, beta_end: float, T: int) -> np.ndar
     return np.cumprod((1.0 - betas).astype(np.float32), dtype=np.float32)
 
 
-def _config_args(config, accepted) -> dict:
+def rescale_zero_terminal_snr(betas: np.ndarray) -> np.ndarray:
+    """diffusers 0.23 ``rescale_zero_terminal_snr`` (Algorithm 1 of "Common Diffusion Noise Schedules and Sample Steps Are
+    Flawed") in float32 like the original: sqrt(alphas_cumprod) is shifted so that its last value is 0 and scaled so that its
+    first one is kept; the betas are read back from the ratios.  The last beta is exactly 1, so alphas_cumprod[-1] == 0."""
+    betas = np.asarray(betas, dtype=np.float32)
+    bar_sqrt = np.sqrt(np.cumprod(np.float32(1.0) - betas, dtype=np.float32))
+    first, last = bar_sqrt[0].copy(), bar_sqrt[-1].copy()
+    bar_sqrt = (bar_sqrt - last) * (first / (first - last))
+    bar = bar_sqrt ** 2
+    alphas = np.concatenate([bar[0:1], bar[1:] / bar[:-1]]).astype(np.float32)
+    return np.float32(1.0) - alphas
+
+
+def _check_prediction_type(prediction_type: str) -> str:
+    if prediction_type not in PREDICTION_TYPES:
+        raise NotImplementedError(f"prediction_type {prediction_type!r}: the coefficient tables implement {PREDICTION_TYPES}")
+    return prediction_type
+
+
+def _check_finite(rows: np.ndarray, sch, what: str) -> np.ndarray:
+    """the table-build-time refusal of a schedule the prediction type cannot step from"""
+    flat = np.asarray(rows, dtype=np.float64)
+    bad = np.flatnonzero(~np.isfinite(flat.reshape(len(flat), -1)).all(axis=1))
+    if len(bad):
+        ts = [float(sch.timesteps[i]) for i in bad]
+        raise ValueError(f"{type(sch).__name__}.{what}: the coefficients of schedule entries {bad.tolist()} (timesteps {ts}) are "
+                         f"not finite: with prediction_type {sch.prediction_type!r} the sample cannot be predicted from the "
+                         "model output where alphas_cumprod is 0 (rescale_betas_zero_snr with a schedule that starts at the "
+                         "last training timestep needs prediction_type='v_prediction')")
+    return rows
+
+
+class SchedulerConfig(dict):
+    """``scheduler.config`` of an engine scheduler: the dict the reference scripts hand to ``Other.from_config(...)``.  Being
+    this type is what tells ``from_config`` that the values describe a scheduler these tables already implement -- a
+    v-prediction or zero-SNR scheduler's own config is taken over as it is -- where a raw diffusers config dict that names
+    v-prediction or zero-SNR betas needs them confirmed as keywords (``_config_args``)."""
+
+
+def _config_args(config, accepted, overrides=None) -> dict:
     """the arguments of a diffusers scheduler config (dict or FrozenDict-like) that this engine scheduler takes; refuses
-    what the coefficient tables do not implement instead of silently computing something else"""
-    cfg = dict(config)
+    what the coefficient tables do not implement instead of silently computing something else.  ``overrides``: the keyword
+    arguments of ``from_config(config, **kwargs)``, which replace the config's values as in diffusers.
+    ``prediction_type="v_prediction"`` and ``rescale_betas_zero_snr`` are taken from an engine scheduler's own ``.config``
+    (``Other.from_config(pipe.scheduler.config)`` keeps the pipeline's prediction type) and from keywords; a RAW config dict
+    that names one of them is refused as it was before they were built -- callers that probe a config for support rely on
+    that answer -- and ``loader.read_scheduler`` passes the saved prediction type on as a keyword."""
+    cfg, overrides = dict(config), dict(overrides or {})
+    own = isinstance(config, SchedulerConfig)
+    unknown = sorted(set(overrides) - {"prediction_type", *accepted})
+    if unknown:
+        raise TypeError(f"from_config: unexpected keyword arguments {unknown}")
     if cfg.get("beta_schedule", "scaled_linear") != "scaled_linear" or cfg.get("trained_betas") is not None:
         raise NotImplementedError(f"beta_schedule {cfg.get('beta_schedule')!r} / trained_betas: only scaled_linear is built")
-    if cfg.get("prediction_type", "epsilon") != "epsilon":
-        raise NotImplementedError(f"prediction_type {cfg.get('prediction_type')!r}: the step kernel implements epsilon prediction")
+    if not own and "prediction_type" not in overrides and cfg.get("prediction_type", "epsilon") != "epsilon":
+        raise NotImplementedError(f"prediction_type {cfg.get('prediction_type')!r} in a raw scheduler config is not taken over: "
+                                  f"pass it explicitly, from_config(config, prediction_type=...) with one of {PREDICTION_TYPES}")
+    zero_snr = bool(cfg.get("rescale_betas_zero_snr")) and "rescale_betas_zero_snr" not in overrides
+    if zero_snr and "rescale_betas_zero_snr" not in accepted:
+        raise NotImplementedError("rescale_betas_zero_snr: zero-SNR betas are built for DDIMScheduler only (the one of these "
+                                  "classes that has the flag in diffusers 0.23)")
     if cfg.get("use_karras_sigmas") or cfg.get("interpolation_type", "linear") != "linear" or cfg.get("clip_sample") \
-            or cfg.get("thresholding") or cfg.get("rescale_betas_zero_snr"):
-        raise NotImplementedError("karras sigmas / log-linear interpolation / clip_sample / thresholding / zero-SNR betas are not built")
-    return {k: cfg[k] for k in accepted if k in cfg and cfg[k] is not None}
+            or cfg.get("thresholding") or (zero_snr and not own):
+        raise NotImplementedError("karras sigmas / log-linear interpolation / clip_sample / thresholding are not built; zero-SNR "
+                                  "betas in a raw scheduler config are not taken over (DDIMScheduler takes rescale_betas_zero_snr "
+                                  "as a keyword)")
+    cfg.update(overrides)
+    return {k: cfg[k] for k in ("prediction_type", *accepted) if k in cfg and cfg[k] is not None}
 
 
 def _spaced_timesteps(T: int, n: int, spacing: str, offset: int) -> np.ndarray:
@@ -90,11 +152,15 @@ class DDIMScheduler:
     multistep = False        # eta = 0 is cid_cfg_ddim_step_f16's two-coefficient update; eta > 0 takes coefficient_rows
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
-                 steps_offset: int = 1, set_alpha_to_one: bool = False, timestep_spacing: str = "leading"):
+                 steps_offset: int = 1, set_alpha_to_one: bool = False, timestep_spacing: str = "leading",
+                 prediction_type: str = "epsilon", rescale_betas_zero_snr: bool = False):
         if timestep_spacing not in SPACINGS:
             raise ValueError(f"timestep_spacing {timestep_spacing!r}: one of {SPACINGS}")
+        self.prediction_type = _check_prediction_type(prediction_type)
         betas = np.linspace(np.float32(beta_start) ** 0.5, np.float32(beta_end) ** 0.5, num_train_timesteps,
                             dtype=np.float32) ** 2
+        if rescale_betas_zero_snr:
+            betas = rescale_zero_terminal_snr(betas)
         self.alphas_cumprod = np.cumprod((1.0 - betas).astype(np.float32), dtype=np.float32)
         self.final_alpha_cumprod = np.float32(1.0) if set_alpha_to_one else self.alphas_cumprod[0]
         self.num_train_timesteps = num_train_timesteps
@@ -102,22 +168,36 @@ class DDIMScheduler:
         self.timesteps: np.ndarray = np.zeros(0, dtype=np.int64)
         self.num_inference_steps = 0
         # what ``OtherScheduler.from_config(pipe.scheduler.config)`` of the reference scripts reads
-        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+        self.config = SchedulerConfig(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                            beta_schedule="scaled_linear", trained_betas=None, steps_offset=steps_offset,
-                           set_alpha_to_one=set_alpha_to_one, timestep_spacing=timestep_spacing, prediction_type="epsilon",
-                           clip_sample=False)
+                           set_alpha_to_one=set_alpha_to_one, timestep_spacing=timestep_spacing,
+                           prediction_type=prediction_type, clip_sample=False,
+                           rescale_betas_zero_snr=bool(rescale_betas_zero_snr))
 
     @classmethod
-    def from_config(cls, config) -> "DDIMScheduler":
+    def from_config(cls, config, **kwargs) -> "DDIMScheduler":
         """``DDIMScheduler.from_config(pipe.scheduler.config)`` (demo/controlnet_demo.py:67): a diffusers scheduler config
         (the dict of ``scheduler/scheduler_config.json``, or ``scheduler.config``) -> the engine's coefficient tables"""
         return cls(**_config_args(config, ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "set_alpha_to_one",
-                                           "timestep_spacing")))
+                                           "timestep_spacing", "rescale_betas_zero_snr"), kwargs))
 
     def set_timesteps(self, num_inference_steps: int, device=None):
         self.num_inference_steps = num_inference_steps
         ts = _spaced_timesteps(self.num_train_timesteps, num_inference_steps, self.timestep_spacing, self.steps_offset)
         self.timesteps = ts.round().astype(np.int64)
+
+    def _step_pair(self, t: int, sigma: float = 0.0) -> Tuple[float, float]:
+        """(c_x, c_out) of x' = c_x x + c_out model_output [+ sigma z].  v-prediction: x0 = sqrt(a_t) x - sqrt(1 - a_t) v and
+        eps = sqrt(a_t) v + sqrt(1 - a_t) x go into x' = sqrt(a_p) x0 + sqrt(1 - a_p - sigma^2) eps as they are -- nothing is
+        divided by sqrt(a_t), so the pair is finite at a_t = 0 (the terminal step of a zero-SNR schedule).  Epsilon
+        prediction divides there: inf / nan, which the table builders refuse."""
+        a_t, a_p = self.alphas(t)
+        d = (1.0 - a_p - sigma * sigma) ** 0.5
+        if self.prediction_type == "v_prediction":
+            return (a_p ** 0.5) * (a_t ** 0.5) + d * ((1.0 - a_t) ** 0.5), d * (a_t ** 0.5) - (a_p ** 0.5) * ((1.0 - a_t) ** 0.5)
+        if a_t == 0.0:
+            return float("inf"), float("nan")
+        return (a_p / a_t) ** 0.5, d - (a_p ** 0.5) * ((1.0 - a_t) ** 0.5) / (a_t ** 0.5)
 
     def scale_model_input(self, sample, t=None):
         return sample
@@ -129,11 +209,8 @@ class DDIMScheduler:
         return a_t, a_p
 
     def step_coefficients(self, t: int) -> Tuple[float, float]:
-        """x_prev = c_x * x + c_eps * eps  (eta = 0)."""
-        a_t, a_p = self.alphas(t)
-        c_x = (a_p / a_t) ** 0.5
-        c_eps = (1.0 - a_p) ** 0.5 - (a_p ** 0.5) * ((1.0 - a_t) ** 0.5) / (a_t ** 0.5)
-        return c_x, c_eps
+        """x_prev = c_x * x + c_out * model_output  (eta = 0; the model output is eps or v, by ``prediction_type``)."""
+        return self._step_pair(t)
 
     def add_noise_coefficients(self, t) -> Tuple[float, float]:
         a = float(self.alphas_cumprod[int(t)])
@@ -150,22 +227,23 @@ class DDIMScheduler:
             if inpaint and i < len(ts) - 1:
                 ci, cn = self.add_noise_coefficients(int(ts[i + 1]))
             rows.append([c_x, c_e, ci, cn, 1.0])          # last column: model-input scale (identity for DDIM)
-        return np.asarray(rows, dtype=np.float32)
+        return _check_finite(np.asarray(rows, dtype=np.float32), self, "coefficient_table")
 
     def coefficient_rows(self, inpaint: bool = False, first_step: int = 0, dtype=np.float32, eta: float = 0.0) -> np.ndarray:
         """[len(timesteps), 16] multistep rows of DDIM with ``eta`` (diffusers' ``step(..., eta=, variance_noise=)``):
         sigma_t = eta sqrt((1 - a_prev) / (1 - a_t) (1 - a_t / a_prev)),
         x' = sqrt(a_prev) (x - sqrt(1 - a_t) e) / sqrt(a_t) + sqrt(1 - a_prev - sigma_t^2) e + sigma_t z[k],
-        k counting the executed steps from ``first_step``.  The engine takes this path for eta > 0 only."""
+        k counting the executed steps from ``first_step``; v-prediction as in ``_step_pair``.  The engine takes this path for
+        eta > 0 only."""
         ts = self.timesteps
         rows = [_idle_row() for _ in range(min(first_step, len(ts)))]
         for i in range(first_step, len(ts)):
             a_t, a_p = self.alphas(int(ts[i]))
             sigma = float(eta) * ((1.0 - a_p) / (1.0 - a_t) * (1.0 - a_t / a_p)) ** 0.5
-            c_e = (1.0 - a_p - sigma * sigma) ** 0.5 - (a_p ** 0.5) * ((1.0 - a_t) ** 0.5) / (a_t ** 0.5)
+            c_x, c_e = self._step_pair(int(ts[i]), sigma)
             ci, cn = _next_blend(self, inpaint, i)
-            rows.append(_row(c_x=(a_p / a_t) ** 0.5, c_m=c_e, c_z=sigma, c_init=ci, c_noise=cn, z_row=i - first_step))
-        return np.asarray(rows, dtype=np.float64).reshape(-1, ROW_WORDS).astype(dtype)
+            rows.append(_row(c_x=c_x, c_m=c_e, c_z=sigma, c_init=ci, c_noise=cn, z_row=i - first_step))
+        return _check_finite(np.asarray(rows, dtype=np.float64).reshape(-1, ROW_WORDS), self, "coefficient_rows").astype(dtype)
 
 
 class EulerDiscreteScheduler:
@@ -178,12 +256,13 @@ class EulerDiscreteScheduler:
     multistep = False
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
-                 steps_offset: int = 1, timestep_spacing: str = "leading"):
+                 steps_offset: int = 1, timestep_spacing: str = "leading", prediction_type: str = "epsilon"):
         # "leading" is what ``EulerDiscreteScheduler.from_config(pipe.scheduler.config)`` inherits from the base models'
         # PNDM / DDIM / Euler scheduler configs (a loaded scheduler's config carries every init argument, defaults included);
         # diffusers' own class default would be "linspace" -- pass the base model's config to from_config to be sure
         if timestep_spacing not in SPACINGS:
             raise ValueError(f"timestep_spacing {timestep_spacing!r}: one of {SPACINGS}")
+        self.prediction_type = _check_prediction_type(prediction_type)
         betas = np.linspace(np.float32(beta_start) ** 0.5, np.float32(beta_end) ** 0.5, num_train_timesteps,
                             dtype=np.float32) ** 2
         ac = np.cumprod((1.0 - betas).astype(np.float32), dtype=np.float32)
@@ -192,17 +271,18 @@ class EulerDiscreteScheduler:
         self.sigmas = np.concatenate([self._train_sigmas[::-1], [0.0]]).astype(np.float32)
         self.timesteps: np.ndarray = np.zeros(0, dtype=np.float32)
         self.num_inference_steps = 0
-        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+        self.config = SchedulerConfig(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                            beta_schedule="scaled_linear", trained_betas=None, steps_offset=steps_offset,
-                           timestep_spacing=timestep_spacing, prediction_type="epsilon", interpolation_type="linear",
+                           timestep_spacing=timestep_spacing, prediction_type=prediction_type, interpolation_type="linear",
                            use_karras_sigmas=False)
 
     @classmethod
-    def from_config(cls, config) -> "EulerDiscreteScheduler":
+    def from_config(cls, config, **kwargs) -> "EulerDiscreteScheduler":
         """``EulerDiscreteScheduler.from_config(pipe.scheduler.config)`` (infer.py:33, infer_SDXL.py:37).  A raw
         ``scheduler_config.json`` without a ``timestep_spacing`` key belongs to a scheduler class whose default is
         "leading" (PNDM, DDIM): that is what the loaded scheduler's config would hand over, so it is the fallback here."""
-        return cls(**_config_args(config, ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "timestep_spacing")))
+        return cls(**_config_args(config, ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "timestep_spacing"),
+                                  kwargs))
 
     @property
     def init_noise_sigma(self) -> float:
@@ -226,15 +306,20 @@ class EulerDiscreteScheduler:
         return 1.0, float(self.sigmas[i])
 
     def coefficient_table(self, inpaint: bool = False) -> np.ndarray:
-        """[steps, 5] fp32: c_x, c_eps, c_init, c_noise, c_in (see DDIMScheduler.coefficient_table)"""
+        """[steps, 5] fp32: c_x, c_eps, c_init, c_noise, c_in (see DDIMScheduler.coefficient_table).  v-prediction (diffusers:
+        pred_original = -sigma v / sqrt(sigma^2 + 1) + x / (sigma^2 + 1), derivative = (x - pred_original) / sigma):
+        x' = x (1 + dt sigma / (sigma^2 + 1)) + v dt / sqrt(sigma^2 + 1), dt = sigma_next - sigma; c_in is the same."""
         rows: List[List[float]] = []
         for i in range(len(self.timesteps)):
             s, nxt = float(self.sigmas[i]), float(self.sigmas[i + 1])
             ci, cn = 1.0, 0.0
             if inpaint and i < len(self.timesteps) - 1:
                 ci, cn = 1.0, nxt                           # add_noise at the NEXT timestep: init + sigma_next * noise
-            rows.append([1.0, nxt - s, ci, cn, 1.0 / (s * s + 1.0) ** 0.5])
-        return np.asarray(rows, dtype=np.float32)
+            c_x, c_e = 1.0, nxt - s
+            if self.prediction_type == "v_prediction":
+                c_x, c_e = 1.0 + (nxt - s) * s / (s * s + 1.0), (nxt - s) / (s * s + 1.0) ** 0.5
+            rows.append([c_x, c_e, ci, cn, 1.0 / (s * s + 1.0) ** 0.5])
+        return _check_finite(np.asarray(rows, dtype=np.float32), self, "coefficient_table")
 
 
 class PNDMScheduler:
@@ -250,7 +335,8 @@ class PNDMScheduler:
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
                  steps_offset: int = 1, set_alpha_to_one: bool = False, timestep_spacing: str = "leading",
-                 skip_prk_steps: bool = True):
+                 skip_prk_steps: bool = True, prediction_type: str = "epsilon"):
+        self.prediction_type = _check_prediction_type(prediction_type)
         if not skip_prk_steps:
             raise NotImplementedError("skip_prk_steps=False: the Runge-Kutta warm-up steps are not built")
         if timestep_spacing not in SPACINGS:
@@ -261,16 +347,16 @@ class PNDMScheduler:
         self.steps_offset, self.timestep_spacing = steps_offset, timestep_spacing
         self.timesteps: np.ndarray = np.zeros(0, dtype=np.int64)
         self.num_inference_steps = 0
-        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+        self.config = SchedulerConfig(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                            beta_schedule="scaled_linear", trained_betas=None, steps_offset=steps_offset,
-                           set_alpha_to_one=set_alpha_to_one, timestep_spacing=timestep_spacing, prediction_type="epsilon",
-                           skip_prk_steps=True)
+                           set_alpha_to_one=set_alpha_to_one, timestep_spacing=timestep_spacing,
+                           prediction_type=prediction_type, skip_prk_steps=True)
 
     @classmethod
-    def from_config(cls, config) -> "PNDMScheduler":
+    def from_config(cls, config, **kwargs) -> "PNDMScheduler":
         """a config without ``skip_prk_steps`` (another scheduler class's) gets the built variant; an explicit false raises"""
         return cls(**_config_args(config, ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "set_alpha_to_one",
-                                           "timestep_spacing", "skip_prk_steps")))
+                                           "timestep_spacing", "skip_prk_steps"), kwargs))
 
     def set_timesteps(self, num_inference_steps: int, device=None):
         T, n = self.num_train_timesteps, num_inference_steps
@@ -294,7 +380,9 @@ class PNDMScheduler:
     def coefficient_rows(self, inpaint: bool = False, first_step: int = 0, dtype=np.float32) -> np.ndarray:
         """[len(timesteps), 16] multistep rows: ``step_plms`` over entries [first_step, len) with a counter and a history
         that start empty at ``first_step``, as a fresh scheduler stepping over the truncated list does.  The kernel's m is
-        the model output itself (a = 0, b = 1); ring slot k mod 4 takes the k-th appended one."""
+        the model output itself (a = 0, b = 1); ring slot k mod 4 takes the k-th appended one.  v-prediction: ``_get_prev_sample``
+        converts the COMBINED output with the step's source sample, eps = sqrt(a_t) v + sqrt(1 - a_t) src; the combination's
+        weights sum to 1, so every model-output coefficient is multiplied by sqrt(a_t) and c_x gains c_mo sqrt(1 - a_t)."""
         ts, T = self.timesteps, self.num_train_timesteps
         ratio = T // self.num_inference_steps
         rows = [_idle_row() for _ in range(min(first_step, len(ts)))]
@@ -312,6 +400,8 @@ class PNDMScheduler:
             a_p = float(self.alphas_cumprod[prev]) if prev >= 0 else float(self.final_alpha_cumprod)
             c_x = (a_p / a_t) ** 0.5
             c_mo = -(a_p - a_t) / (a_t * (1.0 - a_p) ** 0.5 + (a_t * (1.0 - a_t) * a_p) ** 0.5)
+            if self.prediction_type == "v_prediction":
+                c_x, c_mo = c_x + c_mo * (1.0 - a_t) ** 0.5, c_mo * a_t ** 0.5
             held = min(appended, 4)
             slot = lambda back: (appended - back) % 4          # ring slot of ets[-back]
             if counter == 1:                                    # (e + ets[-1]) / 2 from the remembered sample
@@ -327,7 +417,7 @@ class PNDMScheduler:
             ci, cn = _next_blend(self, inpaint, i)
             rows.append(_row(a=0.0, b=1.0, c_x=c_x, c_m=c_m, c_hist=c_hist, c_init=ci, c_noise=cn, w=w, flags=flags))
             counter += 1
-        return np.asarray(rows, dtype=np.float64).reshape(-1, ROW_WORDS).astype(dtype)
+        return _check_finite(np.asarray(rows, dtype=np.float64).reshape(-1, ROW_WORDS), self, "coefficient_rows").astype(dtype)
 
 
 class DPMSolverMultistepScheduler:
@@ -345,9 +435,10 @@ class DPMSolverMultistepScheduler:
                   euler_at_final=False, use_lu_lambdas=False)
 
     def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
-                 steps_offset: int = 0, timestep_spacing: str = "linspace"):
+                 steps_offset: int = 0, timestep_spacing: str = "linspace", prediction_type: str = "epsilon"):
         if timestep_spacing not in SPACINGS:
             raise ValueError(f"timestep_spacing {timestep_spacing!r}: one of {SPACINGS}")
+        self.prediction_type = _check_prediction_type(prediction_type)
         self.alphas_cumprod = _train_alphas_cumprod(beta_start, beta_end, num_train_timesteps)
         ac = self.alphas_cumprod.astype(np.float64)
         self._train_sigmas = ((1.0 - ac) / ac) ** 0.5
@@ -355,12 +446,12 @@ class DPMSolverMultistepScheduler:
         self.timesteps: np.ndarray = np.zeros(0, dtype=np.int64)
         self.sigmas: np.ndarray = np.zeros(0, dtype=np.float64)
         self.num_inference_steps = 0
-        self.config = dict(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+        self.config = SchedulerConfig(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
                            beta_schedule="scaled_linear", trained_betas=None, steps_offset=steps_offset,
-                           timestep_spacing=timestep_spacing, prediction_type="epsilon", **self._BUILT)
+                           timestep_spacing=timestep_spacing, prediction_type=prediction_type, **self._BUILT)
 
     @classmethod
-    def from_config(cls, config) -> "DPMSolverMultistepScheduler":
+    def from_config(cls, config, **kwargs) -> "DPMSolverMultistepScheduler":
         """a config without ``timestep_spacing`` belongs to a class whose default is "leading" (PNDM, DDIM; see
         EulerDiscreteScheduler.from_config); diffusers' own default for this class, "linspace", is the constructor's"""
         cfg = dict(config)
@@ -374,7 +465,7 @@ class DPMSolverMultistepScheduler:
                 ok = got == built
             if not ok:
                 raise NotImplementedError(f"{key}={got!r}: DPMSolverMultistepScheduler is built for {key}={built!r} only")
-        args = _config_args(cfg, ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "timestep_spacing"))
+        args = _config_args(config, ("num_train_timesteps", "beta_start", "beta_end", "steps_offset", "timestep_spacing"), kwargs)
         args.setdefault("timestep_spacing", "leading")
         return cls(**args)
 
@@ -402,7 +493,8 @@ class DPMSolverMultistepScheduler:
         """[len(timesteps), 16] multistep rows over entries [first_step, len); the history starts empty at ``first_step``.
         With alpha = 1 / sqrt(sigma^2 + 1), s = sigma alpha, lambda = log alpha - log s, h = lambda_(i+1) - lambda_i,
         D = -alpha_(i+1) (exp(-h) - 1):  x' = (s_(i+1) / s_i) x + D m_i  [+ D / (2 r) (m_i - m_(i-1)),
-        r = (lambda_i - lambda_(i-1)) / h]."""
+        r = (lambda_i - lambda_(i-1)) / h].  m is the data prediction: (x - s_i e) / alpha_i for epsilon prediction,
+        alpha_i x - s_i v for v-prediction."""
         n = len(self.timesteps)
         alpha = 1.0 / (self.sigmas ** 2 + 1.0) ** 0.5
         s = self.sigmas * alpha
@@ -418,6 +510,7 @@ class DPMSolverMultistepScheduler:
                 c_m = D + D / (2.0 * r)
                 c_hist[(k - 1) % 4] = -D / (2.0 * r)
             ci, cn = _next_blend(self, inpaint, i)
-            rows.append(_row(a=1.0 / alpha[i], b=-s[i] / alpha[i], c_x=s[i + 1] / s[i], c_m=float(c_m), c_hist=c_hist,
+            a, b = (alpha[i], -s[i]) if self.prediction_type == "v_prediction" else (1.0 / alpha[i], -s[i] / alpha[i])
+            rows.append(_row(a=a, b=b, c_x=s[i + 1] / s[i], c_m=float(c_m), c_hist=c_hist,
                              c_init=ci, c_noise=cn, w=k % 4))
-        return np.asarray(rows, dtype=np.float64).reshape(-1, ROW_WORDS).astype(dtype)
+        return _check_finite(np.asarray(rows, dtype=np.float64).reshape(-1, ROW_WORDS), self, "coefficient_rows").astype(dtype)

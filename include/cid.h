@@ -27,7 +27,7 @@ extern "C" {
 typedef void* cid_stream_t;      /* hipStream_t */
 typedef uint16_t cid_half;       /* IEEE binary16 bit pattern */
 
-int cid_version(void);          /* 107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
+int cid_version(void);          /* 108: cid_cfg_rescale_f16, cid_cfg_ddim_step_scaled_f16, cid_cfg_multistep_step_scaled_f16 added.  107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
                                  * pointer (102: act, 101: pad_mode; set them or zero the struct) */
 const char* cid_last_error(void);
 
@@ -504,6 +504,34 @@ int cid_cfg_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hi
                                const cid_half* z, int32_t z_rows, const void* row, float guidance,
                                const cid_half* mask, const cid_half* init, const cid_half* noise,
                                int32_t B, int32_t per_sample, cid_stream_t stream);
+/* guidance_rescale ("Common Diffusion Noise Schedules and Sample Steps Are Flawed", section 3.4; diffusers 0.23
+ * rescale_noise_cfg, applied between the CFG combine and scheduler.step): the per-sample factor of the guided prediction.
+ * eps: fp16 [2B][per_sample], unconditional half first -- what the step kernels read.  escale: DEVICE fp32 [B], written:
+ *    c = eps[B + b],  e = u + g (c - u) in fp32, the step kernels' own expression,
+ *    escale[b] = 1 - rescale + rescale * std(c) / std(e)        (both over the whole sample; their N - 1 cancels)
+ * so that e * escale[b] = rescale * (e * std(c) / std(e)) + (1 - rescale) * e.  DEVIATION: where std(e) == 0 (a constant
+ * prediction) escale[b] = 1.0; diffusers divides by zero there and hands NaN to the scheduler.
+ * One launch, one 1024-thread workgroup per sample, nothing on the host and no allocation (graph-capturable).  The
+ * variances are merged (count, mean, M2) triples -- Chan's pairwise update per 8-half item, per thread, across lanes and
+ * across waves -- not sum / sum of squares, so a mean far from zero costs no accuracy (|relative error| of the ratio
+ * ~1e-6 against fp64); no atomics and a fixed merge order: the same input gives the same bits on every launch.
+ * -22 before any launch: a null pointer, B <= 0, per_sample <= 0, not a multiple of 8 or above 2^24 (the element counts
+ * are fp32, exact up to there; the largest sample of the models is 65 536), eps not 16-byte aligned, rescale negative or
+ * not finite. */
+int cid_cfg_rescale_f16(const cid_half* eps, float guidance, float rescale, float* escale, int32_t B, int32_t per_sample,
+                        cid_stream_t stream);
+/* cid_cfg_ddim_step_f16 / cid_cfg_multistep_step_f16 with e = (eps_u + g (eps_c - eps_u)) * escale[sample]; everything
+ * downstream of e is as documented there (m = a x + b e, ring, saved sample, z, inpaint blend).  escale: DEVICE fp32 [B]
+ * (cid_cfg_rescale_f16 writes it).  per_sample % 8 == 0 here -- an 8-half item must lie inside one sample -- where the
+ * unscaled entries ask for B * per_sample % 8 == 0 only, and B * per_sample < 2^34 (the sample of an item is a 32-bit division).  With escale all 1.0 the results are bit-identical to the
+ * unscaled entries', which compile to the instructions they had before these existed (one kernel body, a compile-time switch). */
+int cid_cfg_ddim_step_scaled_f16(const cid_half* eps, cid_half* latents, const float* coef, float guidance,
+                                 const cid_half* mask, const cid_half* init, const cid_half* noise,
+                                 int32_t B, int32_t per_sample, const float* escale, cid_stream_t stream);
+int cid_cfg_multistep_step_scaled_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
+                                      const cid_half* z, int32_t z_rows, const void* row, float guidance,
+                                      const cid_half* mask, const cid_half* init, const cid_half* noise,
+                                      int32_t B, int32_t per_sample, const float* escale, cid_stream_t stream);
 /* y[i] += a[i mod na] (ControlNet residual adds, CN :418-425) */
 int cid_add_inplace_f16(cid_half* y, const cid_half* a, int64_t n, int64_t na, cid_stream_t stream);
 
