@@ -444,6 +444,27 @@ int launch_attn(const half_t* q, const half_t* k, const half_t* vt, half_t* out,
     return 0;
 }
 
+// Queries per workgroup on a token axis that is a multiple of 128: 128 (four waves) where that grid gives every CU a
+// workgroup, 64 (two waves, the instance of the other token counts) where it would not -- SD1.5's 16 x 16 level at CFG batch 8
+// is 2 x 8 x 8 = 128 workgroups of 128 queries on 256 CUs.  CID_ATTN_BQ = 128 / 64 forces one (A/B switch).
+// -> 1 / 0, or -1 if the device cannot be asked for its CU count
+int attn_bq128(int B, int N, int heads) {
+    if (N % 128 != 0) return 0;
+    static int force = -1, cus = 0;
+    if (force < 0) { const char* e = getenv("CID_ATTN_BQ"); force = e ? atoi(e) : 0; }
+    if (force == 128 || force == 64) return force == 128;
+    if (cus <= 0) {
+        int dev = 0, n = 0;
+        if (hipGetDevice(&dev) != hipSuccess || hipDeviceGetAttribute(&n, hipDeviceAttributeMultiprocessorCount, dev) != hipSuccess ||
+            n <= 0) {
+            cid_set_error("cid_self_attn_f16: cannot read the device's CU count");
+            return -1;
+        }
+        cus = n;
+    }
+    return (long)(N / 128) * heads * B >= cus;
+}
+
 }  // namespace
 
 extern "C" int cid_self_attn_f16(const cid_half* q, const cid_half* k, const cid_half* vt, cid_half* out,
@@ -463,9 +484,13 @@ extern "C" int cid_self_attn_keys_f16(const cid_half* q, const cid_half* k, cons
     half_t* O = (half_t*)out;
     hipStream_t s = (hipStream_t)stream;
     int rc = -22;
+    // (an unsupported head width is refused below without asking the device for anything)
+    const int bq = (d == 40 || d == 64 || d == 80 || d == 160 || d == 32) ? attn_bq128(B, N, heads) : 0;
+    if (bq < 0) return -5;
+    const bool bq128 = bq == 1;
 #define CID_ATTN(DD, QT, NWV) rc = launch_attn<DD, QT, NWV>(Q, K, V, O, B, N, heads, ldq, ldk, dvp, ldo, n_keys, s)
 #define CID_ATTN_MASKED(DD) \
-    rc = (N % 128 == 0) ? launch_attn<DD, 1, 4, true>(Q, K, V, O, B, N, heads, ldq, ldk, dvp, ldo, n_keys, s) \
+    rc = bq128 ? launch_attn<DD, 1, 4, true>(Q, K, V, O, B, N, heads, ldq, ldk, dvp, ldo, n_keys, s) \
                         : launch_attn<DD, 1, 2, true>(Q, K, V, O, B, N, heads, ldq, ldk, dvp, ldo, n_keys, s)
     if (n_keys != N) {
         // padded key axis (CLIP towers with 257 tokens; UNet levels whose token count is not a multiple of 64 at
@@ -482,7 +507,7 @@ extern "C" int cid_self_attn_keys_f16(const cid_half* q, const cid_half* k, cons
     }
     if (d == 40) {
         // one 32-query tile per wave: ~3 waves per SIMD, so one wave's softmax (VALU) overlaps another's MFMAs
-        if (N % 128 == 0) CID_ATTN(40, 1, 4); else CID_ATTN(40, 1, 2);
+        if (bq128) CID_ATTN(40, 1, 4); else CID_ATTN(40, 1, 2);
     } else if (d == 64 || d == 80) {
         // one 32-query tile per wave by default: two tiles per wave (K/V fragments reused, 256 registers, one wave per
         // SIMD) measured slower end to end at every level that occurs (SDXL 1024^2: 1.43 vs 1.51 images/s; SD1.5 equal)
@@ -490,14 +515,14 @@ extern "C" int cid_self_attn_keys_f16(const cid_half* q, const cid_half* k, cons
         if (force_qt < 0) { const char* e = getenv("CID_ATTN_QT"); force_qt = e ? atoi(e) : 0; }
         const bool qt2 = (N % 256 == 0) && force_qt == 2;
         if (d == 64) {
-            if (qt2) CID_ATTN(64, 2, 4); else if (N % 128 == 0) CID_ATTN(64, 1, 4); else CID_ATTN(64, 1, 2);
+            if (qt2) CID_ATTN(64, 2, 4); else if (bq128) CID_ATTN(64, 1, 4); else CID_ATTN(64, 1, 2);
         } else {
-            if (qt2) CID_ATTN(80, 2, 4); else if (N % 128 == 0) CID_ATTN(80, 1, 4); else CID_ATTN(80, 1, 2);
+            if (qt2) CID_ATTN(80, 2, 4); else if (bq128) CID_ATTN(80, 1, 4); else CID_ATTN(80, 1, 2);
         }
     } else if (d == 160) {
-        if (N % 128 == 0) CID_ATTN(160, 1, 4); else CID_ATTN(160, 1, 2);
+        if (bq128) CID_ATTN(160, 1, 4); else CID_ATTN(160, 1, 2);
     } else if (d == 32) {
-        if (N % 128 == 0) CID_ATTN(32, 1, 4); else CID_ATTN(32, 1, 2);
+        if (bq128) CID_ATTN(32, 1, 4); else CID_ATTN(32, 1, 2);
     } else {
         cid_set_error("cid_self_attn_f16: unsupported head dim %d (40, 64, 80, 160, 32)", d);
         return -22;

@@ -268,20 +268,33 @@ gn_apply_kernel(const half_t* __restrict__ x1, const half_t* __restrict__ x2, in
 // At the 8 x 8 / 16 x 16 levels a (sample, group) slice is at most 40 KB: one workgroup keeps it
 // in registers -- read once, reduce, normalise, write -- instead of a statistics launch plus an apply launch that are
 // both pure latency at that size (30 of the 61 GroupNorms of an SD1.5 forward).  Fixed reduction order (no atomics).
-constexpr int GNS_MAXPER = 20;                       // 4-channel pieces per thread
-constexpr long GNS_MAXELEM = 256L * GNS_MAXPER * 4;  // elements of a (sample, group) slice: 20480
+// The one launch is latency too: at CFG batch 8 it is 256 workgroups, one per CU.  GNS_THREADS lanes share a slice, each
+// holds at most gns_per() pieces of E channels (E = 8, 16-byte loads, where a group is a whole number of octets; E = 4
+// otherwise), asks for all of them and for their gamma / beta before it waits for anything, and every lane folds the
+// waves' partial sums itself, so a reduction costs one barrier.
+constexpr long GNS_MAXELEM = 20480;                  // elements of a (sample, group) slice the single launch takes
 #ifndef GNS_MAXHW
 #define GNS_MAXHW 256                                // pixels per sample up to which the single launch is used
 #endif
+#ifndef GNS_THREADS
+#define GNS_THREADS 1024                             // lanes per (sample, group) slice
+#endif
+constexpr int gns_per(int nt, int e) { return (int)((GNS_MAXELEM + nt * e - 1) / (nt * e)); }   // pieces per lane
 
-template <bool SILU>
-__global__ void __launch_bounds__(256)
+template <int E> struct GnsVec;
+template <> struct GnsVec<4> { using type = half4; };
+template <> struct GnsVec<8> { using type = half8; };
+
+template <bool SILU, int NT, int E>
+__global__ void __launch_bounds__(NT)
 gn_small_kernel(const half_t* __restrict__ x1, const half_t* __restrict__ x2, int c1, int c2, half_t* __restrict__ out,
                 const half_t* __restrict__ gamma, const half_t* __restrict__ beta, int B, int HW, int groups, float eps,
-                int step_r, int step_c) {          // 256 / (cg / 4), 256 % (cg / 4): piece index -> (pixel, piece) without divisions
-    __shared__ float wsum[4], wsq[4];
-    __shared__ float sstat[2];
-    const int C = c1 + c2, cg = C / groups, cq = cg >> 2;
+                int step_r, int step_c,            // NT / (cg / E), NT % (cg / E): piece index -> (pixel, piece) without divisions
+                double inv_n) {                    // 1 / (HW * cg)
+    using vec_t = typename GnsVec<E>::type;
+    constexpr int PER = gns_per(NT, E), NW = NT / 64;
+    __shared__ float wsum[NW], wsq[NW];
+    const int C = c1 + c2, cg = C / groups, cq = cg / E;
     // workgroup -> (sample, group); with a multiple of 8 samples an XCD owns whole samples: the groups whose 40..160-byte
     // row pieces share cache lines meet in ONE L2 (consecutive workgroups go to consecutive XCDs)
     int b, g;
@@ -292,65 +305,73 @@ gn_small_kernel(const half_t* __restrict__ x1, const half_t* __restrict__ x2, in
     }
     const int nchunk = HW * cq;
     const int r_first = (int)threadIdx.x / cq, c_first = (int)threadIdx.x - r_first * cq;
-    half4 v[GNS_MAXPER];
-    float s = 0.f, q = 0.f;
+    vec_t v[PER], gm[PER], bt[PER];
     int r = r_first, cc = c_first;
 #pragma unroll
-    for (int k = 0; k < GNS_MAXPER; ++k) {
-        const int idx = threadIdx.x + k * 256;
-        if (idx < nchunk) {
-            const int ch0 = g * cg + 4 * cc;
+    for (int k = 0; k < PER; ++k) {
+        if ((int)threadIdx.x + k * NT < nchunk) {
+            const int ch0 = g * cg + E * cc;
             const long row = (long)b * HW + r;
-            v[k] = ch0 < c1 ? *reinterpret_cast<const half4*>(x1 + row * c1 + ch0)
-                            : *reinterpret_cast<const half4*>(x2 + row * c2 + (ch0 - c1));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) s += (float)v[k][i];
+            v[k] = ch0 < c1 ? *reinterpret_cast<const vec_t*>(x1 + row * c1 + ch0)
+                            : *reinterpret_cast<const vec_t*>(x2 + row * c2 + (ch0 - c1));
         }
         r += step_r; cc += step_c;
         if (cc >= cq) { cc -= cq; ++r; }
     }
+    cc = c_first;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        if ((int)threadIdx.x + k * NT < nchunk) {
+            gm[k] = *reinterpret_cast<const vec_t*>(gamma + g * cg + E * cc);
+            bt[k] = *reinterpret_cast<const vec_t*>(beta + g * cg + E * cc);
+        }
+        cc += step_c;
+        if (cc >= cq) cc -= cq;
+    }
     // two passes over the registers: the mean first, then the sum of (x - mean)^2 -- a single pass of x and x^2 in fp32
     // loses precision in proportion to (mean / std)^2
-    const double n = (double)HW * (double)cg;
+    float s = 0.f, q = 0.f;
+#pragma unroll
+    for (int k = 0; k < PER; ++k) {
+        if ((int)threadIdx.x + k * NT < nchunk) {
+#pragma unroll
+            for (int i = 0; i < E; ++i) s += (float)v[k][i];
+        }
+    }
     s = wave_sum(s);
     if ((threadIdx.x & 63) == 0) wsum[threadIdx.x >> 6] = s;
     __syncthreads();
-    if (threadIdx.x == 0)
-        sstat[0] = (float)(((double)wsum[0] + (double)wsum[1] + (double)wsum[2] + (double)wsum[3]) / n);
-    __syncthreads();
-    const float mean = sstat[0];
+    double ts = 0.0;
 #pragma unroll
-    for (int k = 0; k < GNS_MAXPER; ++k) {
-        if ((int)threadIdx.x + k * 256 < nchunk) {
+    for (int w = 0; w < NW; ++w) ts += (double)wsum[w];        // every lane, the same order: the same mean in all of them
+    const float mean = (float)(ts * inv_n);
 #pragma unroll
-            for (int i = 0; i < 4; ++i) { const float d = (float)v[k][i] - mean; q = __builtin_fmaf(d, d, q); }
+    for (int k = 0; k < PER; ++k) {
+        if ((int)threadIdx.x + k * NT < nchunk) {
+#pragma unroll
+            for (int i = 0; i < E; ++i) { const float d = (float)v[k][i] - mean; q = __builtin_fmaf(d, d, q); }
         }
     }
     q = wave_sum(q);
     if ((threadIdx.x & 63) == 0) wsq[threadIdx.x >> 6] = q;
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const double var = ((double)wsq[0] + (double)wsq[1] + (double)wsq[2] + (double)wsq[3]) / n;
-        sstat[1] = (float)(1.0 / sqrt(var + (double)eps));
-    }
-    __syncthreads();
-    const float rstd = sstat[1];
+    double tq = 0.0;
+#pragma unroll
+    for (int w = 0; w < NW; ++w) tq += (double)wsq[w];
+    const float rstd = rsqrtf((float)(tq * inv_n) + eps);
     r = r_first; cc = c_first;
 #pragma unroll
-    for (int k = 0; k < GNS_MAXPER; ++k) {
-        const int idx = threadIdx.x + k * 256;
-        if (idx < nchunk) {
-            const int ch0 = g * cg + 4 * cc;
-            const half4 gm = *reinterpret_cast<const half4*>(gamma + ch0), bt = *reinterpret_cast<const half4*>(beta + ch0);
-            half4 o;
+    for (int k = 0; k < PER; ++k) {
+        if ((int)threadIdx.x + k * NT < nchunk) {
+            vec_t o;
 #pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const float sc = rstd * (float)gm[i];
-                float y = (float)v[k][i] * sc + ((float)bt[i] - mean * sc);
+            for (int i = 0; i < E; ++i) {
+                const float sc = rstd * (float)gm[k][i];
+                float y = (float)v[k][i] * sc + ((float)bt[k][i] - mean * sc);
                 if (SILU) y = silu_f(y);
                 o[i] = (half_t)y;
             }
-            *reinterpret_cast<half4*>(out + ((long)b * HW + r) * C + ch0) = o;
+            *reinterpret_cast<vec_t*>(out + ((long)b * HW + r) * C + g * cg + E * cc) = o;
         }
         r += step_r; cc += step_c;
         if (cc >= cq) { cc -= cq; ++r; }
@@ -456,15 +477,22 @@ extern "C" int cid_groupnorm_f16(const cid_half* x1, const cid_half* x2, int32_t
     hipStream_t s = (hipStream_t)stream;
     const int cg = C / groups;
     // a (sample, group) slice fits one workgroup's registers; measured faster than the two launches up to 16 x 16 pixels
-    // (tools/kbench.py --only norm: 20.2 -> 18 us at 256 pixels x 2560 channels, 12.1 -> 9.5 us at 64 x 1280; slower at 1024 x 640)
+    // (tools/kbench.py --only norm: 20.2 -> 18 us at 256 pixels x 2560 channels, 12.1 -> 9.5 us at 64 x 1280; slower at 1024 x 640;
+    // with 1024 lanes per slice, back to back in a graph: 17.6 -> 8.3 us and 5.1 -> 4.2 us, profiles/deep_direct_ab.txt)
     if (cg % 4 == 0 && HW <= GNS_MAXHW && (long)HW * cg <= GNS_MAXELEM) {
-        const int cq = cg / 4;
-        if (silu)
-            hipLaunchKernelGGL(gn_small_kernel<true>, dim3(groups * B), dim3(256), 0, s, (const half_t*)x1, (const half_t*)x2, c1, c2,
-                               (half_t*)out, (const half_t*)gamma, (const half_t*)beta, B, HW, groups, eps, 256 / cq, 256 % cq);
-        else
-            hipLaunchKernelGGL(gn_small_kernel<false>, dim3(groups * B), dim3(256), 0, s, (const half_t*)x1, (const half_t*)x2, c1, c2,
-                               (half_t*)out, (const half_t*)gamma, (const half_t*)beta, B, HW, groups, eps, 256 / cq, 256 % cq);
+        // 16-byte pieces where a group is a whole number of channel octets (c1 is one by the check above, so no piece
+        // straddles the two sources) and every operand starts on a 16-byte boundary; 8-byte pieces otherwise (cg = 60)
+        const uintptr_t ptrs = (uintptr_t)x1 | (uintptr_t)x2 | (uintptr_t)out | (uintptr_t)gamma | (uintptr_t)beta;
+        const bool wide = cg % 8 == 0 && ptrs % 16 == 0;
+        const int cq = cg / (wide ? 8 : 4);
+        const double inv_n = 1.0 / ((double)HW * (double)cg);
+        constexpr int NT = GNS_THREADS;
+#define CID_GNS(SILU, E) hipLaunchKernelGGL((gn_small_kernel<SILU, NT, E>), dim3(groups * B), dim3(NT), 0, s, (const half_t*)x1, \
+                                            (const half_t*)x2, c1, c2, (half_t*)out, (const half_t*)gamma, (const half_t*)beta, B, HW, \
+                                            groups, eps, NT / cq, NT % cq, inv_n)
+        if (wide) { if (silu) CID_GNS(true, 8); else CID_GNS(false, 8); }
+        else      { if (silu) CID_GNS(true, 4); else CID_GNS(false, 4); }
+#undef CID_GNS
         CID_CHECK_LAUNCH("cid_groupnorm_f16");
         return 0;
     }
