@@ -829,6 +829,41 @@ def add_inplace(y: torch.Tensor, a: torch.Tensor):
     return y
 
 
+def freeu_ws_bytes(B: int, c_skip: int, H: int, W: int) -> int:
+    """scratch :func:`freeu` needs for this shape (0 for a shape it refuses); grows with H * W only up to a bound, so
+    ``freeu_ws_bytes(B, c, 1024, 1024)`` serves every H x W"""
+    return int(_lib.load().cid_freeu_ws_bytes(B, c_skip, H, W))
+
+
+def freeu(x: torch.Tensor, skip: torch.Tensor, ws: torch.Tensor, *, B: int, H: int, W: int, c_x: int, c_skip: int,
+          s: float, b: float, out: Optional[torch.Tensor] = None):
+    """FreeU on the two inputs of an up-block resnet (cid.h, cid_freeu_f16): ``x`` fp16 [B * H * W, c_x], its first
+    c_x / 2 channels times ``b`` in place; ``skip`` fp16 [B * H * W, c_skip] through diffusers' ``fourier_filter(threshold=1,
+    scale=s)`` into ``out`` (default: in place).  ``ws``: >= ``freeu_ws_bytes`` bytes of device scratch.  Two launches,
+    deterministic.  Returns the filtered tensor."""
+    lib = _lib.load()
+    out = skip if out is None else out
+    if H < 2 or W < 2:
+        raise _lib.CidError(f"freeu: H x W = {H} x {W}; both sides must be at least 2 (the filter's box is empty on a side of 1)")
+    if c_x <= 0 or c_x % 16 or c_skip <= 0 or c_skip % 8:
+        raise _lib.CidError(f"freeu: c_x = {c_x} must be a positive multiple of 16 and c_skip = {c_skip} of 8")
+    if x.numel() != B * H * W * c_x or skip.numel() != B * H * W * c_skip or out.numel() != skip.numel():
+        raise _lib.CidError(f"freeu: x / skip / out hold {x.numel()} / {skip.numel()} / {out.numel()} elements; B = {B}, "
+                            f"H x W = {H} x {W}, c_x = {c_x}, c_skip = {c_skip}")
+    for name, t in (("x", x), ("skip", skip), ("out", out)):
+        _req(t, f"freeu.{name}")
+        if not t.is_contiguous():
+            raise _lib.CidError(f"freeu.{name}: not contiguous")
+    if not ws.is_cuda or ws.data_ptr() % 16 or ws.numel() * ws.element_size() < freeu_ws_bytes(B, c_skip, H, W):
+        raise _lib.CidError(f"freeu.ws: {freeu_ws_bytes(B, c_skip, H, W)} bytes of 16-byte aligned device scratch needed")
+    for t in (x, out):
+        if hasattr(t, "_gn_stats"):
+            del t._gn_stats          # the epilogue statistics describe the tensor BEFORE this update
+    check(lib.cid_freeu_f16(_p(x), c_x, float(b), _p(skip), _p(out), c_skip, float(s), B, H, W, ws.data_ptr(), _stream()),
+          "cid_freeu_f16")
+    return out
+
+
 def residual_accum(ys, rs, scales: torch.Tensor):
     """cid_residual_accum_f16: ``ys[j] += sum_k scales[k] * rs[k][j]`` (fp32 sum in net order, one rounding) for up to 16
     destinations and up to 4 nets in ONE launch.  ``rs[k]`` holds net k's residual of every destination -- ``rs[k][j]`` with

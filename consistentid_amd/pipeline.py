@@ -31,6 +31,7 @@ SURVEY.md Appendix B): B independent samples, each with its own CFG pair.
 """
 from __future__ import annotations
 
+import math
 import os
 from dataclasses import dataclass
 from typing import Any, List, Optional, Union
@@ -130,6 +131,21 @@ class _BasePipeline:
 
     enable_model_cpu_offload = enable_sequential_cpu_offload = enable_vae_slicing = enable_vae_tiling = _nothing_to_do
     enable_xformers_memory_efficient_attention = set_progress_bar_config = _nothing_to_do
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """``pipe.enable_freeu(s1, s2, b1, b2)`` of diffusers 0.23, which the reference pipelines inherit (FreeU,
+        arXiv 2309.11497): in the UNet's first two up blocks the skip features' low frequencies are scaled by s1 / s2 and the
+        first half of the backbone's channels by b1 / b2 (``HipUNet.enable_freeu``, cid_freeu_f16).  All four are required,
+        finite real numbers -- diffusers does not check them; a NaN there becomes a NaN image."""
+        vals = (s1, s2, b1, b2)
+        for name, v in zip(("s1", "s2", "b1", "b2"), vals):
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError(f"enable_freeu: {name} must be a finite number (got {v!r})")
+        self.unet.enable_freeu(*(float(v) for v in vals))
+
+    def disable_freeu(self):
+        """``pipe.disable_freeu()`` of diffusers 0.23: the up blocks run as without FreeU, with no extra launch"""
+        self.unet.disable_freeu()
 
     @property
     def scheduler(self):

@@ -100,6 +100,24 @@ class HipUNet:
         # 1: the first-generation xattn.hip); CID_XATTN_V2=0 is the older spelling of generation 1
         self._xattn_gen = ops.xattn_generation()
         self._t_buf = torch.zeros(1, dtype=torch.float32, device=self.device)
+        self._freeu = None      # (s1, s2, b1, b2) while FreeU is enabled
+
+    def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
+        """diffusers' ``enable_freeu`` (0.23, UNet2DConditionModel): the inputs of every resnet of up block i in {0, 1} go
+        through cid_freeu_f16 -- the skip tensor through the low-frequency filter with scale s_{i+1}, the first half of the
+        backbone's channels times b_{i+1}.  The four values are launch scalars kept on the host: captured steps hold the
+        old ones, so the epoch moves (and the workspace may grow)."""
+        vals = tuple(float(v) for v in (s1, s2, b1, b2))
+        if vals != self._freeu:
+            self._freeu = vals
+            self.epoch += 1
+        return self
+
+    def disable_freeu(self):
+        if self._freeu is not None:
+            self._freeu = None
+            self.epoch += 1
+        return self
 
     def load_adapter_modules(self, adapter_sd: Dict[str, torch.Tensor], lora_scale: Optional[float] = None):
         """``adapter_modules`` of a ConsistentID checkpoint -> packed weights, in place (needs ``keep_base=True``);
@@ -187,6 +205,8 @@ class HipUNet:
     # ------------------------------------------------------------------ forward
     def _ws(self, B: int) -> torch.Tensor:
         need = ops.groupnorm_ws_bytes(B, 2560)
+        if self._freeu is not None:     # cid_freeu_f16's partial sums share the scratch: launches on one stream, each done with it
+            need = max([need] + [ops.freeu_ws_bytes(B, c, 1024, 1024) for c in set(self.config.block_out_channels)])
         if self._gn_ws is None or self._gn_ws.numel() < need:
             self._gn_ws = torch.zeros(need, dtype=torch.uint8, device=self.device)
         return self._gn_ws
@@ -563,10 +583,15 @@ class HipUNet:
             ops.residual_accum([x], [None if m is None else [m] for m in mid_residual], residual_scales)
         elif mid_residual is not None:     # (x is the mid block's own output here: nobody else holds it)
             ops.add_inplace(x, mid_residual.to(device=self.device, dtype=torch.float16).contiguous())
-        for blk in self.ups:
+        for bi, blk in enumerate(self.ups):
             for j, r in enumerate(blk.resnets):
                 s, sc_, sh, sw = skips.pop()
                 assert (sh, sw) == (H, Wd)
+                if self._freeu is not None and bi < 2:
+                    # FreeU, IN PLACE on both: a skip tensor is read exactly once on the up path -- by this resnet -- and the
+                    # down path, the mid block and the residual adds above are done with it (the two exceptions there got
+                    # their copies); x is the previous block's own output, which nobody else holds.
+                    ops.freeu(x, s, self._ws(B), B=B, H=H, W=Wd, c_x=c, c_skip=sc_, s=self._freeu[bi], b=self._freeu[2 + bi])
                 x = self._resnet(r, x, s, c, sc_, B, H, Wd, temb, trows)
                 c = r.cout
                 if blk.attentions:

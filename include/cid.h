@@ -27,7 +27,7 @@ extern "C" {
 typedef void* cid_stream_t;      /* hipStream_t */
 typedef uint16_t cid_half;       /* IEEE binary16 bit pattern */
 
-int cid_version(void);          /* 108: cid_cfg_rescale_f16, cid_cfg_ddim_step_scaled_f16, cid_cfg_multistep_step_scaled_f16 added.  107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
+int cid_version(void);          /* 109: cid_freeu_f16, cid_freeu_ws_bytes added.  108: cid_cfg_rescale_f16, cid_cfg_ddim_step_scaled_f16, cid_cfg_multistep_step_scaled_f16 added.  107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
                                  * pointer (102: act, 101: pad_mode; set them or zero the struct) */
 const char* cid_last_error(void);
 
@@ -532,6 +532,25 @@ int cid_cfg_multistep_step_scaled_f16(const cid_half* eps, cid_half* latents, fl
                                       const cid_half* z, int32_t z_rows, const void* row, float guidance,
                                       const cid_half* mask, const cid_half* init, const cid_half* noise,
                                       int32_t B, int32_t per_sample, const float* escale, cid_stream_t stream);
+/* FreeU (D: utils/torch_utils.py apply_freeu / fourier_filter, called from UpBlock2D / CrossAttnUpBlock2D.forward on the
+ * inputs of every resnet of the first two up blocks, in front of torch.cat([hidden, skip], 1)):
+ *    x[.., : c_x / 2] *= b          x: fp16 [B*H*W][c_x] in place, fp32 product, one rounding; the upper half is not touched
+ *    skip_out = fourier_filter(skip, threshold = 1, scale = s)       skip, skip_out: fp16 [B*H*W][c_skip]; skip_out may BE skip
+ * threshold = 1 puts the four frequencies {-1, 0}^2 into the filter's box (even and odd sides alike), so with
+ * th = 2 pi h / H, tw = 2 pi w / W and phi = {1, cos th, sin th, cos tw, sin tw, cos(th + tw), sin(th + tw)} per plane
+ *    skip_out[h, w] = skip[h, w] + (s - 1) / (H W) * sum_k ( sum_{h', w'} skip[h', w'] phi_k[h', w'] ) phi_k[h, w]
+ * -- no FFT and no NCHW permute.  fp32 sums and update, one rounding to fp16 per element; twiddles from sincospif.  Two
+ * launches: the seven sums per (sample, channel), as partials over slices of the token axis into ws (as many slices as bring
+ * the grid of (sample, 64-channel slab) workgroups to 256), then the update, which adds the partials in slice order.  No atomics:
+ * the same input gives the same bits, in place and out of place.  ws: >= cid_freeu_ws_bytes() of DEVICE scratch (fp32).
+ * x must not overlap skip or skip_out; skip_out is skip itself or does not overlap it.
+ * -22 before any launch: a null pointer, B outside 1..65535, H or W outside 2..1024 (diffusers' slice is empty on a side of 1;
+ * the twiddle table sits in LDS), c_x not a positive multiple of 16 (the scaled half ends on a 16-byte vector), c_skip not a
+ * positive multiple of 8, a tensor base that is not 16-byte aligned, s or b not finite.  cid_freeu_ws_bytes is host-only and
+ * returns 0 for a shape cid_freeu_f16 refuses. */
+int64_t cid_freeu_ws_bytes(int32_t B, int32_t c_skip, int32_t H, int32_t W);
+int cid_freeu_f16(cid_half* x, int32_t c_x, float b, const cid_half* skip, cid_half* skip_out, int32_t c_skip, float s,
+                  int32_t B, int32_t H, int32_t W, float* ws, cid_stream_t stream);
 /* y[i] += a[i mod na] (ControlNet residual adds, CN :418-425) */
 int cid_add_inplace_f16(cid_half* y, const cid_half* a, int64_t n, int64_t na, cid_stream_t stream);
 
