@@ -1,14 +1,20 @@
 """Test-only harness for the denoise engine's state machine: the tiny models (SD1.5 UNet, two ControlNets, SDXL UNet), their
 fp32 oracles and fp16 arms built once; a generation as a small frozen ``Spec``; the inputs, the pipeline call, a fresh eager
-run and the oracle pair of a spec, each memoised per spec and left unchanged.  tests/test_gpu_engine_reuse.py runs lists
-of specs on one live pipeline; tests/test_gpu_multicontrolnet.py takes its models and loop inputs from here."""
+run and the oracle pair of a spec, each memoised per spec and left unchanged; ``Gen`` and ``run_scenario``, which run a
+list of specs on one live pipeline and hold every generation to the fresh eager bits, the oracle and the capture count.
+tests/test_gpu_engine_reuse.py and tests/test_gpu_engine_features.py are lists of such scenarios;
+tests/test_gpu_multicontrolnet.py takes its models and loop inputs from here.
+
+FreeU and community LoRAs are state of the UNet, not arguments of a call: ``apply_features`` brings a live pipeline from the
+state its UNet is in to the one a spec names, and calls nothing where they agree."""
 import functools
+import weakref
 from dataclasses import dataclass, replace
-from typing import Optional, Tuple
+from typing import Any, Callable, Optional, Tuple
 
 import torch
 
-from conftest import dev_half, half_arm
+from conftest import check_vs_fp16_arm, dev_half, half_arm
 from oracle_utils import build_oracle, make_weights, product_cfg
 
 NET_SEEDS = {"A": 3, "B": 4}        # the two tiny ControlNets
@@ -116,6 +122,11 @@ class Spec:
     adapter: int = 0                            # which adapter the UNet has merged
     null_post: bool = False                     # "sdxl": a second unconditional set after the merge
     time_ids: Tuple[int, int] = (0, 0)          # "sdxl": crop offsets in add_time_ids
+    freeu: Optional[Tuple[float, float, float, float]] = None       # (s1, s2, b1, b2) of enable_freeu; None: disabled
+    rescale: float = 0.0                        # guidance_rescale
+    prediction: str = "epsilon"                 # the scheduler's prediction_type: "epsilon" | "v_prediction"
+    zero_snr: bool = False                      # DDIM with test_gpu_guidance_rescale.ZERO_SNR (needs "v_prediction")
+    loras: Tuple[Tuple[int, float], ...] = ()   # (seed of lora_cases.unet_lora, adapter weight), in load order
 
     def but(self, **kw):
         return replace(self, **kw)
@@ -132,10 +143,38 @@ def pipeline_class(spec):
             "controlnet": pipeline.StableDiffusionControlNetInpaintConsistentIDPipeline}[spec.pipe]
 
 
+def scheduler_kwargs(spec):
+    """the constructor arguments both the product's scheduler and its restatement take: none for an all-default spec"""
+    kw = {}
+    if spec.prediction != "epsilon":
+        kw["prediction_type"] = spec.prediction
+    if spec.zero_snr:
+        from test_gpu_guidance_rescale import ZERO_SNR
+        assert spec.scheduler == "ddim", "rescale_betas_zero_snr is DDIMScheduler's"
+        kw.update(ZERO_SNR)
+    return kw
+
+
 def product_scheduler(spec):
     from consistentid_amd import scheduler
     return {"ddim": scheduler.DDIMScheduler, "euler": scheduler.EulerDiscreteScheduler,
-            "dpm": scheduler.DPMSolverMultistepScheduler, "pndm": scheduler.PNDMScheduler}[spec.scheduler]()
+            "dpm": scheduler.DPMSolverMultistepScheduler, "pndm": scheduler.PNDMScheduler}[spec.scheduler](**scheduler_kwargs(spec))
+
+
+def scheduler_key(spec):
+    """what ``pipe.scheduler`` has to be rebuilt for"""
+    return spec.scheduler, spec.prediction, spec.zero_snr
+
+
+def active_sets(spec):
+    """{tuple of the indices of the nets that run: number of executed steps it runs in} (() where no net runs), from the
+    product's own keep table"""
+    from collections import Counter
+    from consistentid_amd.controlnet import active_nets, controlnet_keep_table
+    n = executed_steps(spec)                # (the engine's windows count schedule entries, PNDM's doubled first step included)
+    if not spec.nets:
+        return {(): n}
+    return dict(Counter(active_nets(row) for row in controlnet_keep_table(n, [w[0] for w in spec.windows], [w[1] for w in spec.windows])))
 
 
 def executed_steps(spec):
@@ -179,6 +218,8 @@ def call_pipeline(pipe, spec, dev):
         kw["callback"] = lambda i, t, lat: steps.append(lat.clone())
     if spec.eta > 0.0:
         kw.update(eta=spec.eta, variance_noise=d(inp["variance_noise"]))
+    if spec.rescale > 0.0:
+        kw["guidance_rescale"] = spec.rescale
     if spec.pipe in ("inpaint", "controlnet"):
         kw.update(image_latents=d(inp["init"]), noise=d(inp["noise"]), mask_latents=d(inp["mask"]), strength=spec.strength)
     if spec.pipe == "controlnet" and spec.nets:
@@ -200,6 +241,51 @@ def call_pipeline(pipe, spec, dev):
     return out, steps
 
 
+# --------------------------------------------------------------------------- FreeU and LoRA: state of the UNet
+@functools.lru_cache(maxsize=None)
+def lora_file(name, seed):
+    """``lora_cases.unet_lora(name, seed)`` as a kohya file of its family: SD1.5 with proj_in / proj_out shaped like 1x1
+    convolutions, SDXL with SGM names (what tests/test_gpu_lora.py loads)"""
+    import lora_cases as L
+    from consistentid_amd import lora
+    modules = L.unet_lora(name, seed=seed)
+    if name == "tinyxl":
+        cfg = product_cfg(name)
+        return L.to_kohya(modules, name_of=lambda p: lora.sgm_path(cfg, p))
+    return L.to_kohya(modules, conv=True)
+
+
+# UNet -> (the loras of the last spec applied to it, a weak reference to the pipeline that loaded them): the adapters are held
+# by a pipeline but merged into the UNet, which several pipelines may share
+_LORA_STATE = weakref.WeakKeyDictionary()
+
+
+def apply_features(pipe, spec):
+    """bring ``pipe``'s UNet from the FreeU / LoRA state it is in to ``spec``'s, through ``pipe``'s own diffusers-style methods
+    and only where the state differs: enable_freeu / disable_freeu, and unload_lora_weights (on the pipeline that loaded)
+    / load_lora_weights / set_adapters.  -> whether anything was called"""
+    unet, name = pipe.unet, spec.name
+    called = False
+    if unet._freeu != spec.freeu:
+        if spec.freeu is None:
+            pipe.disable_freeu()
+        else:
+            pipe.enable_freeu(*spec.freeu)
+        called = True
+    assert unet._freeu == spec.freeu
+    loaded, holder = _LORA_STATE.get(unet, ((), None))
+    if loaded != spec.loras:
+        if loaded:
+            holder().unload_lora_weights()
+        for seed, _ in spec.loras:
+            pipe.load_lora_weights(lora_file(name, seed), adapter_name=f"seed{seed}")
+        if any(w != 1.0 for _, w in spec.loras):
+            pipe.set_adapters([f"seed{seed}" for seed, _ in spec.loras], [w for _, w in spec.loras])
+        _LORA_STATE[unet] = (spec.loras, weakref.ref(pipe) if spec.loras else None)
+        called = True
+    return called
+
+
 def controlnet_of(spec, net_objects):
     """the pipeline's ``controlnet`` for ``spec`` out of {label: HipControlNet}"""
     from consistentid_amd.controlnet import HipMultiControlNet
@@ -210,57 +296,189 @@ def controlnet_of(spec, net_objects):
 
 @functools.lru_cache(maxsize=None)
 def fresh_eager(spec, dev_str):
-    """``spec`` on objects nothing else has touched: a new HipUNet, new HipControlNets from the same state dicts, a new
-    pipeline with use_graph=False -> (latents, [per-step clones])"""
+    """``spec`` on objects nothing else has touched: a new HipUNet (with ``keep_base`` where a LoRA is to be merged), new
+    HipControlNets from the same state dicts, a new pipeline with use_graph=False brought to the spec's FreeU / LoRA state
+    -> (latents, [per-step clones])"""
     dev = torch.device(dev_str)
     kw = {}
     if spec.pipe == "controlnet":
         kw["controlnet"] = controlnet_of(spec, {k: new_net(dev_str, k) for k in spec.nets})
-    pipe = pipeline_class(spec)(new_unet(dev_str, spec.name, spec.adapter), scheduler=product_scheduler(spec), use_graph=False, **kw)
+    unet = new_unet(dev_str, spec.name, spec.adapter, keep_base=bool(spec.loras))
+    pipe = pipeline_class(spec)(unet, scheduler=product_scheduler(spec), use_graph=False, **kw)
+    apply_features(pipe, spec)
     out, steps = call_pipeline(pipe, spec, dev)
     assert not pipe._engine.captures
     return out.clone(), steps
 
 
+# --------------------------------------------------------------------------- the oracle of a spec
 @functools.lru_cache(maxsize=None)
-def oracle_pair(spec, dev_str):
-    """(fp32 oracle latents, fp16-arm latents) of ``spec`` from oracle.loop.denoise"""
+def oracle_models(dev_str, name="tiny", adapter=0, loras=()):
+    """(fp32 oracle, fp16 arm) of the UNet with the LoRAs of ``loras`` merged in float64 (lora_cases.merged_state_dict);
+    ``loras`` = (): the pair of ``unet_models``"""
+    _, sd, ad, oracle, arm = unet_models(dev_str, name, adapter)
+    if not loras:
+        return oracle, arm
+    import lora_cases as L
+    merged = build_oracle(name, L.merged_state_dict(sd, [(L.unet_lora(name, seed=seed), w) for seed, w in loras]), ad, rank=8)
+    return merged, half_arm(merged, torch.device(dev_str))
+
+
+def reference_scheduler(spec, noises):
+    """the stateful restatement ``oracle.loop.denoise`` steps with, timesteps set: tests/multistep_ref.py and oracle/ddim.py
+    as before for an epsilon-prediction spec, tests/vpred_ref.py wherever ``prediction`` or ``zero_snr`` is set"""
     from multistep_ref import DDIMEtaRef, DPMSolverPP2MRef, PNDMRef
-    from oracle import ddim, loop
+    from oracle import ddim
+    kw = scheduler_kwargs(spec)
+    if spec.eta > 0.0:
+        assert spec.scheduler == "ddim"
+    if kw:
+        from vpred_ref import DDIMRef, DPMSolverVRef, EulerRef, PNDMVRef
+        if spec.scheduler == "ddim":
+            sch = DDIMRef(eta=spec.eta, noises=noises if spec.eta > 0.0 else (), **kw)
+        else:
+            sch = {"euler": EulerRef, "dpm": DPMSolverVRef, "pndm": PNDMVRef}[spec.scheduler](**kw)
+    elif spec.eta > 0.0:
+        return DDIMEtaRef(spec.eta, noises)
+    else:
+        sch = {"ddim": ddim.DDIMScheduler, "euler": ddim.EulerDiscreteScheduler, "dpm": DPMSolverPP2MRef, "pndm": PNDMRef}[spec.scheduler]()
+    sch.set_timesteps(spec.steps)       # the pipelines set the timesteps before scaling the initial noise (ref :510, :517)
+    return sch
+
+
+@functools.lru_cache(maxsize=None)
+def oracle_run(spec, dev_str, arm=False):
+    """``spec`` through ``oracle.loop.denoise``, unchanged: on the fp32 oracle on the CPU (needs no GPU), or with ``arm`` on its
+    fp16 copy on ``dev_str``.  LoRAs are merged into the oracle's state dict; guidance_rescale wraps the UNet
+    (vpred_ref.RescaledUNet); FreeU hooks the UNet's first two up blocks (freeu_ref.install_freeu) for this call only -- the
+    models are memoised and shared with other modules, so the handles are removed before this returns."""
+    from freeu_ref import install_freeu
+    from oracle import loop
+    from vpred_ref import RescaledUNet
     dev = torch.device(dev_str)
     M = models(dev_str)
-    _, _, _, o_unet, a_unet = unet_models(dev_str, spec.name, spec.adapter)
+    unet = oracle_models(dev_str, spec.name, spec.adapter, spec.loras)[int(arm)]
+    pool = M["a_cns" if arm else "o_cns"]
+    nets = [pool[list(NET_SEEDS).index(k)] for k in spec.nets]
+    f = (lambda t: dev_half(t, dev)) if arm else (lambda t: t.float())
     inp = inputs(spec, dev_str)
-    noises = list(inp["variance_noise"].float())
+    sch = reference_scheduler(spec, list(inp["variance_noise"].float()))
+    kw = dict(num_inference_steps=spec.steps, guidance_scale=spec.guidance, start_merge_step=spec.merge)
+    if spec.pipe in ("inpaint", "controlnet"):
+        kw.update(inpaint_mask=f(inp["mask"]), inpaint_init=f(inp["init"]), inpaint_noise=f(inp["noise"]), strength=spec.strength)
+    if spec.pipe == "sdxl":
+        kw.update(add_text_embeds_null=f(inp["pooled_null"]), add_text_embeds_text=f(inp["pooled_text"]),
+                  add_text_embeds_aug=f(inp["pooled_augmented"]), add_time_ids=f(inp["time_ids"]))
+        if spec.null_post:
+            kw["null_embeds_post"] = f(inp["null_post"])
+    wrap = None
+    if nets and spec.multi:
+        wrap = OracleMulti(nets, list(spec.scales), list(spec.windows), executed_steps(spec))
+        kw.update(controlnet=wrap, control_image=[f(inp["imgs"][k]) for k in spec.nets])
+    elif nets:
+        kw.update(controlnet=nets[0], control_image=f(inp["imgs"][spec.nets[0]]), conditioning_scale=spec.scales[0],
+                  control_guidance_start=spec.windows[0][0], control_guidance_end=spec.windows[0][1])
+    handles = install_freeu(unet, *spec.freeu) if spec.freeu is not None else []
+    try:
+        model = RescaledUNet(unet, spec.guidance, spec.rescale) if spec.rescale > 0.0 and spec.guidance > 1.0 else unet
+        out = loop.denoise(model, sch, f(inp["latents"]) * float(sch.init_noise_sigma), f(inp["null"]), f(inp["augmented"]),
+                           f(inp["text"]), **kw)
+    finally:
+        for h in handles:
+            h.remove()
+    assert wrap is None or wrap.calls == executed_steps(spec)
+    return out
 
-    def scheduler():
-        if spec.eta > 0.0:
-            assert spec.scheduler == "ddim"
-            return DDIMEtaRef(spec.eta, noises)
-        sch = {"ddim": ddim.DDIMScheduler, "euler": ddim.EulerDiscreteScheduler, "dpm": DPMSolverPP2MRef, "pndm": PNDMRef}[spec.scheduler]()
-        sch.set_timesteps(spec.steps)       # the pipelines set the timesteps before scaling the initial noise (ref :510, :517)
-        return sch
 
-    out = []
-    nets_of = lambda pool: [pool[list(NET_SEEDS).index(k)] for k in spec.nets]
-    for unet, nets, f in ((o_unet, nets_of(M["o_cns"]), lambda t: t.float()), (a_unet, nets_of(M["a_cns"]), lambda t: dev_half(t, dev))):
-        sch = scheduler()
-        kw = dict(num_inference_steps=spec.steps, guidance_scale=spec.guidance, start_merge_step=spec.merge)
-        if spec.pipe in ("inpaint", "controlnet"):
-            kw.update(inpaint_mask=f(inp["mask"]), inpaint_init=f(inp["init"]), inpaint_noise=f(inp["noise"]), strength=spec.strength)
-        if spec.pipe == "sdxl":
-            kw.update(add_text_embeds_null=f(inp["pooled_null"]), add_text_embeds_text=f(inp["pooled_text"]),
-                      add_text_embeds_aug=f(inp["pooled_augmented"]), add_time_ids=f(inp["time_ids"]))
-            if spec.null_post:
-                kw["null_embeds_post"] = f(inp["null_post"])
-        wrap = None
-        if nets and spec.multi:
-            wrap = OracleMulti(nets, list(spec.scales), list(spec.windows), executed_steps(spec))
-            kw.update(controlnet=wrap, control_image=[f(inp["imgs"][k]) for k in spec.nets])
-        elif nets:
-            kw.update(controlnet=nets[0], control_image=f(inp["imgs"][spec.nets[0]]), conditioning_scale=spec.scales[0],
-                      control_guidance_start=spec.windows[0][0], control_guidance_end=spec.windows[0][1])
-        out.append(loop.denoise(unet, sch, f(inp["latents"]) * float(sch.init_noise_sigma), f(inp["null"]), f(inp["augmented"]),
-                                f(inp["text"]), **kw))
-        assert wrap is None or wrap.calls == executed_steps(spec)
-    return tuple(out)
+def oracle_pair(spec, dev_str):
+    """(fp32 oracle latents, fp16-arm latents) of ``spec``"""
+    return oracle_run(spec, dev_str), oracle_run(spec, dev_str, True)
+
+
+def hooked_modules(*roots):
+    """the submodules of ``roots`` that carry a forward pre-hook: none, unless ``oracle_run`` left FreeU installed"""
+    return [m for root in roots for m in root.modules() if m._forward_pre_hooks]
+
+
+FEATURES = ("freeu", "rescale", "loras")        # the fields a spec can switch on that the engine could silently ignore
+
+
+def features_on(spec):
+    return [k for k in FEATURES if getattr(spec, k) != getattr(Spec(), k)]
+
+
+@functools.lru_cache(maxsize=None)
+def features_moved(spec, dev_str="cpu"):
+    """{feature that ``spec`` switches on: relative L2 distance, on the fp32 oracle alone, between ``spec`` and the same spec
+    with only that feature off}.  A parity test of ``spec`` says something about the feature only where this is far above
+    the parity tolerance (``assert_features_matter``)."""
+    from conftest import rel_l2
+    spec = spec.but(callback=False)
+    return {k: rel_l2(oracle_run(spec, dev_str), oracle_run(spec.but(**{k: getattr(Spec(), k)}), dev_str)) for k in features_on(spec)}
+
+
+def assert_features_matter(spec, dev_str="cpu"):
+    """the thresholds of the features' own tests: 20 * TOL_L2 for FreeU and guidance_rescale (tests/test_gpu_freeu.py),
+    lora_cases.MATTERS for a LoRA"""
+    from conftest import TOL_L2
+    from lora_cases import MATTERS
+    need = {"freeu": 20 * TOL_L2, "rescale": 20 * TOL_L2, "loras": MATTERS}
+    for k, moved in features_moved(spec, dev_str).items():
+        print(f"[engine] {k} moves the fp32 oracle of this spec by rel_l2={moved:.3e} (needs >= {need[k]:.1e})")
+        assert moved >= need[k], f"{k} moves the fp32 oracle by {moved:.3e} < {need[k]:.1e}: the comparison would be vacuous for {spec}"
+
+
+
+
+# --------------------------------------------------------------------------- a scenario: generations on one live pipeline
+@dataclass
+class Gen:
+    what: str                       # the one thing that differs from the generation before
+    spec: Spec
+    oracle: bool = False            # follows a change of net or UNet (the first and last generation are checked anyway)
+    same_graphs: bool = False       # a transition the engine promises not to re-capture for
+    pipe: Any = None                # scenarios over several pipelines: the one this generation runs on
+    before: Optional[Callable[[], None]] = None     # runs first (e.g. loads an adapter)
+
+
+def run_scenario(dev, scenario, gens, pipe=None, net_objects=None):
+    """-> the latents of every generation"""
+    assert all(executed_steps(g.spec) >= 3 for g in gens)
+    outs, held, multis, last = [], [], {}, {}
+    for n, g in enumerate(gens):
+        p, spec = g.pipe or pipe, g.spec
+        eng = p._engine
+        if g.before is not None:
+            g.before()
+        apply_features(p, spec)         # (nothing is called where ``before`` or the generation before left the spec's state)
+        if id(p) not in last or scheduler_key(last[id(p)]) != scheduler_key(spec):
+            p.scheduler = product_scheduler(spec)
+        if spec.nets and (id(p) not in last or (last[id(p)].nets, last[id(p)].multi) != (spec.nets, spec.multi)):
+            key = (spec.nets, spec.multi)
+            if key not in multis:
+                multis[key] = controlnet_of(spec, net_objects)
+            p.controlnet = multis[key]
+            held.append(p.controlnet)
+        last[id(p)] = spec
+        before = len(eng.captures)
+        got, steps = call_pipeline(p, spec, dev)
+        got = got.clone()
+        print(f"[engine] {scenario}: generation {n} ({g.what}): captures {before} -> {len(eng.captures)}"
+              f"{' (promised: none)' if g.same_graphs else ''}; graphs now {sorted(eng._graphs)}")
+        want, want_steps = fresh_eager(spec, str(dev))
+        assert torch.isfinite(got.float()).all(), f"{scenario}, generation {n} ({g.what}): not finite"
+        assert torch.equal(got, want), (f"{scenario}, generation {n} ({g.what}): differs from the fresh eager run, max |diff| = "
+                                        f"{(got.float() - want.float()).abs().max():.3e}")
+        if spec.callback:
+            assert len(steps) == len(want_steps) == executed_steps(spec)
+            for i, (a, b) in enumerate(zip(steps, want_steps)):
+                assert torch.equal(a, b), f"{scenario}, generation {n} ({g.what}): step {i} differs from the fresh eager run"
+        if g.oracle or n in (0, len(gens) - 1):
+            assert_features_matter(spec, str(dev))
+            check_vs_fp16_arm(got, *oracle_pair(spec.but(callback=False), str(dev)), f"{scenario}, generation {n} ({g.what})")
+        if g.same_graphs:
+            assert len(eng.captures) == before, f"{scenario}, generation {n} ({g.what}): re-captured {eng.captures[before:]}"
+        outs.append(got)
+    for p in {id(g.pipe or pipe): g.pipe or pipe for g in gens}.values():
+        assert p._engine.captures, f"{scenario}: nothing was ever captured, so nothing was replayed"
+    return outs

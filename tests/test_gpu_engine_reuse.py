@@ -6,68 +6,13 @@ the last generation and every one that follows a change of net or UNet are also 
 (conftest.check_vs_fp16_arm, defaults), so two engines that are wrong in the same way cannot agree their way through.  Where
 the engine promises to keep its graphs ``len(eng.captures)`` must not grow; elsewhere the count is printed
 as an ``[engine]`` line.  Every generation has at least 3 steps on one set of active nets: eager, capture, replay."""
-from dataclasses import dataclass
-from typing import Any, Callable, Optional
-
 import pytest
 import torch
 
-from conftest import check_vs_fp16_arm
-from engine_cases import (Spec, call_pipeline, controlnet_of, executed_steps, fresh_eager, new_net, new_unet, oracle_pair,
-                          pipeline_class, product_scheduler, unet_models)
+from engine_cases import Gen, Spec, new_net, new_unet, pipeline_class, unet_models
+from engine_cases import run_scenario as _run       # (Gen and the runner live in engine_cases: test_gpu_engine_features shares them)
 
 pytestmark = pytest.mark.gpu
-
-
-@dataclass
-class Gen:
-    what: str                       # the one thing that differs from the generation before
-    spec: Spec
-    oracle: bool = False            # follows a change of net or UNet (the first and last generation are checked anyway)
-    same_graphs: bool = False       # a transition the engine promises not to re-capture for
-    pipe: Any = None                # scenarios over several pipelines: the one this generation runs on
-    before: Optional[Callable[[], None]] = None     # runs first (e.g. loads an adapter)
-
-
-def _run(dev, scenario, gens, pipe=None, net_objects=None):
-    """-> the latents of every generation"""
-    assert all(executed_steps(g.spec) >= 3 for g in gens)
-    outs, held, multis, last = [], [], {}, {}
-    for n, g in enumerate(gens):
-        p, spec = g.pipe or pipe, g.spec
-        eng = p._engine
-        if g.before is not None:
-            g.before()
-        if last.get(id(p), spec).scheduler != spec.scheduler or id(p) not in last:
-            p.scheduler = product_scheduler(spec)
-        if spec.nets and (id(p) not in last or (last[id(p)].nets, last[id(p)].multi) != (spec.nets, spec.multi)):
-            key = (spec.nets, spec.multi)
-            if key not in multis:
-                multis[key] = controlnet_of(spec, net_objects)
-            p.controlnet = multis[key]
-            held.append(p.controlnet)
-        last[id(p)] = spec
-        before = len(eng.captures)
-        got, steps = call_pipeline(p, spec, dev)
-        got = got.clone()
-        print(f"[engine] {scenario}: generation {n} ({g.what}): captures {before} -> {len(eng.captures)}"
-              f"{' (promised: none)' if g.same_graphs else ''}; graphs now {sorted(eng._graphs)}")
-        want, want_steps = fresh_eager(spec, str(dev))
-        assert torch.isfinite(got.float()).all(), f"{scenario}, generation {n} ({g.what}): not finite"
-        assert torch.equal(got, want), (f"{scenario}, generation {n} ({g.what}): differs from the fresh eager run, max |diff| = "
-                                        f"{(got.float() - want.float()).abs().max():.3e}")
-        if spec.callback:
-            assert len(steps) == len(want_steps) == executed_steps(spec)
-            for i, (a, b) in enumerate(zip(steps, want_steps)):
-                assert torch.equal(a, b), f"{scenario}, generation {n} ({g.what}): step {i} differs from the fresh eager run"
-        if g.oracle or n in (0, len(gens) - 1):
-            check_vs_fp16_arm(got, *oracle_pair(spec.but(callback=False), str(dev)), f"{scenario}, generation {n} ({g.what})")
-        if g.same_graphs:
-            assert len(eng.captures) == before, f"{scenario}, generation {n} ({g.what}): re-captured {eng.captures[before:]}"
-        outs.append(got)
-    for p in {id(g.pipe or pipe): g.pipe or pipe for g in gens}.values():
-        assert p._engine.captures, f"{scenario}: nothing was ever captured, so nothing was replayed"
-    return outs
 
 
 # --------------------------------------------------------------------------- 1. txt2img
