@@ -82,6 +82,10 @@ SIGNATURES = {
     "cid_id_xattn_core_f16": (C.c_int, [c_half_p] * 4 + [C.c_void_p] + [C.c_int32] * 6 + [C.c_float, c_stream]),
     "cid_kv_pack_elems": (C.c_int64, [C.c_int32] * 3),
     "cid_kv_pack_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 5 + [c_stream]),
+    "cid_xattn_long_max_txt": (C.c_int32, []),
+    "cid_id_xattn_long_f16": (C.c_int, [c_half_p] * 4 + [C.c_void_p] + [C.c_int32] * 6 + [C.c_float, c_stream]),
+    "cid_kv_pack_long_elems": (C.c_int64, [C.c_int32] * 5),
+    "cid_kv_pack_long_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 5 + [c_stream]),
     "cid_pack_wfrag_f16": (C.c_int, [c_half_p] * 2 + [C.c_int32] * 2 + [c_stream]),
     "cid_kv_pack2_elems": (C.c_int64, [C.c_int32] * 3),
     "cid_id_xattn3_supported": (C.c_int, [C.c_int32] * 4),

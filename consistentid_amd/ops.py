@@ -321,6 +321,47 @@ def id_xattn(x: torch.Tensor, out: torch.Tensor, *, wq: torch.Tensor, wo: torch.
     return out
 
 
+def xattn_long_max_txt() -> int:
+    """most text rows the long-context kernel takes (CID_XATTN_LONG_MAX_TXT of the built library)"""
+    return int(_lib.load().cid_xattn_long_max_txt())
+
+
+XATTN_LONG_MAX_IP = 32      # CID_XATTN_LONG_MAX_IP (include/cid.h): the ID keys fill one key tile at the most
+XATTN_SHORT_MAX = 96        # key slots of the register-resident kernels (csrc/xattn_core.h); longer contexts run csrc/xattn_long.hip
+
+
+def kv_pack_long_elems(C_: int, heads: int, n_txt: int, n_ip: int):
+    lib = _lib.load()
+    ke, ve = (int(lib.cid_kv_pack_long_elems(C_, heads, n_txt, n_ip, w)) for w in (0, 1))
+    if ke < 0 or ve < 0:
+        raise ValueError(f"kv_pack_long_elems: no long-context layout for C={C_} heads={heads} n_txt={n_txt} n_ip={n_ip} "
+                         f"(1..{xattn_long_max_txt()} text rows, 0..{XATTN_LONG_MAX_IP} ID rows)")
+    return ke, ve
+
+
+def kv_pack_long(kv_txt: torch.Tensor, kv_ip: torch.Tensor, kp: torch.Tensor, vp: torch.Tensor, *, R: int, C_: int,
+                 heads: int, n_txt: int, n_ip: int):
+    """projected [K | V] rows ([R, L, 2C], text and ID projections) -> the operands of cid_id_xattn_long_f16 (include/cid.h):
+    key tiles of 32 slots, the ID keys on a tile of their own behind the last text tile"""
+    lib = _lib.load()
+    for name, t in (("kv_txt", kv_txt), ("kv_ip", kv_ip), ("kp", kp), ("vp", vp)):
+        _req(t, f"kv_pack_long.{name}")
+    check(lib.cid_kv_pack_long_f16(_p(kv_txt), _p(kv_ip), _p(kp), _p(vp), R, C_, heads, n_txt, n_ip, _stream()),
+          "cid_kv_pack_long_f16")
+
+
+def id_xattn_long(q: torch.Tensor, out: torch.Tensor, *, kp: torch.Tensor, vp: torch.Tensor, kvrow: torch.Tensor,
+                  B: int, N: int, C_: int, heads: int, n_txt: int, n_ip: int, ip_scale: float):
+    """two-stream attention core over a long context (kv_pack_long operands); q [B * N, C_] projected and pre-scaled"""
+    lib = _lib.load()
+    for name, t in (("q", q), ("out", out), ("kp", kp), ("vp", vp)):
+        _req(t, f"id_xattn_long.{name}")
+    _req(kvrow, "id_xattn_long.kvrow", torch.int32)
+    check(lib.cid_id_xattn_long_f16(_p(q), _p(out), _p(kp), _p(vp), _p(kvrow), B, N, C_, heads, n_txt, n_ip,
+                                    float(ip_scale), _stream()), "cid_id_xattn_long_f16")
+    return out
+
+
 def kv_pack2_elems(C_: int, heads: int):
     lib = _lib.load()
     return int(lib.cid_kv_pack2_elems(C_, heads, 0)), int(lib.cid_kv_pack2_elems(C_, heads, 1))
@@ -350,22 +391,31 @@ def kv_pack2(kv_txt: torch.Tensor, kv_ip: torch.Tensor, kp: torch.Tensor, vp: to
 
 
 def context_kv(ehs: torch.Tensor, w_txt: torch.Tensor, w_ip: torch.Tensor, *, R: int, L: int, C_: int, heads: int,
-               n_txt: int, n_ip: int, v3: bool, kp: Optional[torch.Tensor] = None, vp: Optional[torch.Tensor] = None):
+               n_txt: int, n_ip: int, v3: bool, kp: Optional[torch.Tensor] = None, vp: Optional[torch.Tensor] = None,
+               long: bool = False):
     """The packed K/V of one cross-attention layer for context rows ``ehs`` [R, L, Dc]: both [K | V] projections
-    (``w_txt`` / ``w_ip`` [2 C, Dc]), then the operand layout of the third-generation fused kernel (``v3``) or of the
-    first-generation kernels.  ``kp`` / ``vp`` are written in place where their size fits (a captured step keeps their
-    addresses).  Returns (kp, vp, whether they are new tensors)."""
+    (``w_txt`` / ``w_ip`` [2 C, Dc]), then the operand layout of the third-generation fused kernel (``v3``), of the
+    long-context kernel (``long``: run-time key-tile count, csrc/xattn_long.hip) or of the first-generation kernels.
+    ``kp`` / ``vp`` are written in place where their size fits (a captured step keeps their addresses).  Returns
+    (kp, vp, whether they are new tensors)."""
+    assert not (v3 and long), "context_kv: one operand layout"
     M, Dc = R * L, ehs.shape[-1]
     kv_txt = torch.empty(M, 2 * C_, dtype=torch.float16, device=ehs.device)
     kv_ip = torch.empty(M, 2 * C_, dtype=torch.float16, device=ehs.device)
     gemm(ehs, w_txt, kv_txt, M=M, N=2 * C_, c1=Dc)
     gemm(ehs, w_ip, kv_ip, M=M, N=2 * C_, c1=Dc)
-    ke, ve = kv_pack2_elems(C_, heads) if v3 else kv_pack_elems(C_, heads)
-    moved = kp is None or kp.numel() != R * ke
+    if long:
+        ke, ve = kv_pack_long_elems(C_, heads, n_txt, n_ip)
+    else:
+        ke, ve = kv_pack2_elems(C_, heads) if v3 else kv_pack_elems(C_, heads)
+    # (both sizes: a K image of one layout can be as large as another layout's while the V^T images differ)
+    moved = kp is None or kp.numel() != R * ke or vp.numel() != R * ve
     if moved:
         kp = torch.empty(R * ke, dtype=torch.float16, device=ehs.device)
         vp = torch.empty(R * ve, dtype=torch.float16, device=ehs.device)
-    if v3:
+    if long:
+        kv_pack_long(kv_txt, kv_ip, kp, vp, R=R, C_=C_, heads=heads, n_txt=n_txt, n_ip=n_ip)
+    elif v3:
         kv_pack2(kv_txt, kv_ip, kp, vp, R=R, L=L, C_=C_, heads=heads, n_txt=n_txt, n_ip=n_ip, order="reg")
     else:
         kv_pack(kv_txt, kv_ip, kp, vp, R=R, C_=C_, heads=heads, n_txt=n_txt, n_ip=n_ip)

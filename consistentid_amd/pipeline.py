@@ -410,20 +410,23 @@ class _SD15PromptEncoding:
 
     def encode_prompt(self, prompt, device=None, num_images_per_prompt: int = 1, do_classifier_free_guidance: bool = True,
                       negative_prompt=None, prompt_embeds=None, negative_prompt_embeds=None, lora_scale=None,
-                      clip_skip=None):
-        """-> (prompt_embeds, negative_prompt_embeds), fp16 on the engine's device"""
+                      clip_skip=None, max_embeddings_multiples: int = 1):
+        """-> (prompt_embeds, negative_prompt_embeds), fp16 on the engine's device.  ``max_embeddings_multiples`` >= 2: long
+        weighted prompts (prompt_weighting.py): ``(word)``, ``[word]``, ``(word:1.3)`` are parsed and the texts encoded in up
+        to that many chunks of 75 tokens, [B, 77 m, Dc]; 1 (default): diffusers' path, brackets literal, cut at 77."""
         from .prompt_encode import encode_prompt
         return encode_prompt(self.tokenizer, self.text_encoder, prompt, device or self.device, num_images_per_prompt,
                              do_classifier_free_guidance, negative_prompt, prompt_embeds, negative_prompt_embeds, lora_scale,
-                             clip_skip)
+                             clip_skip, max_embeddings_multiples=max_embeddings_multiples)
 
     def _encode_prompt(self, prompt, device=None, num_images_per_prompt: int = 1, do_classifier_free_guidance: bool = True,
-                       negative_prompt=None, prompt_embeds=None, negative_prompt_embeds=None, lora_scale=None):
+                       negative_prompt=None, prompt_embeds=None, negative_prompt_embeds=None, lora_scale=None,
+                       max_embeddings_multiples: int = 1):
         """legacy form the reference calls (ref :469-475, :494-501): cat([negative, prompt])"""
         from .prompt_encode import encode_prompt_legacy
         return encode_prompt_legacy(self.tokenizer, self.text_encoder, prompt, device or self.device, num_images_per_prompt,
                                     do_classifier_free_guidance, negative_prompt, prompt_embeds, negative_prompt_embeds,
-                                    lora_scale)
+                                    lora_scale, max_embeddings_multiples=max_embeddings_multiples)
 
     def encode_prompt_with_trigger_word(self, prompt: str, face_caption: str, key_parsing_mask_list=None,
                                         image_token: str = "<|image|>", facial_token: str = "<|facial|>",
@@ -469,14 +472,16 @@ class _IDPreLoop:
             raise ValueError("give either prompt + input_id_images or prompt_embeds, not both")
         return True
 
-    def _id_call_prompt_embeds(self, prompt, input_id_images, negative_prompt, num_images_per_prompt) -> torch.Tensor:
-        """``prompt_embeds`` [3n, 77 + num_tokens, Dc] of a pre-loop call: the pre-loop runs once and each of its three row
+    def _id_call_prompt_embeds(self, prompt, input_id_images, negative_prompt, num_images_per_prompt,
+                               max_embeddings_multiples: int = 1) -> torch.Tensor:
+        """``prompt_embeds`` [3n, 77 m + num_tokens, Dc] of a pre-loop call (m = 1 unless ``max_embeddings_multiples`` >= 2 and
+        the negative prompt needs more chunks): the pre-loop runs once and each of its three row
         groups is repeated ``num_images_per_prompt`` = n times, which is diffusers' meaning of the argument (the reference
         itself breaks on n > 1)."""
         n = 1 if num_images_per_prompt is None else int(num_images_per_prompt)
         if n < 1:
             raise ValueError(f"num_images_per_prompt must be at least 1, got {num_images_per_prompt}")
-        pe = self.prepare_id_prompt_embeds(prompt, input_id_images, negative_prompt)
+        pe = self.prepare_id_prompt_embeds(prompt, input_id_images, negative_prompt, max_embeddings_multiples)
         return pe if n == 1 else torch.cat([rows.repeat(n, 1, 1) for rows in pe.chunk(3)])
 
     def get_prepare_faceid(self, face_image) -> torch.Tensor:
@@ -547,10 +552,19 @@ class _IDPreLoop:
         return (fe(prompt_embeds, emb, facial_token_masks, valid_facial_token_idx_mask),
                 fe(negative_prompt_embeds, uncond, facial_token_masks, valid_facial_token_idx_mask))
 
-    def prepare_id_prompt_embeds(self, prompt: str, input_id_images, negative_prompt=None) -> torch.Tensor:
+    def prepare_id_prompt_embeds(self, prompt: str, input_id_images, negative_prompt=None,
+                                 max_embeddings_multiples: int = 1) -> torch.Tensor:
         """``prompt_embeds`` [3, 77 + num_tokens, Dc] = cat([null, augmented, text_only]) of ONE prompt and its ID images,
         assembled as ref :437-507 does.  The CLIP tower runs each distinct image once: the face, its real crops and one zero
-        image, whose hidden states stand for every padded crop and every uncond input."""
+        image, whose hidden states stand for every padded crop and every uncond input.
+        ``max_embeddings_multiples`` >= 2 (prompt_weighting.py): the NEGATIVE prompt is parsed for emphasis, weighted and
+        encoded in the m <= max_embeddings_multiples chunks it needs.  The trigger-word machinery is the reference's and is
+        defined on the 77 window, so the prompt (with the trigger word and the facial caption) is tokenised as always, its
+        brackets literal; both positive sets are continued to 77 m rows with the tower's output for the empty chunk
+        [bos, pad x 75, eos] and the facial token mask with zeros -> [3, 77 m + num_tokens, Dc].  Emphasis in the positive
+        prompt of an ID call: ``encode_prompt(..., max_embeddings_multiples=)`` + ``prepare_prompt_embeds``."""
+        from .prompt_weighting import check_multiples
+        check_multiples(max_embeddings_multiples)
         missing = self._missing_id_components()
         if missing:
             raise NotImplementedError("prompt + input_id_images need: " + ", ".join(missing))
@@ -565,8 +579,19 @@ class _IDPreLoop:
         text_only, clean_ids, masks_align, fmask, _, fidx_mask = self.encode_prompt_with_trigger_word(
             prompt, caption, masks, max_num_facials=5, num_id_images=len(images))           # :445-458
         text_embeds = self.text_encoder(clean_ids.to(dev))[0]                               # :467
-        both = self._encode_prompt(text_only, dev, 1, True, negative_prompt)               # :469-477
-        neg, pos = both[:1], both[1:]
+        if max_embeddings_multiples == 1:
+            both = self._encode_prompt(text_only, dev, 1, True, negative_prompt)           # :469-477
+            neg, pos = both[:1], both[1:]
+        else:
+            from . import prompt_weighting as pw
+            from .prompt_encode import _uncond_tokens
+            pos = self.encode_prompt(text_only, dev, 1, False)[0]
+            neg, _, m = pw.encode_weighted(self.tokenizer, self.text_encoder, _uncond_tokens(text_only, negative_prompt, 1),
+                                           None, max_embeddings_multiples, dev)
+            neg = neg.to(device=dev, dtype=torch.float16)
+            pos = pw.extend_with_empty_chunks(self.text_encoder, self.tokenizer, pos, m, dev)
+            text_embeds = pw.extend_with_empty_chunks(self.text_encoder, self.tokenizer, text_embeds, m, dev)
+            fmask = torch.nn.functional.pad(fmask, (0, pw.WINDOW * (m - 1)))
         from .face_prep import clip_preprocess
         crops, _ = self.get_prepare_clip_image(img, masks_align, image_size=512, max_num_facials=5)    # :482
         n = len(masks_align)
@@ -590,16 +615,20 @@ class ConsistentIDStableDiffusionPipeline(_IDPreLoop, _SD15PromptEncoding, _Base
                  cross_attention_kwargs=None, original_size=None, target_size=None, callback=None,
                  callback_steps: int = 1, input_id_images=None, start_merge_step: int = 0,
                  class_tokens_mask=None, prompt_embeds_text_only=None, variance_noise: Optional[torch.Tensor] = None,
-                 guidance_rescale: float = 0.0):
+                 max_embeddings_multiples: int = 1, guidance_rescale: float = 0.0):
         """``guidance_rescale`` (diffusers 0.23 StableDiffusionPipeline; rescale_noise_cfg's phi): > 0 rescales the guided
         prediction to the conditional one's standard deviation, per sample and step.
+        ``max_embeddings_multiples`` >= 2: the negative prompt of a pre-loop call is a long weighted prompt
+        (prepare_id_prompt_embeds).  ``prompt_embeds`` may have any [3B, T + num_tokens, Dc] the
+        cross-attention kernels take (T <= 1024 text rows).
         ``pipe(prompt, input_id_images=[face], ...)`` runs the reference's pre-loop (prepare_id_prompt_embeds) and, without
         ``latents``, draws them like diffusers' prepare_latents (randn_tensor on the generator's device); or pass
         ``prompt_embeds`` (cat([null, augmented, text_only])) and ``latents`` directly.  ``num_images_per_prompt`` = n on the
         prompt path: n samples of the one identity -- the embeds repeated n times, the latents one draw of [n, C, h, w]."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         if self._takes_id_pre_loop(prompt, input_id_images, prompt_embeds):
-            prompt_embeds = self._id_call_prompt_embeds(prompt, input_id_images, negative_prompt, num_images_per_prompt)
+            prompt_embeds = self._id_call_prompt_embeds(prompt, input_id_images, negative_prompt, num_images_per_prompt,
+                                                        max_embeddings_multiples)
             n = prompt_embeds.shape[0] // 3
             if latents is None:
                 from .vae import randn_tensor
@@ -637,7 +666,9 @@ class ConsistentIDStableDiffusionXLPipeline(_BasePipeline):
                       prompt_embeds=None, negative_prompt_embeds=None, pooled_prompt_embeds=None,
                       negative_pooled_prompt_embeds=None, lora_scale=None):
         """D: StableDiffusionXLPipeline.encode_prompt (ref SDXL :552-565) on the two HIP towers -> (prompt_embeds,
-        negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds)"""
+        negative_prompt_embeds, pooled_prompt_embeds, negative_pooled_prompt_embeds).  No ``max_embeddings_multiples`` here:
+        strings are cut at 77 tokens and their brackets are literal; the SDXL pipeline takes long prompts only as
+        ``prompt_embeds`` / ``negative_prompt_embeds`` of T + num_tokens rows (T <= 1024) built elsewhere."""
         from .prompt_encode import encode_prompt_sdxl
         toks, encs = [self.tokenizer, self.tokenizer_2], [self.text_encoder, self.text_encoder_2]
         if self.text_encoder is None:
@@ -723,7 +754,7 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
     default_guidance = 7.5
 
     def _call_inputs(self, prompt, input_id_images, prompt_embeds, negative_prompt, num_images_per_prompt, image, mask_image,
-                     height, width):
+                     height, width, max_embeddings_multiples: int = 1):
         """What the reference does between its arguments and the VAE encode (inpaint ref :127-239, CN :180-265): the ID
         pre-loop on ``input_id_images[0]`` for ``prompt`` + ``input_id_images``, and image_prep.py for PIL images.  The init
         image is ``image`` when given, else ``input_id_images[0]`` (ref :157, :232-234); PIL inputs are brought to ``height``
@@ -746,7 +777,8 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                 mask_image = image_prep.preprocess_mask(mask_image, height, width)
             height, width = (image if torch.is_tensor(image) else mask_image).shape[-2:]
         if id_call:
-            prompt_embeds = self._id_call_prompt_embeds(prompt, input_id_images, negative_prompt, num_images_per_prompt)
+            prompt_embeds = self._id_call_prompt_embeds(prompt, input_id_images, negative_prompt, num_images_per_prompt,
+                                                        max_embeddings_multiples)
         return prompt_embeds, image, mask_image, height, width, normalize
 
     def _strength_window(self, strength: float, num_inference_steps: int, latents, image_latents, noise):
@@ -867,9 +899,9 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                  prompt_embeds_text_only=None, image_latents: Optional[torch.Tensor] = None,
                  noise: Optional[torch.Tensor] = None, mask_latents: Optional[torch.Tensor] = None,
                  down_block_res_samples=None, mid_block_res_sample=None, variance_noise: Optional[torch.Tensor] = None,
-                 guidance_rescale: float = 0.0):
-        """``guidance_rescale``: an engine extension here (diffusers' inpaint pipelines do not take it), as in
-        ConsistentIDStableDiffusionPipeline.__call__.  The reference's call, ``pipe(prompt, input_id_images=face, mask_image=mask, height=, width=, ...)``, runs its whole
+                 max_embeddings_multiples: int = 1, guidance_rescale: float = 0.0):
+        """``guidance_rescale`` / ``max_embeddings_multiples``: engine extensions here (diffusers' inpaint pipelines do not take
+        them), as in ConsistentIDStableDiffusionPipeline.__call__.  The reference's call, ``pipe(prompt, input_id_images=face, mask_image=mask, height=, width=, ...)``, runs its whole
         pre-loop: the ID pre-loop on ``input_id_images[0]`` (prepare_id_prompt_embeds; ref :157-229), image_prep.py on the
         PIL init image and mask (ref :232-239), the VAE encode on ``vae_encoder`` (ref :255-291).  ``prompt_embeds``
         (cat([null, augmented, text_only])) replaces the first part; the pre-computed ``image_latents`` (init latents),
@@ -890,18 +922,19 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                              start_merge_step=start_merge_step, image_latents=image_latents, noise=noise,
                              mask_latents=mask_latents, down_block_res_samples=down_block_res_samples,
                              mid_block_res_sample=mid_block_res_sample, variance_noise=variance_noise,
-                             guidance_rescale=guidance_rescale)
+                             guidance_rescale=guidance_rescale, max_embeddings_multiples=max_embeddings_multiples)
 
     def _inpaint(self, *, prompt, image, mask_image, masked_image_latents, height, width, strength, num_inference_steps,
                  guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents, prompt_embeds,
                  output_type, return_dict, callback, callback_steps, input_id_images, start_merge_step, image_latents,
                  noise, mask_latents, down_block_res_samples, mid_block_res_sample, variance_noise, control=None,
-                 guidance_rescale: float = 0.0):
+                 max_embeddings_multiples: int = 1, guidance_rescale: float = 0.0):
         """The body both inpaint ``__call__``s share (inpaint ref :127-359, CN :180-456).  ``control``: the ControlNet
         pipeline's (control_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end)."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         prompt_embeds, image, mask_image, height, width, normalize = self._call_inputs(
-            prompt, input_id_images, prompt_embeds, negative_prompt, num_images_per_prompt, image, mask_image, height, width)
+            prompt, input_id_images, prompt_embeds, negative_prompt, num_images_per_prompt, image, mask_image, height, width,
+            max_embeddings_multiples)
         if image is not None or mask_image is not None:
             image_latents, noise, mask_latents, masked_image_latents = self._encode_images(
                 image, mask_image, height, width, latents, strength, generator, prompt_embeds,
@@ -962,8 +995,8 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
                  image_latents: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                  mask_latents: Optional[torch.Tensor] = None, down_block_res_samples=None, mid_block_res_sample=None,
                  masked_image_latents: Optional[torch.Tensor] = None, variance_noise: Optional[torch.Tensor] = None,
-                 guidance_rescale: float = 0.0):
-        """``prompt`` / ``input_id_images`` / ``image`` / ``mask_image`` / ``guidance_rescale``: as in
+                 max_embeddings_multiples: int = 1, guidance_rescale: float = 0.0):
+        """``prompt`` / ``input_id_images`` / ``image`` / ``mask_image`` / ``guidance_rescale`` / ``max_embeddings_multiples``: as in
         StableDiffusionInpaintConsistentIDPipeline.__call__ (CN :180-265).  ``control_image``: a float tensor [B, 3, 8h, 8w]
         in [0, 1], or one PIL image (or a list of one), converted to RGB and resized to the final height x width by
         image_prep.preprocess_control (CN :267-280).
@@ -985,4 +1018,5 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
                              mask_latents=mask_latents, down_block_res_samples=down_block_res_samples,
                              mid_block_res_sample=mid_block_res_sample, variance_noise=variance_noise,
                              control=(control_image, controlnet_conditioning_scale, control_guidance_start,
-                             control_guidance_end), guidance_rescale=guidance_rescale)
+                             control_guidance_end), guidance_rescale=guidance_rescale,
+                             max_embeddings_multiples=max_embeddings_multiples)

@@ -69,11 +69,19 @@ def _uncond_tokens(prompt, negative_prompt, batch_size: int) -> List[str]:
 def encode_prompt(tokenizer, text_encoder, prompt: PromptT, device=None, num_images_per_prompt: int = 1,
                   do_classifier_free_guidance: bool = True, negative_prompt: PromptT = None,
                   prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
-                  lora_scale=None, clip_skip=None):
+                  lora_scale=None, clip_skip=None, max_embeddings_multiples: int = 1):
     """D: StableDiffusionPipeline.encode_prompt (0.23) -> (prompt_embeds, negative_prompt_embeds): the last hidden state
     (after final_layer_norm) of the padded, truncated prompt; the negative defaults to ""; each row repeated
-    ``num_images_per_prompt`` times.  Without CFG the negative comes back as given (None by default)."""
+    ``num_images_per_prompt`` times.  Without CFG the negative comes back as given (None by default).
+    ``max_embeddings_multiples`` >= 2: long weighted prompts (prompt_weighting.py) -- the emphasis syntax is parsed and the
+    texts are encoded in up to that many chunks of 75 tokens, [B, 77 m, Dc]; 1 is diffusers' path above (brackets are
+    literal characters, truncation at 77)."""
+    from .prompt_weighting import check_multiples
     _refuse(lora_scale, clip_skip)
+    if check_multiples(max_embeddings_multiples) > 1:
+        return _encode_prompt_weighted(tokenizer, text_encoder, prompt, device, num_images_per_prompt,
+                                       do_classifier_free_guidance, negative_prompt, prompt_embeds, negative_prompt_embeds,
+                                       max_embeddings_multiples)
     batch_size = _batch_size(prompt, prompt_embeds)
     if prompt_embeds is None:
         if text_encoder is None or tokenizer is None:
@@ -94,13 +102,44 @@ def encode_prompt(tokenizer, text_encoder, prompt: PromptT, device=None, num_ima
     return prompt_embeds, negative_prompt_embeds
 
 
+def _encode_prompt_weighted(tokenizer, text_encoder, prompt, device, num_images_per_prompt, do_classifier_free_guidance,
+                            negative_prompt, prompt_embeds, negative_prompt_embeds, max_embeddings_multiples):
+    """encode_prompt with ``max_embeddings_multiples`` >= 2: the texts that have to be encoded share one effective multiple;
+    given embeddings of 77 m rows fix it"""
+    from . import prompt_weighting as pw
+    batch_size = _batch_size(prompt, prompt_embeds)
+    need_neg = do_classifier_free_guidance and negative_prompt_embeds is None
+    if (prompt_embeds is None or need_neg) and (text_encoder is None or tokenizer is None):
+        raise ValueError("encoding a prompt string needs a tokenizer and a text_encoder")
+    prompts = None if prompt_embeds is not None else ([prompt] if isinstance(prompt, str) else list(prompt))
+    negatives = _uncond_tokens(prompt, negative_prompt, batch_size) if need_neg else None
+    if prompts is not None:
+        prompt_embeds, neg, _ = pw.encode_weighted(tokenizer, text_encoder, prompts, negatives, max_embeddings_multiples, device)
+    elif negatives is not None:
+        rows = prompt_embeds.shape[1]
+        if rows % pw.WINDOW or rows // pw.WINDOW > max_embeddings_multiples:
+            raise ValueError(f"prompt_embeds of {rows} rows with max_embeddings_multiples = {max_embeddings_multiples}: the "
+                             f"negative prompt is encoded in chunks of {pw.WINDOW} rows, at most that many")
+        neg, _, _ = pw.encode_weighted(tokenizer, text_encoder, negatives, None, rows // pw.WINDOW, device)
+        neg = pw.extend_with_empty_chunks(text_encoder, tokenizer, neg, rows // pw.WINDOW, device)    # (a shorter negative prompt)
+    if need_neg:
+        negative_prompt_embeds = neg
+    prompt_embeds = _repeat(prompt_embeds.to(device=device, dtype=torch.float16), num_images_per_prompt)
+    if do_classifier_free_guidance:
+        if negative_prompt_embeds.shape[0] != batch_size:
+            raise ValueError(f"negative_prompt_embeds has batch size {negative_prompt_embeds.shape[0]}, the prompt {batch_size}")
+        negative_prompt_embeds = _repeat(negative_prompt_embeds.to(device=device, dtype=torch.float16), num_images_per_prompt)
+    return prompt_embeds, negative_prompt_embeds
+
+
 def encode_prompt_legacy(tokenizer, text_encoder, prompt: PromptT, device=None, num_images_per_prompt: int = 1,
                          do_classifier_free_guidance: bool = True, negative_prompt: PromptT = None,
                          prompt_embeds: Optional[torch.Tensor] = None, negative_prompt_embeds: Optional[torch.Tensor] = None,
-                         lora_scale=None):
+                         lora_scale=None, max_embeddings_multiples: int = 1):
     """D: ``_encode_prompt`` (deprecated form of 0.23, the one the reference calls): cat([negative, prompt])"""
     pos, neg = encode_prompt(tokenizer, text_encoder, prompt, device, num_images_per_prompt, do_classifier_free_guidance,
-                             negative_prompt, prompt_embeds, negative_prompt_embeds, lora_scale)
+                             negative_prompt, prompt_embeds, negative_prompt_embeds, lora_scale,
+                             max_embeddings_multiples=max_embeddings_multiples)
     return torch.cat([neg, pos]) if neg is not None else pos
 
 

@@ -43,7 +43,8 @@ class _Ctx:
     def __init__(self):
         self.kp: Dict[str, torch.Tensor] = {}
         self.vp: Dict[str, torch.Tensor] = {}
-        self.v2: Dict[str, int] = {}       # generation (0 / 2 / 3) of the fused kernel whose K/V operand layout the layer holds
+        # generation (0 / 2 / 3) of the fused kernel whose K/V operand layout the layer holds, or LONG_CONTEXT
+        self.v2: Dict[str, int] = {}
         self.rows = 0
         self.n_txt = 0
         self.n_ip = 0
@@ -52,6 +53,9 @@ class _Ctx:
         # to the NEXT prompt's embeddings and the stale K/V would be served
         self.key = None
         self.key_ref = None
+
+
+LONG_CONTEXT = 4    # _Ctx.v2 value: the K/V images are those of the long-context kernel (more than 96 context rows)
 
 
 def _tensor_key(t: torch.Tensor):
@@ -157,6 +161,14 @@ class HipUNet:
         nt = self.num_tokens if num_tokens is None else num_tokens
         given, ehs = ehs, ehs.to(device=self.device, dtype=torch.float16).contiguous()
         R, L, _ = ehs.shape
+        # more than 96 context rows (weighted / chunked prompts of 77 k rows): every layer is packed for the long-context
+        # kernel (csrc/xattn_long.hip), whose caps are checked here, before anything is launched or changed
+        long_ctx = L > ops.XATTN_SHORT_MAX
+        if long_ctx:
+            cap = ops.xattn_long_max_txt()
+            if L - nt > cap or L - nt < 1 or not 0 <= nt <= ops.XATTN_LONG_MAX_IP:
+                raise ValueError(f"set_context: {L - nt} text rows + {nt} ID rows; the cross-attention kernels take at most "
+                                 f"{cap} text rows and {ops.XATTN_LONG_MAX_IP} ID rows")
         ctx = self._ctx
         ctx.rows, ctx.n_txt, ctx.n_ip = R, L - nt, nt
         moved = False
@@ -165,14 +177,14 @@ class HipUNet:
             C_ = wt.shape[0] // 2
             heads = self._heads_of(b)
             # fragment order of the third-generation fused kernel (SD1.5 level 0) where it serves
-            v3 = (self._xattn_gen >= 3 and f"{b}.attn2.wq_p" in self.W
+            v3 = (not long_ctx and self._xattn_gen >= 3 and f"{b}.attn2.wq_p" in self.W
                   and ops.id_xattn3_supported(C_, heads, ctx.n_txt, ctx.n_ip))
             # (the buffers of the last context are reused: addresses stay stable across generations)
             ctx.kp[b], ctx.vp[b], new = ops.context_kv(ehs, wt, self.W[f"{b}.attn2.kv_ip.w"], R=R, L=L, C_=C_, heads=heads,
                                                        n_txt=ctx.n_txt, n_ip=ctx.n_ip, v3=v3, kp=ctx.kp.get(b),
-                                                       vp=ctx.vp.get(b))
+                                                       vp=ctx.vp.get(b), long=long_ctx)
             moved |= new
-            ctx.v2[b] = 3 if v3 else 0
+            ctx.v2[b] = LONG_CONTEXT if long_ctx else 3 if v3 else 0
         ctx.key, ctx.key_ref = _tensor_key(given), given
         if moved:       # the allocator may hand an old address out again: the addresses alone do not tell
             self.epoch += 1
@@ -278,7 +290,8 @@ class HipUNet:
         # zero-padded token axis: every other op of the block is row-wise, the self-attention masks the pad keys
         # (cid_self_attn_keys_f16), and the pad rows are dropped at the end.
         gens = {ctx.v2.get(f"{n}.transformer_blocks.{k}", 0) for k in range(t.n_layers)}
-        need = 128 if (2 in gens or (c <= self._xattn_fused_max_c and c > 128 and not gens <= {3})) else 64
+        # (the long-context core tiles 32 tokens; the self-attention's 64 decide there)
+        need = 128 if (2 in gens or (c <= self._xattn_fused_max_c and c > 128 and not gens <= {3, LONG_CONTEXT})) else 64
         N_real = N
         if N % need:
             N = (N + need - 1) // need * need
@@ -325,7 +338,7 @@ class HipUNet:
             # the last block's ff2 and proj_out as one GEMM over the row [ff | h3]: both live in ONE
             # [M, 5c] buffer, written at pitch 5c by their producers (the first-generation fused kernel has no pitched form)
             fold = (k == t.n_layers - 1 and ops.ff2_fold(M, c, gn_hw)
-                    and (ctx.v2.get(b) == 3 or not self._fused_gen1(c, M)))
+                    and (ctx.v2.get(b) in (3, LONG_CONTEXT) or not self._fused_gen1(c, M)))
             buf = self._empty(M, 5 * c) if fold else None
             ldh = 5 * c if fold else c
             h3 = self.cross_attention(b, h2, B, N, c, t.heads, kvrow, out=buf[:, 4 * c:] if fold else None)
@@ -362,14 +375,29 @@ class HipUNet:
             LayerNorm folded into Wq, x read from HBM once;
           * C <= CID_XATTN_FUSED_MAX_C otherwise: one launch of the first-generation fused kernel;
           * wider levels: LayerNorm + q GEMM + two-stream attention core + out GEMM (+ bias + residual) -- a
-            [tokens x C] tile does not fit in LDS next to the weight slabs there.
+            [tokens x C] tile does not fit in LDS next to the weight slabs there;
+          * any level, more than 96 context rows: (LayerNorm +) q GEMM + long-context core (csrc/xattn_long.hip) + out GEMM.
         ``out``: a [B * N, c] column block of a wider buffer to write instead of a fresh contiguous tensor (its row stride is
         the pitch; not with the first-generation fused kernel)."""
         W, ctx = self.W, self._ctx
         M = B * N
         h3 = self._empty(M, c) if out is None else out
         ldo = None if out is None else out.stride(0)
-        if ctx.v2.get(b) == 3:
+        if ctx.v2.get(b) == LONG_CONTEXT:
+            # more than 96 context rows (tested first: _fused_gen1 does not look at the context): the (LayerNorm-folded)
+            # query projection, the long-context core (csrc/xattn_long.hip), the out projection (+ bias + residual)
+            q2 = self._empty(M, c)
+            if ops.ln_fold(M):
+                ops.gemm(h2, W[f"{b}.attn2.wql"], q2, M=M, N=c, c1=c, ln=self._ln(b, "attn2.wq_ln"))
+            else:
+                ln2 = self._empty(M, c)
+                ops.layernorm(h2, ln2, W[f"{b}.norm2.g"], W[f"{b}.norm2.b"], M=M, C_=c)
+                ops.gemm(ln2, W[f"{b}.attn2.wq"], q2, M=M, N=c, c1=c)
+            o2 = self._empty(M, c)
+            ops.id_xattn_long(q2, o2, kp=ctx.kp[b], vp=ctx.vp[b], kvrow=kvrow, B=B, N=N, C_=c, heads=heads,
+                              n_txt=ctx.n_txt, n_ip=ctx.n_ip, ip_scale=self.packed.ip_scale[b])
+            ops.gemm(o2, W[f"{b}.attn2.wo"], h3, M=M, N=c, c1=c, ldo=ldo, bias=W[f"{b}.attn2.bo"], res=h2, ldr=c)
+        elif ctx.v2.get(b) == 3:
             ops.id_xattn3(h2, h3, wq_p=W[f"{b}.attn2.wq_p"], q_rowsum=W[f"{b}.attn2.qs"].view(torch.float32),
                           q_bias=W[f"{b}.attn2.qb"].view(torch.float32), wo_p=W[f"{b}.attn2.wo_p"], bo=W[f"{b}.attn2.bo"],
                           kp=ctx.kp[b], vp=ctx.vp[b], kvrow=kvrow, B=B, N=N, C_=c, heads=heads, n_txt=ctx.n_txt,
@@ -420,6 +448,10 @@ class HipUNet:
         roofline block, tools/xattn_levels.py) -- the same predicates on the same arguments as the method itself"""
         assert B > 0 and N > 0, "cross_attention_path: B samples of N tokens (the shape decides the launch sequence)"
         tokens = B * N
+        if self._ctx.v2.get(b) == LONG_CONTEXT:
+            return (f"q GEMM + id_xattn_long core<{self._ctx.n_txt},{self._ctx.n_ip}> + out GEMM (three launches)"
+                    if ops.ln_fold(tokens) else
+                    f"layernorm + q GEMM + id_xattn_long core<{self._ctx.n_txt},{self._ctx.n_ip}> + out GEMM (four launches)")
         if self._ctx.v2.get(b):
             gen = self._ctx.v2[b]
             return f"id_xattn{gen}_kernel<{self._ctx.n_txt},{self._ctx.n_ip}> (one launch)"

@@ -27,7 +27,7 @@ extern "C" {
 typedef void* cid_stream_t;      /* hipStream_t */
 typedef uint16_t cid_half;       /* IEEE binary16 bit pattern */
 
-int cid_version(void);          /* 109: cid_freeu_f16, cid_freeu_ws_bytes added.  108: cid_cfg_rescale_f16, cid_cfg_ddim_step_scaled_f16, cid_cfg_multistep_step_scaled_f16 added.  107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
+int cid_version(void);          /* 110: cid_id_xattn_long_f16, cid_kv_pack_long_f16, cid_kv_pack_long_elems, cid_xattn_long_max_txt added (contexts beyond 96 keys).  109: cid_freeu_f16, cid_freeu_ws_bytes added.  108: cid_cfg_rescale_f16, cid_cfg_ddim_step_scaled_f16, cid_cfg_multistep_step_scaled_f16 added.  107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
                                  * pointer (102: act, 101: pad_mode; set them or zero the struct) */
 const char* cid_last_error(void);
 
@@ -214,6 +214,34 @@ int cid_kv_pack_f16(const cid_half* kv_txt, const cid_half* kv_ip, cid_half* kp,
                     cid_stream_t stream);
 /* [rows][K] fp16 row-major -> MFMA A-fragment order [rows/32][K/16][64 lanes][8]. */
 int cid_pack_wfrag_f16(const cid_half* w, cid_half* wp, int32_t rows, int32_t K, cid_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * Long contexts (csrc/xattn_long.hip, since cid_version() 110): the attention core of cid_id_xattn_core_f16 over
+ * 1 <= n_txt <= CID_XATTN_LONG_MAX_TXT text rows and 0 <= n_ip <= CID_XATTN_LONG_MAX_IP ID rows -- weighted / chunked
+ * prompts of 77 k rows.  The key axis is walked in 32-slot tiles under an online softmax (fp32), the ID keys sit on a
+ * tile of their own behind the last text tile:
+ *   out = softmax2(q Kt^T) Vt + ip_scale * softmax2(q Kip^T) Vip        (attention.py:259-279; the ID term is absent for n_ip = 0)
+ *   q, out : [B][N][C] fp16 (ld = C), q projected and pre-scaled by d^-0.5 * log2(e); N % 32 == 0;
+ *            head width C / heads in {32, 40, 64, 80, 160};  kvrow[s] = packed context row of sample s.
+ * Deterministic (no atomics).  Everything else is refused with -22 before any launch. */
+#define CID_XATTN_LONG_MAX_TXT 1024
+#define CID_XATTN_LONG_MAX_IP 32
+int32_t cid_xattn_long_max_txt(void);      /* CID_XATTN_LONG_MAX_TXT of the library that was built */
+int cid_id_xattn_long_f16(const cid_half* q, cid_half* out, const cid_half* kp, const cid_half* vp,
+                          const int32_t* kvrow, int32_t B, int32_t N, int32_t C, int32_t heads,
+                          int32_t n_txt, int32_t n_ip, float ip_scale, cid_stream_t stream);
+/* halfs of one packed K row (which = 0) / V^T row (which = 1) of that kernel, per context row; -22 outside the range above.
+ * With QKS = ceil(d / 16), DVT = ceil(d / 32), NT = ceil(n_txt / 32), NK = NT + (n_ip > 0):
+ *   K   [heads][NK][QKS][64 lanes][8]      lane (idx = lane & 31, hi = lane >> 5), element i: key slot 32 kt + idx,
+ *                                          head dim 16 kk + 8 hi + i
+ *   V^T [heads][DVT][2 NK][64 lanes][8]    head dim 32 dt + idx, key slot 16 ks + 4 hi + (i & 3) + 8 (i >> 2)
+ * Key slot s < 32 NT is text row s (absent for s >= n_txt); slot 32 NT + j is ID row j (absent for j >= n_ip). */
+int64_t cid_kv_pack_long_elems(int32_t C, int32_t heads, int32_t n_txt, int32_t n_ip, int32_t which /*0=K,1=V*/);
+/* kv_txt, kv_ip as for cid_kv_pack_f16 ([R][L][2C], L = n_txt + n_ip).  Every slot of both images is written; absent
+ * key slots and head dims >= d are zero. */
+int cid_kv_pack_long_f16(const cid_half* kv_txt, const cid_half* kv_ip, cid_half* kp, cid_half* vp,
+                         int32_t R, int32_t C, int32_t heads, int32_t n_txt, int32_t n_ip,
+                         cid_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Fused identity cross-attention with the BasicTransformerBlock wrapper, ONE launch (csrc/xattn3.hip):
