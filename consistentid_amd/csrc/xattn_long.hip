@@ -228,12 +228,16 @@ kv_pack_long_kernel(const half_t* __restrict__ kv_txt, const half_t* __restrict_
 
 bool long_head_dim(int D) { return D == 32 || D == 40 || D == 64 || D == 80 || D == 160; }
 
+// most text rows next to n_ip ID rows: 33 key tiles at the most either way (a context without ID rows, as a ControlNet sees
+// a pipeline's text + ID rows, may use the ID tile's slots for text)
+int long_max_txt(int n_ip) { return CID_XATTN_LONG_MAX_TXT + (n_ip > 0 ? 0 : CID_XATTN_LONG_MAX_IP); }
+
 }  // namespace
 
 extern "C" int32_t cid_xattn_long_max_txt(void) { return CID_XATTN_LONG_MAX_TXT; }
 
 extern "C" int64_t cid_kv_pack_long_elems(int32_t C, int32_t heads, int32_t n_txt, int32_t n_ip, int32_t which) {
-    if (heads <= 0 || C <= 0 || C % heads || n_txt < 1 || n_txt > CID_XATTN_LONG_MAX_TXT || n_ip < 0 || n_ip > CID_XATTN_LONG_MAX_IP)
+    if (heads <= 0 || C <= 0 || C % heads || n_txt < 1 || n_txt > long_max_txt(n_ip) || n_ip < 0 || n_ip > CID_XATTN_LONG_MAX_IP)
         return -22;
     const int D = C / heads;
     const int QKS = (D + 15) / 16, DVT = (D + 31) / 32;
@@ -245,8 +249,8 @@ extern "C" int cid_kv_pack_long_f16(const cid_half* kv_txt, const cid_half* kv_i
                                     int32_t R, int32_t C, int32_t heads, int32_t n_txt, int32_t n_ip, cid_stream_t stream) {
     CID_CHECK_ARG(kv_txt && kv_ip && kp && vp, "cid_kv_pack_long_f16: null pointer");
     CID_CHECK_ARG(R > 0 && heads > 0 && C > 0 && C % heads == 0 && (C / heads) % 8 == 0, "cid_kv_pack_long_f16: bad C/heads");
-    CID_CHECK_ARG(n_txt >= 1 && n_txt <= CID_XATTN_LONG_MAX_TXT, "cid_kv_pack_long_f16: 1 to %d text rows (got %d)",
-                  CID_XATTN_LONG_MAX_TXT, n_txt);
+    CID_CHECK_ARG(n_txt >= 1 && n_txt <= long_max_txt(n_ip), "cid_kv_pack_long_f16: 1 to %d text rows (got %d)",
+                  long_max_txt(n_ip), n_txt);
     CID_CHECK_ARG(n_ip >= 0 && n_ip <= CID_XATTN_LONG_MAX_IP, "cid_kv_pack_long_f16: 0 to %d ID rows (got %d)",
                   CID_XATTN_LONG_MAX_IP, n_ip);
     const int NT = (n_txt + 31) / 32, NK = NT + (n_ip > 0 ? 1 : 0);
@@ -267,8 +271,8 @@ extern "C" int cid_id_xattn_long_f16(const cid_half* q, cid_half* out, const cid
     CID_CHECK_ARG(N % 32 == 0, "cid_id_xattn_long_f16: N=%d is not a multiple of 32 tokens", N);
     const int D = C / heads;
     CID_CHECK_ARG(long_head_dim(D), "cid_id_xattn_long_f16: no kernel for head_dim=%d (32, 40, 64, 80, 160)", D);
-    CID_CHECK_ARG(n_txt >= 1 && n_txt <= CID_XATTN_LONG_MAX_TXT, "cid_id_xattn_long_f16: 1 to %d text rows (got %d)",
-                  CID_XATTN_LONG_MAX_TXT, n_txt);
+    CID_CHECK_ARG(n_txt >= 1 && n_txt <= long_max_txt(n_ip), "cid_id_xattn_long_f16: 1 to %d text rows (got %d)",
+                  long_max_txt(n_ip), n_txt);
     CID_CHECK_ARG(n_ip >= 0 && n_ip <= CID_XATTN_LONG_MAX_IP, "cid_id_xattn_long_f16: 0 to %d ID rows (got %d)",
                   CID_XATTN_LONG_MAX_IP, n_ip);
     const long units = (long)B * heads * (N / 32);

@@ -335,7 +335,8 @@ def kv_pack_long_elems(C_: int, heads: int, n_txt: int, n_ip: int):
     ke, ve = (int(lib.cid_kv_pack_long_elems(C_, heads, n_txt, n_ip, w)) for w in (0, 1))
     if ke < 0 or ve < 0:
         raise ValueError(f"kv_pack_long_elems: no long-context layout for C={C_} heads={heads} n_txt={n_txt} n_ip={n_ip} "
-                         f"(1..{xattn_long_max_txt()} text rows, 0..{XATTN_LONG_MAX_IP} ID rows)")
+                         f"(1..{xattn_long_max_txt()} text rows, {XATTN_LONG_MAX_IP} more without ID rows; "
+                         f"0..{XATTN_LONG_MAX_IP} ID rows)")
     return ke, ve
 
 

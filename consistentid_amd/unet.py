@@ -165,7 +165,9 @@ class HipUNet:
         # kernel (csrc/xattn_long.hip), whose caps are checked here, before anything is launched or changed
         long_ctx = L > ops.XATTN_SHORT_MAX
         if long_ctx:
-            cap = ops.xattn_long_max_txt()
+            # (a context without ID rows -- a ControlNet's: the pipeline's text AND ID rows as one stream -- may be longer
+            # by the ID tile's slots, or a prompt at the cap would be refused by its ControlNet)
+            cap = ops.xattn_long_max_txt() + (0 if nt else ops.XATTN_LONG_MAX_IP)
             if L - nt > cap or L - nt < 1 or not 0 <= nt <= ops.XATTN_LONG_MAX_IP:
                 raise ValueError(f"set_context: {L - nt} text rows + {nt} ID rows; the cross-attention kernels take at most "
                                  f"{cap} text rows and {ops.XATTN_LONG_MAX_IP} ID rows")

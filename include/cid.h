@@ -223,6 +223,8 @@ int cid_pack_wfrag_f16(const cid_half* w, cid_half* wp, int32_t rows, int32_t K,
  *   out = softmax2(q Kt^T) Vt + ip_scale * softmax2(q Kip^T) Vip        (attention.py:259-279; the ID term is absent for n_ip = 0)
  *   q, out : [B][N][C] fp16 (ld = C), q projected and pre-scaled by d^-0.5 * log2(e); N % 32 == 0;
  *            head width C / heads in {32, 40, 64, 80, 160};  kvrow[s] = packed context row of sample s.
+ * Without ID rows (n_ip == 0) the text stream may be CID_XATTN_LONG_MAX_TXT + CID_XATTN_LONG_MAX_IP rows long -- the same
+ * 33 key tiles at the most: a ControlNet is handed a pipeline's text AND ID rows as one text stream.
  * Deterministic (no atomics).  Everything else is refused with -22 before any launch. */
 #define CID_XATTN_LONG_MAX_TXT 1024
 #define CID_XATTN_LONG_MAX_IP 32

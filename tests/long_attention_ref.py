@@ -5,6 +5,24 @@ import numpy as np
 import torch
 
 
+XL_WAVES = 4             # units -- (sample, head, 32 tokens) -- per workgroup of the core (csrc/xattn_long.hip)
+PACK_GRID_CAP = 2048     # blocks of 256 threads cid_kv_pack_long_f16 launches at the most; the rest is a grid-stride loop
+
+
+def units(B, heads, N):
+    """units of one core launch"""
+    return B * heads * (N // 32)
+
+
+def core_blocks(B, heads, N):
+    return -(-units(B, heads, N) // XL_WAVES)
+
+
+def pack_blocks(k_elems, v_elems, R):
+    """256-thread blocks that one thread per 16-byte chunk of both images of R context rows would need"""
+    return -(-(R * (k_elems + v_elems) // 8) // 256)
+
+
 def tiles(n_txt, n_ip):
     """(NT text tiles, NK key tiles)"""
     nt = (n_txt + 31) // 32

@@ -73,7 +73,8 @@ def test_every_generation_warms_up_captures_and_replays():
     three, except (0,) in the 5-step generations of scenario b, whose windows the scenario fixes: (0, 1) three times, (0,)
     twice, and once more twice in each generation after the first."""
     specs = F.all_specs()
-    assert len(specs) == len(F.SCENARIO_A) + len(F.SCENARIO_B) + len(F.SCENARIO_C) + len(F.SCENARIO_D) + len(F.LARGE) + len(F.PAIRWISE)
+    assert len(specs) == (len(F.SCENARIO_A) + len(F.SCENARIO_B) + len(F.SCENARIO_C) + len(F.SCENARIO_D) + len(F.SCENARIO_G)
+                          + len(F.LARGE) + len(F.PAIRWISE))
     two_sets = 0
     for what, spec in specs.items():
         assert executed_steps(spec) >= 3, what
@@ -115,6 +116,10 @@ def test_scenarios_are_the_sequences_they_claim():
         for (_, a), (what, b) in zip(rows, rows[1:-1]):
             diff = [f.name for f in dataclasses.fields(Spec) if getattr(a, f.name) != getattr(b, f.name)]
             assert 1 <= len(diff) <= 2, (what, diff)
+    g = [s for _, s in F.SCENARIO_G]        # a long context under the switches, down to 77 rows and back
+    assert len(g) == 7 and g[0] == g[4] == g[6] == F.CN_A.but(text_len=154) and g[5] == F.CN_A and g[0].steps == 4
+    assert [features_on(s) for s in g] == [[], ["loras"], ["freeu", "loras"], ["freeu", "rescale", "loras"], [], [], []]
+    assert inputs(g[0], "cpu")["text"].shape[1] == 154 + 4 and inputs(g[0], "cpu") is inputs(g[3], "cpu") is not inputs(g[5], "cpu")
     d = F.SCENARIO_D
     assert d[-1][2] == d[0][2] and d[-2][2] == d[1][2] and d[-1][1] == "P1" and d[-2][1] == "P2"
     assert all(via is None or via != p for _, p, _, via, _ in d), "every switch of (d) is made through the OTHER pipeline"

@@ -7,7 +7,7 @@ bit for bit, the same spec run eagerly on fresh objects, lie within the fp16 arm
 lora_cases' merged state dicts -- and every feature a spec switches on must move the fp32 oracle by the threshold of that
 feature's own tests (engine_cases.assert_features_matter), so an engine that ignored it could not pass.
 
-The scenarios are data (``SCENARIO_A`` .. ``SCENARIO_D``, ``LARGE``, ``PAIRWISE``): tests/test_engine_features_host.py checks
+The scenarios are data (``SCENARIO_A`` .. ``SCENARIO_D``, ``SCENARIO_G``, ``LARGE``, ``PAIRWISE``): tests/test_engine_features_host.py checks
 without a GPU that the pairwise list covers every pair of factor values and that every spec runs enough steps."""
 import pytest
 import torch
@@ -60,6 +60,14 @@ SCENARIO_C = _chain(XL, [
     ("FreeU on", dict(freeu=FREEU)), ("second unconditional set", dict(null_post=True)), ("LoRA loaded", dict(loras=LORA)),
     ("guidance_rescale 0.7, Euler", dict(rescale=PHI, scheduler="euler")),
     ("everything off", dict(freeu=None, null_post=False, loras=(), rescale=0.0, scheduler="ddim"))])
+
+# g. the same switches under a long context (154 text rows: every cross-attention layer on csrc/xattn_long.hip, its K/V images
+# packed by ops.context_kv(long=True) into buffers of another size), then down to 77 rows and up again
+CN_LONG = CN_A.but(text_len=154)
+SCENARIO_G = _chain(CN_LONG, [
+    ("LoRA loaded", dict(loras=LORA)), ("FreeU on", dict(freeu=FREEU)), ("guidance_rescale 0.7", dict(rescale=PHI)),
+    ("everything off", dict(loras=(), freeu=None, rescale=0.0)), ("77 text rows", dict(text_len=77)),
+    ("154 text rows again", dict(text_len=154))])
 
 # d. one UNet under a txt2img pipeline P1 and an inpaint pipeline P2: (what, the pipeline that generates, its spec, the
 # pipeline whose enable_freeu / disable_freeu / load_lora_weights / unload_lora_weights brings the UNet there or None,
@@ -146,7 +154,7 @@ PAIRWISE["zero-SNR DDIM, v_prediction, FreeU, rescale, LoRA"] = ZERO_SNR_SPEC
 def all_specs():
     """{label: spec} of every generation of this module"""
     out = {}
-    for name, rows in (("a", SCENARIO_A), ("b", SCENARIO_B), ("c", SCENARIO_C)):
+    for name, rows in (("a", SCENARIO_A), ("b", SCENARIO_B), ("c", SCENARIO_C), ("g", SCENARIO_G)):
         out.update({f"{name}: {n} {what}": s for n, (what, s) in enumerate(rows)})
     out.update({f"d: {n} {row[0]}": row[2] for n, row in enumerate(SCENARIO_D)})
     out.update({f"e: {k}": s for k, s in LARGE.items()})
@@ -187,6 +195,39 @@ def test_sdxl_one_switch_at_a_time(dev):
     pipe = _pipe(dev, XL)
     outs = run_scenario(dev, "features on SDXL", [Gen(what, s, oracle=True) for what, s in SCENARIO_C], pipe)
     assert torch.equal(outs[-1], outs[0]), "everything off again, and the first generation does not come back"
+
+
+# --------------------------------------------------------------------------- g: a long context under the switches
+def test_long_context_one_switch_at_a_time(dev):
+    """base -> LoRA -> FreeU -> guidance_rescale -> all off -> 77 text rows -> 154 again, graphs on.  A LoRA changes the K/V
+    projections: the long K/V images must be packed anew from the merged weights (every generation is held to a fresh eager
+    run of its spec and to the oracle with the LoRA merged), in the long layout, into the same buffers."""
+    from test_gpu_long_context import _long_layers
+    nets = _nets(dev, CN_LONG)
+    pipe = _pipe(dev, CN_LONG, nets)
+    layer = next(iter(pipe.unet.packed.xattn_layers))
+    seen = {}
+
+    def look(what):
+        def before():           # the state the generation BEFORE this one left behind
+            ctx = pipe.unet._ctx
+            seen[what] = (ctx.kp[layer].clone(), ctx.kp[layer].data_ptr(), ctx.n_txt, list(_long_layers(pipe.unet)),
+                          [list(_long_layers(n)) for n in nets.values()])
+        return before
+    gens = [Gen(what, s, oracle=True) for what, s in SCENARIO_G]
+    gens[1].before, gens[2].before, gens[5].before = look("base"), look("LoRA"), look("all off")
+    outs = run_scenario(dev, "features under a long context", gens, pipe, nets)
+    assert torch.equal(outs[-1], outs[0]), "154 text rows again, and the first generation does not come back"
+    assert torch.equal(outs[4], outs[0]), "everything off again, and the first generation does not come back"
+    assert not torch.equal(outs[1], outs[0]) and not torch.equal(outs[5], outs[0])
+    for what in ("base", "LoRA", "all off"):
+        kp, ptr, n_txt, layers, net_layers = seen[what]
+        assert n_txt == 154 and layers and all(layers), f"after {what}: a layer is not packed for the long-context kernel"
+        assert all(l and all(l) for l in net_layers), f"after {what}: a ControlNet layer is not packed for the long-context kernel"
+    assert seen["LoRA"][0].shape == seen["base"][0].shape and seen["LoRA"][1] == seen["base"][1], "the K image moved under a LoRA"
+    assert not torch.equal(seen["LoRA"][0], seen["base"][0]), "the long K image did not follow the LoRA's to_k"
+    assert torch.equal(seen["all off"][0], seen["base"][0]), "the long K image of the base did not come back after the unload"
+    assert all(_long_layers(pipe.unet)) and pipe.unet._ctx.n_txt == 154 and "seed11" not in pipe.get_list_adapters()
 
 
 # --------------------------------------------------------------------------- d: a shared UNet

@@ -72,6 +72,22 @@ def test_rows_beyond_the_cap_are_refused_on_the_host(dev):
     unet.set_context(torch.zeros(2, 81, dc, dtype=torch.float16, device=dev))      # (nothing was left half-changed)
 
 
+def test_a_controlnet_takes_the_cap_with_the_id_rows(dev):
+    """a prompt of 1024 text rows reaches the ControlNet as 1024 + 4 rows of ONE text stream (``num_tokens=0``): it was refused
+    there with the text cap.  Without ID rows the stream may fill the ID tile's slots too (33 key tiles either way)."""
+    from consistentid_amd import ops
+    net = new_net(str(dev), "A")
+    cap, dc = ops.xattn_long_max_txt(), net.config.cross_attention_dim
+    ehs = torch.randn(2, cap + 4, dc, generator=torch.Generator().manual_seed(0)).half().to(dev)
+    net.set_context(ehs, num_tokens=0)
+    assert (net._ctx.n_txt, net._ctx.n_ip) == (cap + 4, 0) and all(_long_layers(net))
+    net.set_context(ehs[:, :4].repeat(1, (cap + 32) // 4, 1), num_tokens=0)
+    assert net._ctx.n_txt == cap + ops.XATTN_LONG_MAX_IP
+    with pytest.raises(ValueError, match=f"at most {cap + 32} text rows"):
+        net.set_context(torch.zeros(2, cap + 33, dc, dtype=torch.float16, device=dev), num_tokens=0)
+    assert net._ctx.n_txt == cap + 32                   # (nothing was left half-changed)
+
+
 # ------------------------------------------------------------------------------------------------ encode_prompt
 class _Tok(FakeTokenizer):
     pad_token_id = FakeTokenizer.eos_token_id       # CLIP-L pads with the end-of-text id

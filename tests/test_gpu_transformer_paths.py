@@ -9,7 +9,12 @@ that transformer only) and asserts
   * the launches are the combination the case is filed under (``observed(trace) == predict(shape) ==`` the table's row);
   * parity with the oracle's own ``Transformer2DModel`` in fp32 on the CPU, held to the oracle's fp16 arm on the GPU
     (conftest.check_vs_fp16_arm at its default slack);
-  * a finite output that differs from the input, the same bits on a second call, B * H * W rows whatever the padding."""
+  * a finite output that differs from the input, the same bits on a second call, B * H * W rows whatever the padding.
+
+The rows under "long" run the same case at 154 + 4, 231 + 4 and 158 + 0 context rows and, at 1280 channels, at 1024 text rows:
+every layer on the long-context core (csrc/xattn_long.hip) between ``attn2.wql`` or ``norm2`` + ``attn2.wq`` and the out
+projection, which writes at pitch 5c where the tail is folded; ``cross_attention_path`` must name what ran.  They follow the
+short rows of their width, so one engine's K/V buffers grow from 81 to 158 to 1028 rows."""
 import dataclasses
 import gc
 
@@ -22,7 +27,7 @@ from oracle_utils import build_oracle, make_weights
 
 pytestmark = pytest.mark.gpu
 BLOCK = "down_blocks.0.attentions.0"
-CASES = [(f, shp, comb) for f, rows in tp.load()["cases"].items() for shp, comb in rows]
+CASES = tp.ordered_cases(tp.load())         # a width's long-context rows behind its short ones: one engine serves both
 
 
 def _overrides(c, heads, n_layers):
@@ -77,9 +82,16 @@ def engines(dev):
     held.clear()
 
 
-def _check_launches(tr, shp, comb):
+def _check_launches(tr, shp, comb, hip):
     got, want = tp.observed(tr), tp.predict(*shp)
     assert got == want == comb, f"launched {dict(zip(tp.FIELDS, got))}, predicted {dict(zip(tp.FIELDS, want))}, filed under {comb}"
+    c, heads, n_layers, n_txt, n_ip, B, Bp, H, W = shp
+    if tp.long_context(n_txt, n_ip):        # what the engine says it runs is what it ran
+        assert (hip._ctx.n_txt, hip._ctx.n_ip) == (n_txt, n_ip)
+        launches = {"long+fold": "(three launches)", "long": "(four launches)"}[got[3]]
+        for k in range(n_layers):
+            path = hip.cross_attention_path(f"{BLOCK}.transformer_blocks.{k}", c, B, tp.padded_tokens(c, heads, n_txt, n_ip, H, W))
+            assert f"id_xattn_long core<{n_txt},{n_ip}>" in path and path.endswith(launches), (path, got[3])
 
 
 def _block_case(dev, eng, family, shp, comb):
@@ -101,7 +113,7 @@ def _block_case(dev, eng, family, shp, comb):
         out = hip._transformer(eng.spec, xd, B, H, W, kvrow)
     again = hip._transformer(eng.spec, xd, B, H, W, kvrow)
     torch.cuda.synchronize()
-    _check_launches(tr, shp, comb)
+    _check_launches(tr, shp, comb, hip)
     assert out.shape == (B * N, c), f"{tuple(out.shape)} for {B} x {N} tokens"
     assert torch.equal(out, again), "a second call gives other bits"
     assert torch.isfinite(out.float()).all() and (out.float() - xd.float()).abs().max() > 1e-2
@@ -126,7 +138,7 @@ def _dedup_case(dev, eng, family, shp, comb):
     x, y = tr.block_in, tr.block_out
     again = hip.forward_tokens(lat.to(dev), hip._t_buf, kvrow, B)
     torch.cuda.synchronize()
-    _check_launches(tr, shp, comb)
+    _check_launches(tr, shp, comb, hip)
     assert x.shape == (Bp * H * W, c) and y.shape == (B * H * W, c), (tuple(x.shape), tuple(y.shape))
     assert torch.equal(out, again), "a second call gives other bits"
     assert torch.isfinite(y.float()).all() and (y.float() - x.float().repeat(rep, 1)).abs().max() > 1e-2

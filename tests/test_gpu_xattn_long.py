@@ -7,7 +7,10 @@ agreement with cid_id_xattn_core_f16 at (77, 4), which both take.
 As test_xattn_core_general_context: B = 2 samples on R = 3 context rows through KVROW = [2, 0], N = 64 tokens (two token
 tiles), random fp16 [K | V] rows (no GEMM: the fp64 reference reads the same values), the packed images compared element for
 element with the numpy model (tests/long_attention_ref.py) in sentinel-filled buffers, the output written twice into
-guarded buffers (guards intact, second launch bit-identical) and held to attention_ref.two_stream_ref at ATTN_TOL."""
+guarded buffers (guards intact, second launch bit-identical) and held to attention_ref.two_stream_ref at ATTN_TOL.
+
+The same harness on other geometries (``_case``): at the caps (1024 text rows, 32 ID rows, a last text tile of one key, the
+pack beyond its 2048-block grid) and on grids whose (sample, head, 32 tokens) units do not fill the last workgroup."""
 import pytest
 import torch
 
@@ -39,7 +42,7 @@ CASES = [(C, h, *ctx) for (C, h) in SMALL for ctx in CONTEXTS] + [(C, h, *ctx) f
 PROPERTY_CONFIGS = [(128, 2), (640, 8), (320, 8)]
 
 
-def _pack(dev, kv_txt, kv_ip, C, heads, n_txt, n_ip):
+def _pack(dev, kv_txt, kv_ip, C, heads, n_txt, n_ip, R_X=R_X):
     """cid_kv_pack_long_f16 into sentinel-filled operands: every slot written, every element the model's"""
     from consistentid_amd import ops
     ke, ve = ops.kv_pack_long_elems(C, heads, n_txt, n_ip)
@@ -55,7 +58,7 @@ def _pack(dev, kv_txt, kv_ip, C, heads, n_txt, n_ip):
     return kp, vp
 
 
-def _streams(kv_txt, kv_ip, C, heads, n_txt, n_ip):
+def _streams(kv_txt, kv_ip, C, heads, n_txt, n_ip, B_X=B_X, R_X=R_X, KVROW=KVROW):
     """the rows the pack takes, per sample (through KVROW) and head: k_txt, v_txt, k_ip, v_ip [B, n, heads, d]"""
     L, d = n_txt + n_ip, C // heads
     t, i = (x.view(R_X, L, 2 * C)[KVROW] for x in (kv_txt, kv_ip))
@@ -63,7 +66,7 @@ def _streams(kv_txt, kv_ip, C, heads, n_txt, n_ip):
     return sp(t[:, :n_txt, :C]), sp(t[:, :n_txt, C:]), sp(i[:, n_txt:, :C]), sp(i[:, n_txt:, C:])
 
 
-def _long(dev, q, kp, vp, C, heads, n_txt, n_ip, ip_scale, what):
+def _long(dev, q, kp, vp, C, heads, n_txt, n_ip, ip_scale, what, B_X=B_X, KVROW=KVROW):
     """cid_id_xattn_long_f16 twice into guarded outputs: guards intact, second launch bit-identical; returns [B * N, C]"""
     from consistentid_amd import ops
     M = q.shape[0]
@@ -91,6 +94,63 @@ def test_xattn_long_contexts(dev, C, heads, n_txt, n_ip):
     out = _long(dev, q, kp, vp, C, heads, n_txt, n_ip, IP_SCALE, what)
     ref = ar.two_stream_ref(q.view(B_X, N_X, heads, d), *_streams(kv_txt, kv_ip, C, heads, n_txt, n_ip), IP_SCALE)
     check_close(out, ref.reshape(B_X * N_X, C), what, **ATTN_TOL)
+
+
+def _case(dev, C, heads, n_txt, n_ip, B, N, R, kvrow, what):
+    """one geometry through the module's harness: the pack against the numpy model in sentinel-filled buffers, the core twice
+    into guarded buffers, the fp64 two-stream reference at ATTN_TOL"""
+    d, L = C // heads, n_txt + n_ip
+    print(f"[case] {what}: B={B} N={N} R={R} kvrow={kvrow}, {lr.units(B, heads, N)} units in {lr.core_blocks(B, heads, N)} "
+          f"workgroups of {lr.XL_WAVES}, key tiles {lr.tiles(n_txt, n_ip)}, pack blocks "
+          f"{lr.pack_blocks(*lr.long_elems(C, heads, n_txt, n_ip), R)} (grid cap {lr.PACK_GRID_CAP})")
+    kv_txt, kv_ip = rnd(R * L, 2 * C, seed=C + L), rnd(R * L, 2 * C, seed=C + L + 1)
+    q = rnd(B * N, C, seed=C + L + 2, scale=4.0 * d ** -0.5)
+    kp, vp = _pack(dev, kv_txt, kv_ip, C, heads, n_txt, n_ip, R)
+    out = _long(dev, q, kp, vp, C, heads, n_txt, n_ip, IP_SCALE, what, B, kvrow)
+    ref = ar.two_stream_ref(q.view(B, N, heads, d), *_streams(kv_txt, kv_ip, C, heads, n_txt, n_ip, B, R, kvrow), IP_SCALE)
+    return check_close(out, ref.reshape(B * N, C), what, **ATTN_TOL)
+
+
+# The caps: 1024 text rows (cid_xattn_long_max_txt) -- the key loop runs 32 tiles, the packed images are 33 tiles deep with ID
+# rows -- at ten K fragments per tile (d = 160) and at two (d = 32); (993, 4): the 32nd text tile holds ONE key; (1056, 0): the
+# longest text stream without ID rows (a ControlNet's view of 1024 + up to 32 rows), 33 text tiles.  At 1280 channels on
+# R = 2 context rows the pack has more chunks than its 2048-block grid covers in one pass: the grid-stride loop runs.
+CAP_CONFIGS = [(1280, 8, 2, [1, 0]), (64, 2, R_X, KVROW)]          # (C, heads, R, kvrow)
+CAP_CONTEXTS = [(1024, 32), (1024, 0), (993, 4), (1056, 0)]
+
+
+@pytest.mark.parametrize("n_txt,n_ip", CAP_CONTEXTS)
+@pytest.mark.parametrize("C,heads,R,kvrow", CAP_CONFIGS, ids=lambda v: str(v).replace(" ", ""))
+def test_xattn_long_at_the_caps(dev, C, heads, R, kvrow, n_txt, n_ip):
+    from consistentid_amd import ops
+    cap = ops.xattn_long_max_txt()
+    assert n_txt in (cap, cap - 31, cap + ops.XATTN_LONG_MAX_IP) and lr.tiles(n_txt, n_ip)[1] in (32, 33)
+    if C == 1280:
+        blocks = lr.pack_blocks(*ops.kv_pack_long_elems(C, heads, n_txt, n_ip), R)
+        assert blocks > lr.PACK_GRID_CAP, f"{blocks} blocks: the pack's grid-stride loop would not run"
+    _case(dev, C, heads, n_txt, n_ip, B_X, N_X, R, kvrow, f"xattn long at the cap n_txt={n_txt} n_ip={n_ip} C={C} d={C // heads}")
+
+
+# Ragged grids: a unit is (sample, head, 32 tokens), a workgroup runs four.  Where the units are no multiple of four the last
+# workgroup's idle waves must leave (``u >= units``): their unit index lies behind the last sample, so what they would write
+# are the rows behind the output -- the guards.  R = B + 1 context rows through a selector that is no identity (and repeats
+# a row where B > 1).
+RAGGED = [(1, 32, 64, 2),       # 2 units: half a workgroup
+          (1, 96, 640, 10),     # 30 units: the last workgroup half full, three token tiles
+          (3, 32, 320, 8),      # 24 units: one token tile per sample
+          (5, 160, 128, 2)]     # 50 units
+
+
+@pytest.mark.parametrize("n_txt,n_ip", [(154, 4), (129, 0)])
+@pytest.mark.parametrize("B,N,C,heads", RAGGED)
+def test_xattn_long_ragged_grids(dev, B, N, C, heads, n_txt, n_ip):
+    units = lr.units(B, heads, N)
+    assert units == {(1, 32): 2, (1, 96): 30, (3, 32): 24, (5, 160): 50}[(B, N)]
+    assert units % lr.XL_WAVES or N == 32, "every workgroup would be full and every sample have two token tiles"
+    kvrow = [B - i for i in range(B)]
+    if B > 1:
+        kvrow[-1] = kvrow[0]
+    _case(dev, C, heads, n_txt, n_ip, B, N, B + 1, kvrow, f"xattn long ragged B={B} N={N} C={C} d={C // heads} ({n_txt}, {n_ip})")
 
 
 @pytest.mark.parametrize("C,heads", PROPERTY_CONFIGS)
@@ -134,15 +194,25 @@ def test_xattn_long_scores_far_apart(dev, C, heads, plan):
     2^-100) or below them (every later tile underflows against the first); the ID scores lie >= 100 above / below the text
     scores; at (129, 0) the text scores lie >= 100 below the zero scores of the 31 padding slots of the last tile.  Every
     gap is asserted on the fp64 scores."""
+    _far_apart(dev, C, heads, plan, *((129, 0) if plan == "padding above" else (154, 4)))
+
+
+def test_xattn_long_scores_far_apart_at_the_cap(dev):
+    """"tiles rising" over the 32 text tiles of (1024, 4): the running maximum rises, and the accumulator is rescaled by
+    <= 2^-100, 31 times in a row; what is left is the last tile's softmax (head width 80)"""
+    from consistentid_amd import ops
+    _far_apart(dev, 640, 8, "tiles rising", ops.xattn_long_max_txt(), 4)
+
+
+def _far_apart(dev, C, heads, plan, n_txt, n_ip):
     d = C // heads
-    n_txt, n_ip = (129, 0) if plan == "padding above" else (154, 4)
     L = n_txt + n_ip
     g = torch.Generator().manual_seed(C + len(plan))
     e = torch.zeros(heads, d)
     e[:, :8] = 1.0                                            # common direction of every query and the shifted keys
     e = e.reshape(C)
     q = (torch.randn(B_X * N_X, C, generator=g) * 0.1 + 2.0 * e).half()
-    tile = torch.arange(n_txt) // 32                          # 0 .. 4
+    tile = torch.arange(n_txt) // 32                          # 0 .. 4 (0 .. 31 at the cap)
     level = {"tiles rising": tile.float(), "tiles falling": (tile.max() - tile).float(), "id above": torch.zeros(n_txt),
              "id below": torch.ones(n_txt), "padding above": -torch.ones(n_txt)}[plan]
     ip_level = {"id above": 1.0, "id below": 0.0}.get(plan, 0.0)

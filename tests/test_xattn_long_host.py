@@ -76,6 +76,27 @@ def test_pack_refusals_before_any_launch(lib):
         assert lib.cid_kv_pack_long_elems(*bad, 0) == -22 and lib.cid_kv_pack_long_elems(*bad, 1) == -22, bad
 
 
+def test_a_context_without_id_rows_may_use_the_id_tile_for_text(lib):
+    """a ControlNet is handed a pipeline's text AND ID rows as one text stream with n_ip = 0: 1024 text rows + 4 ID rows must
+    not be refused there.  Without ID rows the text may fill the ID tile's 32 slots too -- 33 key tiles at the most either
+    way, so no packed image grows beyond that of (1024, 32)."""
+    err = lib.cid_last_error
+    cap, ip = lib.cid_xattn_long_max_txt(), 32
+    for C, heads in ((1280, 8), (64, 2)):
+        biggest = [lib.cid_kv_pack_long_elems(C, heads, cap, ip, w) for w in (0, 1)]
+        for n_txt in (cap + 4, cap + ip):
+            got = [lib.cid_kv_pack_long_elems(C, heads, n_txt, 0, w) for w in (0, 1)]
+            assert got == list(lr.long_elems(C, heads, n_txt, 0)) == biggest, (C, heads, n_txt, got)
+        assert lib.cid_kv_pack_long_elems(C, heads, cap + ip + 1, 0, 0) == -22
+        assert lib.cid_kv_pack_long_elems(C, heads, cap + 1, 1, 0) == -22
+    # the entries: refused one row later, with the limit that holds in the message; (cap + 4, 0) gets as far as the launch
+    assert lib.cid_id_xattn_long_f16(64, 64, 64, 64, 64, 2, 64, 320, 8, cap + ip + 1, 0, 1.0, None) == -22
+    assert f"1 to {cap + ip} text rows".encode() in err()
+    assert lib.cid_kv_pack_long_f16(64, 64, 64, 64, 2, 320, 8, cap + ip + 1, 0, None) == -22
+    assert f"1 to {cap + ip} text rows".encode() in err()
+    assert lib.cid_kv_pack_long_f16(64, 64, 64, 64, 2, 320, 8, cap + 1, 4, None) == -22 and f"1 to {cap} text rows".encode() in err()
+
+
 @pytest.mark.parametrize("C,heads", HEAD_CONFIGS)
 def test_pack_elems_match_the_model(lib, C, heads):
     for n_txt, n_ip in ((93, 4), (97, 0), (128, 4), (129, 3), (154, 4), (231, 4), (231, 32), (235, 0), (1, 0), (77, 4),

@@ -11,7 +11,12 @@ launched and ``observed`` reads the same fields off that record.  The two share 
 tests/golden/transformer_paths.json files one shape under every combination the three model families reach on GRID (the
 smallest ``B * Np * c`` that has it; tests/golden/make_golden_transformer_paths.py writes it, no GPU needed).
 tests/test_transformer_paths_host.py checks the table against the predicates, tests/test_gpu_transformer_paths.py runs one
-parity case per row."""
+parity case per row.
+
+Contexts past ``ops.XATTN_SHORT_MAX`` = 96 rows (``LONG_CONTEXT``, ``CAP_CONTEXT``) take the long-context core in every layer
+(``xattn`` = "long+fold" / "long"), pad the token axis to 64 at every width and fold the tail wherever ``ops.ff2_fold`` holds.
+Their rows stand under "long" in the same file, one per ``LONG_KEY`` -- the fields such a context changes (``enumerate_long``) --
+and one per family at 1024 text rows (``cap_shape``); the rows under "cases" are those of the default context, unchanged."""
 import contextlib
 import json
 from pathlib import Path
@@ -22,7 +27,7 @@ REGENERATE = "python tests/golden/make_golden_transformer_paths.py   (no GPU nee
 FIELDS = ("pad", "dedup", "qkv", "xattn", "tail", "geglu", "stats")
 SHAPE = ("c", "heads", "n_layers", "n_txt", "n_ip", "B", "Bp", "H", "W")
 QKV = ("fold", "ln+gemm")
-XATTN = ("gen3", "gen1", "qattn+fold", "qattn", "core+fold", "core")
+XATTN = ("gen3", "gen1", "qattn+fold", "qattn", "core+fold", "core", "long+fold", "long")
 TAIL = ("folded", "ff2+proj_out")
 GEGLU = ("fold", "ln+h32", "ln+gemm")
 
@@ -51,23 +56,29 @@ COVERED_BEFORE = {
 TEST_LAYERS = 2
 
 
-def family_config(family: str):
-    """the product's UNetConfig of a family and its context layout (n_txt, n_ip)"""
-    from consistentid_amd import unet_spec
-    if family == "sdxl":
-        return unet_spec.sdxl_config(), 77, 4
-    return (unet_spec.sd15_config(),) + ((81, 0) if family == "controlnet" else (77, 4))
-
-
 FAMILIES = ("sd15", "sdxl", "controlnet")
+CONTEXT = {"sd15": (77, 4), "sdxl": (77, 4), "controlnet": (81, 0)}             # (n_txt, n_ip) of the default prompt
+# contexts past ops.XATTN_SHORT_MAX rows (csrc/xattn_long.hip): two and three 77-row chunks, and the most rows a pipeline takes
+# (1024 text rows + the ID rows).  The ControlNet is handed text and ID rows as ONE text stream: 154 + 4 and 1024 + 4 rows
+LONG_CONTEXT = {"sd15": (154, 4), "sdxl": (231, 4), "controlnet": (158, 0)}
+CAP_CONTEXT = {"sd15": (1024, 4), "sdxl": (1024, 4), "controlnet": (1028, 0)}
+CAP_CHANNELS = 1280
+LONG_KEY = ("c", "heads", "pad", "dedup", "xattn", "tail")      # what a long row is filed under: see enumerate_long
 
 
-def levels(family: str, B: int, Bp: int, H: int, W: int):
+def family_config(family: str, context=None):
+    """the product's UNetConfig of a family and its context layout (n_txt, n_ip): ``context``, or the default prompt's"""
+    from consistentid_amd import unet_spec
+    cfg = unet_spec.sdxl_config() if family == "sdxl" else unet_spec.sd15_config()
+    return (cfg,) + tuple(CONTEXT[family] if context is None else context)
+
+
+def levels(family: str, B: int, Bp: int, H: int, W: int, context=None):
     """every transformer the family's model runs on a (B, Bp) batch of H x W latents, in execution order, as SHAPE tuples.
     Only SD1.5's first transformer sees the Bp distinct samples of a CFG batch (HipUNet.forward_tokens: a shared timestep
     row, and the first down block has attention); the ControlNet is the encoder half."""
     from consistentid_amd import unet_spec
-    cfg, n_txt, n_ip = family_config(family)
+    cfg, n_txt, n_ip = family_config(family, context)
     downs, mid, ups = unet_spec.walk(cfg)
     out, first = [], family == "sd15"
     for blk in downs:
@@ -88,9 +99,17 @@ def levels(family: str, B: int, Bp: int, H: int, W: int):
 
 
 # ----------------------------------------------------------------------------- prediction (host predicates only)
+def long_context(n_txt, n_ip) -> bool:
+    """more context rows than the register-resident cross-attention kernels hold: every layer runs csrc/xattn_long.hip"""
+    from consistentid_amd import ops
+    return n_txt + n_ip > ops.XATTN_SHORT_MAX
+
+
 def padded_tokens(c, heads, n_txt, n_ip, H, W) -> int:
     """tokens per sample after HipUNet._transformer's zero-padding of the token axis"""
     from consistentid_amd import ops
+    if long_context(n_txt, n_ip):       # the long core tiles 32 tokens: the self-attention's 64 decide
+        return -(-H * W // 64) * 64
     gen3 = ops.xattn_generation() >= 3 and ops.id_xattn3_supported(c, heads, n_txt, n_ip)
     need = 128 if (128 < c <= int(SWITCHES["CID_XATTN_FUSED_MAX_C"]) and not gen3) else 64
     return -(-H * W // need) * need
@@ -104,9 +123,12 @@ def predict(c, heads, n_layers, n_txt, n_ip, B, Bp, H, W) -> tuple:
     pad = Np != H * W
     M1, M = Bp * Np, B * Np         # rows up to the self-attention / from the cross-attention on
     qkv = "fold" if ops.ln_fold(M1) else "ln+gemm"
-    gen3 = ops.xattn_generation() >= 3 and ops.id_xattn3_supported(c, heads, n_txt, n_ip)
-    gen1 = unet.fused_gen1(c, M)
-    if gen3:
+    long = long_context(n_txt, n_ip)
+    gen3 = not long and ops.xattn_generation() >= 3 and ops.id_xattn3_supported(c, heads, n_txt, n_ip)
+    gen1 = not long and unet.fused_gen1(c, M)
+    if long:
+        xattn = "long+fold" if ops.ln_fold(M) else "long"
+    elif gen3:
         xattn = "gen3"
     elif gen1:
         xattn = "gen1"
@@ -115,7 +137,7 @@ def predict(c, heads, n_layers, n_txt, n_ip, B, Bp, H, W) -> tuple:
     else:
         xattn = "core+fold" if ops.ln_fold(M) else "core"
     gn_hw = 0 if pad else Np
-    tail = "folded" if ops.ff2_fold(M, c, gn_hw) and (gen3 or not gen1) else "ff2+proj_out"
+    tail = "folded" if ops.ff2_fold(M, c, gn_hw) and (long or gen3 or not gen1) else "ff2+proj_out"
     if ops.ln_fold_geglu(M, c):
         geglu = "fold"
     else:
@@ -129,7 +151,7 @@ class Trace:
     block calls (every caller goes through the module attribute), in order: its name and the keywords that tell the paths
     apart.  ``tr.only(engine, name)`` restricts the record to the transformer called ``name`` and keeps that call's input
     and output in ``tr.block_in`` / ``tr.block_out``."""
-    OPS = ("gemm", "layernorm", "self_attn", "id_xattn", "id_xattn3", "id_xattn_core")
+    OPS = ("gemm", "layernorm", "self_attn", "id_xattn", "id_xattn3", "id_xattn_core", "id_xattn_long")
     INTS = ("M", "N", "c1", "ld1", "ldo", "mode", "ntok", "n_keys", "gn_hw", "ldx", "B", "C_")
     HAS = ("ln", "att", "out2", "res")
 
@@ -213,12 +235,13 @@ def observed(trace) -> tuple:
             xattn.append("gen3")
         elif r["op"] == "id_xattn":
             xattn.append("gen1")
-        elif r["op"] == "id_xattn_core":
+        elif r["op"] in ("id_xattn_core", "id_xattn_long"):
+            name = "core" if r["op"] == "id_xattn_core" else "long"
             q = rs[i - 1] if before(i, "gemm") else {"ln": False, "mode": -1}
             if q["mode"] != 0:
-                xattn.append("core without q")
+                xattn.append(f"{name} without q")
             else:
-                xattn.append("core+fold" if q["ln"] else ("core" if before(i - 1, "layernorm") else "core without norm2"))
+                xattn.append(f"{name}+fold" if q["ln"] else (name if before(i - 1, "layernorm") else f"{name} without norm2"))
     first = next(r for r in rs if r["op"] == "gemm" and r["mode"] == 2)
     keys = _one([(r["N"], r["n_keys"]) for r in rs if r["op"] == "self_attn"], "self_attn")
     ntok = _one([r["ntok"] for r in rs if r["op"] == "gemm" and r["mode"] in (2, 3)], "ntok")
@@ -255,25 +278,79 @@ def combinations_of(family: str, shapes) -> set:
     return {(shp[0],) + predict(*shp) for s in shapes for shp in levels(family, *s)}
 
 
+def long_key(shp) -> tuple:
+    """(c, heads, pad, dedup, xattn, tail) of a SHAPE: LONG_KEY"""
+    pad, dedup, _, xattn, tail, _, _ = predict(*shp)
+    return (shp[0], shp[1], pad, dedup, xattn, tail)
+
+
+def enumerate_long(family: str, shapes=GRID) -> dict:
+    """{LONG_KEY tuple: the smallest SHAPE that has it} under the family's LONG_CONTEXT within MAX_TOKENS tokens, sized and
+    tie-broken as in ``enumerate_grid``.  A long context changes the cross-attention, the padding rule and the tail's
+    condition only; ``qkv``, ``geglu`` and ``stats`` are decided as at 77 rows, where every value has a row, so they are no
+    part of the key.  The ControlNet runs the same ``_transformer``: of its keys only the smallest shape per width stays."""
+    best = {}
+    for B, Bp, H, W in shapes:
+        for shp in levels(family, B, Bp, H, W, LONG_CONTEXT[family]):
+            c, heads, _, n_txt, n_ip, b, bp, h, w = shp
+            if b * h * w > MAX_TOKENS:
+                continue
+            size = (b * padded_tokens(c, heads, n_txt, n_ip, h, w) * c, shp)
+            key = long_key(shp)
+            if key not in best or size < best[key]:
+                best[key] = size
+    if family == "controlnet":
+        per_width = {}
+        for key, size in best.items():
+            if key[0] not in per_width or size < per_width[key[0]][1]:
+                per_width[key[0]] = (key, size)
+        best = dict(per_width.values())
+    return {k: v[1] for k, v in sorted(best.items(), key=lambda kv: str(kv[0]))}
+
+
+def cap_shape(family: str, shapes=GRID) -> tuple:
+    """the smallest SHAPE of a CAP_CHANNELS-wide level under the family's CAP_CONTEXT"""
+    sized = [(shp[5] * padded_tokens(shp[0], shp[1], shp[3], shp[4], shp[7], shp[8]) * shp[0], shp) for s in shapes
+             for shp in levels(family, *s, CAP_CONTEXT[family]) if shp[0] == CAP_CHANNELS and shp[5] * shp[7] * shp[8] <= MAX_TOKENS]
+    return min(sized)[1]
+
+
 def load(path=GOLDEN) -> dict:
-    """-> {"cases": {family: [(SHAPE tuple, combination tuple), ...]}, "omitted": {family: [(c, combination, reason), ...]}}"""
+    """-> {"cases": {family: [(SHAPE tuple, combination tuple), ...]}, "omitted": {family: [(c, combination, reason), ...]},
+    "long": {family: [(SHAPE tuple, combination tuple), ...]}}: "cases" at the default context, "long" under LONG_CONTEXT and
+    (the last row of a family) CAP_CONTEXT"""
     z = json.loads(Path(path).read_text())
     assert tuple(z["shape"]) == SHAPE and tuple(z["fields"]) == FIELDS, f"{path} was written for other fields: {REGENERATE}"
     n = len(SHAPE)
-    return {"cases": {f: [(tuple(r[:n]), tuple(r[n:])) for r in rows] for f, rows in z["cases"].items()},
+    rows = lambda d: {f: [(tuple(r[:n]), tuple(r[n:])) for r in rs] for f, rs in d.items()}
+    return {"cases": rows(z["cases"]), "long": rows(z["long"]),
             "omitted": {f: [(r[0], tuple(r[1:1 + len(FIELDS)]), r[-1]) for r in rows] for f, rows in z["omitted"].items()}}
 
 
-def dump(cases: dict, omitted: dict, path):
-    """``cases``: {family: {(c,) + combination: SHAPE}}; ``omitted``: {family: [((c,) + combination, reason), ...]}"""
+def dump(cases: dict, omitted: dict, long: dict, path):
+    """``cases``: {family: {(c,) + combination: SHAPE}}; ``omitted``: {family: [((c,) + combination, reason), ...]};
+    ``long``: {family: [SHAPE, ...]} (filed under ``predict`` of each)"""
     row = lambda r: "   " + json.dumps(list(r), separators=(",", ":"))
     block = lambda d: ",\n".join(f"  {json.dumps(f)}: [\n" + ",\n".join(row(r) for r in rows) + "\n  ]" for f, rows in d.items())
     c = {f: sorted((list(shp) + list(key[1:]) for key, shp in d.items()), key=lambda r: r[:len(SHAPE)]) for f, d in cases.items()}
     o = {f: [list(key) + [reason] for key, reason in rows] for f, rows in omitted.items()}
+    lg = {f: [list(shp) + list(predict(*shp)) for shp in sorted(shapes)] for f, shapes in long.items()}
     Path(path).write_text("{\n" + f' "shape": {json.dumps(list(SHAPE))},\n "fields": {json.dumps(list(FIELDS))},\n'
-                          + ' "cases": {\n' + block(c) + '\n },\n "omitted": {\n' + block(o) + "\n }\n}\n")
+                          + ' "cases": {\n' + block(c) + '\n },\n "omitted": {\n' + block(o) + '\n },\n "long": {\n' + block(lg)
+                          + "\n }\n}\n")
 
 
 def case_id(family, shp) -> str:
     c, heads, n_layers, n_txt, n_ip, B, Bp, H, W = shp
-    return f"{family}-c{c}-B{B}" + (f"of{Bp}" if Bp != B else "") + f"-{H}x{W}"
+    ctx = "" if (n_txt, n_ip) == CONTEXT[family] else f"-ctx{n_txt}+{n_ip}"
+    return f"{family}-c{c}-B{B}" + (f"of{Bp}" if Bp != B else "") + f"-{H}x{W}" + ctx
+
+
+def ordered_cases(table) -> list:
+    """[(family, SHAPE, combination)]: family by family, width by width, a width's long rows behind its short rows -- one
+    engine per (family, width) serves them in turn and crosses 81, 158 and 1028 context rows"""
+    out = []
+    for f in table["cases"]:
+        rows = [(shp[0], long_context(shp[3], shp[4]), shp, comb) for shp, comb in table["cases"][f] + table["long"].get(f, [])]
+        out += [(f, shp, comb) for _, _, shp, comb in sorted(rows, key=lambda r: r[:3])]
+    return out
