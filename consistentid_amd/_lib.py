@@ -139,6 +139,8 @@ SIGNATURES = {
                                         C.c_int32, C.c_int32, c_stream]),
     "cid_cfg_multistep_step_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, c_half_p, c_half_p, C.c_int32, C.c_void_p,
                                              C.c_float, c_half_p, c_half_p, c_half_p, C.c_int32, C.c_int32, c_stream]),
+    "cid_multistep_step_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, c_half_p, c_half_p, C.c_int32, C.c_void_p,
+                                         c_half_p, c_half_p, c_half_p, C.c_int32, C.c_int32, c_stream]),
     "cid_cfg_rescale_f16": (C.c_int, [c_half_p, C.c_float, C.c_float, C.c_void_p, C.c_int32, C.c_int32, c_stream]),
     "cid_cfg_ddim_step_scaled_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, C.c_float, c_half_p, c_half_p, c_half_p,
                                                C.c_int32, C.c_int32, C.c_void_p, c_stream]),

@@ -15,7 +15,7 @@ void cid_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* cid_last_error(void) { return g_err; }
-extern "C" int cid_version(void) { return 110; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4, 104: cid_gemm_plan, 105: cid_cfg_multistep_step_f16, 106: cid_residual_accum_f16, 107: cid_clip_head_f16 / cid_blackout_f16, 108: cid_cfg_rescale_f16 / cid_cfg_*_step_scaled_f16, 109: cid_freeu_f16 (freeu.hip), 110: cid_id_xattn_long_f16 / cid_kv_pack_long_* (xattn_long.hip)
+extern "C" int cid_version(void) { return 111; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4, 104: cid_gemm_plan, 105: cid_cfg_multistep_step_f16, 106: cid_residual_accum_f16, 107: cid_clip_head_f16 / cid_blackout_f16, 108: cid_cfg_rescale_f16 / cid_cfg_*_step_scaled_f16, 109: cid_freeu_f16 (freeu.hip), 110: cid_id_xattn_long_f16 / cid_kv_pack_long_* (xattn_long.hip), 111: cid_multistep_step_f16
 
 namespace {
 
@@ -501,7 +501,9 @@ cfg_ddim_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, const 
 // per-step value -- coefficients, the ring slot that receives m, the save / restore flags, the noise row -- is read from the
 // 16-word device row, so the launch is the same for every step.  A ring slot, `saved` and `z` are loaded only where the
 // row gives them a non-zero coefficient (wave-uniform branches): an unwritten buffer may hold NaN, and 0 * NaN is NaN.
-template <bool SCALED>      // as cfg_ddim_kernel's
+// CFG = false (cid_multistep_step_f16, the single pass): eps holds ONE model output per sample, [B][per_sample], and e is that
+// value -- no second half is loaded (eps + n is past the end of the buffer) and g is not read.
+template <bool SCALED, bool CFG = true>      // SCALED as cfg_ddim_kernel's
 __global__ void __launch_bounds__(256)
 cfg_multistep_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, float* hist, half_t* saved,
                      const half_t* __restrict__ z, int z_rows, const float* __restrict__ row, float g,
@@ -515,17 +517,22 @@ cfg_multistep_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, f
     const int zr = irow[14] < 0 ? 0 : (irow[14] > z_rows - 1 ? z_rows - 1 : irow[14]);   // a bad row cannot index past z
     const bool put = w >= 0 && w < 4, save = flags & 1, restore = flags & 2;
     for (long q = ((long)blockIdx.x * 256 + threadIdx.x) * 8; q < n; q += (long)gridDim.x * 256 * 8) {
-        const half8 eu = ld_global_h8(eps + q), ec = ld_global_h8(eps + n + q), xl = ld_global_h8(lat + q);
+        const half8 eu = ld_global_h8(eps + q);
+        half8 ec;
+        if constexpr (CFG) ec = ld_global_h8(eps + n + q);
+        const half8 xl = ld_global_h8(lat + q);
         const half8 src = restore ? ld_global_h8(saved + q) : xl;
         float es = 1.f;
         if constexpr (SCALED) es = escale[(unsigned)(q >> 3) / (unsigned)sample_items];   // fewer than 2^31 items: the entry checks
         float m[8], v[8];
 #pragma unroll
         for (int i = 0; i < 8; ++i) {
-            const float u = (float)eu[i], c = (float)ec[i];
-            float e = u + g * (c - u);
+            const float u = (float)eu[i];
+            float e = u;
+            if constexpr (CFG) { const float c = (float)ec[i]; e = u + g * (c - u); }
             if constexpr (SCALED) e *= es;
-            m[i] = a * (float)xl[i] + b * e;
+            if constexpr (CFG) m[i] = a * (float)xl[i] + b * e;
+            else m[i] = __builtin_fmaf(a, (float)xl[i], b * e);     // the contraction the CFG instantiations compile to: the same bits on equal halves
             v[i] = cx * (float)src[i] + cm * m[i];
         }
 #pragma unroll
@@ -930,6 +937,27 @@ extern "C" int cid_cfg_multistep_step_f16(const cid_half* eps, cid_half* latents
                        (const float*)row, guidance, (const half_t*)mask, (const half_t*)init, (const half_t*)noise, n,
                        (const float*)nullptr, 0);
     CID_CHECK_LAUNCH("cid_cfg_multistep_step_f16");
+    return 0;
+}
+
+extern "C" int cid_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
+                                      const cid_half* z, int32_t z_rows, const void* row,
+                                      const cid_half* mask, const cid_half* init, const cid_half* noise,
+                                      int32_t B, int32_t per_sample, cid_stream_t stream) {
+    CID_CHECK_ARG(eps && latents && hist && saved && row, "cid_multistep_step_f16: null pointer");
+    CID_CHECK_ARG((z == nullptr) == (z_rows == 0) && z_rows >= 0, "cid_multistep_step_f16: z and z_rows must come together");
+    CID_CHECK_ARG((mask == nullptr) == (init == nullptr) && (mask == nullptr) == (noise == nullptr),
+                  "cid_multistep_step_f16: mask/init/noise must come together");
+    const long n = (long)B * per_sample;
+    CID_CHECK_ARG(B > 0 && per_sample > 0 && n % 8 == 0, "cid_multistep_step_f16: B * per_sample must be a multiple of 8");
+    for (const void* p : {(const void*)eps, (const void*)latents, (const void*)hist, (const void*)saved, (const void*)z,
+                          (const void*)row, (const void*)mask, (const void*)init, (const void*)noise})
+        CID_CHECK_ARG((uintptr_t)p % 16 == 0, "cid_multistep_step_f16: every buffer must be 16-byte aligned");
+    hipLaunchKernelGGL((cfg_multistep_kernel<false, false>), dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z, (int)z_rows,
+                       (const float*)row, 0.f, (const half_t*)mask, (const half_t*)init, (const half_t*)noise, n,
+                       (const float*)nullptr, 0);
+    CID_CHECK_LAUNCH("cid_multistep_step_f16");
     return 0;
 }
 

@@ -2,6 +2,11 @@
 S x [ControlNets + UNet(2B) + CFG + scheduler step].  The step is captured once into a hipGraph and replayed; every
 per-step host value of the reference's loops lives in one device table (ops.StepTable).
 
+The single pass: under ``LCMScheduler`` with ``guidance_scale <= 1`` -- diffusers'
+``do_classifier_free_guidance = guidance_scale > 1`` -- or on a UNet with ``time_cond_proj_dim`` (guidance is in its time
+embedding) a step is [ControlNets + UNet(B) on the conditional rows + cid_multistep_step_f16]: no unconditional half and no
+CFG combine.  The four other schedulers launch what they always launched at every guidance value.
+
 ``DenoiseEngine.run`` is a driver over phases that take and return named values: the static-buffer pool, the graph
 cache, the step coefficients (``_StepCoefficients``), the ControlNet plan (``_ControlPlan``), the embed-row selectors
 (``step_rows``), what the step reads of objects the engine does not own (``captured_reads``), the step table and the
@@ -22,7 +27,7 @@ import torch
 
 from . import ops
 from .controlnet import HipMultiControlNet, active_nets, controlnet_keep_table
-from .scheduler import C_IN, DDIMScheduler, pack_step_rows
+from .scheduler import C_IN, DDIMScheduler, LCMScheduler, pack_step_rows
 from .unet import HipUNet
 
 
@@ -37,10 +42,11 @@ def check_guidance_rescale(guidance_rescale) -> float:
 
 def check_eta(scheduler, eta: float, variance_noise=None) -> float:
     """``eta`` / ``variance_noise`` of the reference ``__call__``s (prepare_extra_step_kwargs -> DDIMScheduler.step(eta=,
-    variance_noise=)): only DDIM has the term, its eta is in [0, 1], and the noise needs a coefficient.  -> float(eta)"""
+    variance_noise=)): only DDIM has the term, its eta is in [0, 1], and the noise needs a coefficient -- which
+    LCMScheduler's own noise has without eta (sqrt(1 - alphas_cumprod) of the next timestep).  -> float(eta)"""
     eta = float(eta)
     if eta == 0.0:
-        if variance_noise is not None:
+        if variance_noise is not None and not isinstance(scheduler, LCMScheduler):
             raise ValueError("variance_noise without eta: the noise term has the coefficient eta * sigma_t")
         return eta
     if not isinstance(scheduler, DDIMScheduler):
@@ -56,17 +62,21 @@ StepRows = namedtuple("StepRows", "unet controlnet merged")
 
 
 def step_rows(n_ts: int, first_step: int, start_merge_step: int, B: int, has_null_post: bool, device="cpu",
-              controlnet: bool = True) -> StepRows:
+              controlnet: bool = True, single_pass: bool = False) -> StepRows:
     """The embed sets every schedule entry reads (ref :542-549: text-only while i <= start_merge_step, i counted from
     ``first_step`` like the reference's enumerate over the truncated timestep list).  The UNet's K/V cache holds rows
     [0,B) null, [B,2B) text-only, [2B,3B) augmented (ref :527-531) and, for SDXL's second unconditional set (ref SDXL
     :586-590, :620-631), [3B,4B) null-post: a step selects (null, text) before the merge, (null or null-post, augmented)
-    after it.  A ControlNet's cache holds [0,B) text-only and [B,2B) augmented, selected the same way (CN :389-396)."""
+    after it.  A ControlNet's cache holds [0,B) text-only and [B,2B) augmented, selected the same way (CN :389-396).
+    ``single_pass``: the UNet runs the conditional rows only -- [n_ts, B], text-only [B,2B) up to the merge and augmented
+    [2B,3B) after it, in the same K/V row numbering."""
     ar = torch.arange(B, dtype=torch.int32, device=device)
     merged = torch.tensor([(i - first_step) > start_merge_step for i in range(n_ts)], device=device)
     pre = torch.cat([ar, ar + B])
     post = torch.cat([ar + (3 * B if has_null_post else 0), ar + 2 * B])
     cn = torch.where(merged[:, None], (ar + B)[None], ar[None]) if controlnet else None
+    if single_pass:
+        pre, post = ar + B, ar + 2 * B
     return StepRows(torch.where(merged[:, None], post[None], pre[None]), cn, merged)
 
 
@@ -84,18 +94,23 @@ def captured_reads(unet, nets: Sequence[Any]) -> tuple:
 @dataclass
 class _StepCoefficients:
     """The scheduler's side of a step: cid_cfg_ddim_step_f16 for the two first-order updates (DDIM at eta = 0, Euler),
-    cid_cfg_multistep_step_f16 for PNDM, DPM-Solver++ and DDIM with eta > 0 (history ring, remembered sample, noise row)"""
+    cid_cfg_multistep_step_f16 for PNDM, DPM-Solver++, DDIM with eta > 0 and LCM (history ring, remembered sample, noise
+    row); cid_multistep_step_f16 for the single pass, whose ``eps`` is one model output per sample"""
     buf: torch.Tensor                           # the row the step table fills: 5 fp32, or the 16-word multistep row (cid.h)
     row: torch.Tensor                           # ``buf`` as the step kernel reads it (fp32)
     in_scale: torch.Tensor                      # the model-input scale inside ``row``: conv_in reads it in place
     table: torch.Tensor                         # [n_ts, ...] per-step rows, dtype of ``buf``
     hist: Optional[torch.Tensor] = None         # multistep: fp32 ring of earlier model outputs
     saved: Optional[torch.Tensor] = None        # multistep: the sample PNDM steps from twice
-    z: Optional[torch.Tensor] = None            # DDIM eta > 0: the variance noise of every executed step
+    z: Optional[torch.Tensor] = None            # DDIM eta > 0: the variance noise of every executed step; LCM: of all but the last
     escale: Optional[torch.Tensor] = None       # guidance_rescale: fp32 [B], the factor cid_cfg_rescale_f16 writes every step
     rescale: float = 0.0
+    single_pass: bool = False
 
     def update(self, eps, lat, guidance_scale, **kw):
+        if self.single_pass:                    # no CFG combine (and so no rescale of one)
+            ops.multistep_step(eps, lat, self.hist, self.saved, self.row, z=self.z, **kw)
+            return
         if self.escale is not None:             # UNet -> factor -> scaled step; the scaled entries of the same two kernels
             ops.cfg_rescale(eps, guidance_scale, self.rescale, self.escale, B=kw["B"], per_sample=kw["per_sample"])
             kw["escale"] = self.escale
@@ -135,7 +150,8 @@ class DenoiseEngine:
         self._config_key = None
         self.captures: List[Any] = []           # key of every capture this engine ever made, in order (re-captures show twice)
         self._static: Dict[str, torch.Tensor] = {}
-        self.step_path: Optional[str] = None    # the step launch of the last run: "cfg_ddim" or "cfg_multistep", "+rescale" with guidance_rescale
+        # the step launch of the last run: "cfg_ddim" or "cfg_multistep", "+rescale" with guidance_rescale; "multistep" = the single pass
+        self.step_path: Optional[str] = None
 
     def invalidate(self):
         """forget the captured graphs AND their eager warm-up (the first step after a change must run eagerly again)"""
@@ -170,11 +186,12 @@ class DenoiseEngine:
         cur.copy_(like.to(device=self.unet.device, dtype=dtype))
         return cur
 
-    def _step_coefficients(self, lat, inpaint: bool, first_step: int, eta: float, variance_noise) -> _StepCoefficients:
+    def _step_coefficients(self, lat, inpaint: bool, first_step: int, eta: float, variance_noise,
+                           single_pass: bool = False) -> _StepCoefficients:
         sch, S, dev = self.scheduler, self._static_tensor, self.unet.device
         n_ts = len(sch.timesteps)
         multistep = bool(getattr(sch, "multistep", False)) or eta > 0.0
-        self.step_path = "cfg_multistep" if multistep else "cfg_ddim"
+        self.step_path = "multistep" if single_pass else "cfg_multistep" if multistep else "cfg_ddim"
         if not multistep:
             table = torch.from_numpy(sch.coefficient_table(inpaint)).to(dev).view(n_ts, 5).float()
             buf = S("coef", torch.zeros(5), torch.float32)      # c_x, c_eps, c_init, c_noise, model-input scale
@@ -188,11 +205,18 @@ class DenoiseEngine:
                 raise ValueError(f"eta = {eta} needs variance_noise of shape {(n_run, *lat.shape)} (one tensor per executed "
                                  f"step), got {None if variance_noise is None else tuple(variance_noise.shape)}")
             z = S("z", variance_noise, torch.float16)
+        elif isinstance(sch, LCMScheduler) and n_ts - first_step > 1:
+            n_z = n_ts - first_step - 1
+            if variance_noise is None or tuple(variance_noise.shape) != (n_z, *lat.shape):
+                raise ValueError(f"LCMScheduler over {n_z + 1} executed steps needs variance_noise of shape {(n_z, *lat.shape)} "
+                                 f"(one tensor per executed step but the last), got "
+                                 f"{None if variance_noise is None else tuple(variance_noise.shape)}")
+            z = S("z", variance_noise, torch.float16)
         buf = S("ms_row", torch.zeros(16), torch.int32)     # the multistep row (cid.h): 12 fp32 words, 4 int32 words
         row = buf.view(torch.float32)
         return _StepCoefficients(buf, row, row[C_IN:C_IN + 1], table,
                                  hist=S("ms_hist", torch.zeros(4, lat.numel()), torch.float32),
-                                 saved=S("ms_saved", torch.zeros(lat.numel()), torch.float16), z=z)
+                                 saved=S("ms_saved", torch.zeros(lat.numel()), torch.float16), z=z, single_pass=single_pass)
 
     def _control_plan(self, controlnet, control_image, conditioning_scale, starts, ends, text_embeds, augmented_embeds,
                       rows: StepRows, tvals, first_step: int, temb_table: bool) -> _ControlPlan:
@@ -244,6 +268,10 @@ class DenoiseEngine:
         """``guidance_rescale`` > 0 with ``guidance_scale`` > 1 (diffusers' condition): every step runs UNet ->
         cid_cfg_rescale_f16 (the per-sample factor, into a static buffer) -> the scaled step entry; at 0 the step is the
         one it always was.
+        Under ``LCMScheduler`` ``guidance_scale`` <= 1 takes the single pass (module docstring): the UNet runs the B
+        conditional rows and ``guidance_rescale`` is inert, as it is at ``guidance_scale`` <= 1 everywhere.  A UNet with
+        ``time_cond_proj_dim`` takes it at every ``guidance_scale`` (the scale conditions its time embedding), needs
+        LCMScheduler and refuses ``guidance_rescale`` > 0.  LCM's noise comes as ``variance_noise`` [executed steps - 1, B, C, h, w].
         ``eta`` > 0 (DDIMScheduler only) with ``variance_noise`` [executed steps, B, C, h, w]: the noise diffusers' DDIM
         ``step(..., eta=, variance_noise=)`` adds, one tensor per executed step in loop order.
         ``first_step``: the loop runs schedule entries [first_step, S) -- the inpaint pipelines' ``strength`` < 1
@@ -257,6 +285,17 @@ class DenoiseEngine:
         eta = check_eta(sch, eta, variance_noise)
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         dev, B = unet.device, latents.shape[0]
+        lcm = isinstance(sch, LCMScheduler)
+        embedded_guidance = getattr(unet.config, "time_cond_proj_dim", None) is not None
+        if embedded_guidance and not lcm:
+            raise NotImplementedError(f"{type(sch).__name__} on a UNet with time_cond_proj_dim: a distilled latent consistency "
+                                      "model is sampled with LCMScheduler (pipe.scheduler = LCMScheduler.from_config("
+                                      "pipe.scheduler.config))")
+        if embedded_guidance and guidance_rescale > 0.0:
+            raise ValueError(f"guidance_rescale = {guidance_rescale}: a UNet with time_cond_proj_dim takes guidance_scale in its "
+                             "time embedding; there is no classifier-free combine to rescale")
+        single = lcm and (embedded_guidance or guidance_scale <= 1.0)
+        n_b = B if single else 2 * B            # the UNet's batch rows
         sch.set_timesteps(num_inference_steps)                      # ref :510, before prepare_latents (:517)
         # prepare_latents (diffusers; ref :517-526) scales the initial noise by the scheduler's init_noise_sigma
         lat = S("lat", latents.to(dev).float() * (float(sch.init_noise_sigma) if scale_initial else 1.0), torch.float16)
@@ -269,19 +308,20 @@ class DenoiseEngine:
         ts = sch.timesteps
         n_ts = len(ts)
         inpaint = inpaint_mask is not None
-        coef = self._step_coefficients(lat, inpaint, first_step, eta, variance_noise)
-        if guidance_rescale > 0.0 and guidance_scale > 1.0:
+        coef = self._step_coefficients(lat, inpaint, first_step, eta, variance_noise, single)
+        if guidance_rescale > 0.0 and guidance_scale > 1.0 and not single:
             coef.escale, coef.rescale = S("escale", torch.ones(B), torch.float32), guidance_rescale
             self.step_path += "+rescale"
         tvals = torch.tensor(ts.astype(np.float32), device=dev)
-        rows = step_rows(n_ts, first_step, start_merge_step, B, null_embeds_post is not None, dev, controlnet is not None)
+        rows = step_rows(n_ts, first_step, start_merge_step, B, null_embeds_post is not None, dev, controlnet is not None,
+                         single_pass=single)
         t_buf = S("t", torch.zeros(1), torch.float32)
         kvrow = S("kvrow", rows.unet[0], torch.int32)
         added = None
         if time_ids is not None:
             p_null, p_text, p_aug = [p.to(device=dev, dtype=torch.float16) for p in pooled]
-            added = {"text_embeds": S("pooled", torch.cat([p_null, p_text], 0), torch.float16),
-                     "time_ids": S("time_ids", time_ids, torch.float32)}
+            added = {"text_embeds": S("pooled", p_text if single else torch.cat([p_null, p_text], 0), torch.float16),
+                     "time_ids": S("time_ids", time_ids[-B:] if single else time_ids, torch.float32)}   # [2B, 6]: negative rows first
         blend = dict(mask=None, init=None, noise=None)
         if inpaint:
             if unet_extra is not None:
@@ -301,9 +341,12 @@ class DenoiseEngine:
         # text_time conditioning, whose rows also depend on the sample)
         temb_tab = temb_buf = None
         if unet.config.addition_embed_type is None and not os.environ.get("CID_NO_TEMB_TABLE"):
-            temb_tab = unet.time_embed_table(tvals)
+            # (with time_cond_proj_dim the rows also depend on guidance_scale: built anew in every generation, like this)
+            temb_tab = unet.time_embed_table(tvals, **({"guidance_scale": guidance_scale} if embedded_guidance else {}))
             temb_buf = S("temb", temb_tab[:1], torch.float16)
-        cn = self._control_plan(controlnet, control_image, conditioning_scale, control_guidance_start, control_guidance_end,
+        elif embedded_guidance:
+            unet.set_guidance_embedding(guidance_scale)     # the per-step time path adds this row (a buffer at a stable address)
+        cn =self._control_plan(controlnet, control_image, conditioning_scale, control_guidance_start, control_guidance_end,
                                 text_embeds, augmented_embeds, rows, tvals, first_step, temb_buf is not None)
         # every per-step host value of the reference's `for i, t in enumerate(timesteps)` as one device table: row i holds t,
         # the scheduler coefficients, the embed-set rows, the time-embedding row and SDXL's pooled embeds (ref SDXL
@@ -316,7 +359,7 @@ class DenoiseEngine:
             cols.append((temb_buf, temb_tab.view(n_ts, -1)))
         cols += [c for c in (cn.temb_column, cn.scale_column) if c is not None]
         if added is not None:
-            pre, post = torch.cat([p_null, p_text], 0), torch.cat([p_null, p_aug], 0)
+            pre, post = (p_text, p_aug) if single else (torch.cat([p_null, p_text], 0), torch.cat([p_null, p_aug], 0))
             cols.append((added["text_embeds"], torch.where(rows.merged[:, None, None], post[None], pre[None])))
         table = ops.StepTable(cols, dev, alloc=S)     # table + counter are static buffers too
         table.reset(first_step)
@@ -325,12 +368,12 @@ class DenoiseEngine:
         # anything else than what the graphs were captured under in the UNet or the nets (another object, moved K/V or
         # workspace, a new epoch) -- whoever changed it, this engine or another one that shares the object.  The multi path
         # reads its scales from the step table: they are not part of the key
-        unet.reserve_workspace(2 * B)
+        unet.reserve_workspace(n_b)
         for net in cn.nets:
             net.reserve_workspace(B)
         key = (captured_reads(unet, cn.nets), B, tuple(lat.shape), float(guidance_scale), inpaint, time_ids is not None,
                dres is not None, bool(cn.nets), ("multi", len(cn.nets)) if cn.scale_column else cn.fold, extra is not None,
-               coef.hist is not None, coef.z is not None, coef.rescale)
+               coef.hist is not None, coef.z is not None, coef.rescale, single)
         if key != self._config_key:
             self.invalidate()
             self._config_key = key
@@ -349,7 +392,7 @@ class DenoiseEngine:
                 # unscaled residuals (None: the net did not run); the UNet adds sum_k cn_scale[k] * r_k in two launches
                 d, m = ([res[k][j] if k in res else None for k in range(len(cn.nets))] for j in (0, 1))
                 scales = cn.scale_column[0]
-            eps = unet.forward_tokens(lat, t_buf, kvrow, 2 * B, added, d, m, temb=temb_buf, in_scale=coef.in_scale,
+            eps = unet.forward_tokens(lat, t_buf, kvrow, n_b, added, d, m, temb=temb_buf, in_scale=coef.in_scale,
                                       extra=extra, residual_scales=scales)
             coef.update(eps, lat, guidance_scale, B=B, per_sample=per_sample, **blend)
 

@@ -85,6 +85,7 @@ def unet_config_from_diffusers(cfg: Dict) -> UNetConfig:
         use_linear_projection=bool(cfg.get("use_linear_projection", False)), addition_embed_type=add,
         addition_time_embed_dim=cfg.get("addition_time_embed_dim"),
         projection_class_embeddings_input_dim=cfg.get("projection_class_embeddings_input_dim"),
+        time_cond_proj_dim=None if cfg.get("time_cond_proj_dim") is None else int(cfg["time_cond_proj_dim"]),
         family="sdxl" if add == "text_time" else "sd15")
 
 
@@ -294,13 +295,14 @@ def read_scheduler(root: Union[str, os.PathLike]):
     if not os.path.isfile(spath):
         return None
     import warnings
-    from .scheduler import DDIMScheduler, EulerDiscreteScheduler
+    from .scheduler import DDIMScheduler, EulerDiscreteScheduler, LCMScheduler
     with open(spath) as f:
         cfg = json.load(f)
     # the base model's sampler class: SDXL base ships EulerDiscrete (built), SD1.5 PNDM (not built: DDIM on its config)
     name = cfg.get("_class_name", "DDIMScheduler")
-    cls = EulerDiscreteScheduler if name == "EulerDiscreteScheduler" else DDIMScheduler
-    if name not in ("EulerDiscreteScheduler", "DDIMScheduler"):
+    # a distilled latent-consistency model directory names LCMScheduler (built: few-step sampling)
+    cls = {"EulerDiscreteScheduler": EulerDiscreteScheduler, "LCMScheduler": LCMScheduler}.get(name, DDIMScheduler)
+    if name not in ("EulerDiscreteScheduler", "DDIMScheduler", "LCMScheduler"):
         warnings.warn(f"{name} is not built: the engine samples with DDIM on its config until pipe.scheduler is replaced "
                       "(infer.py:33 / demo/controlnet_demo.py:67 do that on the next line)")
     def make(c):

@@ -870,6 +870,38 @@ def cfg_multistep_step(eps: torch.Tensor, latents: torch.Tensor, hist: torch.Ten
     return latents
 
 
+def multistep_step(eps: torch.Tensor, latents: torch.Tensor, hist: torch.Tensor, saved: torch.Tensor, row: torch.Tensor, *,
+                   B: int, per_sample: int, z: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                   init: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None):
+    """``cfg_multistep_step`` without classifier-free guidance (cid_multistep_step_f16, the single pass): ``eps`` fp16
+    [B, per_sample] is the model output itself; every other argument as there."""
+    lib = _lib.load()
+    n = B * per_sample
+    _req(eps, "multistep_step.eps")
+    _req(latents, "multistep_step.latents")
+    _req(hist, "multistep_step.hist", torch.float32)
+    _req(saved, "multistep_step.saved")
+    _req(row, "multistep_step.row", torch.float32)
+    if eps.numel() != n or latents.numel() != n or hist.numel() != 4 * n or saved.numel() != n or row.numel() != 16:
+        raise _lib.CidError(f"multistep_step: eps / latents / hist / saved / row hold {eps.numel()} / {latents.numel()} / "
+                            f"{hist.numel()} / {saved.numel()} / {row.numel()} elements; B * per_sample = {n} needs "
+                            f"{n} / {n} / {4 * n} / {n} / 16")
+    z_rows = 0
+    if z is not None:
+        _req(z, "multistep_step.z")
+        if z.numel() == 0 or z.numel() % n:
+            raise _lib.CidError(f"multistep_step.z: {z.numel()} elements are not rows of B * per_sample = {n}")
+        z_rows = z.numel() // n
+    for name, t in (("mask", mask), ("init", init), ("noise", noise)):
+        if t is not None:
+            _req(t, f"multistep_step.{name}")
+            if t.numel() != n:
+                raise _lib.CidError(f"multistep_step.{name}: {t.numel()} elements, B * per_sample = {n}")
+    check(lib.cid_multistep_step_f16(_p(eps), _p(latents), _p(hist), _p(saved), _p(z), z_rows, _p(row), _p(mask), _p(init),
+                                     _p(noise), B, per_sample, _stream()), "cid_multistep_step_f16")
+    return latents
+
+
 def add_inplace(y: torch.Tensor, a: torch.Tensor):
     lib = _lib.load()
     _req(y, "add_inplace.y")

@@ -41,7 +41,8 @@ import torch
 
 from .controlnet import HipMultiControlNet, prepare_control_arguments
 from .denoise import DenoiseEngine, check_eta, check_guidance_rescale
-from .scheduler import DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler, PNDMScheduler  # noqa: F401
+from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler, LCMScheduler,  # noqa: F401
+                        PNDMScheduler)
 from .unet import HipUNet
 
 
@@ -159,7 +160,7 @@ class _BasePipeline:
     def scheduler(self, sch):
         if not (hasattr(sch, "coefficient_table") or hasattr(sch, "coefficient_rows")):
             raise TypeError(f"{type(sch).__name__}: the engine takes consistentid_amd.scheduler.DDIMScheduler / "
-                            "EulerDiscreteScheduler / PNDMScheduler / DPMSolverMultistepScheduler (build one with "
+                            "EulerDiscreteScheduler / PNDMScheduler / DPMSolverMultistepScheduler / LCMScheduler (build one with "
                             ".from_config(diffusers_scheduler.config))")
         self._engine.scheduler = sch
 
@@ -167,13 +168,19 @@ class _BasePipeline:
         """``eta`` of the reference ``__call__``s (prepare_extra_step_kwargs -> DDIMScheduler.step(eta=, generator=)): with
         DDIM and eta > 0 every executed step adds sigma_t * randn.  The tensors are drawn here, before the loop, one
         ``randn_tensor`` [B, C, h, w] fp16 per executed step in loop order on ``generator`` -- after every pre-loop draw, so
-        the generator's stream is consumed in diffusers' order -- or taken from ``variance_noise`` [steps, B, C, h, w]."""
-        if check_eta(self.scheduler, eta, variance_noise) == 0.0 or variance_noise is not None:
+        the generator's stream is consumed in diffusers' order -- or taken from ``variance_noise`` [steps, B, C, h, w].
+        ``LCMScheduler`` (eta stays 0) noises the sample again after every executed step but the last: executed steps - 1
+        tensors, drawn or taken in the same way; a single step needs none."""
+        lcm = isinstance(self.scheduler, LCMScheduler)
+        if (check_eta(self.scheduler, eta, variance_noise) == 0.0 and not lcm) or variance_noise is not None:
             return variance_noise       # no noise term (None), or the caller's tensors
         from .vae import randn_tensor
         self.scheduler.set_timesteps(num_inference_steps)
+        n_draw = len(self.scheduler.timesteps) - first_step - (1 if lcm else 0)
+        if n_draw <= 0:
+            return None
         return torch.stack([randn_tensor(tuple(latents.shape), generator=generator, device=self.device, dtype=torch.float16)
-                            for _ in range(len(self.scheduler.timesteps) - first_step)])
+                            for _ in range(n_draw)])
 
     # -- surface kept from the reference ------------------------------------------------------
     @classmethod

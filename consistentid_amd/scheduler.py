@@ -17,7 +17,11 @@ diffusers 0.23 schedulers, UNPINNED like oracle/ddim.py
 ``prediction_type="v_prediction"`` (all four classes) and ``DDIMScheduler(rescale_betas_zero_snr=True)`` -- constructor
 arguments, or keywords of ``from_config(config, **kwargs)`` -- are other coefficients in the same tables: the update stays linear in the sample and the model output.  A
 schedule entry whose coefficients are not finite -- epsilon prediction at a timestep whose alphas_cumprod is 0, the terminal
-step of a zero-SNR schedule -- raises ValueError when the table is built."""
+step of a zero-SNR schedule -- raises ValueError when the table is built.
+
+``LCMScheduler`` (multistep latent consistency sampling, 1 to 8 steps) is one more writer of such
+rows: its update is linear in the sample, the model output and one fresh noise tensor per step.  At ``guidance_scale <= 1``
+the engine steps it with cid_multistep_step_f16, the same row contract on ONE model output per sample (denoise.py)."""
 from __future__ import annotations
 
 from typing import List, Tuple
@@ -513,4 +517,97 @@ class DPMSolverMultistepScheduler:
             a, b = (alpha[i], -s[i]) if self.prediction_type == "v_prediction" else (1.0 / alpha[i], -s[i] / alpha[i])
             rows.append(_row(a=a, b=b, c_x=s[i + 1] / s[i], c_m=float(c_m), c_hist=c_hist,
                              c_init=ci, c_noise=cn, w=k % 4))
+        return _check_finite(np.asarray(rows, dtype=np.float64).reshape(-1, ROW_WORDS), self, "coefficient_rows").astype(dtype)
+
+
+class LCMScheduler:
+    """Multistep latent consistency sampling (Luo et al. 2023, "Latent Consistency Models", Algorithm 3) with diffusers
+    0.23's defaults: what ``pipe.scheduler = LCMScheduler.from_config(pipe.scheduler.config)`` gives beside an LCM-LoRA or
+    on a distilled checkpoint.  Restated from the published algorithm, UNPINNED like the other samplers here (diffusers is
+    not vendored).  The schedule is a subset of the ``original_inference_steps`` timesteps the model was distilled on:
+    c = T // original_inference_steps, origin = c, 2c, ... minus 1, every (original_inference_steps // n)-th of them from
+    the top -- 4 steps are [999, 759, 519, 279].  With s = timestep_scaling t, c_skip = sigma_data^2 / (s^2 + sigma_data^2)
+    and c_out = s / sqrt(s^2 + sigma_data^2), a step denoises and, but for the last one, noises again to the next timestep:
+        den = c_out x0 + c_skip x;    x' = sqrt(a_next) den + sqrt(1 - a_next) z_k    (x' = den on the last step)
+    with x0 = (x - sqrt(1 - a_t) e) / sqrt(a_t) for epsilon prediction and sqrt(a_t) x - sqrt(1 - a_t) v for v-prediction.
+    z_k is a fresh standard normal tensor per executed step k, drawn before the loop (pipeline ``_variance_noise``) or given
+    as ``variance_noise`` [executed steps - 1, B, C, h, w]; the final latents carry no noise.  ``steps_offset``,
+    ``set_alpha_to_one`` and ``timestep_spacing`` are carried in ``.config`` for the class a later ``from_config`` builds; the
+    LCM schedule does not use them (neither does diffusers')."""
+    order = 1
+    init_noise_sigma = 1.0
+    multistep = True
+
+    def __init__(self, num_train_timesteps: int = 1000, beta_start: float = 0.00085, beta_end: float = 0.012,
+                 original_inference_steps: int = 50, timestep_scaling: float = 10.0, sigma_data: float = 0.5,
+                 prediction_type: str = "epsilon", steps_offset: int = 0, set_alpha_to_one: bool = True,
+                 timestep_spacing: str = "leading"):
+        if timestep_spacing not in SPACINGS:
+            raise ValueError(f"timestep_spacing {timestep_spacing!r}: one of {SPACINGS}")
+        if not 1 <= int(original_inference_steps) <= num_train_timesteps:
+            raise ValueError(f"original_inference_steps = {original_inference_steps!r}: 1 .. num_train_timesteps")
+        self.prediction_type = _check_prediction_type(prediction_type)
+        self.alphas_cumprod = _train_alphas_cumprod(beta_start, beta_end, num_train_timesteps)
+        self.num_train_timesteps, self.original_inference_steps = num_train_timesteps, int(original_inference_steps)
+        self.timestep_scaling, self.sigma_data = float(timestep_scaling), float(sigma_data)
+        self.steps_offset, self.timestep_spacing = steps_offset, timestep_spacing
+        self.timesteps: np.ndarray = np.zeros(0, dtype=np.int64)
+        self.num_inference_steps = 0
+        self.config = SchedulerConfig(num_train_timesteps=num_train_timesteps, beta_start=beta_start, beta_end=beta_end,
+                           beta_schedule="scaled_linear", trained_betas=None, steps_offset=steps_offset,
+                           set_alpha_to_one=set_alpha_to_one, timestep_spacing=timestep_spacing,
+                           prediction_type=prediction_type, original_inference_steps=int(original_inference_steps),
+                           timestep_scaling=float(timestep_scaling), sigma_data=float(sigma_data), clip_sample=False,
+                           thresholding=False)
+
+    @classmethod
+    def from_config(cls, config, **kwargs) -> "LCMScheduler":
+        """``LCMScheduler.from_config(pipe.scheduler.config)``: betas and prediction type of the pipeline's scheduler, the
+        LCM defaults for what its config does not name"""
+        return cls(**_config_args(config, ("num_train_timesteps", "beta_start", "beta_end", "original_inference_steps",
+                                           "timestep_scaling", "sigma_data", "steps_offset", "set_alpha_to_one",
+                                           "timestep_spacing"), kwargs))
+
+    def set_timesteps(self, num_inference_steps: int, device=None):
+        n, orig = int(num_inference_steps), self.original_inference_steps
+        if n < 1 or n > orig:
+            raise ValueError(f"num_inference_steps = {num_inference_steps!r}: LCMScheduler takes 1 .. original_inference_steps "
+                             f"= {orig} steps")
+        self.num_inference_steps = n
+        origin = np.arange(1, orig + 1, dtype=np.int64) * (self.num_train_timesteps // orig) - 1
+        self.timesteps = origin[::-(orig // n)][:n].copy()
+
+    def scale_model_input(self, sample, t=None):
+        return sample
+
+    def add_noise_coefficients(self, t) -> Tuple[float, float]:
+        a = float(self.alphas_cumprod[int(t)])
+        return a ** 0.5, (1.0 - a) ** 0.5
+
+    def boundary_scalings(self, t) -> Tuple[float, float]:
+        """(c_skip, c_out) of the consistency parameterisation at timestep t"""
+        s, sd = self.timestep_scaling * float(t), self.sigma_data
+        return sd * sd / (s * s + sd * sd), s / (s * s + sd * sd) ** 0.5
+
+    def coefficient_rows(self, inpaint: bool = False, first_step: int = 0, dtype=np.float32) -> np.ndarray:
+        """[len(timesteps), 16] multistep rows over entries [first_step, len).  The kernel's m is the predicted sample x0
+        (a, b by prediction type), x' = f c_skip x + f c_out m + g z[k] with (f, g) = (sqrt(a_next), sqrt(1 - a_next)) and
+        k = i - first_step, or (1, 0) on the last entry, which reads no noise row.  No ring slot, no flags."""
+        ts = self.timesteps
+        rows = [_idle_row() for _ in range(min(first_step, len(ts)))]
+        for i in range(first_step, len(ts)):
+            a_t = float(self.alphas_cumprod[int(ts[i])])
+            c_skip, c_out = self.boundary_scalings(ts[i])
+            if self.prediction_type == "v_prediction":
+                a, b = a_t ** 0.5, -(1.0 - a_t) ** 0.5
+            elif a_t == 0.0:
+                a, b = float("inf"), float("nan")
+            else:
+                a, b = 1.0 / a_t ** 0.5, -(1.0 - a_t) ** 0.5 / a_t ** 0.5
+            f, g, z_row = 1.0, 0.0, 0
+            if i < len(ts) - 1:
+                f, g = self.add_noise_coefficients(ts[i + 1])
+                z_row = i - first_step
+            ci, cn = _next_blend(self, inpaint, i)
+            rows.append(_row(a=a, b=b, c_x=f * c_skip, c_m=f * c_out, c_z=g, c_init=ci, c_noise=cn, z_row=z_row))
         return _check_finite(np.asarray(rows, dtype=np.float64).reshape(-1, ROW_WORDS), self, "coefficient_rows").astype(dtype)

@@ -20,6 +20,7 @@ Design (MI355X-first, not a module tree):
 from __future__ import annotations
 
 import itertools
+import math
 import os
 
 from dataclasses import dataclass
@@ -68,6 +69,17 @@ def fused_gen1(c: int, tokens: int, fused_max_c: int = 320) -> bool:
     return c <= fused_max_c or (c <= 640 and tokens >= 16384 and fused_max_c >= 320)
 
 
+def guidance_scale_embedding(w, dim: int, device="cpu") -> torch.Tensor:
+    """diffusers' ``get_guidance_scale_embedding`` (LatentConsistencyModelPipeline; w = guidance_scale - 1) -> fp32 [1, dim]:
+    1000 w exp(-ln(10000) / (dim / 2 - 1) arange(dim / 2)) as [sin | cos], zero-padded to an odd ``dim``.  What a UNet with
+    ``time_cond_proj_dim`` = dim projects (``time_embedding.cond_proj``, no bias) and adds to the timestep's sinusoid row."""
+    half = dim // 2
+    freq = torch.exp(torch.arange(half, dtype=torch.float32, device=device) * -(math.log(10000.0) / (half - 1)))
+    arg = (torch.tensor([1000.0 * float(w)], dtype=torch.float32, device=device))[:, None] * freq[None, :]
+    emb = torch.cat([torch.sin(arg), torch.cos(arg)], dim=1)
+    return torch.nn.functional.pad(emb, (0, 1)) if dim % 2 else emb
+
+
 class HipUNet:
     _serials = itertools.count(1)       # one number per object ever built (id() is recycled after garbage collection)
 
@@ -105,6 +117,29 @@ class HipUNet:
         self._xattn_gen = ops.xattn_generation()
         self._t_buf = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._freeu = None      # (s1, s2, b1, b2) while FreeU is enabled
+        # time_cond_proj_dim: cond_proj(guidance embedding) [1, c0] of the current generation, at a stable address
+        self._cond_row: Optional[torch.Tensor] = None
+
+    def set_guidance_embedding(self, guidance_scale: float) -> torch.Tensor:
+        """A UNet with ``time_cond_proj_dim`` (a distilled latent consistency model): the row ``time_embedding.cond_proj``
+        adds to every timestep's sinusoid, [1, c0] fp16, for w = guidance_scale - 1.  Once per generation: the embedding in
+        fp32 torch, cast to fp16 as diffusers hands it to the UNet, the projection on cid_linear_small_f16."""
+        dim = self.config.time_cond_proj_dim
+        assert dim is not None, "set_guidance_embedding: the UNet has no time_cond_proj_dim"
+        c0 = self.config.block_out_channels[0]
+        if self._cond_row is None:
+            self._cond_row = torch.zeros(1, c0, dtype=torch.float16, device=self.device)
+        w_emb = guidance_scale_embedding(float(guidance_scale) - 1.0, dim, self.device).half().contiguous()
+        ops.linear_small(w_emb, self.W["time_embedding.cond_proj.w"], None, self._cond_row, M=1, N=c0, K=dim)
+        return self._cond_row
+
+    def _add_guidance(self, sc: torch.Tensor):
+        """sinusoid rows += the guidance row, in front of linear_1 (nothing without time_cond_proj_dim)"""
+        if self.config.time_cond_proj_dim is not None:
+            if self._cond_row is None:
+                raise RuntimeError("a UNet with time_cond_proj_dim needs its guidance embedding first: "
+                                   "set_guidance_embedding(guidance_scale) (the denoise engine does that in every generation)")
+            ops.add_inplace(sc, self._cond_row)
 
     def enable_freeu(self, s1: float, s2: float, b1: float, b2: float):
         """diffusers' ``enable_freeu`` (0.23, UNet2DConditionModel): the inputs of every resnet of up block i in {0, 1} go
@@ -472,6 +507,7 @@ class HipUNet:
         c0, ted = cfg.block_out_channels[0], cfg.time_embed_dim
         sc = self._empty(1, c0)
         ops.sincos_embed(t_dev, sc, rows=1, dim=c0)
+        self._add_guidance(sc)
         e1 = self._empty(1, ted)
         ops.linear_small(sc, W["time_embedding.linear_1.w"], W["time_embedding.linear_1.b"], e1,
                          M=1, N=ted, K=c0, act_out=1)
@@ -503,13 +539,18 @@ class HipUNet:
         return out
 
     @torch.no_grad()
-    def time_embed_table(self, tvals: torch.Tensor) -> torch.Tensor:
+    def time_embed_table(self, tvals: torch.Tensor, guidance_scale: Optional[float] = None) -> torch.Tensor:
         """The time path of EVERY step of a generation at once: [S] timesteps -> [S, sum(Cout)].  Without SDXL's
         text_time conditioning the per-resnet time rows depend on the timestep only, so the three GEMVs that would
         otherwise re-read 50 MB of time-projection weights in every step run once per generation; a step then takes
-        its row from the table (``forward_tokens(temb=...)``)."""
+        its row from the table (``forward_tokens(temb=...)``).  ``guidance_scale``: required by a UNet with
+        ``time_cond_proj_dim`` -- its rows are MLP(sinusoid(t) + cond_proj(guidance embedding)), see set_guidance_embedding."""
         cfg, W = self.config, self.W
         assert cfg.addition_embed_type is None
+        if cfg.time_cond_proj_dim is not None:
+            if guidance_scale is None:
+                raise ValueError("time_embed_table: a UNet with time_cond_proj_dim needs guidance_scale")
+            self.set_guidance_embedding(guidance_scale)
         c0, ted = cfg.block_out_channels[0], cfg.time_embed_dim
         tv = tvals.to(device=self.device, dtype=torch.float32).contiguous()
         S = tv.numel()
@@ -518,6 +559,7 @@ class HipUNet:
             n = min(64, S - lo)
             sc, e1, emb = self._empty(n, c0), self._empty(n, ted), self._empty(n, ted)
             ops.sincos_embed(tv[lo:lo + n], sc, rows=n, dim=c0)
+            self._add_guidance(sc)
             ops.linear_small(sc, W["time_embedding.linear_1.w"], W["time_embedding.linear_1.b"], e1,
                              M=n, N=ted, K=c0, act_out=1)
             ops.linear_small(e1, W["time_embedding.linear_2.w"], W["time_embedding.linear_2.b"], emb, M=n, N=ted, K=ted)

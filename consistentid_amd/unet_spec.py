@@ -28,6 +28,9 @@ class UNetConfig:
     addition_time_embed_dim: Optional[int] = None
     projection_class_embeddings_input_dim: Optional[int] = None
     family: str = "sd15"
+    # a distilled latent consistency model: width of the guidance-scale embedding that time_embedding.cond_proj (no bias)
+    # projects onto the timestep's sinusoid row; None for every other UNet
+    time_cond_proj_dim: Optional[int] = None
 
     @property
     def time_embed_dim(self) -> int:
@@ -250,6 +253,8 @@ def unet_param_shapes(cfg: UNetConfig, encoder_only: bool = False) -> "OrderedDi
     conv("conv_in", boc[0], cfg.in_channels, 3)
     lin("time_embedding.linear_1", ted, boc[0])
     lin("time_embedding.linear_2", ted, ted)
+    if cfg.time_cond_proj_dim is not None:
+        lin("time_embedding.cond_proj", boc[0], cfg.time_cond_proj_dim, bias=False)
     if cfg.addition_embed_type == "text_time":
         lin("add_embedding.linear_1", ted, cfg.projection_class_embeddings_input_dim)
         lin("add_embedding.linear_2", ted, ted)

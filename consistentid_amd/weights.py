@@ -142,6 +142,10 @@ class PackedUNet:
         for n in ("time_embedding.linear_1", "time_embedding.linear_2") + (
                 ("add_embedding.linear_1", "add_embedding.linear_2") if cfg.addition_embed_type else ()):
             W[f"{n}.w"], W[f"{n}.b"] = _h(sd[f"{n}.weight"], dev), _h(sd[f"{n}.bias"], dev)
+        if cfg.time_cond_proj_dim is not None:      # [c0, dim], no bias: the guidance-scale embedding of a distilled LCM
+            if cfg.time_cond_proj_dim % 8:
+                raise NotImplementedError(f"time_cond_proj_dim = {cfg.time_cond_proj_dim}: a multiple of 8 (cid_linear_small_f16)")
+            W["time_embedding.cond_proj.w"] = _h(sd["time_embedding.cond_proj.weight"], dev)
 
         # ---- resnets (+ stacked time_emb_proj)
         tw, tb, off = [], [], 0

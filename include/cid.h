@@ -534,6 +534,17 @@ int cid_cfg_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hi
                                const cid_half* z, int32_t z_rows, const void* row, float guidance,
                                const cid_half* mask, const cid_half* init, const cid_half* noise,
                                int32_t B, int32_t per_sample, cid_stream_t stream);
+/* The single pass (since cid_version() 111): one step of the same row contract WITHOUT classifier-free guidance.
+ * eps [B][per_sample] holds ONE model output per sample and e = eps; nothing behind eps + B * per_sample is read.  Every
+ * other argument, the multistep row, the ring, `saved`, z and the inpaint blend are cid_cfg_multistep_step_f16's; with
+ * eps_u == eps_c that entry gives the same bits at every guidance value (u + g (u - u) is u).  consistentid_amd/scheduler.py
+ * LCMScheduler at guidance_scale <= 1 steps with it.
+ * -22 before any launch: a null eps / latents / hist / saved / row, z without z_rows or z_rows without z, mask / init / noise
+ * not all or none, B <= 0, per_sample <= 0, B * per_sample % 8 != 0, a buffer that is not 16-byte aligned. */
+int cid_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
+                           const cid_half* z, int32_t z_rows, const void* row,
+                           const cid_half* mask, const cid_half* init, const cid_half* noise,
+                           int32_t B, int32_t per_sample, cid_stream_t stream);
 /* guidance_rescale ("Common Diffusion Noise Schedules and Sample Steps Are Flawed", section 3.4; diffusers 0.23
  * rescale_noise_cfg, applied between the CFG combine and scheduler.step): the per-sample factor of the guided prediction.
  * eps: fp16 [2B][per_sample], unconditional half first -- what the step kernels read.  escale: DEVICE fp32 [B], written:
