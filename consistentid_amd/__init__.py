@@ -5,5 +5,15 @@ Importing the package does not touch the GPU; the HIP library is loaded on first
 (``consistentid_amd._lib.load()``) and there is no CPU fallback."""
 from .unet_spec import UNetConfig, sd15_config, sdxl_config, tiny_config  # noqa: F401
 
-__all__ = ["UNetConfig", "sd15_config", "sdxl_config", "tiny_config"]
+__all__ = ["UNetConfig", "sd15_config", "sdxl_config", "tiny_config", "HipAutoencoderTiny"]
+
+
+def __getattr__(name):
+    # the engines import torch: resolved on first use, so that importing the package stays light
+    if name == "HipAutoencoderTiny":
+        from .vae_tiny import HipAutoencoderTiny
+        return HipAutoencoderTiny
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
+
+
 __version__ = "0.1.0"

@@ -6,7 +6,11 @@ sub-folder per component.  This module reads the components the hot path needs, 
 
     <root>/unet/config.json + diffusion_pytorch_model.{safetensors,bin}     -> HipUNet      (required)
     <root>/vae/config.json  + diffusion_pytorch_model.{safetensors,bin}     -> HipVAEDecoder (optional; + HipVAEEncoder for the
-                                                                             inpaint pipelines when encoder.* weights are there)
+                                                                             inpaint pipelines when encoder.* weights are there);
+                                                                             a config whose _class_name is AutoencoderTiny
+                                                                             -> HipAutoencoderTiny (decoder only)
+    <taesd dir>/config.json + diffusion_pytorch_model.{safetensors,bin}     -> HipAutoencoderTiny (load_tiny_vae: the local
+                                                                             AutoencoderTiny.from_pretrained(path))
     <controlnet dir>/config.json + diffusion_pytorch_model.{safetensors,bin} -> HipControlNet (separate call, like the
                                                                                 reference: demo/controlnet_demo.py:44-47)
     <root>/text_encoder{,_2}/config.json + model{.fp16,}.safetensors | pytorch_model{.fp16,}.bin
@@ -142,10 +146,35 @@ def load_controlnet(folder, device="cuda:0"):
     return HipControlNet(unet_config_from_diffusers(cfg), sd, device=device)
 
 
-def load_vae(root: Union[str, os.PathLike], device="cuda:0", subfolder: str = "vae"):
+def is_tiny_vae(cfg: Dict) -> bool:
+    """a ``vae/config.json`` of diffusers' AutoencoderTiny (TAESD / taesdxl) rather than AutoencoderKL"""
+    return cfg.get("_class_name") == "AutoencoderTiny"
+
+
+def _make_decoder(cfg: Dict, sd, device):
+    """the decoder engine for a ``vae/`` folder, by the config's ``_class_name``"""
+    if is_tiny_vae(cfg):
+        from .vae_tiny import HipAutoencoderTiny
+        return HipAutoencoderTiny(cfg, sd, device=device)
     from .vae import make_vae_decoder
-    cfg, sd = read_component(os.path.join(os.fspath(root), subfolder) if subfolder else root)
     return make_vae_decoder(vae_config_from_diffusers(cfg), sd, device=device)      # fp32 engine for force_upcast (SDXL)
+
+
+def load_vae(root: Union[str, os.PathLike], device="cuda:0", subfolder: str = "vae"):
+    cfg, sd = read_component(os.path.join(os.fspath(root), subfolder) if subfolder else root)
+    return _make_decoder(cfg, sd, device)
+
+
+def load_tiny_vae(folder: Union[str, os.PathLike], device="cuda:0"):
+    """The local ``AutoencoderTiny.from_pretrained(path)``: a stand-alone TAESD / taesdxl folder (``config.json`` + weights,
+    as ``madebyollin/taesd`` is laid out) -> HipAutoencoderTiny, for ``pipe.vae = load_tiny_vae(path)`` on any pipeline.
+    Hub ids are not resolved."""
+    from .vae_tiny import HipAutoencoderTiny
+    cfg, sd = read_component(folder)
+    if cfg.get("_class_name", "AutoencoderTiny") != "AutoencoderTiny":
+        raise NotImplementedError(f"{os.fspath(folder)}: _class_name={cfg['_class_name']!r} is not AutoencoderTiny "
+                                  "(load_vae reads AutoencoderKL folders)")
+    return HipAutoencoderTiny(cfg, sd, device=device)
 
 
 def load_vae_encoder(root: Union[str, os.PathLike], device="cuda:0", subfolder: str = "vae"):
@@ -353,7 +382,9 @@ def from_pretrained(pipeline_cls, root: Union[str, os.PathLike], torch_dtype=tor
     ControlNetModel, or a list of those for a HipMultiControlNet.  ``text_encoder=`` / ``tokenizer=`` / ``text_encoder_2=`` / ``tokenizer_2=`` take a ready object, or
     None to skip that component.  ``safety_checker=`` / ``feature_extractor=`` likewise, for the SD1.5-family pipelines: the
     checker is loaded when ``safety_checker/`` exists and the caller did not pass ``safety_checker=None``; the SDXL pipeline
-    never has one (the reference's has none)."""
+    never has one (the reference's has none).  ``vae=`` takes a built decoder engine (``load_tiny_vae(path)`` for diffusers'
+    ``vae=AutoencoderTiny.from_pretrained(...)``) in place of the ``vae/`` folder's decoder; the inpaint pipelines' encoder still
+    comes from that folder.  A ``vae/`` folder whose config names AutoencoderTiny is built as HipAutoencoderTiny."""
     if torch_dtype not in (torch.float16, None):
         raise NotImplementedError("the engine computes in fp16 (the reference's own inference dtype, infer.py:19)")
     # diffusers loader keywords the reference scripts pass (infer.py:17-21 variant="fp16"; demo/controlnet_demo.py
@@ -363,6 +394,11 @@ def from_pretrained(pipeline_cls, root: Union[str, os.PathLike], torch_dtype=tor
                  "local_files_only", "cache_dir", "revision", "low_cpu_mem_usage", "add_watermarker"):
         kw.pop(name, None)
     safety_given = {k: kw.pop(k) for k in SAFETY_COMPONENTS if k in kw}
+    vae_given = "vae" in kw
+    vae = kw.pop("vae", None)              # a built decoder (HipVAEDecoder / HipAutoencoderTiny ...), as diffusers takes vae=
+    if vae_given and (vae is None or not hasattr(vae, "decode_latents")):
+        raise TypeError(f"from_pretrained: vae= takes a built decoder engine (HipVAEDecoder, HipVAEDecoderF32, "
+                        f"HipAutoencoderTiny), got {type(vae).__name__}")
     unknown = [k for k in kw if k not in ("scheduler", "num_tokens", "lora_rank") + TEXT_COMPONENTS]
     if unknown:
         raise TypeError(f"from_pretrained: unexpected keyword(s) {unknown}")
@@ -370,16 +406,17 @@ def from_pretrained(pipeline_cls, root: Union[str, os.PathLike], torch_dtype=tor
     if not os.path.isdir(root):
         raise FileNotFoundError(f"{root}: local diffusers model directory expected (no hub access)")
     unet = load_unet(root, device=device)
-    vae = vae_encoder = None
+    vae_encoder = None
     if os.path.isdir(os.path.join(root, "vae")):
         from .pipeline import StableDiffusionInpaintConsistentIDPipeline
-        from .vae import HipVAEEncoder, make_vae_decoder
+        from .vae import HipVAEEncoder
         vcfg, vsd = read_component(os.path.join(root, "vae"))
-        vcfg = vae_config_from_diffusers(vcfg)
-        vae = make_vae_decoder(vcfg, vsd, device=device)          # fp32 engine for force_upcast (SDXL)
-        # the encoder only for the two inpaint pipelines (their image= / mask_image= pre-loop), and only if the weights are there
-        if issubclass(pipeline_cls, StableDiffusionInpaintConsistentIDPipeline) and _has_encoder(vsd):
-            vae_encoder = HipVAEEncoder(vcfg, vsd, device=device)
+        if not vae_given:                 # a given vae= replaces the folder's DECODER only
+            vae = _make_decoder(vcfg, vsd, device)
+        # the encoder only for the two inpaint pipelines (their image= / mask_image= pre-loop), and only if the weights are
+        # there; an AutoencoderTiny folder brings none (its encoder is not built)
+        if issubclass(pipeline_cls, StableDiffusionInpaintConsistentIDPipeline) and not is_tiny_vae(vcfg) and _has_encoder(vsd):
+            vae_encoder = HipVAEEncoder(vae_config_from_diffusers(vcfg), vsd, device=device)
     text = read_text_components(root, device=device, given={k: kw.pop(k) for k in TEXT_COMPONENTS if k in kw})
     args = dict(use_graph=use_graph, vae=vae, **kw, **{k: v for k, v in text.items() if v is not None})
     from .pipeline import ConsistentIDStableDiffusionXLPipeline

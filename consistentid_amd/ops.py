@@ -701,6 +701,84 @@ def vae_encode_out(x: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: to
     return out
 
 
+# --------------------------------------------------------------------------- AutoencoderTiny decoder (csrc/taesd.hip)
+def _req_shape(t: torch.Tensor, name: str, shape):
+    """dtype, the exact shape and contiguity of one operand (host-side facts: every operand is held to them first, then
+    ``_req`` tests device and alignment)"""
+    if t.dtype != torch.float16:
+        raise _lib.CidError(f"{name}: expected {torch.float16}, got {t.dtype}")
+    if tuple(t.shape) != tuple(shape):
+        raise _lib.CidError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
+    if not t.is_contiguous():
+        raise _lib.CidError(f"{name}: tensor must be contiguous")
+
+
+def tiny_conv64_tile():
+    """(tile_h, tile_w, grid_cap) of cid_tiny_conv64_f16: its output tile and the most workgroups a launch has"""
+    v = [C.c_int32() for _ in range(3)]
+    _lib.load().cid_tiny_conv64_tile(*(C.byref(i) for i in v))
+    return tuple(i.value for i in v)
+
+
+def tiny_conv64(x: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None, *, B: int, H: int,
+                W: int, res: Optional[torch.Tensor] = None, relu: bool = False, up: bool = False):
+    """AutoencoderTiny's 64 -> 64 3x3 convolution (cid_tiny_conv64_f16): ``x`` token-major [B, H * W, 64], ``out``
+    [B, Ho * Wo, 64] with (Ho, Wo) = (H, W), or (2H, 2W) with ``up`` (nearest 2x in front of the conv, never materialised);
+    ``w`` [64, 9, 64] = [cout, tap, cin]; out = act(conv + bias + res)."""
+    lib = _lib.load()
+    Ho, Wo = (2 * H, 2 * W) if up else (H, W)
+    _req_shape(x, "tiny_conv64.x", (B, H * W, 64))
+    _req_shape(out, "tiny_conv64.out", (B, Ho * Wo, 64))
+    _req_shape(w, "tiny_conv64.w", (64, 9, 64))
+    if bias is not None:
+        _req_shape(bias, "tiny_conv64.bias", (64,))
+    if res is not None:
+        _req_shape(res, "tiny_conv64.res", (B, Ho * Wo, 64))
+    for name, t in (("x", x), ("out", out), ("w", w), ("bias", bias), ("res", res)):
+        if t is not None:
+            _req(t, f"tiny_conv64.{name}")
+    check(lib.cid_tiny_conv64_f16(_p(x), _p(out), _p(w), _p(bias), _p(res), B, H, W, int(bool(up)), int(bool(relu)), _stream()),
+          "cid_tiny_conv64_f16")
+    return out
+
+
+def tiny_decode_in(z: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: torch.Tensor):
+    """AutoencoderTiny's decoder head (cid_tiny_decode_in_f16): ``z`` NCHW latents [B, 4, h, w] -> relu(conv(tanh(z / 3) * 3) +
+    bias), token-major [B, h * w, 64]; ``w`` [64, 9, 4]."""
+    lib = _lib.load()
+    if z.dim() != 4 or z.shape[1] != 4:
+        raise _lib.CidError(f"tiny_decode_in.z: expected [B, 4, h, w], got {tuple(z.shape)}")
+    _req_shape(z, "tiny_decode_in.z", z.shape)
+    B, _, H, W = z.shape
+    _req_shape(out, "tiny_decode_in.out", (B, H * W, 64))
+    _req_shape(w, "tiny_decode_in.w", (64, 9, 4))
+    _req_shape(bias, "tiny_decode_in.bias", (64,))
+    if not z.is_cuda:       # (the NCHW latents need no alignment: a batch slice at an odd size is read as it is)
+        raise _lib.CidError(f"tiny_decode_in.z: tensor must live on the GPU (got {z.device}); libcid has no CPU path")
+    for name, t in (("out", out), ("w", w), ("bias", bias)):
+        _req(t, f"tiny_decode_in.{name}")
+    check(lib.cid_tiny_decode_in_f16(_p(z), _p(out), _p(w), _p(bias), B, H, W, _stream()), "cid_tiny_decode_in_f16")
+    return out
+
+
+def tiny_decode_out(x: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, clamp01: bool = False):
+    """AutoencoderTiny's decoder tail (cid_tiny_decode_out_f16): ``x`` token-major [B, H * W, 64] -> v = conv + bias; ``out``
+    NCHW [B, 3, H, W] = 2 v - 1, or clamp(v, 0, 1) with ``clamp01`` (decode_latents' range); ``w`` [3, 9, 64]."""
+    lib = _lib.load()
+    if out.dim() != 4 or out.shape[1] != 3:
+        raise _lib.CidError(f"tiny_decode_out.out: expected [B, 3, H, W], got {tuple(out.shape)}")
+    _req_shape(out, "tiny_decode_out.out", out.shape)
+    B, _, H, W = out.shape
+    _req_shape(x, "tiny_decode_out.x", (B, H * W, 64))
+    _req_shape(w, "tiny_decode_out.w", (3, 9, 64))
+    _req_shape(bias, "tiny_decode_out.bias", (3,))
+    for name, t in (("x", x), ("out", out), ("w", w), ("bias", bias)):
+        _req(t, f"tiny_decode_out.{name}")
+    check(lib.cid_tiny_decode_out_f16(_p(x), _p(out), _p(w), _p(bias), B, H, W, int(bool(clamp01)), _stream()),
+          "cid_tiny_decode_out_f16")
+    return out
+
+
 # --------------------------------------------------------------------------- face parser (csrc/parsing.hip)
 def parse_stem(img: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: torch.Tensor):
     """BiSeNet stem (cid_parse_stem_f16): ``img`` uint8 [B, H, W, 3] -> ImageNet normalisation -> conv 7x7/2 (fp32 ``w``

@@ -27,7 +27,7 @@ extern "C" {
 typedef void* cid_stream_t;      /* hipStream_t */
 typedef uint16_t cid_half;       /* IEEE binary16 bit pattern */
 
-int cid_version(void);          /* 110: cid_id_xattn_long_f16, cid_kv_pack_long_f16, cid_kv_pack_long_elems, cid_xattn_long_max_txt added (contexts beyond 96 keys).  109: cid_freeu_f16, cid_freeu_ws_bytes added.  108: cid_cfg_rescale_f16, cid_cfg_ddim_step_scaled_f16, cid_cfg_multistep_step_scaled_f16 added.  107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
+int cid_version(void);          /* 112: cid_tiny_conv64_f16, cid_tiny_decode_in_f16, cid_tiny_decode_out_f16, cid_tiny_conv64_tile added (AutoencoderTiny decoder).  111: cid_multistep_step_f16 added.  110: cid_id_xattn_long_f16, cid_kv_pack_long_f16, cid_kv_pack_long_elems, cid_xattn_long_max_txt added (contexts beyond 96 keys).  109: cid_freeu_f16, cid_freeu_ws_bytes added.  108: cid_cfg_rescale_f16, cid_cfg_ddim_step_scaled_f16, cid_cfg_multistep_step_scaled_f16 added.  107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
                                  * pointer (102: act, 101: pad_mode; set them or zero the struct) */
 const char* cid_last_error(void);
 
@@ -447,6 +447,35 @@ int cid_vae_encode_in_f16(const float* image, int32_t Bi, const float* mask, int
 int cid_vae_encode_out_f16(const cid_half* x, cid_half* out, float* moments, const cid_half* w, const float* bias,
                            const cid_half* eps, int32_t B, int32_t H, int32_t W, int32_t cin, int32_t L, float scale,
                            cid_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * AutoencoderTiny decoder (csrc/taesd.hip, since cid_version() 112).  D: diffusers 0.23 AutoencoderTiny.decode ->
+ * vae.DecoderTiny (TAESD / taesdxl), the decoder diffusers documents beside LCM: `tanh(z / 3) * 3`, conv 4 -> 64 + ReLU,
+ * AutoencoderTinyBlock x n / nearest 2x / bias-less conv per level, conv 64 -> 3, then `mul(2).sub(1)`.  64 channels
+ * everywhere, ReLU, no normalisation, no attention.  All three entries: 3x3, pad 1, stride 1, zeros outside the image, fp32
+ * accumulation, one rounding to fp16 at the store; weights [cout][9][cin] (tap = 3 ky + kx); deterministic (no atomics, no
+ * split-K, a fixed contraction order); any H, W >= 1.
+ * cid_tiny_conv64_f16: the 64 -> 64 body convolution, weight-stationary.  x token-major [B][H * W][64]; out token-major
+ *   [B][Ho * Wo][64] with (Ho, Wo) = (H, W), or (2H, 2W) with up = 1: the input is then read through a nearest 2x upsample
+ *   (output (y, x) reads input (y >> 1, x >> 1)) that is never materialised.  out = act(acc + bias + res): bias [64] or NULL,
+ *   res token-major [B][Ho * Wo][64] or NULL (added BEFORE the activation), relu 0 | 1.  The whole 72 KiB weight is staged in
+ *   LDS once per workgroup; an output tile is tile_h x tile_w pixels (cid_tiny_conv64_tile) staged with a one-pixel halo,
+ *   ragged at the right and bottom edges; the launch has at most grid_cap workgroups, which loop over the tiles.
+ *   Refused (-22): a NULL x / out / w; B, H or W <= 0; up or relu outside {0, 1}; a pointer that is not 16-byte aligned;
+ *   out == x or out == res (a tile reads its neighbours' pixels); B * Ho * Wo * 64 >= 2^32 - 2 output elements.
+ * cid_tiny_decode_in_f16: z NCHW fp16 [B][4][H][W] (the latents as the denoise loop leaves them) -> relu(conv(tanh(z / 3) * 3)
+ *   + bias), token-major [B][H * W][64]; w [64][9][4], bias [64].  tanh is evaluated in fp32 and is finite for every finite
+ *   fp16 input (|z| = 65504 gives exactly 3).  out / bias 16-byte aligned.
+ * cid_tiny_decode_out_f16: x token-major [B][H * W][64] -> v = conv(x) + bias (w [3][9][64], bias [3]); out NCHW fp16
+ *   [B][3][H][W] = 2 v - 1 (mode 0: what AutoencoderTiny.decode returns, in [-1, 1]) or clamp(v, 0, 1) (mode 1: the
+ *   `(image / 2 + 0.5).clamp(0, 1)` of StableDiffusionPipeline.decode_latents applied to 2 v - 1, without the extra pass). */
+void cid_tiny_conv64_tile(int32_t* tile_h, int32_t* tile_w, int32_t* grid_cap);    /* host query; any pointer may be NULL */
+int cid_tiny_conv64_f16(const cid_half* x, cid_half* out, const cid_half* w, const cid_half* bias, const cid_half* res,
+                        int32_t B, int32_t H, int32_t W, int32_t up, int32_t relu, cid_stream_t stream);
+int cid_tiny_decode_in_f16(const cid_half* z, cid_half* out, const cid_half* w, const cid_half* bias, int32_t B, int32_t H,
+                           int32_t W, cid_stream_t stream);
+int cid_tiny_decode_out_f16(const cid_half* x, cid_half* out, const cid_half* w, const cid_half* bias, int32_t B, int32_t H,
+                            int32_t W, int32_t mode, cid_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Face parser (csrc/parsing.hip): BiSeNet (models/BiSeNet/model.py:230-254, resnet.py:58-80) as the reference runs it, once
