@@ -5,6 +5,10 @@ list of specs on one live pipeline and hold every generation to the fresh eager 
 tests/test_gpu_engine_reuse.py and tests/test_gpu_engine_features.py are lists of such scenarios;
 tests/test_gpu_multicontrolnet.py takes its models and loop inputs from here.
 
+A spec with ``scheduler="lcm"`` runs LCMScheduler with the noise of its inputs; at guidance_scale <= 1, or on the UNet with
+``time_cond_proj_dim`` (``time_cond``), the engine takes the single pass (``single_pass``): the oracle then sees the conditional
+rows only (lcm_ref.CondOnly), and ``run_scenario`` holds the step launch and the UNet's batch rows of every generation.
+
 FreeU and community LoRAs are state of the UNet, not arguments of a call: ``apply_features`` brings a live pipeline from the
 state its UNet is in to the one a spec names, and calls nothing where they agree."""
 import functools
@@ -90,8 +94,12 @@ def unet_models(dev_str, name="tiny", adapter=0):
     return cfg, sd, ad, oracle, half_arm(oracle, torch.device(dev_str))
 
 
-def new_unet(dev_str, name="tiny", adapter=0, keep_base=False):
+def new_unet(dev_str, name="tiny", adapter=0, keep_base=False, time_cond=False):
     from consistentid_amd.unet import HipUNet
+    if time_cond:
+        assert (name, adapter) == ("tiny", 0)
+        C = time_cond_models(dev_str)
+        return HipUNet(C["cfg"], C["sd"], C["ad"], device=torch.device(dev_str), keep_base=keep_base)
     cfg, sd, ad, _, _ = unet_models(dev_str, name, adapter)
     return HipUNet(cfg, sd, ad, device=torch.device(dev_str), keep_base=keep_base)
 
@@ -100,11 +108,47 @@ def new_net(dev_str, label):
     return models(dev_str)["new_cn"](list(NET_SEEDS).index(label))
 
 
+# --------------------------------------------------------------------------- a UNet with time_cond_proj_dim
+COND_DIM = 32
+_COND = {}
+
+
+def time_cond_models(dev):
+    """tiny SD1.5 UNet with time_cond_proj_dim = 32: (cfg, state dict, HipUNet, (fp32 oracle, fp16 arm), the guidance holder).
+    The oracle UNet has no cond_proj: a forward pre-hook on its time_embedding adds cond_proj(w_emb) to the sinusoid rows,
+    computed here in fp32 from the fp16 embedding the UNet is handed.  One set per device (``hip`` on a GPU only): the oracle
+    pair reads the guidance row from ``holder``, which ``set_guidance`` fills before a run."""
+    dev = torch.device(dev)
+    if str(dev) not in _COND:
+        cfg, sd, ad = make_weights("tiny", rank=8, time_cond_proj_dim=COND_DIM)
+        w_cond = sd["time_embedding.cond_proj.weight"].half().float()
+        assert tuple(w_cond.shape) == (cfg.block_out_channels[0], COND_DIM)
+        oracle = build_oracle("tiny", {k: v for k, v in sd.items() if k != "time_embedding.cond_proj.weight"}, ad, rank=8)
+        holder = {}
+
+        def add_cond(mod, args):
+            return (args[0] + holder["row"].to(args[0]),)
+        oracle.time_embedding.register_forward_pre_hook(add_cond)
+        C = dict(cfg=cfg, sd=sd, ad=ad, w_cond=w_cond, holder=holder, oracles=(oracle, half_arm(oracle, dev)))
+        if dev.type == "cuda":
+            from consistentid_amd.unet import HipUNet
+            C["hip"] = HipUNet(cfg, sd, ad, device=dev)
+        _COND[str(dev)] = C
+    return _COND[str(dev)]
+
+
+def set_guidance(C, guidance):
+    from lcm_ref import guidance_scale_embedding
+    w_emb = torch.from_numpy(guidance_scale_embedding(guidance - 1.0, COND_DIM)).half().float()
+    C["holder"]["row"] = (w_emb @ C["w_cond"].T)[None]
+    return w_emb
+
+
 # --------------------------------------------------------------------------- a generation
 @dataclass(frozen=True)
 class Spec:
     pipe: str = "txt2img"                       # "txt2img" | "inpaint" | "controlnet" (SD1.5 tiny) | "sdxl" (SDXL tiny)
-    scheduler: str = "ddim"                     # "ddim" | "euler" | "dpm" | "pndm"
+    scheduler: str = "ddim"                     # "ddim" | "euler" | "dpm" | "pndm" | "lcm"
     steps: int = 4                              # num_inference_steps
     guidance: float = 5.0
     merge: int = 1                              # start_merge_step
@@ -127,6 +171,7 @@ class Spec:
     prediction: str = "epsilon"                 # the scheduler's prediction_type: "epsilon" | "v_prediction"
     zero_snr: bool = False                      # DDIM with test_gpu_guidance_rescale.ZERO_SNR (needs "v_prediction")
     loras: Tuple[Tuple[int, float], ...] = ()   # (seed of lora_cases.unet_lora, adapter weight), in load order
+    time_cond: bool = False                     # the tiny SD1.5 UNet with time_cond_proj_dim = 32 (``time_cond_models``; needs "lcm")
 
     def but(self, **kw):
         return replace(self, **kw)
@@ -157,8 +202,24 @@ def scheduler_kwargs(spec):
 
 def product_scheduler(spec):
     from consistentid_amd import scheduler
-    return {"ddim": scheduler.DDIMScheduler, "euler": scheduler.EulerDiscreteScheduler,
+    return {"ddim": scheduler.DDIMScheduler, "euler": scheduler.EulerDiscreteScheduler, "lcm": scheduler.LCMScheduler,
             "dpm": scheduler.DPMSolverMultistepScheduler, "pndm": scheduler.PNDMScheduler}[spec.scheduler](**scheduler_kwargs(spec))
+
+
+def single_pass(spec):
+    """whether the engine runs the B conditional rows only: LCMScheduler at guidance_scale <= 1, or on the
+    UNet with time_cond_proj_dim"""
+    assert not spec.time_cond or (spec.scheduler == "lcm" and spec.pipe != "sdxl" and not spec.adapter and not spec.loras)
+    return spec.scheduler == "lcm" and (spec.time_cond or spec.guidance <= 1.0)
+
+
+def expected_step_path(spec):
+    """the step launch the engine must report: the single-pass kernel; else the first-order CFG kernel for DDIM at eta 0 and
+    Euler, the multistep CFG kernel for the others, ``+rescale`` where guidance_rescale is honoured"""
+    if single_pass(spec):
+        return "multistep"
+    first_order = spec.scheduler in ("ddim", "euler") and spec.eta == 0.0
+    return ("cfg_ddim" if first_order else "cfg_multistep") + ("+rescale" if spec.rescale > 0.0 and spec.guidance > 1.0 else "")
 
 
 def scheduler_key(spec):
@@ -218,6 +279,8 @@ def call_pipeline(pipe, spec, dev):
         kw["callback"] = lambda i, t, lat: steps.append(lat.clone())
     if spec.eta > 0.0:
         kw.update(eta=spec.eta, variance_noise=d(inp["variance_noise"]))
+    if spec.scheduler == "lcm" and executed_steps(spec) > 1:    # one tensor per executed step but the last; one step: none
+        kw["variance_noise"] = d(inp["variance_noise"][:executed_steps(spec) - 1])
     if spec.rescale > 0.0:
         kw["guidance_rescale"] = spec.rescale
     if spec.pipe in ("inpaint", "controlnet"):
@@ -303,7 +366,7 @@ def fresh_eager(spec, dev_str):
     kw = {}
     if spec.pipe == "controlnet":
         kw["controlnet"] = controlnet_of(spec, {k: new_net(dev_str, k) for k in spec.nets})
-    unet = new_unet(dev_str, spec.name, spec.adapter, keep_base=bool(spec.loras))
+    unet = new_unet(dev_str, spec.name, spec.adapter, keep_base=bool(spec.loras), time_cond=spec.time_cond)
     pipe = pipeline_class(spec)(unet, scheduler=product_scheduler(spec), use_graph=False, **kw)
     apply_features(pipe, spec)
     out, steps = call_pipeline(pipe, spec, dev)
@@ -313,9 +376,12 @@ def fresh_eager(spec, dev_str):
 
 # --------------------------------------------------------------------------- the oracle of a spec
 @functools.lru_cache(maxsize=None)
-def oracle_models(dev_str, name="tiny", adapter=0, loras=()):
+def oracle_models(dev_str, name="tiny", adapter=0, loras=(), time_cond=False):
     """(fp32 oracle, fp16 arm) of the UNet with the LoRAs of ``loras`` merged in float64 (lora_cases.merged_state_dict);
-    ``loras`` = (): the pair of ``unet_models``"""
+    ``loras`` = (): the pair of ``unet_models``.  ``time_cond``: the hooked pair of ``time_cond_models``"""
+    if time_cond:
+        assert (name, adapter, loras) == ("tiny", 0, ())
+        return time_cond_models(dev_str)["oracles"]
     _, sd, ad, oracle, arm = unet_models(dev_str, name, adapter)
     if not loras:
         return oracle, arm
@@ -326,13 +392,17 @@ def oracle_models(dev_str, name="tiny", adapter=0, loras=()):
 
 def reference_scheduler(spec, noises):
     """the stateful restatement ``oracle.loop.denoise`` steps with, timesteps set: tests/multistep_ref.py and oracle/ddim.py
-    as before for an epsilon-prediction spec, tests/vpred_ref.py wherever ``prediction`` or ``zero_snr`` is set"""
+    as before for an epsilon-prediction spec, tests/vpred_ref.py wherever ``prediction`` or ``zero_snr`` is set,
+    tests/lcm_ref.py for "lcm"."""
+    from lcm_ref import LCMLoopRef
     from multistep_ref import DDIMEtaRef, DPMSolverPP2MRef, PNDMRef
     from oracle import ddim
     kw = scheduler_kwargs(spec)
     if spec.eta > 0.0:
         assert spec.scheduler == "ddim"
-    if kw:
+    if spec.scheduler == "lcm":         # tests/lcm_ref.py: the noises of the executed steps but the last, in call order
+        sch = LCMLoopRef(noises[:executed_steps(spec) - 1], **kw)
+    elif kw:
         from vpred_ref import DDIMRef, DPMSolverVRef, EulerRef, PNDMVRef
         if spec.scheduler == "ddim":
             sch = DDIMRef(eta=spec.eta, noises=noises if spec.eta > 0.0 else (), **kw)
@@ -351,13 +421,21 @@ def oracle_run(spec, dev_str, arm=False):
     """``spec`` through ``oracle.loop.denoise``, unchanged: on the fp32 oracle on the CPU (needs no GPU), or with ``arm`` on its
     fp16 copy on ``dev_str``.  LoRAs are merged into the oracle's state dict; guidance_rescale wraps the UNet
     (vpred_ref.RescaledUNet); FreeU hooks the UNet's first two up blocks (freeu_ref.install_freeu) for this call only -- the
-    models are memoised and shared with other modules, so the handles are removed before this returns."""
+    models are memoised and shared with other modules, so the handles are removed before this returns.  Where the engine
+    takes the single pass (``single_pass``) the UNet sits behind lcm_ref.CondOnly -- the loop's u + g (c - u) is then exactly c
+    -- and guidance_rescale is inert, as in the product; the time-cond pair gets its guidance row first."""
     from freeu_ref import install_freeu
+    from lcm_ref import CondOnly
     from oracle import loop
     from vpred_ref import RescaledUNet
+    single = single_pass(spec)
+    if single and spec.rescale > 0.0:
+        return oracle_run(spec.but(rescale=0.0), dev_str, arm)
     dev = torch.device(dev_str)
     M = models(dev_str)
-    unet = oracle_models(dev_str, spec.name, spec.adapter, spec.loras)[int(arm)]
+    unet = oracle_models(dev_str, spec.name, spec.adapter, spec.loras, spec.time_cond)[int(arm)]
+    if spec.time_cond:
+        set_guidance(time_cond_models(dev_str), spec.guidance)
     pool = M["a_cns" if arm else "o_cns"]
     nets = [pool[list(NET_SEEDS).index(k)] for k in spec.nets]
     f = (lambda t: dev_half(t, dev)) if arm else (lambda t: t.float())
@@ -381,6 +459,7 @@ def oracle_run(spec, dev_str, arm=False):
     handles = install_freeu(unet, *spec.freeu) if spec.freeu is not None else []
     try:
         model = RescaledUNet(unet, spec.guidance, spec.rescale) if spec.rescale > 0.0 and spec.guidance > 1.0 else unet
+        model = CondOnly(model) if single else model
         out = loop.denoise(model, sch, f(inp["latents"]) * float(sch.init_noise_sigma), f(inp["null"]), f(inp["augmented"]),
                            f(inp["text"]), **kw)
     finally:
@@ -404,7 +483,8 @@ FEATURES = ("freeu", "rescale", "loras")        # the fields a spec can switch o
 
 
 def features_on(spec):
-    return [k for k in FEATURES if getattr(spec, k) != getattr(Spec(), k)]
+    """(guidance_rescale is inert in the single pass: it is no feature of such a spec)"""
+    return [k for k in FEATURES if getattr(spec, k) != getattr(Spec(), k) and not (k == "rescale" and single_pass(spec))]
 
 
 @functools.lru_cache(maxsize=None)
@@ -417,16 +497,23 @@ def features_moved(spec, dev_str="cpu"):
     return {k: rel_l2(oracle_run(spec, dev_str), oracle_run(spec.but(**{k: getattr(Spec(), k)}), dev_str)) for k in features_on(spec)}
 
 
-def assert_features_matter(spec, dev_str="cpu"):
+def assert_features_matter(spec, dev_str="cpu", guidance_vs=None):
     """the thresholds of the features' own tests: 20 * TOL_L2 for FreeU and guidance_rescale (tests/test_gpu_freeu.py),
-    lora_cases.MATTERS for a LoRA"""
-    from conftest import TOL_L2
+    lora_cases.MATTERS for a LoRA.  ``guidance_vs``: the generation is there because ``spec`` and the same spec at that
+    guidance_scale differ (the single pass against the CFG path): the two fp32 oracle runs are 20 * TOL_L2 apart, the
+    threshold of test_gpu_lcm.test_tiny_lcm_with_guidance_takes_the_cfg_path"""
+    from conftest import TOL_L2, rel_l2
     from lora_cases import MATTERS
-    need = {"freeu": 20 * TOL_L2, "rescale": 20 * TOL_L2, "loras": MATTERS}
-    for k, moved in features_moved(spec, dev_str).items():
-        print(f"[engine] {k} moves the fp32 oracle of this spec by rel_l2={moved:.3e} (needs >= {need[k]:.1e})")
-        assert moved >= need[k], f"{k} moves the fp32 oracle by {moved:.3e} < {need[k]:.1e}: the comparison would be vacuous for {spec}"
-
+    need = {"freeu": 20 * TOL_L2, "rescale": 20 * TOL_L2, "loras": MATTERS, "guidance": 20 * TOL_L2}
+    moves = dict(features_moved(spec, dev_str))
+    if guidance_vs is not None:
+        assert guidance_vs != spec.guidance
+        spec = spec.but(callback=False)
+        moves["guidance"] = rel_l2(oracle_run(spec, dev_str), oracle_run(spec.but(guidance=guidance_vs), dev_str))
+    for k, moved in moves.items():
+        what = f"guidance_scale {spec.guidance} against {guidance_vs}" if k == "guidance" else k
+        print(f"[engine] {what} moves the fp32 oracle of this spec by rel_l2={moved:.3e} (needs >= {need[k]:.1e})")
+        assert moved >= need[k], f"{what} moves the fp32 oracle by {moved:.3e} < {need[k]:.1e}: the comparison would be vacuous for {spec}"
 
 
 
@@ -439,6 +526,8 @@ class Gen:
     same_graphs: bool = False       # a transition the engine promises not to re-capture for
     pipe: Any = None                # scenarios over several pipelines: the one this generation runs on
     before: Optional[Callable[[], None]] = None     # runs first (e.g. loads an adapter)
+    guidance_vs: Optional[float] = None             # the point is that this guidance_scale would differ (assert_features_matter)
+    after: Optional[Callable[[Any], None]] = None   # runs last, on the engine (e.g. looks at its static buffers)
 
 
 def run_scenario(dev, scenario, gens, pipe=None, net_objects=None):
@@ -465,6 +554,9 @@ def run_scenario(dev, scenario, gens, pipe=None, net_objects=None):
         got = got.clone()
         print(f"[engine] {scenario}: generation {n} ({g.what}): captures {before} -> {len(eng.captures)}"
               f"{' (promised: none)' if g.same_graphs else ''}; graphs now {sorted(eng._graphs)}")
+        rows = spec.B if single_pass(spec) else 2 * spec.B
+        assert eng.step_path == expected_step_path(spec), f"{scenario}, generation {n} ({g.what}): step launch {eng.step_path}"
+        assert tuple(eng._static["kvrow"].shape) == (rows,), f"{scenario}, generation {n} ({g.what}): the UNet ran {tuple(eng._static['kvrow'].shape)} rows"
         want, want_steps = fresh_eager(spec, str(dev))
         assert torch.isfinite(got.float()).all(), f"{scenario}, generation {n} ({g.what}): not finite"
         assert torch.equal(got, want), (f"{scenario}, generation {n} ({g.what}): differs from the fresh eager run, max |diff| = "
@@ -474,10 +566,12 @@ def run_scenario(dev, scenario, gens, pipe=None, net_objects=None):
             for i, (a, b) in enumerate(zip(steps, want_steps)):
                 assert torch.equal(a, b), f"{scenario}, generation {n} ({g.what}): step {i} differs from the fresh eager run"
         if g.oracle or n in (0, len(gens) - 1):
-            assert_features_matter(spec, str(dev))
+            assert_features_matter(spec, str(dev), g.guidance_vs)
             check_vs_fp16_arm(got, *oracle_pair(spec.but(callback=False), str(dev)), f"{scenario}, generation {n} ({g.what})")
         if g.same_graphs:
             assert len(eng.captures) == before, f"{scenario}, generation {n} ({g.what}): re-captured {eng.captures[before:]}"
+        if g.after is not None:
+            g.after(eng)
         outs.append(got)
     for p in {id(g.pipe or pipe): g.pipe or pipe for g in gens}.values():
         assert p._engine.captures, f"{scenario}: nothing was ever captured, so nothing was replayed"

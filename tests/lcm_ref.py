@@ -92,3 +92,25 @@ class LCMLoopRef(LCMRef):
             z = self.noises[self.calls].to(device=sample.device, dtype=sample.dtype)
             self.calls += 1
         return super().step(model_output, i, sample, z)
+
+
+class CondOnly:
+    """The oracle UNet on the conditional rows only, behind ``oracle.loop.denoise``'s 2B-row call: the second half of every
+    batched argument goes through the UNet once and comes back as both halves, so the loop's u + g (c - u) is exactly c."""
+
+    def __init__(self, unet):
+        self.unet = unet
+
+    def __call__(self, sample, t, encoder_hidden_states, cross_attention_kwargs=None, added_cond_kwargs=None,
+                 down_block_additional_residuals=None, mid_block_additional_residual=None):
+        from oracle.unet import UNetOutput
+        B = sample.shape[0] // 2
+        kw = {}
+        if added_cond_kwargs is not None:
+            kw["added_cond_kwargs"] = {k: v[B:] for k, v in added_cond_kwargs.items()}
+        if down_block_additional_residuals is not None:
+            kw["down_block_additional_residuals"] = [d[B:] for d in down_block_additional_residuals]
+            kw["mid_block_additional_residual"] = mid_block_additional_residual[B:]
+        out = self.unet(sample[B:], t, encoder_hidden_states=encoder_hidden_states[B:],
+                        cross_attention_kwargs=cross_attention_kwargs, **kw).sample
+        return UNetOutput(sample=torch.cat([out, out]))

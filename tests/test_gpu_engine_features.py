@@ -8,13 +8,16 @@ lora_cases' merged state dicts -- and every feature a spec switches on must move
 feature's own tests (engine_cases.assert_features_matter), so an engine that ignored it could not pass.
 
 The scenarios are data (``SCENARIO_A`` .. ``SCENARIO_D``, ``SCENARIO_G``, ``LARGE``, ``PAIRWISE``): tests/test_engine_features_host.py checks
-without a GPU that the pairwise list covers every pair of factor values and that every spec runs enough steps."""
+without a GPU that the pairwise list covers every pair of factor values and that every spec runs enough steps.
+
+``SCENARIO_H``, ``SCENARIO_I`` and ``PAIRWISE_LCM`` put the same switches, a 154-row context and a HipMultiControlNet under the
+LCM single pass, whose UNet batch is B rows, not 2B; tests/test_lcm_engine_host.py checks those lists."""
 import pytest
 import torch
 
 from conftest import check_vs_fp16_arm, dev_half
-from engine_cases import (Gen, Spec, apply_features, hooked_modules, new_net, new_unet, oracle_models, oracle_pair,
-                          pipeline_class, run_scenario)
+from engine_cases import (Gen, Spec, apply_features, expected_step_path, hooked_modules, new_net, new_unet, oracle_models,
+                          oracle_pair, pipeline_class, run_scenario)
 
 pytestmark = pytest.mark.gpu
 
@@ -139,9 +142,9 @@ def pairwise_spec(pipe, sampler, prediction, freeu, rescale, loras):
 
 def step_path(spec):
     """the step launch the engine must report: the first-order kernel for DDIM at eta 0 and Euler, the multistep kernel for
-    the others, ``+rescale`` where guidance_rescale is honoured"""
-    first_order = spec.scheduler in ("ddim", "euler") and spec.eta == 0.0
-    return ("cfg_ddim" if first_order else "cfg_multistep") + ("+rescale" if spec.rescale > 0.0 and spec.guidance > 1.0 else "")
+    the others, ``+rescale`` where guidance_rescale is honoured; ``multistep`` for the LCM single pass
+    (engine_cases.expected_step_path, which run_scenario holds every generation to)"""
+    return expected_step_path(spec)
 
 
 PAIRWISE = {f"{r[0]}, {r[1]}, {r[2]}{', FreeU' if r[3] else ''}{', rescale' if r[4] else ''}{', LoRA' if r[5] else ''}": pairwise_spec(*r)
@@ -151,8 +154,41 @@ ZERO_SNR_SPEC = Spec(zero_snr=True, prediction="v_prediction", rescale=PHI, free
 PAIRWISE["zero-SNR DDIM, v_prediction, FreeU, rescale, LoRA"] = ZERO_SNR_SPEC
 
 
+# h. the LCM single pass (LCMScheduler at guidance_scale 1: the UNet runs the B conditional rows) under the
+# switches that were written while the UNet batch was always 2B.  guidance_rescale is inert there: the same bits as the
+# generation before, the step launch stays "multistep", cid_cfg_rescale_f16 is never launched.
+LCM1 = Spec(scheduler="lcm", steps=4, merge=1, guidance=1.0)
+SCENARIO_H = _chain(LCM1, [
+    ("LoRA loaded", dict(loras=LORA)), ("FreeU on", dict(freeu=FREEU)), ("guidance_rescale 0.7 (inert)", dict(rescale=PHI)),
+    ("everything off", dict(loras=(), freeu=None, rescale=0.0)), ("154 text rows", dict(text_len=154)),
+    ("154 text rows, LoRA and FreeU", dict(loras=LORA, freeu=FREEU)), ("77 text rows", dict(text_len=77))])
+
+# i. the single pass with a HipMultiControlNet [A, B]: 4 steps with B's window ending at 0.5 are (0, 1) twice, then (0,) twice
+# -- warm-up and capture of both sets within the generation; at strength 0.75 (3 executed steps) (0, 1) once and (0,) twice
+_I0 = CN_AB.but(scheduler="lcm", guidance=1.0)
+_I1 = _I0.but(windows=(FULL, (0.0, 0.5)))
+SCENARIO_I = _chain(_I0, [
+    ("B's window ends at 0.5", dict(windows=_I1.windows)), ("new scales", dict(scales=(0.3, 0.9))), ("FreeU on", dict(freeu=FREEU)),
+    ("strength 0.75", dict(strength=0.75)), ("guidance 2: the CFG path", dict(guidance=2.0)), ("guidance 1", dict(guidance=1.0))])
+SCENARIO_I_SAME_GRAPHS = ("new scales",)        # the multi path reads its scales from the step table
+
+# j. pairs of generations on one new pipeline
+XL_LCM1 = XL.but(scheduler="lcm", guidance=1.0)
+PAIRWISE_LCM = {"txt2img, LCM at guidance 1, then with a LoRA": (LCM1, LCM1.but(loras=LORA_07)),
+                "sdxl, LCM with FreeU, guidance 1 then 2": (XL_LCM1.but(freeu=FREEU), XL_LCM1.but(freeu=FREEU, guidance=2.0))}
+
+
+def lcm_specs():
+    """{label: spec} of every generation of (h) - (j)"""
+    out = {}
+    for name, rows in (("h", SCENARIO_H), ("i", SCENARIO_I)):
+        out.update({f"{name}: {n} {what}": s for n, (what, s) in enumerate(rows)})
+    out.update({f"j: {k}, generation {n}": s for k, pair in PAIRWISE_LCM.items() for n, s in enumerate(pair)})
+    return out
+
+
 def all_specs():
-    """{label: spec} of every generation of this module"""
+    """{label: spec} of every generation of (a) - (g)"""
     out = {}
     for name, rows in (("a", SCENARIO_A), ("b", SCENARIO_B), ("c", SCENARIO_C), ("g", SCENARIO_G)):
         out.update({f"{name}: {n} {what}": s for n, (what, s) in enumerate(rows)})
@@ -228,6 +264,52 @@ def test_long_context_one_switch_at_a_time(dev):
     assert not torch.equal(seen["LoRA"][0], seen["base"][0]), "the long K image did not follow the LoRA's to_k"
     assert torch.equal(seen["all off"][0], seen["base"][0]), "the long K image of the base did not come back after the unload"
     assert all(_long_layers(pipe.unet)) and pipe.unet._ctx.n_txt == 154 and "seed11" not in pipe.get_list_adapters()
+
+
+# --------------------------------------------------------------------------- h - j: the LCM single pass
+def _guidance_vs(spec):
+    return {1.0: 2.0, 2.0: 1.0}[spec.guidance]
+
+
+def test_lcm_single_pass_one_switch_at_a_time(dev, monkeypatch):
+    from consistentid_amd import ops
+    launches = []
+    rescale = ops.cfg_rescale
+    monkeypatch.setattr(ops, "cfg_rescale", lambda *a, **k: (launches.append(1), rescale(*a, **k))[1])
+    pipe = _pipe(dev, LCM1)
+    gens = [Gen(what, s, oracle=True, guidance_vs=2.0 if n == 0 else None) for n, (what, s) in enumerate(SCENARIO_H)]
+    outs = run_scenario(dev, "features on the LCM single pass", gens, pipe)
+    assert torch.equal(outs[3], outs[2]), "guidance_rescale moved the single pass"
+    assert not launches and "escale" not in pipe._engine._static, "cid_cfg_rescale_f16 was launched in a single pass"
+    assert torch.equal(outs[4], outs[0]), "everything off again, and the first generation does not come back"
+    assert not torch.equal(outs[1], outs[0]) and not torch.equal(outs[2], outs[1]) and not torch.equal(outs[5], outs[0])
+    assert pipe.unet._ctx.n_txt == 77 and pipe.unet._freeu == FREEU and "seed11" in pipe.get_list_adapters()
+
+
+def test_lcm_single_pass_multicontrolnet(dev):
+    nets = _nets(dev, _I0)
+    pipe = _pipe(dev, _I0, nets)
+    gens = [Gen(what, s, oracle=True, same_graphs=what in SCENARIO_I_SAME_GRAPHS,
+                guidance_vs=_guidance_vs(s) if n in (0, 5, 6) else None) for n, (what, s) in enumerate(SCENARIO_I)]
+    seen = []
+    gens[2].before = lambda: seen.append(list(pipe._engine.captures))
+    outs = run_scenario(dev, "MultiControlNet on the LCM single pass", gens, pipe, nets)
+    assert seen[0][-2:] == [(0, 1), (0,)], f"B fell out of its window and the graphs did not gain (0,): {seen[0]}"
+    assert not torch.equal(outs[2], outs[1]), "the new scales did not reach the replayed step"
+    assert pipe._engine.step_path == "multistep"
+
+
+@pytest.mark.parametrize("case", list(PAIRWISE_LCM))
+def test_pairwise_lcm(dev, case):
+    """two differing generations on one new pipeline: warm-up and capture in the first; the second follows a switch"""
+    first, second = PAIRWISE_LCM[case]
+    pipe = _pipe(dev, first)
+    vs = lambda s: _guidance_vs(s) if first.guidance != second.guidance or not s.loras else None
+    gens = [Gen("the first of the pair", first, oracle=True, guidance_vs=vs(first)),
+            Gen("the second of the pair", second, oracle=True, guidance_vs=vs(second))]
+    a, b = run_scenario(dev, case, gens, pipe)
+    assert pipe._engine.captures and not torch.equal(a, b)
+    assert pipe._engine.step_path == step_path(second)
 
 
 # --------------------------------------------------------------------------- d: a shared UNet

@@ -133,3 +133,125 @@ def test_sdxl_one_change_at_a_time(dev):
         gens.append(Gen(what, s, same_graphs=promised, oracle="unconditional" in what))
     pipe = pipeline_class(base)(new_unet(str(dev), "tinyxl"), use_graph=True)
     _run(dev, "SDXL", gens, pipe)
+
+
+# --------------------------------------------------------------------------- 7. the LCM single pass on a live engine
+# LCMScheduler at guidance_scale <= 1 runs the B conditional rows and cid_multistep_step_f16; every other generation 2B rows
+# and a CFG step.  ``kvrow``, ``pooled``, ``time_ids`` and the UNet workspace change size between the two while ``lat``,
+# ``ms_hist``, ``ms_saved`` and ``ms_row`` keep theirs; engine_cases.run_scenario holds every generation to the step launch and
+# the UNet batch rows its spec names, beside the fresh eager bits.  The scenarios are data: tests/test_lcm_engine_host.py
+# checks their shape without a GPU.
+LCM = Spec(scheduler="lcm", steps=4, merge=1, guidance=1.0)
+FULL = (0.0, 1.0)
+
+
+def _chain(base, changes):
+    """[(what, spec)]: ``base``, then one change after another, each on top of the one before"""
+    out, s = [("base", base)], base
+    for what, change in changes:
+        s = s.but(**change)
+        out.append((what, s))
+    return out
+
+
+LCM_ONE_CHANGE = _chain(LCM, [
+    ("guidance 2: the CFG path, 2B rows", dict(guidance=2.0)), ("guidance 1 again", dict(guidance=1.0)),
+    ("3 steps: z loses a row", dict(steps=3)), ("B = 1", dict(B=1)), ("B = 2", dict(B=2)), ("merge 2", dict(merge=2)),
+    ("callback", dict(callback=True))])
+
+_T2I = Spec(steps=4, merge=1)
+_LCM2 = LCM.but(guidance=2.0)
+LCM_AMONG_SCHEDULERS = [
+    ("DDIM at guidance 5", _T2I), ("LCM at guidance 1", LCM), ("DPM-Solver++ at guidance 1: 2B rows on LCM's ring", _T2I.but(scheduler="dpm", guidance=1.0)),
+    ("LCM at guidance 1 again", LCM), ("PNDM at guidance 5", _T2I.but(scheduler="pndm")), ("LCM at guidance 2", _LCM2),
+    ("DDIM eta 0.5: its own z, one row more than LCM's", _T2I.but(eta=0.5)), ("LCM at guidance 1", LCM)]
+
+XL_LCM = Spec(pipe="sdxl", scheduler="lcm", steps=4, merge=1, guidance=1.0)
+SDXL_LCM = _chain(XL_LCM, [
+    ("second unconditional set, which the single pass ignores", dict(null_post=True)), ("guidance 2: it matters now", dict(guidance=2.0)),
+    ("new time_ids", dict(time_ids=(8, 16))), ("guidance 1", dict(guidance=1.0))])
+
+_INP = Spec(pipe="inpaint", steps=4, merge=1)
+SHARED_LCM = [("P1: LCM single pass", "P1", LCM), ("P2: DDIM inpaint at guidance 5", "P2", _INP), ("P1 again", "P1", LCM),
+              ("P2 at B = 1", "P2", _INP.but(B=1)), ("P1 once more", "P1", LCM)]
+
+TC = Spec(scheduler="lcm", time_cond=True, steps=4, merge=1, guidance=3.0)
+TIME_COND = [("txt2img at guidance 3", "txt2img", TC), ("guidance 8", "txt2img", TC.but(guidance=8.0)),
+             ("inpaint at strength 0.75", "inpaint", TC.but(pipe="inpaint", strength=0.75)),
+             ("ControlNet-inpaint with net A", "controlnet", TC.but(pipe="controlnet", nets=("A",), scales=(0.5,), windows=(FULL,))),
+             ("txt2img at guidance 3 again", "txt2img", TC)]
+
+
+def _other_guidance(spec):
+    """the guidance_scale a single-pass / CFG generation of these scenarios is told apart from"""
+    return {1.0: 2.0, 2.0: 1.0, 3.0: 8.0, 8.0: 3.0}.get(spec.guidance) if spec.scheduler == "lcm" else None
+
+
+def test_lcm_one_change_at_a_time(dev):
+    """single pass -> CFG path -> single pass (``kvrow`` B -> 2B -> B), then the changes that move ``z``, ``lat`` and the ring"""
+    gens = [Gen(what, s, oracle=n <= 2, guidance_vs=_other_guidance(s) if n <= 2 else None, same_graphs=what == "merge 2")
+            for n, (what, s) in enumerate(LCM_ONE_CHANGE)]
+    pipe = pipeline_class(LCM)(new_unet(str(dev)), use_graph=True)
+    outs = _run(dev, "LCM txt2img", gens, pipe)
+    assert torch.equal(outs[2], outs[0]), "guidance 1 after guidance 2 is not the single pass it started with"
+    assert not torch.equal(outs[1], outs[0])
+
+
+def test_lcm_among_the_other_schedulers(dev):
+    """DPM-Solver++ and PNDM share ``ms_row`` / ``ms_hist`` / ``ms_saved`` with LCM and run 2B rows on them; ``z`` comes (LCM: 3
+    rows, DDIM eta: 4) and goes.  The three single passes are the same generation: the same bits."""
+    gens = [Gen(what, s, oracle=True, guidance_vs=_other_guidance(s)) for what, s in LCM_AMONG_SCHEDULERS]
+    pipe = pipeline_class(LCM)(new_unet(str(dev)), use_graph=True)
+    outs = _run(dev, "LCM among the schedulers", gens, pipe)
+    assert torch.equal(outs[3], outs[1]) and torch.equal(outs[7], outs[1]), "the single pass came back with other bits"
+    assert pipe._engine.step_path == "multistep"
+
+
+def test_sdxl_lcm_single_and_cfg(dev):
+    """The pooled column and the time ids have B rows in the single pass (the conditional half's) and 2B on the CFG path; the
+    fourth embed set (``null_post``) lengthens the K/V cache under a single pass that must not read it."""
+    from conftest import rel_l2
+    from engine_cases import fresh_eager, oracle_run, single_pass
+
+    def rows_match(spec):
+        def after(eng):
+            want = spec.B if single_pass(spec) else 2 * spec.B
+            assert eng._static["pooled"].shape[0] == want and eng._static["time_ids"].shape[0] == want, \
+                (spec, eng._static["pooled"].shape, eng._static["time_ids"].shape)
+        return after
+    gens = [Gen(what, s, oracle=True, guidance_vs=_other_guidance(s), after=rows_match(s)) for what, s in SDXL_LCM]
+    pipe = pipeline_class(XL_LCM)(new_unet(str(dev), "tinyxl"), use_graph=True)
+    outs = _run(dev, "SDXL LCM", gens, pipe)
+    assert torch.equal(outs[1], outs[0]), "the second unconditional set moved the single pass"
+    # ... and matters on the CFG path.  Its values (engine_cases._inputs: the null set + 0.5 randn) move the fp32 oracle at
+    # guidance 2 by rel_l2 1.0e-3 only, which no tolerance tells from rounding: that generation 2 read them is held bit for bit,
+    # against a fresh eager run of the same generation without them
+    g2 = SDXL_LCM[2][1]
+    moved = rel_l2(oracle_run(g2, str(dev)), oracle_run(g2.but(null_post=False), str(dev)))
+    print(f"[engine] SDXL LCM: the second unconditional set moves the fp32 oracle at guidance 2 by rel_l2={moved:.3e}")
+    assert moved > 0.0 and not torch.equal(outs[2], fresh_eager(g2.but(null_post=False), str(dev))[0]), \
+        "the second unconditional set did not reach the CFG path"
+
+
+def test_shared_unet_single_pass_and_cfg(dev):
+    """one HipUNet under P1 (txt2img, LCM at guidance 1: B rows) and P2 (inpaint, DDIM at guidance 5: 2B rows, then B = 1):
+    the UNet's workspace and K/V buffers are sized by whoever ran last"""
+    unet = new_unet(str(dev))
+    pipes = {"P1": pipeline_class(LCM)(unet, use_graph=True), "P2": pipeline_class(_INP)(unet, use_graph=True)}
+    gens = [Gen(what, s, oracle=True, pipe=pipes[p], guidance_vs=_other_guidance(s)) for what, p, s in SHARED_LCM]
+    outs = _run(dev, "shared UNet, single pass and CFG", gens)
+    assert torch.equal(outs[2], outs[0]) and torch.equal(outs[4], outs[0]), "P1 does not return to its first result"
+
+
+def test_time_cond_unet_across_pipelines(dev):
+    """the UNet with time_cond_proj_dim (the single pass at every guidance_scale, the scale in its time rows) under three
+    pipelines: it had run txt2img only"""
+    unet = new_unet(str(dev), time_cond=True)
+    nets = {"A": new_net(str(dev), "A")}
+    pipes = {k: pipeline_class(Spec(pipe=k))(unet, use_graph=True, **({"controlnet": nets["A"]} if k == "controlnet" else {}))
+             for k in ("txt2img", "inpaint", "controlnet")}
+    gens = [Gen(what, s, oracle=True, pipe=pipes[p], guidance_vs=_other_guidance(s) if n < 2 else None)
+            for n, (what, p, s) in enumerate(TIME_COND)]
+    outs = _run(dev, "time_cond_proj_dim UNet", gens, net_objects=nets)
+    assert torch.equal(outs[4], outs[0]), "guidance 3 after three other generations is not the guidance 3 it started with"
+    assert not torch.equal(outs[1], outs[0])

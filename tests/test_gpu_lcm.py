@@ -6,10 +6,10 @@ import pytest
 import torch
 
 import engine_cases as E
-from conftest import TOL_L2, check_close, check_vs_fp16_arm, dev_half, half_arm, rel_l2
-from lcm_ref import LCMLoopRef, guidance_scale_embedding
+from conftest import TOL_L2, check_close, check_vs_fp16_arm, dev_half, rel_l2
+from engine_cases import set_guidance as _set_guidance, time_cond_models as _cond_models
+from lcm_ref import CondOnly, LCMLoopRef
 from multistep_ref import RowEmulator
-from oracle_utils import build_oracle, make_weights
 
 pytestmark = pytest.mark.gpu
 
@@ -135,28 +135,6 @@ def test_single_pass_launch_replays_from_a_graph(dev):
 
 
 # ----------------------------------------------------------------------------------------------------------- trajectories
-class CondOnly:
-    """The oracle UNet on the conditional rows only, behind ``oracle.loop.denoise``'s 2B-row call: the second half of every
-    batched argument goes through the UNet once and comes back as both halves, so the loop's u + g (c - u) is exactly c."""
-
-    def __init__(self, unet):
-        self.unet = unet
-
-    def __call__(self, sample, t, encoder_hidden_states, cross_attention_kwargs=None, added_cond_kwargs=None,
-                 down_block_additional_residuals=None, mid_block_additional_residual=None):
-        from oracle.unet import UNetOutput
-        B = sample.shape[0] // 2
-        kw = {}
-        if added_cond_kwargs is not None:
-            kw["added_cond_kwargs"] = {k: v[B:] for k, v in added_cond_kwargs.items()}
-        if down_block_additional_residuals is not None:
-            kw["down_block_additional_residuals"] = [d[B:] for d in down_block_additional_residuals]
-            kw["mid_block_additional_residual"] = mid_block_additional_residual[B:]
-        out = self.unet(sample[B:], t, encoder_hidden_states=encoder_hidden_states[B:],
-                        cross_attention_kwargs=cross_attention_kwargs, **kw).sample
-        return UNetOutput(sample=torch.cat([out, out]))
-
-
 STEPS, MERGE = 4, 1
 _REFS = {}
 
@@ -305,36 +283,6 @@ def test_other_schedulers_keep_their_step_at_guidance_one(dev, name, path):
 
 
 # ----------------------------------------------------------------------------------- a UNet with time_cond_proj_dim
-COND_DIM = 32
-_COND = {}
-
-
-def _cond_models(dev):
-    """tiny SD1.5 UNet with time_cond_proj_dim = 32: (cfg, state dict, HipUNet, (fp32 oracle, fp16 arm), the guidance holder).
-    The oracle UNet has no cond_proj: a forward pre-hook on its time_embedding adds cond_proj(w_emb) to the sinusoid rows,
-    computed here in fp32 from the fp16 embedding the UNet is handed."""
-    if not _COND:
-        from consistentid_amd.unet import HipUNet
-        cfg, sd, ad = make_weights("tiny", rank=8, time_cond_proj_dim=COND_DIM)
-        w_cond = sd["time_embedding.cond_proj.weight"].half().float()
-        assert tuple(w_cond.shape) == (cfg.block_out_channels[0], COND_DIM)
-        oracle = build_oracle("tiny", {k: v for k, v in sd.items() if k != "time_embedding.cond_proj.weight"}, ad, rank=8)
-        holder = {}
-
-        def add_cond(mod, args):
-            return (args[0] + holder["row"].to(args[0]),)
-        oracle.time_embedding.register_forward_pre_hook(add_cond)
-        _COND.update(cfg=cfg, sd=sd, w_cond=w_cond, holder=holder, hip=HipUNet(cfg, sd, ad, device=dev),
-                     oracles=(oracle, half_arm(oracle, dev)))
-    return _COND
-
-
-def _set_guidance(C, guidance):
-    w_emb = torch.from_numpy(guidance_scale_embedding(guidance - 1.0, COND_DIM)).half().float()
-    C["holder"]["row"] = (w_emb @ C["w_cond"].T)[None]
-    return w_emb
-
-
 def test_time_cond_table_rows(dev):
     """time_embed_table of the UNet with time_cond_proj_dim: every row is time_emb_proj(silu(MLP(sincos(t) + cond_proj(w_emb))))
     for all resnets side by side -- recomputed in torch fp32 and, as the arm, in torch fp16 on the GPU (check_vs_fp16_arm: the

@@ -378,3 +378,47 @@ def test_safety_checker_still_runs(dev, tiny):
     assert all(isinstance(f, (bool, np.bool_)) for f in r.nsfw_content_detected)
     assert isinstance(r.images, np.ndarray) and r.images.shape[0] == kw["latents"].shape[0] and np.isfinite(r.images).all()
     assert pipe(output_type="latent", **kw).nsfw_content_detected is None
+
+
+# ----------------------------------------------------------------------------- the few-step configuration
+def few_step_spec():
+    """LCM at guidance_scale 1 (the single pass) with one community LoRA merged -- LCM-LoRA on a base model, the configuration
+    profiles/lcm_cost.txt and profiles/taesd_cost.txt are about; tests/test_lcm_engine_host.py holds the LoRA to its threshold.
+    v-prediction, because the tiny UNet has random weights and is no denoiser: an epsilon LCM step at t = 999 divides by
+    sqrt(alphas_cumprod) = 0.07 and the final latents come out at std 16, where the decoder's tanh(z / 3) is +-1 everywhere and
+    taesd_ref.decode refuses its own activations (1.1e3 > ACT_LIMIT); the v-prediction latents have std 0.6"""
+    import engine_cases as E
+    return E.Spec(scheduler="lcm", steps=4, merge=1, guidance=1.0, loras=((11, 1.0),), prediction="v_prediction")
+
+
+class _AsPixels:
+    """``pipe(**kw)`` of engine_cases.call_pipeline with output_type "pt" in place of "latent\""""
+
+    def __init__(self, pipe):
+        self.pipe = pipe
+
+    def __call__(self, **kw):
+        return self.pipe(**{**kw, "output_type": "pt"})
+
+
+def test_few_step_configuration(dev, tiny):
+    """4-step LCM single pass + LoRA + the tiny decoder on one graph pipeline.  The latents are held like every engine
+    scenario (engine_cases.run_scenario: the fresh eager bits, the fp16 arm of the fp32 oracle with the LoRA merged, the step
+    launch and the B UNet rows); the image by ``_check_decoder`` on those latents.  Then B = 1 and B = 2 again: the decoder
+    releases and rebuilds its per-shape buffers and the engine its static ones, and the third image is the first bit for bit."""
+    import engine_cases as E
+    model, hip = tiny
+    spec = few_step_spec()
+    pipe = E.pipeline_class(spec)(E.new_unet(str(dev), keep_base=True), use_graph=True)
+    pipe.vae = hip
+    (lat,) = E.run_scenario(dev, "few-step configuration", [E.Gen("LCM, LoRA, tiny decoder", spec, oracle=True, guidance_vs=2.0)], pipe)
+    images = []
+    for B in (2, 1, 2):
+        s = spec.but(B=B)
+        img = _nchw(E.call_pipeline(_AsPixels(pipe), s, dev)[0]).clone()
+        want = lat if B == 2 else E.fresh_eager(s, str(dev))[0]
+        assert img.shape == (B, 3, 8 * want.shape[2], 8 * want.shape[3]) and hip._bufs[0][0].shape[0] == B
+        _check_decoder(img, model, want, f"few-step configuration, B = {B}, output_type=pt", clamp01=True)
+        images.append(img)
+    assert pipe._engine.step_path == "multistep" and pipe._engine.captures
+    assert torch.equal(images[2], images[0]), "B = 2 after B = 1 gives another image than the first B = 2"
