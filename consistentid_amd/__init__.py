@@ -5,14 +5,14 @@ Importing the package does not touch the GPU; the HIP library is loaded on first
 (``consistentid_amd._lib.load()``) and there is no CPU fallback."""
 from .unet_spec import UNetConfig, sd15_config, sdxl_config, tiny_config  # noqa: F401
 
-__all__ = ["UNetConfig", "sd15_config", "sdxl_config", "tiny_config", "HipAutoencoderTiny"]
+__all__ = ["UNetConfig", "sd15_config", "sdxl_config", "tiny_config", "HipAutoencoderTiny", "HipAutoencoderTinyEncoder"]
 
 
 def __getattr__(name):
     # the engines import torch: resolved on first use, so that importing the package stays light
-    if name == "HipAutoencoderTiny":
-        from .vae_tiny import HipAutoencoderTiny
-        return HipAutoencoderTiny
+    if name in ("HipAutoencoderTiny", "HipAutoencoderTinyEncoder"):
+        from . import vae_tiny
+        return getattr(vae_tiny, name)
     raise AttributeError(f"module {__name__!r} has no attribute {name!r}")
 
 

@@ -131,6 +131,11 @@ SIGNATURES = {
     "cid_tiny_conv64_f16": (C.c_int, [c_half_p] * 5 + [C.c_int32] * 5 + [c_stream]),
     "cid_tiny_decode_in_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 3 + [c_stream]),
     "cid_tiny_decode_out_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 4 + [c_stream]),
+    "cid_tiny_conv64_s2_tile": (None, [C.POINTER(C.c_int32)] * 3),
+    "cid_tiny_conv64_s2_f16": (C.c_int, [c_half_p] * 3 + [C.c_int32] * 3 + [c_stream]),
+    "cid_tiny_encode_in_f16": (C.c_int, [C.c_void_p, C.c_int32, C.c_void_p, C.c_int32, c_half_p, c_half_p, c_half_p]
+                               + [C.c_int32] * 4 + [c_half_p, c_stream]),
+    "cid_tiny_encode_out_f16": (C.c_int, [c_half_p] * 4 + [C.c_int32] * 3 + [C.c_float, c_stream]),
     "cid_parse_stem_f16": (C.c_int, [C.c_void_p, c_half_p, C.c_void_p, C.c_void_p] + [C.c_int32] * 3 + [c_stream]),
     "cid_chan_mean_f16": (C.c_int, [c_half_p, C.c_void_p] + [C.c_int32] * 4 + [c_stream]),
     "cid_chan_gate_f32": (C.c_int, [C.c_void_p] * 6 + [C.c_int32] * 5 + [c_stream]),

@@ -15,7 +15,7 @@ void cid_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* cid_last_error(void) { return g_err; }
-extern "C" int cid_version(void) { return 112; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4, 104: cid_gemm_plan, 105: cid_cfg_multistep_step_f16, 106: cid_residual_accum_f16, 107: cid_clip_head_f16 / cid_blackout_f16, 108: cid_cfg_rescale_f16 / cid_cfg_*_step_scaled_f16, 109: cid_freeu_f16 (freeu.hip), 110: cid_id_xattn_long_f16 / cid_kv_pack_long_* (xattn_long.hip), 111: cid_multistep_step_f16, 112: cid_tiny_conv64_f16 / cid_tiny_decode_in_f16 / cid_tiny_decode_out_f16 (taesd.hip)
+extern "C" int cid_version(void) { return 113; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4, 104: cid_gemm_plan, 105: cid_cfg_multistep_step_f16, 106: cid_residual_accum_f16, 107: cid_clip_head_f16 / cid_blackout_f16, 108: cid_cfg_rescale_f16 / cid_cfg_*_step_scaled_f16, 109: cid_freeu_f16 (freeu.hip), 110: cid_id_xattn_long_f16 / cid_kv_pack_long_* (xattn_long.hip), 111: cid_multistep_step_f16, 112: cid_tiny_conv64_f16 / cid_tiny_decode_in_f16 / cid_tiny_decode_out_f16 (taesd.hip), 113: cid_tiny_encode_in_f16 / cid_tiny_conv64_s2_f16 / cid_tiny_encode_out_f16
 
 namespace {
 

@@ -8,9 +8,13 @@ sub-folder per component.  This module reads the components the hot path needs, 
     <root>/vae/config.json  + diffusion_pytorch_model.{safetensors,bin}     -> HipVAEDecoder (optional; + HipVAEEncoder for the
                                                                              inpaint pipelines when encoder.* weights are there);
                                                                              a config whose _class_name is AutoencoderTiny
-                                                                             -> HipAutoencoderTiny (decoder only)
+                                                                             -> HipAutoencoderTiny (the decoder; +
+                                                                             HipAutoencoderTinyEncoder for the inpaint
+                                                                             pipelines when encoder.* weights are there)
     <taesd dir>/config.json + diffusion_pytorch_model.{safetensors,bin}     -> HipAutoencoderTiny (load_tiny_vae: the local
-                                                                             AutoencoderTiny.from_pretrained(path))
+                                                                             AutoencoderTiny.from_pretrained(path)) and
+                                                                             HipAutoencoderTinyEncoder (load_tiny_vae_encoder:
+                                                                             its encode half, for pipe.vae_encoder)
     <controlnet dir>/config.json + diffusion_pytorch_model.{safetensors,bin} -> HipControlNet (separate call, like the
                                                                                 reference: demo/controlnet_demo.py:44-47)
     <root>/text_encoder{,_2}/config.json + model{.fp16,}.safetensors | pytorch_model{.fp16,}.bin
@@ -175,6 +179,21 @@ def load_tiny_vae(folder: Union[str, os.PathLike], device="cuda:0"):
         raise NotImplementedError(f"{os.fspath(folder)}: _class_name={cfg['_class_name']!r} is not AutoencoderTiny "
                                   "(load_vae reads AutoencoderKL folders)")
     return HipAutoencoderTiny(cfg, sd, device=device)
+
+
+def load_tiny_vae_encoder(folder: Union[str, os.PathLike], device="cuda:0"):
+    """The encode half of the same stand-alone TAESD / taesdxl folder -> HipAutoencoderTinyEncoder, for
+    ``pipe.vae_encoder = load_tiny_vae_encoder(path)`` on the inpaint pipelines (beside ``pipe.vae = load_tiny_vae(path)`` or
+    a KL decoder: they share a latent space).  Hub ids are not resolved."""
+    from .vae_tiny import HipAutoencoderTinyEncoder
+    cfg, sd = read_component(folder)
+    if cfg.get("_class_name", "AutoencoderTiny") != "AutoencoderTiny":
+        raise NotImplementedError(f"{os.fspath(folder)}: _class_name={cfg['_class_name']!r} is not AutoencoderTiny "
+                                  "(load_vae_encoder reads AutoencoderKL folders)")
+    if not _has_encoder(sd):
+        raise NotImplementedError(f"{os.fspath(folder)}: the weights hold no encoder.* keys (a decoder-only AutoencoderTiny "
+                                  "export); load_tiny_vae reads its decoder")
+    return HipAutoencoderTinyEncoder(cfg, sd, device=device)
 
 
 def load_vae_encoder(root: Union[str, os.PathLike], device="cuda:0", subfolder: str = "vae"):
@@ -384,7 +403,9 @@ def from_pretrained(pipeline_cls, root: Union[str, os.PathLike], torch_dtype=tor
     checker is loaded when ``safety_checker/`` exists and the caller did not pass ``safety_checker=None``; the SDXL pipeline
     never has one (the reference's has none).  ``vae=`` takes a built decoder engine (``load_tiny_vae(path)`` for diffusers'
     ``vae=AutoencoderTiny.from_pretrained(...)``) in place of the ``vae/`` folder's decoder; the inpaint pipelines' encoder still
-    comes from that folder.  A ``vae/`` folder whose config names AutoencoderTiny is built as HipAutoencoderTiny."""
+    comes from that folder unless ``vae_encoder=`` gives a built one (HipVAEEncoder, or ``load_tiny_vae_encoder(path)``).  A
+    ``vae/`` folder whose config names AutoencoderTiny is built as HipAutoencoderTiny, and for the two inpaint pipelines its
+    ``encoder.*`` weights (when there) as HipAutoencoderTinyEncoder."""
     if torch_dtype not in (torch.float16, None):
         raise NotImplementedError("the engine computes in fp16 (the reference's own inference dtype, infer.py:19)")
     # diffusers loader keywords the reference scripts pass (infer.py:17-21 variant="fp16"; demo/controlnet_demo.py
@@ -399,6 +420,11 @@ def from_pretrained(pipeline_cls, root: Union[str, os.PathLike], torch_dtype=tor
     if vae_given and (vae is None or not hasattr(vae, "decode_latents")):
         raise TypeError(f"from_pretrained: vae= takes a built decoder engine (HipVAEDecoder, HipVAEDecoderF32, "
                         f"HipAutoencoderTiny), got {type(vae).__name__}")
+    enc_given = "vae_encoder" in kw
+    vae_encoder = kw.pop("vae_encoder", None)      # a built encoder (HipVAEEncoder / HipAutoencoderTinyEncoder), like vae=
+    if enc_given and (vae_encoder is None or not hasattr(vae_encoder, "encode_inpaint")):
+        raise TypeError(f"from_pretrained: vae_encoder= takes a built encoder engine (HipVAEEncoder, "
+                        f"HipAutoencoderTinyEncoder), got {type(vae_encoder).__name__}")
     unknown = [k for k in kw if k not in ("scheduler", "num_tokens", "lora_rank") + TEXT_COMPONENTS]
     if unknown:
         raise TypeError(f"from_pretrained: unexpected keyword(s) {unknown}")
@@ -406,17 +432,20 @@ def from_pretrained(pipeline_cls, root: Union[str, os.PathLike], torch_dtype=tor
     if not os.path.isdir(root):
         raise FileNotFoundError(f"{root}: local diffusers model directory expected (no hub access)")
     unet = load_unet(root, device=device)
-    vae_encoder = None
     if os.path.isdir(os.path.join(root, "vae")):
         from .pipeline import StableDiffusionInpaintConsistentIDPipeline
         from .vae import HipVAEEncoder
         vcfg, vsd = read_component(os.path.join(root, "vae"))
         if not vae_given:                 # a given vae= replaces the folder's DECODER only
             vae = _make_decoder(vcfg, vsd, device)
-        # the encoder only for the two inpaint pipelines (their image= / mask_image= pre-loop), and only if the weights are
-        # there; an AutoencoderTiny folder brings none (its encoder is not built)
-        if issubclass(pipeline_cls, StableDiffusionInpaintConsistentIDPipeline) and not is_tiny_vae(vcfg) and _has_encoder(vsd):
-            vae_encoder = HipVAEEncoder(vae_config_from_diffusers(vcfg), vsd, device=device)
+        # the encoder only for the two inpaint pipelines (their image= / mask_image= pre-loop), only if the weights are there
+        # and no built one was given; by the config's _class_name like the decoder
+        if (issubclass(pipeline_cls, StableDiffusionInpaintConsistentIDPipeline) and not enc_given and _has_encoder(vsd)):
+            if is_tiny_vae(vcfg):
+                from .vae_tiny import HipAutoencoderTinyEncoder
+                vae_encoder = HipAutoencoderTinyEncoder(vcfg, vsd, device=device)
+            else:
+                vae_encoder = HipVAEEncoder(vae_config_from_diffusers(vcfg), vsd, device=device)
     text = read_text_components(root, device=device, given={k: kw.pop(k) for k in TEXT_COMPONENTS if k in kw})
     args = dict(use_graph=use_graph, vae=vae, **kw, **{k: v for k, v in text.items() if v is not None})
     from .pipeline import ConsistentIDStableDiffusionXLPipeline

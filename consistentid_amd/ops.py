@@ -702,11 +702,11 @@ def vae_encode_out(x: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: to
 
 
 # --------------------------------------------------------------------------- AutoencoderTiny decoder (csrc/taesd.hip)
-def _req_shape(t: torch.Tensor, name: str, shape):
+def _req_shape(t: torch.Tensor, name: str, shape, dtype=torch.float16):
     """dtype, the exact shape and contiguity of one operand (host-side facts: every operand is held to them first, then
     ``_req`` tests device and alignment)"""
-    if t.dtype != torch.float16:
-        raise _lib.CidError(f"{name}: expected {torch.float16}, got {t.dtype}")
+    if t.dtype != dtype:
+        raise _lib.CidError(f"{name}: expected {dtype}, got {t.dtype}")
     if tuple(t.shape) != tuple(shape):
         raise _lib.CidError(f"{name}: expected shape {tuple(shape)}, got {tuple(t.shape)}")
     if not t.is_contiguous():
@@ -776,6 +776,89 @@ def tiny_decode_out(x: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: t
         _req(t, f"tiny_decode_out.{name}")
     check(lib.cid_tiny_decode_out_f16(_p(x), _p(out), _p(w), _p(bias), B, H, W, int(bool(clamp01)), _stream()),
           "cid_tiny_decode_out_f16")
+    return out
+
+
+# --------------------------------------------------------------------------- AutoencoderTiny encoder (csrc/taesd.hip)
+def tiny_conv64_s2_tile():
+    """(tile_h, tile_w, grid_cap) of cid_tiny_conv64_s2_f16: its output tile and the most workgroups a launch has"""
+    v = [C.c_int32() for _ in range(3)]
+    _lib.load().cid_tiny_conv64_s2_tile(*(C.byref(i) for i in v))
+    return tuple(i.value for i in v)
+
+
+def tiny_conv64_s2(x: torch.Tensor, out: torch.Tensor, w: torch.Tensor, *, B: int, H: int, W: int):
+    """AutoencoderTiny's stride-2, pad-1, bias-less 64 -> 64 convolution (cid_tiny_conv64_s2_f16): ``x`` token-major
+    [B, H * W, 64] -> ``out`` [B, ceil(H / 2) * ceil(W / 2), 64]; ``w`` [64, 9, 64] = [cout, tap, cin]."""
+    lib = _lib.load()
+    _req_shape(x, "tiny_conv64_s2.x", (B, H * W, 64))
+    _req_shape(out, "tiny_conv64_s2.out", (B, ((H + 1) // 2) * ((W + 1) // 2), 64))
+    _req_shape(w, "tiny_conv64_s2.w", (64, 9, 64))
+    for name, t in (("x", x), ("out", out), ("w", w)):
+        _req(t, f"tiny_conv64_s2.{name}")
+    check(lib.cid_tiny_conv64_s2_f16(_p(x), _p(out), _p(w), B, H, W, _stream()), "cid_tiny_conv64_s2_f16")
+    return out
+
+
+def tiny_encode_in(image: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *,
+                   mask: Optional[torch.Tensor] = None, normalize: bool = False, blocks: int = 1,
+                   mask_latents: Optional[torch.Tensor] = None):
+    """AutoencoderTiny's encoder head with the inpaint pre-processing folded in (cid_tiny_encode_in_f16): ``image`` fp32
+    [Bi, 3, H, W], ``mask`` fp32 [Bm, 1, H, W] (Bm in {1, Bi}) or None; ``blocks`` bit 0 = the image, bit 1 = image *
+    (mask < 0.5); ``out`` token-major [nblk * Bi, H * W, 64] = conv(half(v + 1) / 2) + bias; ``w`` [64, 9, 3];
+    ``mask_latents`` fp16 [Bm, 1, H / 8, W / 8] or None."""
+    lib = _lib.load()
+    if image.dim() != 4 or image.shape[1] != 3:
+        raise _lib.CidError(f"tiny_encode_in.image: expected [B, 3, H, W], got {tuple(image.shape)}")
+    _req_shape(image, "tiny_encode_in.image", image.shape, torch.float32)
+    Bi, _, H, W = image.shape
+    if blocks not in (1, 2, 3):
+        raise _lib.CidError(f"tiny_encode_in.blocks: 1 (image), 2 (masked image) or 3 (both), got {blocks!r}")
+    _req_shape(out, "tiny_encode_in.out", (Bi * (2 if blocks == 3 else 1), H * W, 64))
+    _req_shape(w, "tiny_encode_in.w", (64, 9, 3))
+    _req_shape(bias, "tiny_encode_in.bias", (64,))
+    if mask is not None:
+        if mask.dim() != 4 or mask.shape[0] not in (1, Bi) or tuple(mask.shape[1:]) != (1, H, W):
+            raise _lib.CidError(f"tiny_encode_in.mask: expected [1 or {Bi}, 1, {H}, {W}], got {tuple(mask.shape)}")
+        _req_shape(mask, "tiny_encode_in.mask", mask.shape, torch.float32)
+    elif blocks & 2 or mask_latents is not None:
+        raise _lib.CidError("tiny_encode_in.mask: the masked image and mask_latents need a mask")
+    if mask_latents is not None:
+        if H % 8 or W % 8:
+            raise _lib.CidError(f"tiny_encode_in.mask_latents: H and W must be multiples of 8 (got {H} x {W})")
+        _req_shape(mask_latents, "tiny_encode_in.mask_latents", (mask.shape[0], 1, H // 8, W // 8))
+    if not image.is_cuda:   # (the fp32 NCHW planes need no alignment)
+        raise _lib.CidError(f"tiny_encode_in.image: tensor must live on the GPU (got {image.device}); libcid has no CPU path")
+    if mask is not None and not mask.is_cuda:
+        raise _lib.CidError(f"tiny_encode_in.mask: tensor must live on the GPU (got {mask.device}); libcid has no CPU path")
+    if mask_latents is not None and not mask_latents.is_cuda:
+        raise _lib.CidError(f"tiny_encode_in.mask_latents: tensor must live on the GPU (got {mask_latents.device}); "
+                            "libcid has no CPU path")
+    for name, t in (("out", out), ("w", w), ("bias", bias)):
+        _req(t, f"tiny_encode_in.{name}")
+    check(lib.cid_tiny_encode_in_f16(_p(image), Bi, _p(mask), mask.shape[0] if mask is not None else 0, _p(out), _p(w),
+                                     _p(bias), H, W, int(bool(normalize)), blocks, _p(mask_latents), _stream()),
+          "cid_tiny_encode_in_f16")
+    return out
+
+
+def tiny_encode_out(x: torch.Tensor, out: torch.Tensor, w: torch.Tensor, bias: torch.Tensor, *, scale: float = 1.0):
+    """AutoencoderTiny's encoder tail (cid_tiny_encode_out_f16): ``x`` token-major [B, H * W, 64] -> ``out`` NCHW [B, 4, H, W]
+    = (conv + bias) * scale; ``w`` [4, 9, 64]."""
+    lib = _lib.load()
+    if out.dim() != 4 or out.shape[1] != 4:
+        raise _lib.CidError(f"tiny_encode_out.out: expected [B, 4, H, W], got {tuple(out.shape)}")
+    _req_shape(out, "tiny_encode_out.out", out.shape)
+    B, _, H, W = out.shape
+    _req_shape(x, "tiny_encode_out.x", (B, H * W, 64))
+    _req_shape(w, "tiny_encode_out.w", (4, 9, 64))
+    _req_shape(bias, "tiny_encode_out.bias", (4,))
+    if not out.is_cuda:     # (the NCHW planes need no alignment)
+        raise _lib.CidError(f"tiny_encode_out.out: tensor must live on the GPU (got {out.device}); libcid has no CPU path")
+    for name, t in (("x", x), ("w", w), ("bias", bias)):
+        _req(t, f"tiny_encode_out.{name}")
+    check(lib.cid_tiny_encode_out_f16(_p(x), _p(out), _p(w), _p(bias), B, H, W, float(scale), _stream()),
+          "cid_tiny_encode_out_f16")
     return out
 
 

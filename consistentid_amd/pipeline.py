@@ -86,8 +86,9 @@ class _BasePipeline:
                  num_tokens: int = 4, lora_rank: int = 128, vae=None, vae_encoder=None, text_encoder=None, tokenizer=None,
                  text_encoder_2=None, tokenizer_2=None, safety_checker=None, feature_extractor=None):
         """``vae``: a ``consistentid_amd.vae.HipVAEDecoder`` -- enables every ``output_type`` besides "latent".
-        ``vae_encoder``: a ``consistentid_amd.vae.HipVAEEncoder`` -- lets the inpaint pipelines take ``image=`` and
-        ``mask_image=`` (the reference's pre-loop VAE encode) instead of pre-computed latents.
+        ``vae_encoder``: a ``consistentid_amd.vae.HipVAEEncoder`` or a ``consistentid_amd.vae_tiny.HipAutoencoderTinyEncoder``
+        (anything with their ``encode_inpaint``) -- lets the inpaint pipelines take ``image=`` and ``mask_image=`` (the
+        reference's pre-loop VAE encode) instead of pre-computed latents.  Either encoder stands beside either decoder.
         ``text_encoder`` / ``text_encoder_2``: ``consistentid_amd.clip_text.HipCLIPTextModel`` (CLIP-L; SDXL's bigG with
         projection), ``tokenizer`` / ``tokenizer_2``: ``transformers.CLIPTokenizer`` -- let ``encode_prompt`` take strings.
         ``safety_checker``: a ``consistentid_amd.safety.HipSafetyChecker`` (or any callable with diffusers' ``(images=,
@@ -828,7 +829,8 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                                       "[B, 3, H, W] and mask_image [B, 1, H, W]; numpy arrays are not taken")
         if self.vae_encoder is None:
             raise ValueError("image= / mask_image= need a VAE encoder: build the pipeline with vae_encoder=HipVAEEncoder(...) "
-                             "(from_pretrained does when vae/ holds encoder weights)")
+                             "or HipAutoencoderTinyEncoder(...), or set pipe.vae_encoder (from_pretrained builds one when "
+                             "vae/ holds encoder weights)")
         enc = self.vae_encoder
         img = image.unsqueeze(0) if image.dim() == 3 else image
         msk = mask_image

@@ -27,7 +27,7 @@ extern "C" {
 typedef void* cid_stream_t;      /* hipStream_t */
 typedef uint16_t cid_half;       /* IEEE binary16 bit pattern */
 
-int cid_version(void);          /* 112: cid_tiny_conv64_f16, cid_tiny_decode_in_f16, cid_tiny_decode_out_f16, cid_tiny_conv64_tile added (AutoencoderTiny decoder).  111: cid_multistep_step_f16 added.  110: cid_id_xattn_long_f16, cid_kv_pack_long_f16, cid_kv_pack_long_elems, cid_xattn_long_max_txt added (contexts beyond 96 keys).  109: cid_freeu_f16, cid_freeu_ws_bytes added.  108: cid_cfg_rescale_f16, cid_cfg_ddim_step_scaled_f16, cid_cfg_multistep_step_scaled_f16 added.  107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
+int cid_version(void);          /* 113: cid_tiny_encode_in_f16, cid_tiny_conv64_s2_f16, cid_tiny_conv64_s2_tile, cid_tiny_encode_out_f16 added (AutoencoderTiny encoder).  112: cid_tiny_conv64_f16, cid_tiny_decode_in_f16, cid_tiny_decode_out_f16, cid_tiny_conv64_tile added (AutoencoderTiny decoder).  111: cid_multistep_step_f16 added.  110: cid_id_xattn_long_f16, cid_kv_pack_long_f16, cid_kv_pack_long_elems, cid_xattn_long_max_txt added (contexts beyond 96 keys).  109: cid_freeu_f16, cid_freeu_ws_bytes added.  108: cid_cfg_rescale_f16, cid_cfg_ddim_step_scaled_f16, cid_cfg_multistep_step_scaled_f16 added.  107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
                                  * pointer (102: act, 101: pad_mode; set them or zero the struct) */
 const char* cid_last_error(void);
 
@@ -476,6 +476,34 @@ int cid_tiny_decode_in_f16(const cid_half* z, cid_half* out, const cid_half* w, 
                            int32_t W, cid_stream_t stream);
 int cid_tiny_decode_out_f16(const cid_half* x, cid_half* out, const cid_half* w, const cid_half* bias, int32_t B, int32_t H,
                             int32_t W, int32_t mode, cid_stream_t stream);
+
+/* ---------------------------------------------------------------------------
+ * AutoencoderTiny encoder (csrc/taesd.hip, since cid_version() 113).  D: diffusers 0.23 AutoencoderTiny.encode ->
+ * vae.EncoderTiny: `x.add(1).div(2)`, conv 3 -> 64 (no activation), then per level a stride-2 bias-less conv (from the second
+ * level on) and AutoencoderTinyBlock x n, conv 64 -> 4.  The Blocks are cid_tiny_conv64_f16 launches; the three entries below
+ * are the rest.  fp32 accumulation, one rounding to fp16 at the store, weights [cout][9][cin] (tap = 3 ky + kx),
+ * deterministic, any H, W >= 1.
+ * cid_tiny_encode_in_f16: the arguments of cid_vae_encode_in_f16 (image fp32 NCHW [Bi][3][H][W]; mask fp32 [Bm][1][H][W], Bm in
+ *   {1, Bi}, or NULL; blocks bit 0 = the image, bit 1 = the masked image; out token-major [nblk * Bi][H * W][64], the image
+ *   block first; mask_latents fp16 [Bm][1][H / 8][W / 8] = the binarised mask at every 8th pixel, or NULL -- only with H and W
+ *   multiples of 8).  Per pixel, in this order: v = half(normalize ? 2x - 1 : x); the masked image is v * (mask < 0.5);
+ *   u = half(v + 1) / 2 (one fp16 rounding, of v + 1); conv 3 -> 64 + bias over u with ZERO padding of u (a tap outside the
+ *   image is 0 in [0, 1] space, i.e. -1 in image space; a masked pixel is u = 0.5); no activation.  w [64][9][3], bias [64].
+ * cid_tiny_conv64_s2_f16: the stride-2, pad-1, bias-less 64 -> 64 convolution.  x token-major [B][Hi * Wi][64]; out token-major
+ *   [B][Ho * Wo][64] with Ho = ceil(Hi / 2), Wo = ceil(Wi / 2); output (y, x) reads input (2y - 1 + dy, 2x - 1 + dx), zeros
+ *   outside on all four sides (NOT cid_gemm_desc.pad_mode 1).  Weight-stationary like cid_tiny_conv64_f16: one workgroup owns
+ *   an output tile of tile_h x tile_w pixels (cid_tiny_conv64_s2_tile), at most grid_cap workgroups loop over the tiles.
+ *   Refused (-22): a NULL or misaligned pointer, B, Hi or Wi <= 0, out == x, B * Hi * Wi * 64 >= 2^32 - 2 input elements.
+ * cid_tiny_encode_out_f16: x token-major [B][H * W][64] -> (conv(x) + bias) * scale (w [4][9][64], bias [4]), out NCHW fp16
+ *   [B][4][H][W]; scale = the config's scaling_factor (1.0 for what AutoencoderTiny.encode returns). */
+void cid_tiny_conv64_s2_tile(int32_t* tile_h, int32_t* tile_w, int32_t* grid_cap);  /* host query; any pointer may be NULL */
+int cid_tiny_conv64_s2_f16(const cid_half* x, cid_half* out, const cid_half* w, int32_t B, int32_t Hi, int32_t Wi,
+                           cid_stream_t stream);
+int cid_tiny_encode_in_f16(const float* image, int32_t Bi, const float* mask, int32_t Bm, cid_half* out, const cid_half* w,
+                           const cid_half* bias, int32_t H, int32_t W, int32_t normalize, int32_t blocks,
+                           cid_half* mask_latents, cid_stream_t stream);
+int cid_tiny_encode_out_f16(const cid_half* x, cid_half* out, const cid_half* w, const cid_half* bias, int32_t B, int32_t H,
+                            int32_t W, float scale, cid_stream_t stream);
 
 /* ---------------------------------------------------------------------------
  * Face parser (csrc/parsing.hip): BiSeNet (models/BiSeNet/model.py:230-254, resnet.py:58-80) as the reference runs it, once
