@@ -156,6 +156,13 @@ SIGNATURES = {
     "cid_cfg_multistep_step_scaled_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, c_half_p, c_half_p, C.c_int32, C.c_void_p,
                                                     C.c_float, c_half_p, c_half_p, c_half_p, C.c_int32, C.c_int32, C.c_void_p,
                                                     c_stream]),
+    "cid_cfg_pag_ddim_step_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, C.c_float, C.c_void_p, c_half_p, c_half_p,
+                                            c_half_p, C.c_int32, C.c_int32, c_stream]),
+    "cid_cfg_pag_multistep_step_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, c_half_p, c_half_p, C.c_int32, C.c_void_p,
+                                                 C.c_float, C.c_void_p, c_half_p, c_half_p, c_half_p, C.c_int32, C.c_int32,
+                                                 c_stream]),
+    "cid_pag_multistep_step_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, c_half_p, c_half_p, C.c_int32, C.c_void_p,
+                                             C.c_void_p, c_half_p, c_half_p, c_half_p, C.c_int32, C.c_int32, c_stream]),
     "cid_freeu_ws_bytes": (C.c_int64, [C.c_int32] * 4),
     "cid_freeu_f16": (C.c_int, [c_half_p, C.c_int32, C.c_float, c_half_p, c_half_p, C.c_int32, C.c_float]
                       + [C.c_int32] * 3 + [C.c_void_p, c_stream]),

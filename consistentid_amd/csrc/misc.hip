@@ -15,7 +15,7 @@ void cid_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* cid_last_error(void) { return g_err; }
-extern "C" int cid_version(void) { return 113; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4, 104: cid_gemm_plan, 105: cid_cfg_multistep_step_f16, 106: cid_residual_accum_f16, 107: cid_clip_head_f16 / cid_blackout_f16, 108: cid_cfg_rescale_f16 / cid_cfg_*_step_scaled_f16, 109: cid_freeu_f16 (freeu.hip), 110: cid_id_xattn_long_f16 / cid_kv_pack_long_* (xattn_long.hip), 111: cid_multistep_step_f16, 112: cid_tiny_conv64_f16 / cid_tiny_decode_in_f16 / cid_tiny_decode_out_f16 (taesd.hip), 113: cid_tiny_encode_in_f16 / cid_tiny_conv64_s2_f16 / cid_tiny_encode_out_f16
+extern "C" int cid_version(void) { return 114; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4, 104: cid_gemm_plan, 105: cid_cfg_multistep_step_f16, 106: cid_residual_accum_f16, 107: cid_clip_head_f16 / cid_blackout_f16, 108: cid_cfg_rescale_f16 / cid_cfg_*_step_scaled_f16, 109: cid_freeu_f16 (freeu.hip), 110: cid_id_xattn_long_f16 / cid_kv_pack_long_* (xattn_long.hip), 111: cid_multistep_step_f16, 112: cid_tiny_conv64_f16 / cid_tiny_decode_in_f16 / cid_tiny_decode_out_f16 (taesd.hip), 113: cid_tiny_encode_in_f16 / cid_tiny_conv64_s2_f16 / cid_tiny_encode_out_f16, 114: cid_cfg_pag_ddim_step_f16 / cid_cfg_pag_multistep_step_f16 / cid_pag_multistep_step_f16 (perturbed-attention guidance)
 
 namespace {
 
@@ -466,16 +466,26 @@ linear_small_kernel(const half_t* __restrict__ x, int ldx, const half_t* __restr
 // SCALED (the *_scaled_f16 entries, guidance_rescale): e is multiplied by escale[sample], the factor cfg_rescale_kernel wrote;
 // per_sample % 8 == 0 there, so an 8-half item lies inside one sample.  The trailing two arguments are not read without it:
 // the unscaled instantiation is the kernel as it was.
-template <bool SCALED>
+// PAG (the cid_*pag*_step_f16 entries, perturbed-attention guidance): eps holds one more block of rows, the perturbed
+// prediction p, behind the conditional one, and e += s (c - p) with s = pag[0], a DEVICE value (a step-table column).  The
+// branch on s != 0 is uniform over the grid: at s == 0 the perturbed rows are never addressed (they may hold NaN, and
+// 0 * NaN is NaN) and e is the sibling's expression.  pag is not read without PAG: those instantiations are the kernels as they were.
+template <bool SCALED, bool PAG = false>
 __global__ void __launch_bounds__(256)
 cfg_ddim_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, const float* __restrict__ coef,
                 float g, const half_t* __restrict__ mask, const half_t* __restrict__ init,
                 const half_t* __restrict__ noise, long n /* B * per_sample, multiple of 8 */,
-                const float* __restrict__ escale, int sample_items /* 8-half items per sample */) {
+                const float* __restrict__ escale, int sample_items /* 8-half items per sample */,
+                const float* __restrict__ pag /* PAG only: one DEVICE value */) {
+    float s = 0.f;
+    if constexpr (PAG) s = pag[0];
+    const bool perturbed = PAG && s != 0.f;
     const float cx = coef[0], ce = coef[1];
     const float ci = mask ? coef[2] : 0.f, cn = mask ? coef[3] : 0.f;
     for (long q = ((long)blockIdx.x * 256 + threadIdx.x) * 8; q < n; q += (long)gridDim.x * 256 * 8) {
         const half8 eu = ld_global_h8(eps + q), ec = ld_global_h8(eps + n + q), xl = ld_global_h8(lat + q);
+        half8 ep;
+        if constexpr (PAG) { if (perturbed) ep = ld_global_h8(eps + 2 * n + q); }
         half8 mk, in0, nz;
         if (mask) { mk = ld_global_h8(mask + q); in0 = ld_global_h8(init + q); nz = ld_global_h8(noise + q); }
         float es = 1.f;
@@ -485,6 +495,7 @@ cfg_ddim_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, const 
         for (int i = 0; i < 8; ++i) {
             const float u = (float)eu[i], c = (float)ec[i];
             float e = u + g * (c - u);
+            if constexpr (PAG) { if (perturbed) e += s * (c - (float)ep[i]); }
             if constexpr (SCALED) e *= es;
             float v = cx * (float)xl[i] + ce * e;
             if (mask) {
@@ -503,12 +514,18 @@ cfg_ddim_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, const 
 // row gives them a non-zero coefficient (wave-uniform branches): an unwritten buffer may hold NaN, and 0 * NaN is NaN.
 // CFG = false (cid_multistep_step_f16, the single pass): eps holds ONE model output per sample, [B][per_sample], and e is that
 // value -- no second half is loaded (eps + n is past the end of the buffer) and g is not read.
-template <bool SCALED, bool CFG = true>      // SCALED as cfg_ddim_kernel's
+// PAG as cfg_ddim_kernel's: the perturbed rows follow the conditional ones -- [3B] rows with CFG, [2B] without, where
+// e = c + s (c - p).
+template <bool SCALED, bool CFG = true, bool PAG = false>      // SCALED, PAG as cfg_ddim_kernel's
 __global__ void __launch_bounds__(256)
 cfg_multistep_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, float* hist, half_t* saved,
                      const half_t* __restrict__ z, int z_rows, const float* __restrict__ row, float g,
                      const half_t* __restrict__ mask, const half_t* __restrict__ init, const half_t* __restrict__ noise,
-                     long n /* B * per_sample, multiple of 8 */, const float* __restrict__ escale, int sample_items /* 8-half items per sample */) {
+                     long n /* B * per_sample, multiple of 8 */, const float* __restrict__ escale, int sample_items /* 8-half items per sample */,
+                     const float* __restrict__ pag /* PAG only: one DEVICE value */) {
+    float s = 0.f;
+    if constexpr (PAG) s = pag[0];
+    const bool perturbed = PAG && s != 0.f;
     const float a = row[0], b = row[1], cx = row[2], cm = row[3], cz = z ? row[11] : 0.f;
     const float ch[4] = {row[4], row[5], row[6], row[7]};
     const float ci = mask ? row[9] : 0.f, cn = mask ? row[10] : 0.f;
@@ -520,6 +537,8 @@ cfg_multistep_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, f
         const half8 eu = ld_global_h8(eps + q);
         half8 ec;
         if constexpr (CFG) ec = ld_global_h8(eps + n + q);
+        half8 ep;
+        if constexpr (PAG) { if (perturbed) ep = ld_global_h8(eps + (CFG ? 2 : 1) * n + q); }
         const half8 xl = ld_global_h8(lat + q);
         const half8 src = restore ? ld_global_h8(saved + q) : xl;
         float es = 1.f;
@@ -530,6 +549,7 @@ cfg_multistep_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, f
             const float u = (float)eu[i];
             float e = u;
             if constexpr (CFG) { const float c = (float)ec[i]; e = u + g * (c - u); }
+            if constexpr (PAG) { if (perturbed) e += s * ((CFG ? (float)ec[i] : u) - (float)ep[i]); }
             if constexpr (SCALED) e *= es;
             if constexpr (CFG) m[i] = a * (float)xl[i] + b * e;
             else m[i] = __builtin_fmaf(a, (float)xl[i], b * e);     // the contraction the CFG instantiations compile to: the same bits on equal halves
@@ -885,7 +905,7 @@ extern "C" int cid_cfg_ddim_step_f16(const cid_half* eps, cid_half* latents, con
     CID_CHECK_ARG(B > 0 && per_sample > 0 && n % 8 == 0, "cid_cfg_ddim_step_f16: B * per_sample must be a multiple of 8");
     hipLaunchKernelGGL(cfg_ddim_kernel<false>, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)eps, (half_t*)latents, coef, guidance, (const half_t*)mask, (const half_t*)init,
-                       (const half_t*)noise, n, (const float*)nullptr, 0);
+                       (const half_t*)noise, n, (const float*)nullptr, 0, (const float*)nullptr);
     CID_CHECK_LAUNCH("cid_cfg_ddim_step_f16");
     return 0;
 }
@@ -902,7 +922,7 @@ extern "C" int cid_cfg_ddim_step_scaled_f16(const cid_half* eps, cid_half* laten
     CID_CHECK_ARG(n / 8 <= 0x7fffffffL, "cid_cfg_ddim_step_scaled_f16: B * per_sample must be below 2^34");
     hipLaunchKernelGGL(cfg_ddim_kernel<true>, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)eps, (half_t*)latents, coef, guidance, (const half_t*)mask, (const half_t*)init,
-                       (const half_t*)noise, n, escale, (int)(per_sample / 8));
+                       (const half_t*)noise, n, escale, (int)(per_sample / 8), (const float*)nullptr);
     CID_CHECK_LAUNCH("cid_cfg_ddim_step_scaled_f16");
     return 0;
 }
@@ -935,7 +955,7 @@ extern "C" int cid_cfg_multistep_step_f16(const cid_half* eps, cid_half* latents
     hipLaunchKernelGGL(cfg_multistep_kernel<false>, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z, (int)z_rows,
                        (const float*)row, guidance, (const half_t*)mask, (const half_t*)init, (const half_t*)noise, n,
-                       (const float*)nullptr, 0);
+                       (const float*)nullptr, 0, (const float*)nullptr);
     CID_CHECK_LAUNCH("cid_cfg_multistep_step_f16");
     return 0;
 }
@@ -956,7 +976,7 @@ extern "C" int cid_multistep_step_f16(const cid_half* eps, cid_half* latents, fl
     hipLaunchKernelGGL((cfg_multistep_kernel<false, false>), dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z, (int)z_rows,
                        (const float*)row, 0.f, (const half_t*)mask, (const half_t*)init, (const half_t*)noise, n,
-                       (const float*)nullptr, 0);
+                       (const float*)nullptr, 0, (const float*)nullptr);
     CID_CHECK_LAUNCH("cid_multistep_step_f16");
     return 0;
 }
@@ -977,10 +997,65 @@ extern "C" int cid_cfg_multistep_step_scaled_f16(const cid_half* eps, cid_half* 
     hipLaunchKernelGGL(cfg_multistep_kernel<true>, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z, (int)z_rows,
                        (const float*)row, guidance, (const half_t*)mask, (const half_t*)init, (const half_t*)noise, n,
-                       escale, (int)(per_sample / 8));
+                       escale, (int)(per_sample / 8), (const float*)nullptr);
     CID_CHECK_LAUNCH("cid_cfg_multistep_step_scaled_f16");
     return 0;
 }
+
+// perturbed-attention guidance: the three step entries with a third (second, without CFG) block of eps rows; cid.h
+#define CID_PAG_STEP_CHECKS(NAME)                                                                                          \
+    CID_CHECK_ARG((mask == nullptr) == (init == nullptr) && (mask == nullptr) == (noise == nullptr),                      \
+                  NAME ": mask/init/noise must come together");                                                           \
+    const long n = (long)B * per_sample;                                                                                   \
+    CID_CHECK_ARG(B > 0 && per_sample > 0 && n % 8 == 0, NAME ": B * per_sample must be a multiple of 8")
+
+extern "C" int cid_cfg_pag_ddim_step_f16(const cid_half* eps, cid_half* latents, const float* coef, float guidance,
+                                         const float* pag, const cid_half* mask, const cid_half* init, const cid_half* noise,
+                                         int32_t B, int32_t per_sample, cid_stream_t stream) {
+    CID_CHECK_ARG(eps && latents && coef && pag, "cid_cfg_pag_ddim_step_f16: null pointer");
+    CID_PAG_STEP_CHECKS("cid_cfg_pag_ddim_step_f16");
+    hipLaunchKernelGGL((cfg_ddim_kernel<false, true>), dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)eps, (half_t*)latents, coef, guidance, (const half_t*)mask, (const half_t*)init,
+                       (const half_t*)noise, n, (const float*)nullptr, 0, pag);
+    CID_CHECK_LAUNCH("cid_cfg_pag_ddim_step_f16");
+    return 0;
+}
+
+#define CID_PAG_MULTISTEP_CHECKS(NAME)                                                                                     \
+    CID_CHECK_ARG(eps && latents && hist && saved && row && pag, NAME ": null pointer");                                  \
+    CID_CHECK_ARG((z == nullptr) == (z_rows == 0) && z_rows >= 0, NAME ": z and z_rows must come together");              \
+    CID_PAG_STEP_CHECKS(NAME)
+
+extern "C" int cid_cfg_pag_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
+                                              const cid_half* z, int32_t z_rows, const void* row, float guidance,
+                                              const float* pag, const cid_half* mask, const cid_half* init,
+                                              const cid_half* noise, int32_t B, int32_t per_sample, cid_stream_t stream) {
+    CID_PAG_MULTISTEP_CHECKS("cid_cfg_pag_multistep_step_f16");
+    hipLaunchKernelGGL((cfg_multistep_kernel<false, true, true>), dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0,
+                       (hipStream_t)stream, (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z,
+                       (int)z_rows, (const float*)row, guidance, (const half_t*)mask, (const half_t*)init,
+                       (const half_t*)noise, n, (const float*)nullptr, 0, pag);
+    CID_CHECK_LAUNCH("cid_cfg_pag_multistep_step_f16");
+    return 0;
+}
+
+extern "C" int cid_pag_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
+                                          const cid_half* z, int32_t z_rows, const void* row, const float* pag,
+                                          const cid_half* mask, const cid_half* init, const cid_half* noise,
+                                          int32_t B, int32_t per_sample, cid_stream_t stream) {
+    CID_PAG_MULTISTEP_CHECKS("cid_pag_multistep_step_f16");
+    for (const void* p : {(const void*)eps, (const void*)latents, (const void*)hist, (const void*)saved, (const void*)z,
+                          (const void*)row, (const void*)mask, (const void*)init, (const void*)noise})       // as cid_multistep_step_f16
+        CID_CHECK_ARG((uintptr_t)p % 16 == 0, "cid_pag_multistep_step_f16: every buffer must be 16-byte aligned");
+    hipLaunchKernelGGL((cfg_multistep_kernel<false, false, true>), dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0,
+                       (hipStream_t)stream, (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z,
+                       (int)z_rows, (const float*)row, 0.f, (const half_t*)mask, (const half_t*)init,
+                       (const half_t*)noise, n, (const float*)nullptr, 0, pag);
+    CID_CHECK_LAUNCH("cid_pag_multistep_step_f16");
+    return 0;
+}
+#undef CID_PAG_MULTISTEP_CHECKS
+#undef CID_PAG_STEP_CHECKS
 
 extern "C" int cid_add_inplace_f16(cid_half* y, const cid_half* a, int64_t n, int64_t na, cid_stream_t stream) {
     CID_CHECK_ARG(y && a && n > 0 && na > 0 && n % 8 == 0 && na % 8 == 0 && n % na == 0, "cid_add_inplace_f16: sizes must be multiples of 8");

@@ -7,6 +7,10 @@ The single pass: under ``LCMScheduler`` with ``guidance
 embedding) a step is [ControlNets + UNet(B) on the conditional rows + cid_multistep_step_f16]: no unconditional half and no
 CFG combine.  The four other schedulers launch what they always launched at every guidance value.
 
+Perturbed-attention guidance: with ``pag_scale`` > 0 the UNet runs B more rows, the perturbed twins of the
+conditional rows, and the step is the ``+pag`` entry of the same kernel with the step's scale read from the step table; with
+``pag_scale`` == 0 nothing here changes.
+
 ``DenoiseEngine.run`` is a driver over phases that take and return named values: the static-buffer pool, the graph
 cache, the step coefficients (``_StepCoefficients``), the ControlNet plan (``_ControlPlan``), the embed-row selectors
 (``step_rows``), what the step reads of objects the engine does not own (``captured_reads``), the step table and the
@@ -40,6 +44,24 @@ def check_guidance_rescale(guidance_rescale) -> float:
     return phi
 
 
+def check_pag(pag_scale, pag_adaptive_scale=0.0) -> tuple:
+    """``pag_scale`` / ``pag_adaptive_scale`` of diffusers' PAG pipelines -> two floats; negative or non-finite values (and
+    booleans, which are no scales) are refused"""
+    for name, v in (("pag_scale", pag_scale), ("pag_adaptive_scale", pag_adaptive_scale)):
+        if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0.0:
+            raise ValueError(f"{name} = {v!r}: a finite number >= 0 (0 = off)")
+    return float(pag_scale), float(pag_adaptive_scale)
+
+
+def pag_scale_column(pag_scale: float, pag_adaptive_scale: float, timesteps) -> np.ndarray:
+    """the PAG scale of every schedule entry, fp32 [n_ts] (diffusers' ``_get_pag_scale``): ``pag_scale`` itself without an
+    adaptive scale, else max(pag_scale - pag_adaptive_scale * (1000 - t_i), 0); taken in float64, rounded once"""
+    t = np.asarray(timesteps, dtype=np.float64)
+    if pag_adaptive_scale == 0.0:
+        return np.full(t.shape, pag_scale, dtype=np.float32)
+    return np.maximum(pag_scale - pag_adaptive_scale * (1000.0 - t), 0.0).astype(np.float32)
+
+
 def check_eta(scheduler, eta: float, variance_noise=None) -> float:
     """``eta`` / ``variance_noise`` of the reference ``__call__``s (prepare_extra_step_kwargs -> DDIMScheduler.step(eta=,
     variance_noise=)): only DDIM has the term, its eta is in [0, 1], and the noise needs a coefficient -- which
@@ -62,14 +84,16 @@ StepRows = namedtuple("StepRows", "unet controlnet merged")
 
 
 def step_rows(n_ts: int, first_step: int, start_merge_step: int, B: int, has_null_post: bool, device="cpu",
-              controlnet: bool = True, single_pass: bool = False) -> StepRows:
+              controlnet: bool = True, single_pass: bool = False, pag: bool = False) -> StepRows:
     """The embed sets every schedule entry reads (ref :542-549: text-only while i <= start_merge_step, i counted from
     ``first_step`` like the reference's enumerate over the truncated timestep list).  The UNet's K/V cache holds rows
     [0,B) null, [B,2B) text-only, [2B,3B) augmented (ref :527-531) and, for SDXL's second unconditional set (ref SDXL
     :586-590, :620-631), [3B,4B) null-post: a step selects (null, text) before the merge, (null or null-post, augmented)
     after it.  A ControlNet's cache holds [0,B) text-only and [B,2B) augmented, selected the same way (CN :389-396).
     ``single_pass``: the UNet runs the conditional rows only -- [n_ts, B], text-only [B,2B) up to the merge and augmented
-    [2B,3B) after it, in the same K/V row numbering."""
+    [2B,3B) after it, in the same K/V row numbering.
+    ``pag``: B more columns behind the others, the perturbed rows -- they read what the conditional rows read at every
+    entry: [n_ts, 3B], or [n_ts, 2B] in the single pass."""
     ar = torch.arange(B, dtype=torch.int32, device=device)
     merged = torch.tensor([(i - first_step) > start_merge_step for i in range(n_ts)], device=device)
     pre = torch.cat([ar, ar + B])
@@ -77,6 +101,8 @@ def step_rows(n_ts: int, first_step: int, start_merge_step: int, B: int, has_nul
     cn = torch.where(merged[:, None], (ar + B)[None], ar[None]) if controlnet else None
     if single_pass:
         pre, post = ar + B, ar + 2 * B
+    if pag:
+        pre, post = torch.cat([pre, ar + B]), torch.cat([post, ar + 2 * B])
     return StepRows(torch.where(merged[:, None], post[None], pre[None]), cn, merged)
 
 
@@ -106,8 +132,17 @@ class _StepCoefficients:
     escale: Optional[torch.Tensor] = None       # guidance_rescale: fp32 [B], the factor cid_cfg_rescale_f16 writes every step
     rescale: float = 0.0
     single_pass: bool = False
+    pag: Optional[torch.Tensor] = None          # PAG: fp32 [1], this step's scale s_i (a step-table column)
 
     def update(self, eps, lat, guidance_scale, **kw):
+        if self.pag is not None:                # eps carries the perturbed rows behind the conditional ones
+            if self.single_pass:
+                ops.pag_multistep_step(eps, lat, self.hist, self.saved, self.row, self.pag, z=self.z, **kw)
+            elif self.hist is None:
+                ops.cfg_pag_ddim_step(eps, lat, self.buf, guidance_scale, self.pag, **kw)
+            else:
+                ops.cfg_pag_multistep_step(eps, lat, self.hist, self.saved, self.row, guidance_scale, self.pag, z=self.z, **kw)
+            return
         if self.single_pass:                    # no CFG combine (and so no rescale of one)
             ops.multistep_step(eps, lat, self.hist, self.saved, self.row, z=self.z, **kw)
             return
@@ -150,7 +185,8 @@ class DenoiseEngine:
         self._config_key = None
         self.captures: List[Any] = []           # key of every capture this engine ever made, in order (re-captures show twice)
         self._static: Dict[str, torch.Tensor] = {}
-        # the step launch of the last run: "cfg_ddim" or "cfg_multistep", "+rescale" with guidance_rescale; "multistep" = the single pass
+        # the step launch of the last run: "cfg_ddim" or "cfg_multistep", "+rescale" with guidance_rescale; "multistep" = the
+        # single pass; "+pag" with perturbed-attention guidance ("cfg_ddim+pag", "cfg_multistep+pag", "multistep+pag")
         self.step_path: Optional[str] = None
 
     def invalidate(self):
@@ -264,8 +300,15 @@ class DenoiseEngine:
             control_guidance_end: Union[float, Sequence[float]] = 1.0,
             callback: Optional[Callable[[int, int, torch.Tensor], None]] = None, callback_steps: int = 1,
             scale_initial: bool = True, unet_extra: Optional[torch.Tensor] = None, eta: float = 0.0,
-            variance_noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0):
-        """``guidance_rescale`` > 0 with ``guidance_scale`` > 1 (diffusers' condition): every step runs UNet ->
+            variance_noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0, pag_scale: float = 0.0,
+            pag_adaptive_scale: float = 0.0):
+        """``pag_scale`` > 0: perturbed-attention guidance.  The UNet runs B more batch rows, the
+        perturbed evaluation of the conditional rows (same latents, time row, context rows and SDXL conditioning; identity
+        self-attention in the layers ``unet.enable_pag`` selected, the default ``("mid",)`` if none were), and the step is
+        e = u + g (c - u) + s_i (c - p) -- e = c + s_i (c - p) in the single pass -- with s_i = ``pag_scale``, or
+        max(pag_scale - ``pag_adaptive_scale`` * (1000 - t_i), 0), a step-table column.  Refused (NotImplementedError)
+        together with ``guidance_rescale`` > 0 and with a ControlNet or ControlNet residuals.  At 0 nothing changes.
+        ``guidance_rescale`` > 0 with ``guidance_scale`` > 1 (diffusers' condition): every step runs UNet ->
         cid_cfg_rescale_f16 (the per-sample factor, into a static buffer) -> the scaled step entry; at 0 the step is the
         one it always was.
         Under ``LCMScheduler`` ``guidance_scale`` <= 1 takes the single pass (module docstring): the UNet runs the B
@@ -284,6 +327,16 @@ class DenoiseEngine:
         unet, sch, S = self.unet, self.scheduler, self._static_tensor
         eta = check_eta(sch, eta, variance_noise)
         guidance_rescale = check_guidance_rescale(guidance_rescale)
+        pag_scale, pag_adaptive_scale = check_pag(pag_scale, pag_adaptive_scale)
+        pag = pag_scale > 0.0
+        if pag and guidance_rescale > 0.0:
+            raise NotImplementedError("pag_scale > 0 together with guidance_rescale > 0 is not built (the rescale factor is "
+                                      "defined on the classifier-free combine alone)")
+        if pag and (controlnet is not None or down_residuals is not None or mid_residual is not None):
+            raise NotImplementedError("PAG with ControlNet residuals is not built: pass pag_scale = 0 or run without a "
+                                      "ControlNet / precomputed residuals")
+        if pag and not unet.pag_layers:
+            unet.enable_pag()                   # diffusers' default pag_applied_layers
         dev, B = unet.device, latents.shape[0]
         lcm = isinstance(sch, LCMScheduler)
         embedded_guidance = getattr(unet.config, "time_cond_proj_dim", None) is not None
@@ -295,7 +348,7 @@ class DenoiseEngine:
             raise ValueError(f"guidance_rescale = {guidance_rescale}: a UNet with time_cond_proj_dim takes guidance_scale in its "
                              "time embedding; there is no classifier-free combine to rescale")
         single = lcm and (embedded_guidance or guidance_scale <= 1.0)
-        n_b = B if single else 2 * B            # the UNet's batch rows
+        n_b = (B if single else 2 * B) + (B if pag else 0)      # the UNet's batch rows: [uncond |] cond [| perturbed]
         sch.set_timesteps(num_inference_steps)                      # ref :510, before prepare_latents (:517)
         # prepare_latents (diffusers; ref :517-526) scales the initial noise by the scheduler's init_noise_sigma
         lat = S("lat", latents.to(dev).float() * (float(sch.init_noise_sigma) if scale_initial else 1.0), torch.float16)
@@ -312,16 +365,28 @@ class DenoiseEngine:
         if guidance_rescale > 0.0 and guidance_scale > 1.0 and not single:
             coef.escale, coef.rescale = S("escale", torch.ones(B), torch.float32), guidance_rescale
             self.step_path += "+rescale"
+        pag_column = None
+        if pag:
+            coef.pag = S("pag", torch.zeros(1), torch.float32)
+            pag_column = (coef.pag, torch.from_numpy(pag_scale_column(pag_scale, pag_adaptive_scale, sch.timesteps)).view(-1, 1))
+            self.step_path += "+pag"
         tvals = torch.tensor(ts.astype(np.float32), device=dev)
         rows = step_rows(n_ts, first_step, start_merge_step, B, null_embeds_post is not None, dev, controlnet is not None,
-                         single_pass=single)
+                         single_pass=single, pag=pag)
         t_buf = S("t", torch.zeros(1), torch.float32)
         kvrow = S("kvrow", rows.unet[0], torch.int32)
         added = None
         if time_ids is not None:
             p_null, p_text, p_aug = [p.to(device=dev, dtype=torch.float16) for p in pooled]
-            added = {"text_embeds": S("pooled", p_text if single else torch.cat([p_null, p_text], 0), torch.float16),
-                     "time_ids": S("time_ids", time_ids[-B:] if single else time_ids, torch.float32)}   # [2B, 6]: negative rows first
+            def stack(neg, pos):
+                """the UNet's batch rows of a per-row condition: [neg |] pos [| pos] -- no unconditional rows in the single
+                pass, and with PAG the perturbed rows repeat the conditional rows' values"""
+                return torch.cat(([] if single else [neg]) + [pos] * (2 if pag else 1), 0)
+            # time_ids is [2B, 6], negative rows first: the last B rows are the conditional ones (without PAG the two slices
+            # put together again are the tensor as it came, whatever its row count; the single pass keeps its last B rows)
+            tid = time_ids.to(dev)
+            added = {"text_embeds": S("pooled", stack(p_null, p_text), torch.float16),
+                     "time_ids": S("time_ids", stack(tid[:-B], tid[-B:]), torch.float32)}
         blend = dict(mask=None, init=None, noise=None)
         if inpaint:
             if unet_extra is not None:
@@ -357,9 +422,9 @@ class DenoiseEngine:
             cols.append((cn.kvrow, rows.controlnet))
         if temb_buf is not None:
             cols.append((temb_buf, temb_tab.view(n_ts, -1)))
-        cols += [c for c in (cn.temb_column, cn.scale_column) if c is not None]
+        cols += [c for c in (cn.temb_column, cn.scale_column, pag_column) if c is not None]
         if added is not None:
-            pre, post = (p_text, p_aug) if single else (torch.cat([p_null, p_text], 0), torch.cat([p_null, p_aug], 0))
+            pre, post = stack(p_null, p_text), stack(p_null, p_aug)
             cols.append((added["text_embeds"], torch.where(rows.merged[:, None, None], post[None], pre[None])))
         table = ops.StepTable(cols, dev, alloc=S)     # table + counter are static buffers too
         table.reset(first_step)
@@ -373,7 +438,7 @@ class DenoiseEngine:
             net.reserve_workspace(B)
         key = (captured_reads(unet, cn.nets), B, tuple(lat.shape), float(guidance_scale), inpaint, time_ids is not None,
                dres is not None, bool(cn.nets), ("multi", len(cn.nets)) if cn.scale_column else cn.fold, extra is not None,
-               coef.hist is not None, coef.z is not None, coef.rescale, single)
+               coef.hist is not None, coef.z is not None, coef.rescale, single, pag, n_b)
         if key != self._config_key:
             self.invalidate()
             self._config_key = key
@@ -393,7 +458,7 @@ class DenoiseEngine:
                 d, m = ([res[k][j] if k in res else None for k in range(len(cn.nets))] for j in (0, 1))
                 scales = cn.scale_column[0]
             eps = unet.forward_tokens(lat, t_buf, kvrow, n_b, added, d, m, temb=temb_buf, in_scale=coef.in_scale,
-                                      extra=extra, residual_scales=scales)
+                                      extra=extra, residual_scales=scales, pag_rows=B if pag else 0)
             coef.update(eps, lat, guidance_scale, B=B, per_sample=per_sample, **blend)
 
         for i in range(first_step, n_ts):

@@ -1063,6 +1063,90 @@ def multistep_step(eps: torch.Tensor, latents: torch.Tensor, hist: torch.Tensor,
     return latents
 
 
+def _req_pag(pag: torch.Tensor, what: str):
+    _req(pag, f"{what}.pag", torch.float32)
+    if pag.numel() != 1:
+        raise _lib.CidError(f"{what}.pag: {pag.numel()} elements; one DEVICE fp32 value (the step's PAG scale)")
+
+
+def _req_step_blend(what: str, n: int, mask, init, noise):
+    for name, t in (("mask", mask), ("init", init), ("noise", noise)):
+        if t is not None:
+            _req(t, f"{what}.{name}")
+            if t.numel() != n:
+                raise _lib.CidError(f"{what}.{name}: {t.numel()} elements, B * per_sample = {n}")
+
+
+def cfg_pag_ddim_step(eps: torch.Tensor, latents: torch.Tensor, coef: torch.Tensor, guidance: float, pag: torch.Tensor, *,
+                      B: int, per_sample: int, mask: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None,
+                      noise: Optional[torch.Tensor] = None):
+    """``cfg_ddim_step`` with perturbed-attention guidance (cid_cfg_pag_ddim_step_f16): ``eps`` fp16 [3B, per_sample] =
+    [uncond | cond | perturbed], e = u + g (c - u) + s (c - p) with s = ``pag`` -- ONE fp32 value on the device, so that a
+    captured launch follows the step table; at s == 0 the perturbed rows are not read and the bits are ``cfg_ddim_step``'s"""
+    lib = _lib.load()
+    n = B * per_sample
+    _req(eps, "cfg_pag_ddim_step.eps")
+    _req(latents, "cfg_pag_ddim_step.latents")
+    _req(coef, "cfg_pag_ddim_step.coef", torch.float32)
+    _req_pag(pag, "cfg_pag_ddim_step")
+    if eps.numel() != 3 * n or latents.numel() != n or coef.numel() < 4:
+        raise _lib.CidError(f"cfg_pag_ddim_step: eps / latents / coef hold {eps.numel()} / {latents.numel()} / {coef.numel()} "
+                            f"elements; B * per_sample = {n} needs {3 * n} / {n} / at least 4")
+    _req_step_blend("cfg_pag_ddim_step", n, mask, init, noise)
+    check(lib.cid_cfg_pag_ddim_step_f16(_p(eps), _p(latents), _p(coef), float(guidance), _p(pag), _p(mask), _p(init), _p(noise),
+                                        B, per_sample, _stream()), "cid_cfg_pag_ddim_step_f16")
+    return latents
+
+
+def _pag_multistep(what: str, eps_rows: int, eps, latents, hist, saved, row, pag, B, per_sample, z, mask, init, noise) -> int:
+    """the shared checks of the two PAG multistep entries -> z_rows"""
+    n = B * per_sample
+    _req(eps, f"{what}.eps")
+    _req(latents, f"{what}.latents")
+    _req(hist, f"{what}.hist", torch.float32)
+    _req(saved, f"{what}.saved")
+    _req(row, f"{what}.row", torch.float32)
+    _req_pag(pag, what)
+    if eps.numel() != eps_rows * n or latents.numel() != n or hist.numel() != 4 * n or saved.numel() != n or row.numel() != 16:
+        raise _lib.CidError(f"{what}: eps / latents / hist / saved / row hold {eps.numel()} / {latents.numel()} / "
+                            f"{hist.numel()} / {saved.numel()} / {row.numel()} elements; B * per_sample = {n} needs "
+                            f"{eps_rows * n} / {n} / {4 * n} / {n} / 16")
+    z_rows = 0
+    if z is not None:
+        _req(z, f"{what}.z")
+        if z.numel() == 0 or z.numel() % n:
+            raise _lib.CidError(f"{what}.z: {z.numel()} elements are not rows of B * per_sample = {n}")
+        z_rows = z.numel() // n
+    _req_step_blend(what, n, mask, init, noise)
+    return z_rows
+
+
+def cfg_pag_multistep_step(eps: torch.Tensor, latents: torch.Tensor, hist: torch.Tensor, saved: torch.Tensor,
+                           row: torch.Tensor, guidance: float, pag: torch.Tensor, *, B: int, per_sample: int,
+                           z: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                           init: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None):
+    """``cfg_multistep_step`` with perturbed-attention guidance (cid_cfg_pag_multistep_step_f16): ``eps`` fp16
+    [3B, per_sample] = [uncond | cond | perturbed], ``pag`` as in ``cfg_pag_ddim_step``"""
+    z_rows = _pag_multistep("cfg_pag_multistep_step", 3, eps, latents, hist, saved, row, pag, B, per_sample, z, mask, init, noise)
+    check(_lib.load().cid_cfg_pag_multistep_step_f16(_p(eps), _p(latents), _p(hist), _p(saved), _p(z), z_rows, _p(row),
+                                                     float(guidance), _p(pag), _p(mask), _p(init), _p(noise), B, per_sample,
+                                                     _stream()), "cid_cfg_pag_multistep_step_f16")
+    return latents
+
+
+def pag_multistep_step(eps: torch.Tensor, latents: torch.Tensor, hist: torch.Tensor, saved: torch.Tensor, row: torch.Tensor,
+                       pag: torch.Tensor, *, B: int, per_sample: int, z: Optional[torch.Tensor] = None,
+                       mask: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None,
+                       noise: Optional[torch.Tensor] = None):
+    """``multistep_step`` (the single pass) with perturbed-attention guidance (cid_pag_multistep_step_f16): ``eps`` fp16
+    [2B, per_sample] = [cond | perturbed], e = c + s (c - p); at s == 0 the bits are ``multistep_step``'s"""
+    z_rows = _pag_multistep("pag_multistep_step", 2, eps, latents, hist, saved, row, pag, B, per_sample, z, mask, init, noise)
+    check(_lib.load().cid_pag_multistep_step_f16(_p(eps), _p(latents), _p(hist), _p(saved), _p(z), z_rows, _p(row), _p(pag),
+                                                 _p(mask), _p(init), _p(noise), B, per_sample, _stream()),
+          "cid_pag_multistep_step_f16")
+    return latents
+
+
 def add_inplace(y: torch.Tensor, a: torch.Tensor):
     lib = _lib.load()
     _req(y, "add_inplace.y")

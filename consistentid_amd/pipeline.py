@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from .controlnet import HipMultiControlNet, prepare_control_arguments
-from .denoise import DenoiseEngine, check_eta, check_guidance_rescale
+from .denoise import DenoiseEngine, check_eta, check_guidance_rescale, check_pag
 from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler, LCMScheduler,  # noqa: F401
                         PNDMScheduler)
 from .unet import HipUNet
@@ -148,6 +148,28 @@ class _BasePipeline:
     def disable_freeu(self):
         """``pipe.disable_freeu()`` of diffusers 0.23: the up blocks run as without FreeU, with no extra launch"""
         self.unet.disable_freeu()
+
+    def enable_pag(self, pag_applied_layers="mid"):
+        """Perturbed-attention guidance (arXiv 2403.17377), diffusers' ``pag_applied_layers``: a string or a list of ``"mid"``,
+        ``"down.block_i"``, ``"up.block_i"``, optionally with ``".attentions_j"``, or module paths such as
+        ``"down_blocks.1.attentions.0"``; every self-attention under a named module is perturbed, an id that names none raises
+        ValueError.  The guidance itself is switched per call: ``pipe(..., pag_scale=3.0, pag_adaptive_scale=0.0)`` -- a call
+        with ``pag_scale`` > 0 and no selection takes ``"mid"``.  Needs a UNet built with ``keep_base=True`` (RuntimeError)."""
+        self.unet.enable_pag(pag_applied_layers)
+
+    def disable_pag(self):
+        """drop the selection of :meth:`enable_pag` (a later call with ``pag_scale`` > 0 selects ``"mid"`` again)"""
+        self.unet.disable_pag()
+
+    def _check_pag(self, pag_scale, pag_adaptive_scale, guidance_rescale: float = 0.0) -> dict:
+        """the two PAG keywords of a ``__call__``, validated -> the engine's keywords; the refusals that need no tensor are
+        made here, before the pre-loop runs"""
+        pag_scale, pag_adaptive_scale = check_pag(pag_scale, pag_adaptive_scale)
+        if pag_scale > 0.0 and guidance_rescale > 0.0:
+            raise NotImplementedError("pag_scale > 0 together with guidance_rescale > 0 is not built")
+        if pag_scale > 0.0 and not self.unet.pag_layers:
+            self.unet.enable_pag()
+        return dict(pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale)
 
     @property
     def scheduler(self):
@@ -623,9 +645,12 @@ class ConsistentIDStableDiffusionPipeline(_IDPreLoop, _SD15PromptEncoding, _Base
                  cross_attention_kwargs=None, original_size=None, target_size=None, callback=None,
                  callback_steps: int = 1, input_id_images=None, start_merge_step: int = 0,
                  class_tokens_mask=None, prompt_embeds_text_only=None, variance_noise: Optional[torch.Tensor] = None,
-                 max_embeddings_multiples: int = 1, guidance_rescale: float = 0.0):
+                 max_embeddings_multiples: int = 1, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
+                 guidance_rescale: float = 0.0):
         """``guidance_rescale`` (diffusers 0.23 StableDiffusionPipeline; rescale_noise_cfg's phi): > 0 rescales the guided
         prediction to the conditional one's standard deviation, per sample and step.
+        ``pag_scale`` / ``pag_adaptive_scale``: perturbed-attention guidance as diffusers' PAG pipelines spell it (``enable_pag``;
+        DESIGN.md 4.28); 0 = off, not together with ``guidance_rescale``.
         ``max_embeddings_multiples`` >= 2: the negative prompt of a pre-loop call is a long weighted prompt
         (prepare_id_prompt_embeds).  ``prompt_embeds`` may have any [3B, T + num_tokens, Dc] the
         cross-attention kernels take (T <= 1024 text rows).
@@ -634,6 +659,7 @@ class ConsistentIDStableDiffusionPipeline(_IDPreLoop, _SD15PromptEncoding, _Base
         ``prompt_embeds`` (cat([null, augmented, text_only])) and ``latents`` directly.  ``num_images_per_prompt`` = n on the
         prompt path: n samples of the one identity -- the embeds repeated n times, the latents one draw of [n, C, h, w]."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
+        pag_kw = self._check_pag(pag_scale, pag_adaptive_scale, guidance_rescale)
         if self._takes_id_pre_loop(prompt, input_id_images, prompt_embeds):
             prompt_embeds = self._id_call_prompt_embeds(prompt, input_id_images, negative_prompt, num_images_per_prompt,
                                                         max_embeddings_multiples)
@@ -654,7 +680,7 @@ class ConsistentIDStableDiffusionPipeline(_IDPreLoop, _SD15PromptEncoding, _Base
         out = self._engine.run(latents, null_e, aug_e, text_e, num_inference_steps=num_inference_steps,
                                guidance_scale=guidance_scale, start_merge_step=start_merge_step,
                                callback=callback, callback_steps=callback_steps, eta=eta, variance_noise=variance_noise,
-                               guidance_rescale=guidance_rescale)
+                               guidance_rescale=guidance_rescale, **pag_kw)
         out, has_nsfw_concept = self._postprocess_checked(out, output_type, legacy_numpy=True)
         return self._output(out, return_dict, has_nsfw_concept)
 
@@ -709,12 +735,15 @@ class ConsistentIDStableDiffusionXLPipeline(_BasePipeline):
                  start_merge_step: int = 0, class_tokens_mask=None, prompt_embeds_text_only=None,
                  pooled_prompt_embeds_text_only=None, add_time_ids: Optional[torch.Tensor] = None,
                  negative_prompt_embeds_facial: Optional[torch.Tensor] = None,
-                 variance_noise: Optional[torch.Tensor] = None):
-        """pooled_prompt_embeds = pooled embeds used AFTER the merge step, pooled_prompt_embeds_text_only
+                 variance_noise: Optional[torch.Tensor] = None, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0):
+        """``pag_scale`` / ``pag_adaptive_scale``: perturbed-attention guidance (``enable_pag``) -- the perturbed
+        rows take the conditional rows' pooled embeds and time ids.
+        pooled_prompt_embeds = pooled embeds used AFTER the merge step, pooled_prompt_embeds_text_only
         BEFORE it, negative_pooled_prompt_embeds for the unconditional half (ref SDXL :620-631);
         add_time_ids [2B, 6] (ref :531-539).  ``guidance_rescale``: diffusers' rescale_noise_cfg, which the reference's loop
         has commented out (ref SDXL :652-654); honoured here, 0 = the reference's behaviour."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
+        pag_kw = self._check_pag(pag_scale, pag_adaptive_scale, guidance_rescale)
         self._check_hot_path_inputs(prompt, input_id_images, prompt_embeds, latents, output_type)
         assert guidance_scale >= 1.0
         variance_noise = self._variance_noise(eta, generator, variance_noise, latents, num_inference_steps)
@@ -751,7 +780,7 @@ class ConsistentIDStableDiffusionXLPipeline(_BasePipeline):
                                pooled=(negative_pooled_prompt_embeds, pooled_prompt_embeds_text_only,
                                        pooled_prompt_embeds), time_ids=add_time_ids,
                                callback=callback, callback_steps=callback_steps, eta=eta, variance_noise=variance_noise,
-                               guidance_rescale=guidance_rescale)
+                               guidance_rescale=guidance_rescale, **pag_kw)
         out = self._postprocess(out, output_type)
         if not return_dict:
             return (out,)
@@ -908,8 +937,11 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                  prompt_embeds_text_only=None, image_latents: Optional[torch.Tensor] = None,
                  noise: Optional[torch.Tensor] = None, mask_latents: Optional[torch.Tensor] = None,
                  down_block_res_samples=None, mid_block_res_sample=None, variance_noise: Optional[torch.Tensor] = None,
-                 max_embeddings_multiples: int = 1, guidance_rescale: float = 0.0):
-        """``guidance_rescale`` / ``max_embeddings_multiples``: engine extensions here (diffusers' inpaint pipelines do not take
+                 max_embeddings_multiples: int = 1, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
+                 guidance_rescale: float = 0.0):
+        """``pag_scale`` / ``pag_adaptive_scale``: perturbed-attention guidance (``enable_pag``), not together
+        with precomputed ControlNet residuals.
+        ``guidance_rescale`` / ``max_embeddings_multiples``: engine extensions here (diffusers' inpaint pipelines do not take
         them), as in ConsistentIDStableDiffusionPipeline.__call__.  The reference's call, ``pipe(prompt, input_id_images=face, mask_image=mask, height=, width=, ...)``, runs its whole
         pre-loop: the ID pre-loop on ``input_id_images[0]`` (prepare_id_prompt_embeds; ref :157-229), image_prep.py on the
         PIL init image and mask (ref :232-239), the VAE encode on ``vae_encoder`` (ref :255-291).  ``prompt_embeds``
@@ -931,16 +963,23 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                              start_merge_step=start_merge_step, image_latents=image_latents, noise=noise,
                              mask_latents=mask_latents, down_block_res_samples=down_block_res_samples,
                              mid_block_res_sample=mid_block_res_sample, variance_noise=variance_noise,
-                             guidance_rescale=guidance_rescale, max_embeddings_multiples=max_embeddings_multiples)
+                             guidance_rescale=guidance_rescale, max_embeddings_multiples=max_embeddings_multiples,
+                             pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale)
 
     def _inpaint(self, *, prompt, image, mask_image, masked_image_latents, height, width, strength, num_inference_steps,
                  guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents, prompt_embeds,
                  output_type, return_dict, callback, callback_steps, input_id_images, start_merge_step, image_latents,
                  noise, mask_latents, down_block_res_samples, mid_block_res_sample, variance_noise, control=None,
-                 max_embeddings_multiples: int = 1, guidance_rescale: float = 0.0):
+                 max_embeddings_multiples: int = 1, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
+                 guidance_rescale: float = 0.0):
         """The body both inpaint ``__call__``s share (inpaint ref :127-359, CN :180-456).  ``control``: the ControlNet
         pipeline's (control_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end)."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
+        if check_pag(pag_scale, pag_adaptive_scale)[0] > 0.0 and (control is not None or down_block_res_samples is not None
+                                                                  or mid_block_res_sample is not None):
+            raise NotImplementedError("PAG with ControlNet residuals is not built: the ControlNet-inpaint pipeline and "
+                                      "precomputed residuals take pag_scale = 0")
+        pag_kw = self._check_pag(pag_scale, pag_adaptive_scale, guidance_rescale)
         prompt_embeds, image, mask_image, height, width, normalize = self._call_inputs(
             prompt, input_id_images, prompt_embeds, negative_prompt, num_images_per_prompt, image, mask_image, height, width,
             max_embeddings_multiples)
@@ -966,7 +1005,7 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                                inpaint_mask=b_mask, inpaint_init=b_init, inpaint_noise=b_noise,
                                callback=callback, callback_steps=callback_steps, first_step=first, scale_initial=scaled,
                                unet_extra=extra, eta=eta, variance_noise=variance_noise, guidance_rescale=guidance_rescale,
-                               **cn_kw)
+                               **pag_kw, **cn_kw)
         out, has_nsfw_concept = self._postprocess_checked(out, output_type)
         return self._output(out, return_dict, has_nsfw_concept)
 
@@ -1004,8 +1043,10 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
                  image_latents: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
                  mask_latents: Optional[torch.Tensor] = None, down_block_res_samples=None, mid_block_res_sample=None,
                  masked_image_latents: Optional[torch.Tensor] = None, variance_noise: Optional[torch.Tensor] = None,
-                 max_embeddings_multiples: int = 1, guidance_rescale: float = 0.0):
-        """``prompt`` / ``input_id_images`` / ``image`` / ``mask_image`` / ``guidance_rescale`` / ``max_embeddings_multiples``: as in
+                 max_embeddings_multiples: int = 1, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
+                 guidance_rescale: float = 0.0):
+        """``pag_scale`` > 0 is refused here (NotImplementedError): PAG with ControlNet residuals is not built.
+        ``prompt`` / ``input_id_images`` / ``image`` / ``mask_image`` / ``guidance_rescale`` / ``max_embeddings_multiples``: as in
         StableDiffusionInpaintConsistentIDPipeline.__call__ (CN :180-265).  ``control_image``: a float tensor [B, 3, 8h, 8w]
         in [0, 1], or one PIL image (or a list of one), converted to RGB and resized to the final height x width by
         image_prep.preprocess_control (CN :267-280).
@@ -1028,4 +1069,5 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
                              mid_block_res_sample=mid_block_res_sample, variance_noise=variance_noise,
                              control=(control_image, controlnet_conditioning_scale, control_guidance_start,
                              control_guidance_end), guidance_rescale=guidance_rescale,
-                             max_embeddings_multiples=max_embeddings_multiples)
+                             max_embeddings_multiples=max_embeddings_multiples, pag_scale=pag_scale,
+                             pag_adaptive_scale=pag_adaptive_scale)

@@ -29,7 +29,7 @@ from typing import Dict, List, Optional, Sequence
 import torch
 
 from . import ops
-from .unet_spec import BlockSpec, ResnetSpec, TransformerSpec, UNetConfig, walk
+from .unet_spec import PAG_DEFAULT_LAYERS, BlockSpec, ResnetSpec, TransformerSpec, UNetConfig, pag_blocks, walk
 from .weights import PackedUNet
 
 
@@ -117,6 +117,7 @@ class HipUNet:
         self._xattn_gen = ops.xattn_generation()
         self._t_buf = torch.zeros(1, dtype=torch.float32, device=self.device)
         self._freeu = None      # (s1, s2, b1, b2) while FreeU is enabled
+        self._pag: tuple = ()   # the transformer blocks whose attn1 is the identity on perturbed rows (enable_pag)
         # time_cond_proj_dim: cond_proj(guidance embedding) [1, c0] of the current generation, at a stable address
         self._cond_row: Optional[torch.Tensor] = None
 
@@ -157,6 +158,36 @@ class HipUNet:
             self._freeu = None
             self.epoch += 1
         return self
+
+    def enable_pag(self, layers=PAG_DEFAULT_LAYERS):
+        """Perturbed-attention guidance (arXiv 2403.17377; diffusers' ``pag_applied_layers``): select the self-attention
+        layers that skip their attention map on the perturbed rows of a forward (``forward_tokens(pag_rows=)``) --
+        ``unet_spec.pag_blocks`` resolves the ids, an unknown one raises ValueError -- and build their folded
+        ``to_out . to_v`` weights (``PackedUNet.set_pag``; RuntimeError without ``keep_base=True``).  Rows that are not
+        perturbed, and forwards without perturbed rows, launch what they always launched.  A captured step holds the
+        selection it was captured under, so the epoch moves when it changes."""
+        blocks = tuple(pag_blocks(self.config, layers))
+        if self.packed.encoder_only:
+            raise NotImplementedError("enable_pag: a ControlNet encoder takes no perturbed rows")
+        if blocks != self._pag:
+            with torch.cuda.device(self.device):
+                self.packed.set_pag(blocks)
+            self._pag = blocks
+            self.epoch += 1
+        return self
+
+    def disable_pag(self):
+        """drop the selection and the folded weights of :meth:`enable_pag`"""
+        if self._pag:
+            self.packed.set_pag(())
+            self._pag = ()
+            self.epoch += 1
+        return self
+
+    @property
+    def pag_layers(self) -> tuple:
+        """the selected transformer blocks (``<transformer>.transformer_blocks.<k>``), () while PAG is off"""
+        return self._pag
 
     def load_adapter_modules(self, adapter_sd: Dict[str, torch.Tensor], lora_scale: Optional[float] = None):
         """``adapter_modules`` of a ConsistentID checkpoint -> packed weights, in place (needs ``keep_base=True``);
@@ -311,14 +342,57 @@ class HipUNet:
         out.view(rep, -1).copy_(t.reshape(1, -1).expand(rep, -1))
         return out
 
-    def _transformer(self, t: TransformerSpec, x, B, H, Wd, kvrow, Bp: Optional[int] = None):
-        """``Bp`` < B: the rows of ``x`` are the Bp distinct samples of a CFG batch B = rep * Bp whose halves were identical
+    def _attn1_core(self, t: TransformerSpec, b: str, h, Bs: int, N: int, N_real: int):
+        """fused q / k / v projection of LayerNorm1(``h``) and the self-attention of ``Bs`` samples of N tokens -> [Bs * N, c]"""
+        W, c = self.W, t.channels
+        d = c // t.heads
+        M = Bs * N
+        qk = self._empty(M, 2 * c)
+        vt = self._empty(Bs * t.heads * ops.dvp_of(d) * N)
+        if ops.ln_fold(M):     # norm1 folded into the projection: the GEMM reads the residual stream itself
+            ops.gemm(h, W[f"{b}.attn1.qkv.wl"], qk, M=M, N=3 * c, c1=c, mode=2, vt=vt, n_vt0=2 * c,
+                     heads=t.heads, dhead=d, ntok=N, ln=self._ln(b, "attn1.qkv.ln"))
+        else:
+            ln = self._empty(M, c)
+            ops.layernorm(h, ln, W[f"{b}.norm1.g"], W[f"{b}.norm1.b"], M=M, C_=c)
+            ops.gemm(ln, W[f"{b}.attn1.qkv.w"], qk, M=M, N=3 * c, c1=c, mode=2, vt=vt, n_vt0=2 * c,
+                     heads=t.heads, dhead=d, ntok=N)
+        ao = self._empty(M, c)
+        ops.self_attn(qk, qk[:, c:], vt, ao, B=Bs, N=N, heads=t.heads, d=d, ldq=2 * c, ldk=2 * c, ldo=c,
+                      n_keys=N_real)
+        return ao
+
+    def _attn1_perturbed(self, t: TransformerSpec, b: str, h, B: int, N: int, N_real: int, pag_rows: int):
+        """``h + attn1(LN1(h))`` of a block PAG selects: the leading B - pag_rows samples run the attention as ever -- their
+        token-major rows are one contiguous range, pad rows of a padded token axis included -- and the trailing ``pag_rows``
+        samples take identity attention, to_out(to_v(LN1(h))): ONE GEMM on the pre-multiplied weight (weights.fold_vo) with the
+        residual in its epilogue; no q / k / v projection, no attention and no out projection run for them."""
+        W, P, c = self.W, self.packed.pag, t.channels
+        lead = B - pag_rows
+        Ml, Mp = lead * N, pag_rows * N
+        h2 = self._empty(B * N, c)
+        if lead:
+            ao = self._attn1_core(t, b, h[:Ml], lead, N, N_real)
+            ops.gemm(ao, W[f"{b}.attn1.out.w"], h2[:Ml], M=Ml, N=c, c1=c, bias=W[f"{b}.attn1.out.b"], res=h[:Ml], ldr=c)
+        hp = h[Ml:]
+        if ops.ln_fold(Mp):     # norm1 folded: the GEMM reads the residual stream itself (to_out's bias is inside lnb)
+            ln = (P[f"{b}.attn1.vo.lns"].view(torch.float32), P[f"{b}.attn1.vo.lnb"].view(torch.float32), ops.LN_EPS)
+            ops.gemm(hp, P[f"{b}.attn1.vo.wl"], h2[Ml:], M=Mp, N=c, c1=c, ln=ln, res=hp, ldr=c)
+        else:
+            ln1 = self._empty(Mp, c)
+            ops.layernorm(hp, ln1, W[f"{b}.norm1.g"], W[f"{b}.norm1.b"], M=Mp, C_=c)
+            ops.gemm(ln1, P[f"{b}.attn1.vo.w"], h2[Ml:], M=Mp, N=c, c1=c, bias=W[f"{b}.attn1.out.b"], res=hp, ldr=c)
+        return h2
+
+    def _transformer(self, t: TransformerSpec, x, B, H, Wd, kvrow, Bp: Optional[int] = None, pag_rows: int = 0):
+        """``pag_rows`` > 0: the trailing ``pag_rows`` samples of the batch are perturbed -- in the blocks ``enable_pag``
+        selected their self-attention is the identity (``_attn1_perturbed``); every other block runs all rows as ever.
+        ``Bp`` < B: the rows of ``x`` are the Bp distinct samples of a CFG batch B = rep * Bp whose halves were identical
         so far (same latents, same timestep).  Everything up to the first cross-attention -- the first place the two
         halves see different inputs -- runs once on Bp samples and is then repeated; the result is the same tensor the
         full batch would produce, row for row."""
         W, n, c = self.W, t.name, t.channels
         N = H * Wd
-        d = c // t.heads
         ctx = self._ctx
         Bc = B if Bp is None else Bp          # batch of the part computed so far
         g = self._gn(x, c, Bc, N, W[f"{n}.norm.g"], W[f"{n}.norm.b"], 1e-6, False)
@@ -344,24 +418,16 @@ class HipUNet:
         for k in range(t.n_layers):
             b = f"{n}.transformer_blocks.{k}"
             # --- self attention (Consistent_AttProcessor, attention.py:110-174)
-            qk = self._empty(M, 2 * c)
-            vt = self._empty(Bc * t.heads * ops.dvp_of(d) * N)
-            if ops.ln_fold(M):     # norm1 folded into the projection: the GEMM reads the residual stream itself
-                ops.gemm(h, W[f"{b}.attn1.qkv.wl"], qk, M=M, N=3 * c, c1=c, mode=2, vt=vt, n_vt0=2 * c,
-                         heads=t.heads, dhead=d, ntok=N, ln=self._ln(b, "attn1.qkv.ln"))
-            else:
-                ln = self._empty(M, c)
-                ops.layernorm(h, ln, W[f"{b}.norm1.g"], W[f"{b}.norm1.b"], M=M, C_=c)
-                ops.gemm(ln, W[f"{b}.attn1.qkv.w"], qk, M=M, N=3 * c, c1=c, mode=2, vt=vt, n_vt0=2 * c,
-                         heads=t.heads, dhead=d, ntok=N)
-            ao = self._empty(M, c)
-            ops.self_attn(qk, qk[:, c:], vt, ao, B=Bc, N=N, heads=t.heads, d=d, ldq=2 * c, ldk=2 * c, ldo=c,
-                          n_keys=N_real)
             rep = B // Bc
-            if rep == 2:    # the halves part ways at the cross-attention: the out projection writes the shared stream twice
+            if pag_rows > 0 and b in self._pag:     # identity attention on the trailing pag_rows samples
+                assert Bc == B, "a perturbed block runs on the whole batch (forward_tokens keeps it out of the de-duplication)"
+                h2 = self._attn1_perturbed(t, b, h, B, N, N_real, pag_rows)
+            elif rep == 2:    # the halves part ways at the cross-attention: the out projection writes the shared stream twice
+                ao = self._attn1_core(t, b, h, Bc, N, N_real)
                 h2 = self._empty(2 * M, c)
                 ops.gemm(ao, W[f"{b}.attn1.out.w"], h2[:M], M=M, N=c, c1=c, bias=W[f"{b}.attn1.out.b"], res=h, ldr=c, out2=h2[M:])
             else:
+                ao = self._attn1_core(t, b, h, Bc, N, N_real)
                 h2 = self._empty(M, c)
                 ops.gemm(ao, W[f"{b}.attn1.out.w"], h2, M=M, N=c, c1=c, bias=W[f"{b}.attn1.out.b"], res=h, ldr=c)
             if Bc != B:     # ... and the block input (the residual of proj_out) exists twice already where its producer wrote it so
@@ -572,7 +638,7 @@ class HipUNet:
                        added_cond_kwargs=None, down_residuals: Optional[Sequence[torch.Tensor]] = None,
                        mid_residual: Optional[torch.Tensor] = None, temb: Optional[torch.Tensor] = None,
                        in_scale: Optional[torch.Tensor] = None, extra: Optional[torch.Tensor] = None,
-                       residual_scales: Optional[torch.Tensor] = None) -> torch.Tensor:
+                       residual_scales: Optional[torch.Tensor] = None, pag_rows: int = 0) -> torch.Tensor:
         """sample: NCHW fp16 [Bin, cin, H, W] with B % Bin == 0 (batch row b reads sample b % Bin,
         i.e. the CFG duplication of ref :537-539 costs no copy).  Returns NCHW fp16 [B, cout, H, W].
         ``residual_scales`` (DEVICE fp32, one value per net) selects the multi-ControlNet form: ``down_residuals`` and
@@ -581,8 +647,18 @@ class HipUNet:
         launches add sum_k scale_k * r_k to the skip tensors and to the mid block's output, whatever the number of nets.
         ``extra`` [Bin, cin2, H, W]: the trailing input channels of a 9-channel inpainting UNet (cat([mask,
         masked_image_latents]), inpaint ref :320-321), read by conv_in beside the latents instead of a concatenated copy
-        and not touched by ``in_scale``."""
+        and not touched by ``in_scale``.
+        ``pag_rows`` > 0 (perturbed-attention guidance): the TRAILING ``pag_rows`` batch rows are the perturbed evaluation of
+        the rows in front of them -- same latents (b % Bin), same time row, whatever ``kvrow`` and ``added_cond_kwargs`` give
+        them -- and the blocks ``enable_pag`` selected run identity self-attention on them."""
         cfg, W = self.config, self.W
+        if pag_rows:
+            if not 0 < pag_rows <= B:
+                raise ValueError(f"forward_tokens: pag_rows = {pag_rows} of B = {B} batch rows")
+            if not self._pag:
+                raise RuntimeError("forward_tokens(pag_rows=): no layer is selected; call enable_pag(layers) first")
+            if down_residuals is not None or mid_residual is not None:
+                raise NotImplementedError("PAG with ControlNet residuals is not built")
         Bin, cin, H, Wd = sample.shape
         if extra is not None:
             cin += extra.shape[1]
@@ -600,6 +676,9 @@ class HipUNet:
         if (self._cfg_dedup and B > Bin and trows == 1 and self.downs and self.downs[0].attentions
                 and self.downs[0].attentions[0].n_layers >= 1):
             Bp = Bin
+        # ... unless PAG perturbs that first self-attention: the perturbed rows then differ from the others inside it
+        if pag_rows and Bp != B and f"{self.downs[0].attentions[0].name}.transformer_blocks.0" in self._pag:
+            Bp = B
         # (conv_in reads latent b % Bin for batch row b: run on all B rows it writes the duplicated skip tensor itself, and the
         #  first Bp samples of that buffer are the deduplicated stream)
         xfull = self._empty(B * H * Wd, c0)
@@ -614,7 +693,7 @@ class HipUNet:
                 x = self._resnet(r, x, None, c, 0, Bp if first else B, H, Wd, temb, trows, rep=2 if first and B == 2 * Bp else 1)
                 c = r.cout
                 if blk.attentions:
-                    x = self._transformer(blk.attentions[j], x, B, H, Wd, kvrow, Bp=Bp if first else None)
+                    x = self._transformer(blk.attentions[j], x, B, H, Wd, kvrow, Bp=Bp if first else None, pag_rows=pag_rows)
                 skips.append((x, c, H, Wd))
             if blk.sampler:
                 n = f"{blk.name}.{blk.sampler}.conv"
@@ -653,7 +732,7 @@ class HipUNet:
                 new.append((s, sc_, sh, sw))
             skips = new
         x = self._resnet(self.mid.resnets[0], x, None, c, 0, B, H, Wd, temb, trows)
-        x = self._transformer(self.mid.attentions[0], x, B, H, Wd, kvrow)
+        x = self._transformer(self.mid.attentions[0], x, B, H, Wd, kvrow, pag_rows=pag_rows)
         x = self._resnet(self.mid.resnets[1], x, None, c, 0, B, H, Wd, temb, trows)
         if multi:
             ops.residual_accum([x], [None if m is None else [m] for m in mid_residual], residual_scales)
@@ -671,7 +750,7 @@ class HipUNet:
                 x = self._resnet(r, x, s, c, sc_, B, H, Wd, temb, trows)
                 c = r.cout
                 if blk.attentions:
-                    x = self._transformer(blk.attentions[j], x, B, H, Wd, kvrow)
+                    x = self._transformer(blk.attentions[j], x, B, H, Wd, kvrow, pag_rows=pag_rows)
             if blk.sampler:
                 n = f"{blk.name}.{blk.sampler}.conv"
                 Ho, Wo = H * 2, Wd * 2

@@ -151,6 +151,52 @@ def attn_processor_names(cfg: UNetConfig) -> List[str]:
     return names
 
 
+PAG_DEFAULT_LAYERS = ("mid",)
+
+
+def _pag_id_components(layer_id: str) -> List[str]:
+    """a ``pag_applied_layers`` id -> the components of the module path it names: diffusers' short spellings ``mid``,
+    ``down.block_i`` / ``up.block_i`` and ``attentions_j`` become ``mid_block``, ``down_blocks.i`` / ``up_blocks.i`` and
+    ``attentions.j``; a module path (``down_blocks.1.attentions.0``) passes as it is"""
+    parts, out, i = layer_id.strip().split("."), [], 0
+    while i < len(parts):
+        p = parts[i]
+        nxt = parts[i + 1] if i + 1 < len(parts) else ""
+        if p == "mid":
+            out.append("mid_block")
+        elif p in ("down", "up") and nxt.startswith("block_") and nxt[6:].isdigit():
+            out += [f"{p}_blocks", nxt[6:]]
+            i += 1
+        elif p.startswith("attentions_") and p[11:].isdigit():
+            out += ["attentions", p[11:]]
+        else:
+            out.append(p)
+        i += 1
+    return out
+
+
+def pag_blocks(cfg: UNetConfig, layers=PAG_DEFAULT_LAYERS) -> List[str]:
+    """``pag_applied_layers`` (a string or a sequence of strings) -> the transformer blocks
+    ``<transformer>.transformer_blocks.<k>`` whose ``attn1`` perturbed-attention guidance perturbs, in execution order
+    (down, mid, up) and without repeats.  An id selects every ``attn1`` under the module it names, compared by whole dotted
+    components (``down.block_1`` is not a prefix of ``down_blocks.10``).  An id that selects nothing raises ValueError."""
+    ids = [layers] if isinstance(layers, str) else list(layers) if isinstance(layers, (list, tuple)) else []
+    if not ids or not all(isinstance(x, str) for x in ids):
+        raise ValueError(f"pag_applied_layers = {layers!r}: a string or a non-empty sequence of strings")
+    downs, mid, ups = walk(cfg)
+    blocks = [f"{t.name}.transformer_blocks.{k}" for blk in downs + [mid] + ups for t in blk.attentions for k in range(t.n_layers)]
+    chosen = set()
+    for x in ids:
+        want = _pag_id_components(x)
+        hit = [b for b in blocks if want and (b.split(".") + ["attn1"])[:len(want)] == want]
+        if not hit:
+            raise ValueError(f"pag_applied_layers: {x!r} selects no self-attention layer of this UNet (ids: 'mid', "
+                             "'down.block_i', 'up.block_i', optionally '.attentions_j', or a module path such as "
+                             "'down_blocks.1.attentions.0')")
+        chosen.update(hit)
+    return [b for b in blocks if b in chosen]
+
+
 def hidden_size_of(cfg: UNetConfig, proc_name: str) -> int:
     """set_ip_adapter's rule (pipline_StableDiffusion_ConsistentID.py:157-164)."""
     if proc_name.startswith("mid_block"):

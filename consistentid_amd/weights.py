@@ -76,6 +76,20 @@ def fold_ln(w: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor, bias: Opti
     return wf, s.view(torch.float16), b.contiguous().view(torch.float16)
 
 
+def fold_vo(wv: torch.Tensor, wo: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+            bias: Optional[torch.Tensor] = None):
+    """Identity self-attention (perturbed-attention guidance): without the attention map ``to_out(to_v(LN(x)))`` is ONE
+    linear map.  ``wv``, ``wo`` fp32 [C, C] (merged) -> Wvo = Wo Wv, the product taken in fp32 on the operands' device, then
+    norm1 folded exactly as :func:`fold_ln` does: returns (W' = Wvo diag(gamma) fp16, s, b') for ``ops.gemm(..., ln=)`` --
+    s the row sums of the ROUNDED W', b' = Wvo beta + ``bias`` (to_out's bias, which the folded launch cannot take apart),
+    both fp32 as raw bits in fp16-typed tensors.  One rounding to fp16 of the composed weight, where the two-GEMM path rounds
+    Wv, the intermediate activation and Wo."""
+    return fold_ln(wo.float() @ wv.float(), gamma, beta, bias)
+
+
+PAG_SUFFIXES = ("w", "wl", "lns", "lnb")     # per selected block: attn1.vo.{w: Wvo fp16 (LayerNorm launch + GEMM), wl / lns / lnb: fold_vo}
+
+
 class PackedUNet:
     """Holds every packed tensor; ``w[name]`` lookups use diffusers-style prefixes."""
 
@@ -99,6 +113,10 @@ class PackedUNet:
         self.w: Dict[str, torch.Tensor] = {}
         self.temb_offsets: Dict[str, int] = {}
         self.ip_scale: Dict[str, float] = {}
+        # perturbed-attention guidance (set_pag): the folded to_out . to_v weights of the selected blocks only, BESIDE ``w`` --
+        # an engine that never enables PAG holds the keys and the bytes it always held
+        self.pag: Dict[str, torch.Tensor] = {}
+        self._pag_blocks: tuple = ()
         dev = device
         sd = unet_sd
         W = self.w
@@ -225,6 +243,19 @@ class PackedUNet:
         out[f"{b}.ff2.w"] = _h(w2, dev)
         return out
 
+    def _merged_weight(self, sd, adapter_sd, lora_scale, extra, base: str, idx: int, which: str) -> torch.Tensor:
+        """fp32 ``to_q`` / ``to_k`` / ``to_v`` / ``to_out.0`` (``which`` = q, k, v, out) of attention ``base`` as the engine
+        merges it: the source weight + lora_scale * the ConsistentID adapter's LoRA of processor ``idx`` + ``extra(path)``"""
+        dev = self.device
+        path = f"{base}.to_{which}" if which != "out" else f"{base}.to_out.0"
+        w = _f(sd[f"{path}.weight"], dev)
+        if adapter_sd is not None:
+            up = _f(adapter_sd[f"{idx}.to_{which}_lora.up.weight"], dev)
+            down = _f(adapter_sd[f"{idx}.to_{which}_lora.down.weight"], dev)
+            w = w + lora_scale * (up @ down)
+        more = extra(path) if extra is not None else None
+        return w if more is None else w + more
+
     def _attention_weights(self, b: str, d: int, sd, adapter_sd, proc_index, lora_scale, ln2=None, ln1=None,
                            extra=None) -> Dict[str, torch.Tensor]:
         """packed projection weights of transformer block ``b`` (head dim ``d``): LoRA merged in fp32 (attention.py
@@ -235,16 +266,7 @@ class PackedUNet:
         ``extra``: module path -> a further fp32 delta or None (``set_lora``), added after the adapter's own LoRA."""
         dev = self.device
         out: Dict[str, torch.Tensor] = {}
-
-        def merged(base: str, idx: int, which: str) -> torch.Tensor:
-            path = f"{base}.to_{which}" if which != "out" else f"{base}.to_out.0"
-            w = _f(sd[f"{path}.weight"], dev)
-            if adapter_sd is not None:
-                up = _f(adapter_sd[f"{idx}.to_{which}_lora.up.weight"], dev)
-                down = _f(adapter_sd[f"{idx}.to_{which}_lora.down.weight"], dev)
-                w = w + lora_scale * (up @ down)
-            more = extra(path) if extra is not None else None
-            return w if more is None else w + more
+        merged = lambda base, idx, which: self._merged_weight(sd, adapter_sd, lora_scale, extra, base, idx, which)
 
         qscale = (d ** -0.5) * LOG2E
         i1 = proc_index[f"{b}.attn1.processor"]
@@ -315,12 +337,46 @@ class PackedUNet:
                             self.w[name].copy_(val)
                     if with_ip:
                         self.ip_scale[b] = 1.0
+        self._repack_pag()      # (load_adapter_modules and set_lora both come through here)
 
-    def require_base(self):
+    def require_base(self, what: str = "set_lora"):
         """raise the RuntimeError of :meth:`set_lora` now, before a caller changes anything else"""
         if not self._base_attn or not self._base_host:
-            raise RuntimeError("set_lora needs the UNet's base weights: construct with keep_base=True (engines built from the "
+            raise RuntimeError(f"{what} needs the UNet's base weights: construct with keep_base=True (engines built from the "
                                "broadcast arena do not carry them)")
+
+    def _pag_weights(self, b: str) -> Dict[str, torch.Tensor]:
+        """``attn1.vo.*`` of transformer block ``b`` (:func:`fold_vo`) from the fp16 base, the kept ConsistentID adapter and
+        the active LoRA entries -- the operands ``_repack_attention`` merges ``attn1.qkv`` / ``attn1.out`` from"""
+        proc = {n: i for i, n in enumerate(attn_processor_names(self.cfg))}[f"{b}.attn1.processor"]
+        extra = (lambda path: merged_delta(self._lora, path, self.device)) if self._lora else None
+        wv, wo = (self._merged_weight(self._base_attn, self._adapter_sd, self._adapter_scale, extra, f"{b}.attn1", proc, which)
+                  for which in ("v", "out"))
+        wl, s, bias = fold_vo(wv, wo, self.w[f"{b}.norm1.g"], self.w[f"{b}.norm1.b"], self.w[f"{b}.attn1.out.b"])
+        return dict(zip((f"{b}.attn1.vo.{x}" for x in PAG_SUFFIXES), (_h(wo @ wv, self.device), wl, s, bias)))
+
+    def _repack_pag(self):
+        for b in self._pag_blocks:
+            for name, val in self._pag_weights(b).items():
+                self.pag[name].copy_(val)
+
+    def set_pag(self, blocks):
+        """The transformer blocks whose ``attn1`` perturbed-attention guidance replaces by identity attention -> ``self.pag``
+        holds their ``attn1.vo.{w,wl,lns,lnb}`` and nothing else.  A block that stays selected keeps its tensors (and their
+        addresses); they follow every later ``load_adapter_modules`` / ``set_lora`` in place.  Built from the un-merged base:
+        needs ``keep_base=True`` at construction, like ``set_lora``."""
+        blocks = tuple(dict.fromkeys(blocks))
+        if blocks:
+            self.require_base("enable_pag")
+        for b in self._pag_blocks:
+            if b not in blocks:
+                for x in PAG_SUFFIXES:
+                    del self.pag[f"{b}.attn1.vo.{x}"]
+        for b in blocks:
+            if b not in self._pag_blocks:
+                self.pag.update(self._pag_weights(b))
+        self._pag_blocks = blocks
+        return self
 
     def set_lora(self, entries):
         """Merge community LoRA deltas IN PLACE (lora.py): ``entries`` is the list of active ``(modules, weight)`` with
@@ -380,6 +436,7 @@ class PackedUNet:
         self.cfg, self.device, self.w = cfg, device, w
         self._base_attn, self._lora_scale = {}, meta.get("lora_scale", 1.0)   # (un-merged weights are not broadcast)
         self._base_host, self._lora, self._adapter_sd, self._adapter_scale = {}, [], None, self._lora_scale
+        self.pag, self._pag_blocks = {}, ()
         self.temb_offsets, self.temb_total = meta["temb_offsets"], meta["temb_total"]
         self.ip_scale, self.xattn_layers = meta["ip_scale"], meta["xattn_layers"]
         self.encoder_only = meta.get("encoder_only", False)

@@ -27,7 +27,7 @@ extern "C" {
 typedef void* cid_stream_t;      /* hipStream_t */
 typedef uint16_t cid_half;       /* IEEE binary16 bit pattern */
 
-int cid_version(void);          /* 113: cid_tiny_encode_in_f16, cid_tiny_conv64_s2_f16, cid_tiny_conv64_s2_tile, cid_tiny_encode_out_f16 added (AutoencoderTiny encoder).  112: cid_tiny_conv64_f16, cid_tiny_decode_in_f16, cid_tiny_decode_out_f16, cid_tiny_conv64_tile added (AutoencoderTiny decoder).  111: cid_multistep_step_f16 added.  110: cid_id_xattn_long_f16, cid_kv_pack_long_f16, cid_kv_pack_long_elems, cid_xattn_long_max_txt added (contexts beyond 96 keys).  109: cid_freeu_f16, cid_freeu_ws_bytes added.  108: cid_cfg_rescale_f16, cid_cfg_ddim_step_scaled_f16, cid_cfg_multistep_step_scaled_f16 added.  107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
+int cid_version(void);          /* 114: cid_cfg_pag_ddim_step_f16, cid_cfg_pag_multistep_step_f16, cid_pag_multistep_step_f16 added (perturbed-attention guidance).  113: cid_tiny_encode_in_f16, cid_tiny_conv64_s2_f16, cid_tiny_conv64_s2_tile, cid_tiny_encode_out_f16 added (AutoencoderTiny encoder).  112: cid_tiny_conv64_f16, cid_tiny_decode_in_f16, cid_tiny_decode_out_f16, cid_tiny_conv64_tile added (AutoencoderTiny decoder).  111: cid_multistep_step_f16 added.  110: cid_id_xattn_long_f16, cid_kv_pack_long_f16, cid_kv_pack_long_elems, cid_xattn_long_max_txt added (contexts beyond 96 keys).  109: cid_freeu_f16, cid_freeu_ws_bytes added.  108: cid_cfg_rescale_f16, cid_cfg_ddim_step_scaled_f16, cid_cfg_multistep_step_scaled_f16 added.  107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
                                  * pointer (102: act, 101: pad_mode; set them or zero the struct) */
 const char* cid_last_error(void);
 
@@ -630,6 +630,29 @@ int cid_cfg_multistep_step_scaled_f16(const cid_half* eps, cid_half* latents, fl
                                       const cid_half* z, int32_t z_rows, const void* row, float guidance,
                                       const cid_half* mask, const cid_half* init, const cid_half* noise,
                                       int32_t B, int32_t per_sample, const float* escale, cid_stream_t stream);
+/* Perturbed-attention guidance (arXiv 2403.17377; since cid_version() 114): the three step entries above with one more
+ * block of eps rows, the prediction p of the perturbed evaluation, behind the conditional rows:
+ *    cid_cfg_pag_ddim_step_f16, cid_cfg_pag_multistep_step_f16:  eps [3B][per_sample] = [uncond | cond | perturbed],
+ *                                                                e = eps_u + g (eps_c - eps_u) + s (eps_c - eps_p)
+ *    cid_pag_multistep_step_f16 (the single pass):               eps [2B][per_sample] = [cond | perturbed],
+ *                                                                e = eps_c + s (eps_c - eps_p)
+ * s = pag[0], ONE fp32 value on the DEVICE (a step-table column: a captured launch follows it).  Everything downstream of e
+ * is the sibling entry's: coefficient row, ring, `saved`, z, inpaint blend; fp32 arithmetic, one rounding at the store of
+ * latents.  The kernel branches once, uniformly, on the loaded value: with s == 0 the perturbed rows are NOT read (they may hold
+ * anything, NaN included) and the launch runs the sibling's instructions -- latents, ring and `saved` get the sibling's bits.
+ * -22 before any launch: exactly what the sibling entry refuses (so cid_pag_multistep_step_f16, like cid_multistep_step_f16,
+ * also a buffer that is not 16-byte aligned), and a null pag. */
+int cid_cfg_pag_ddim_step_f16(const cid_half* eps, cid_half* latents, const float* coef, float guidance, const float* pag,
+                              const cid_half* mask, const cid_half* init, const cid_half* noise,
+                              int32_t B, int32_t per_sample, cid_stream_t stream);
+int cid_cfg_pag_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
+                                   const cid_half* z, int32_t z_rows, const void* row, float guidance, const float* pag,
+                                   const cid_half* mask, const cid_half* init, const cid_half* noise,
+                                   int32_t B, int32_t per_sample, cid_stream_t stream);
+int cid_pag_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
+                               const cid_half* z, int32_t z_rows, const void* row, const float* pag,
+                               const cid_half* mask, const cid_half* init, const cid_half* noise,
+                               int32_t B, int32_t per_sample, cid_stream_t stream);
 /* FreeU (D: utils/torch_utils.py apply_freeu / fourier_filter, called from UpBlock2D / CrossAttnUpBlock2D.forward on the
  * inputs of every resnet of the first two up blocks, in front of torch.cat([hidden, skip], 1)):
  *    x[.., : c_x / 2] *= b          x: fp16 [B*H*W][c_x] in place, fp32 product, one rounding; the upper half is not touched
