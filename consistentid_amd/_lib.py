@@ -163,6 +163,15 @@ SIGNATURES = {
                                                  c_stream]),
     "cid_pag_multistep_step_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, c_half_p, c_half_p, C.c_int32, C.c_void_p,
                                              C.c_void_p, c_half_p, c_half_p, c_half_p, C.c_int32, C.c_int32, c_stream]),
+    "cid_attn_colmass_f16": (C.c_int, [c_half_p, C.c_int32, c_half_p, C.c_int32, C.c_void_p] + [C.c_int32] * 5 + [c_stream]),
+    "cid_sag_degrade_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, c_half_p, C.c_void_p] + [C.c_int32] * 6 + [c_stream]),
+    "cid_cfg_sag_ddim_step_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, C.c_float, c_half_p, C.c_float, c_half_p, c_half_p,
+                                            c_half_p, C.c_int32, C.c_int32, c_stream]),
+    "cid_cfg_sag_multistep_step_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, c_half_p, c_half_p, C.c_int32, C.c_void_p,
+                                                 C.c_float, c_half_p, C.c_float, c_half_p, c_half_p, c_half_p, C.c_int32,
+                                                 C.c_int32, c_stream]),
+    "cid_sag_multistep_step_f16": (C.c_int, [c_half_p, c_half_p, C.c_void_p, c_half_p, c_half_p, C.c_int32, C.c_void_p,
+                                             c_half_p, C.c_float, c_half_p, c_half_p, c_half_p, C.c_int32, C.c_int32, c_stream]),
     "cid_freeu_ws_bytes": (C.c_int64, [C.c_int32] * 4),
     "cid_freeu_f16": (C.c_int, [c_half_p, C.c_int32, C.c_float, c_half_p, c_half_p, C.c_int32, C.c_float]
                       + [C.c_int32] * 3 + [C.c_void_p, c_stream]),

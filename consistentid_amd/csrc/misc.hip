@@ -15,7 +15,7 @@ void cid_set_error(const char* fmt, ...) {
     va_end(ap);
 }
 extern "C" const char* cid_last_error(void) { return g_err; }
-extern "C" int cid_version(void) { return 114; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4, 104: cid_gemm_plan, 105: cid_cfg_multistep_step_f16, 106: cid_residual_accum_f16, 107: cid_clip_head_f16 / cid_blackout_f16, 108: cid_cfg_rescale_f16 / cid_cfg_*_step_scaled_f16, 109: cid_freeu_f16 (freeu.hip), 110: cid_id_xattn_long_f16 / cid_kv_pack_long_* (xattn_long.hip), 111: cid_multistep_step_f16, 112: cid_tiny_conv64_f16 / cid_tiny_decode_in_f16 / cid_tiny_decode_out_f16 (taesd.hip), 113: cid_tiny_encode_in_f16 / cid_tiny_conv64_s2_f16 / cid_tiny_encode_out_f16, 114: cid_cfg_pag_ddim_step_f16 / cid_cfg_pag_multistep_step_f16 / cid_pag_multistep_step_f16 (perturbed-attention guidance)
+extern "C" int cid_version(void) { return 115; }   // 101: cid_gemm_desc.pad_mode, 102: cid_gemm_desc.act, 103: cid_gemm_desc.w_up4, 104: cid_gemm_plan, 105: cid_cfg_multistep_step_f16, 106: cid_residual_accum_f16, 107: cid_clip_head_f16 / cid_blackout_f16, 108: cid_cfg_rescale_f16 / cid_cfg_*_step_scaled_f16, 109: cid_freeu_f16 (freeu.hip), 110: cid_id_xattn_long_f16 / cid_kv_pack_long_* (xattn_long.hip), 111: cid_multistep_step_f16, 112: cid_tiny_conv64_f16 / cid_tiny_decode_in_f16 / cid_tiny_decode_out_f16 (taesd.hip), 113: cid_tiny_encode_in_f16 / cid_tiny_conv64_s2_f16 / cid_tiny_encode_out_f16, 114: cid_cfg_pag_ddim_step_f16 / cid_cfg_pag_multistep_step_f16 / cid_pag_multistep_step_f16 (perturbed-attention guidance), 115: cid_attn_colmass_f16 / cid_sag_degrade_f16 (sag.hip) / cid_cfg_sag_ddim_step_f16 / cid_cfg_sag_multistep_step_f16 / cid_sag_multistep_step_f16 (self-attention guidance)
 
 namespace {
 
@@ -470,22 +470,29 @@ linear_small_kernel(const half_t* __restrict__ x, int ldx, const half_t* __restr
 // prediction p, behind the conditional one, and e += s (c - p) with s = pag[0], a DEVICE value (a step-table column).  The
 // branch on s != 0 is uniform over the grid: at s == 0 the perturbed rows are never addressed (they may hold NaN, and
 // 0 * NaN is NaN) and e is the sibling's expression.  pag is not read without PAG: those instantiations are the kernels as they were.
-template <bool SCALED, bool PAG = false>
+// SAG (the cid_*sag*_step_f16 entries, self-attention guidance): the prediction e_d of the degraded latents comes in a buffer of
+// its own, eps_d [B][per_sample], and e += s (guide - e_d), the guide rows being the unconditional ones with CFG and the
+// conditional ones without; s is a launch argument.  At s == 0 eps_d is never addressed.  Neither is read without SAG.
+template <bool SCALED, bool PAG = false, bool SAG = false>
 __global__ void __launch_bounds__(256)
 cfg_ddim_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, const float* __restrict__ coef,
                 float g, const half_t* __restrict__ mask, const half_t* __restrict__ init,
                 const half_t* __restrict__ noise, long n /* B * per_sample, multiple of 8 */,
                 const float* __restrict__ escale, int sample_items /* 8-half items per sample */,
-                const float* __restrict__ pag /* PAG only: one DEVICE value */) {
+                const float* __restrict__ pag /* PAG only: one DEVICE value */,
+                const half_t* __restrict__ eps_d /* SAG only */, float sag /* SAG only */) {
     float s = 0.f;
     if constexpr (PAG) s = pag[0];
     const bool perturbed = PAG && s != 0.f;
+    const bool degraded = SAG && sag != 0.f;
     const float cx = coef[0], ce = coef[1];
     const float ci = mask ? coef[2] : 0.f, cn = mask ? coef[3] : 0.f;
     for (long q = ((long)blockIdx.x * 256 + threadIdx.x) * 8; q < n; q += (long)gridDim.x * 256 * 8) {
         const half8 eu = ld_global_h8(eps + q), ec = ld_global_h8(eps + n + q), xl = ld_global_h8(lat + q);
         half8 ep;
         if constexpr (PAG) { if (perturbed) ep = ld_global_h8(eps + 2 * n + q); }
+        half8 ed;
+        if constexpr (SAG) { if (degraded) ed = ld_global_h8(eps_d + q); }
         half8 mk, in0, nz;
         if (mask) { mk = ld_global_h8(mask + q); in0 = ld_global_h8(init + q); nz = ld_global_h8(noise + q); }
         float es = 1.f;
@@ -496,6 +503,7 @@ cfg_ddim_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, const 
             const float u = (float)eu[i], c = (float)ec[i];
             float e = u + g * (c - u);
             if constexpr (PAG) { if (perturbed) e += s * (c - (float)ep[i]); }
+            if constexpr (SAG) { if (degraded) e += sag * (u - (float)ed[i]); }
             if constexpr (SCALED) e *= es;
             float v = cx * (float)xl[i] + ce * e;
             if (mask) {
@@ -515,17 +523,19 @@ cfg_ddim_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, const 
 // CFG = false (cid_multistep_step_f16, the single pass): eps holds ONE model output per sample, [B][per_sample], and e is that
 // value -- no second half is loaded (eps + n is past the end of the buffer) and g is not read.
 // PAG as cfg_ddim_kernel's: the perturbed rows follow the conditional ones -- [3B] rows with CFG, [2B] without, where
-// e = c + s (c - p).
-template <bool SCALED, bool CFG = true, bool PAG = false>      // SCALED, PAG as cfg_ddim_kernel's
+// e = c + s (c - p).  SAG as cfg_ddim_kernel's: e += s (eps row 0 - e_d), the unconditional rows with CFG, the only rows without.
+template <bool SCALED, bool CFG = true, bool PAG = false, bool SAG = false>      // SCALED, PAG, SAG as cfg_ddim_kernel's
 __global__ void __launch_bounds__(256)
 cfg_multistep_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, float* hist, half_t* saved,
                      const half_t* __restrict__ z, int z_rows, const float* __restrict__ row, float g,
                      const half_t* __restrict__ mask, const half_t* __restrict__ init, const half_t* __restrict__ noise,
                      long n /* B * per_sample, multiple of 8 */, const float* __restrict__ escale, int sample_items /* 8-half items per sample */,
-                     const float* __restrict__ pag /* PAG only: one DEVICE value */) {
+                     const float* __restrict__ pag /* PAG only: one DEVICE value */,
+                     const half_t* __restrict__ eps_d /* SAG only */, float sag /* SAG only */) {
     float s = 0.f;
     if constexpr (PAG) s = pag[0];
     const bool perturbed = PAG && s != 0.f;
+    const bool degraded = SAG && sag != 0.f;
     const float a = row[0], b = row[1], cx = row[2], cm = row[3], cz = z ? row[11] : 0.f;
     const float ch[4] = {row[4], row[5], row[6], row[7]};
     const float ci = mask ? row[9] : 0.f, cn = mask ? row[10] : 0.f;
@@ -539,6 +549,8 @@ cfg_multistep_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, f
         if constexpr (CFG) ec = ld_global_h8(eps + n + q);
         half8 ep;
         if constexpr (PAG) { if (perturbed) ep = ld_global_h8(eps + (CFG ? 2 : 1) * n + q); }
+        half8 ed;
+        if constexpr (SAG) { if (degraded) ed = ld_global_h8(eps_d + q); }
         const half8 xl = ld_global_h8(lat + q);
         const half8 src = restore ? ld_global_h8(saved + q) : xl;
         float es = 1.f;
@@ -550,6 +562,7 @@ cfg_multistep_kernel(const half_t* __restrict__ eps, half_t* __restrict__ lat, f
             float e = u;
             if constexpr (CFG) { const float c = (float)ec[i]; e = u + g * (c - u); }
             if constexpr (PAG) { if (perturbed) e += s * ((CFG ? (float)ec[i] : u) - (float)ep[i]); }
+            if constexpr (SAG) { if (degraded) e += sag * (u - (float)ed[i]); }
             if constexpr (SCALED) e *= es;
             if constexpr (CFG) m[i] = a * (float)xl[i] + b * e;
             else m[i] = __builtin_fmaf(a, (float)xl[i], b * e);     // the contraction the CFG instantiations compile to: the same bits on equal halves
@@ -905,7 +918,7 @@ extern "C" int cid_cfg_ddim_step_f16(const cid_half* eps, cid_half* latents, con
     CID_CHECK_ARG(B > 0 && per_sample > 0 && n % 8 == 0, "cid_cfg_ddim_step_f16: B * per_sample must be a multiple of 8");
     hipLaunchKernelGGL(cfg_ddim_kernel<false>, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)eps, (half_t*)latents, coef, guidance, (const half_t*)mask, (const half_t*)init,
-                       (const half_t*)noise, n, (const float*)nullptr, 0, (const float*)nullptr);
+                       (const half_t*)noise, n, (const float*)nullptr, 0, (const float*)nullptr, (const half_t*)nullptr, 0.f);
     CID_CHECK_LAUNCH("cid_cfg_ddim_step_f16");
     return 0;
 }
@@ -922,7 +935,7 @@ extern "C" int cid_cfg_ddim_step_scaled_f16(const cid_half* eps, cid_half* laten
     CID_CHECK_ARG(n / 8 <= 0x7fffffffL, "cid_cfg_ddim_step_scaled_f16: B * per_sample must be below 2^34");
     hipLaunchKernelGGL(cfg_ddim_kernel<true>, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)eps, (half_t*)latents, coef, guidance, (const half_t*)mask, (const half_t*)init,
-                       (const half_t*)noise, n, escale, (int)(per_sample / 8), (const float*)nullptr);
+                       (const half_t*)noise, n, escale, (int)(per_sample / 8), (const float*)nullptr, (const half_t*)nullptr, 0.f);
     CID_CHECK_LAUNCH("cid_cfg_ddim_step_scaled_f16");
     return 0;
 }
@@ -955,7 +968,7 @@ extern "C" int cid_cfg_multistep_step_f16(const cid_half* eps, cid_half* latents
     hipLaunchKernelGGL(cfg_multistep_kernel<false>, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z, (int)z_rows,
                        (const float*)row, guidance, (const half_t*)mask, (const half_t*)init, (const half_t*)noise, n,
-                       (const float*)nullptr, 0, (const float*)nullptr);
+                       (const float*)nullptr, 0, (const float*)nullptr, (const half_t*)nullptr, 0.f);
     CID_CHECK_LAUNCH("cid_cfg_multistep_step_f16");
     return 0;
 }
@@ -976,7 +989,7 @@ extern "C" int cid_multistep_step_f16(const cid_half* eps, cid_half* latents, fl
     hipLaunchKernelGGL((cfg_multistep_kernel<false, false>), dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z, (int)z_rows,
                        (const float*)row, 0.f, (const half_t*)mask, (const half_t*)init, (const half_t*)noise, n,
-                       (const float*)nullptr, 0, (const float*)nullptr);
+                       (const float*)nullptr, 0, (const float*)nullptr, (const half_t*)nullptr, 0.f);
     CID_CHECK_LAUNCH("cid_multistep_step_f16");
     return 0;
 }
@@ -997,7 +1010,7 @@ extern "C" int cid_cfg_multistep_step_scaled_f16(const cid_half* eps, cid_half* 
     hipLaunchKernelGGL(cfg_multistep_kernel<true>, dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z, (int)z_rows,
                        (const float*)row, guidance, (const half_t*)mask, (const half_t*)init, (const half_t*)noise, n,
-                       escale, (int)(per_sample / 8), (const float*)nullptr);
+                       escale, (int)(per_sample / 8), (const float*)nullptr, (const half_t*)nullptr, 0.f);
     CID_CHECK_LAUNCH("cid_cfg_multistep_step_scaled_f16");
     return 0;
 }
@@ -1016,7 +1029,7 @@ extern "C" int cid_cfg_pag_ddim_step_f16(const cid_half* eps, cid_half* latents,
     CID_PAG_STEP_CHECKS("cid_cfg_pag_ddim_step_f16");
     hipLaunchKernelGGL((cfg_ddim_kernel<false, true>), dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
                        (const half_t*)eps, (half_t*)latents, coef, guidance, (const half_t*)mask, (const half_t*)init,
-                       (const half_t*)noise, n, (const float*)nullptr, 0, pag);
+                       (const half_t*)noise, n, (const float*)nullptr, 0, pag, (const half_t*)nullptr, 0.f);
     CID_CHECK_LAUNCH("cid_cfg_pag_ddim_step_f16");
     return 0;
 }
@@ -1034,7 +1047,7 @@ extern "C" int cid_cfg_pag_multistep_step_f16(const cid_half* eps, cid_half* lat
     hipLaunchKernelGGL((cfg_multistep_kernel<false, true, true>), dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0,
                        (hipStream_t)stream, (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z,
                        (int)z_rows, (const float*)row, guidance, (const half_t*)mask, (const half_t*)init,
-                       (const half_t*)noise, n, (const float*)nullptr, 0, pag);
+                       (const half_t*)noise, n, (const float*)nullptr, 0, pag, (const half_t*)nullptr, 0.f);
     CID_CHECK_LAUNCH("cid_cfg_pag_multistep_step_f16");
     return 0;
 }
@@ -1050,10 +1063,58 @@ extern "C" int cid_pag_multistep_step_f16(const cid_half* eps, cid_half* latents
     hipLaunchKernelGGL((cfg_multistep_kernel<false, false, true>), dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0,
                        (hipStream_t)stream, (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z,
                        (int)z_rows, (const float*)row, 0.f, (const half_t*)mask, (const half_t*)init,
-                       (const half_t*)noise, n, (const float*)nullptr, 0, pag);
+                       (const half_t*)noise, n, (const float*)nullptr, 0, pag, (const half_t*)nullptr, 0.f);
     CID_CHECK_LAUNCH("cid_pag_multistep_step_f16");
     return 0;
 }
+
+// self-attention guidance: the three step entries with the degraded prediction in a buffer of its own; cid.h
+extern "C" int cid_cfg_sag_ddim_step_f16(const cid_half* eps, cid_half* latents, const float* coef, float guidance,
+                                         const cid_half* eps_d, float sag, const cid_half* mask, const cid_half* init,
+                                         const cid_half* noise, int32_t B, int32_t per_sample, cid_stream_t stream) {
+    CID_CHECK_ARG(eps && latents && coef && eps_d, "cid_cfg_sag_ddim_step_f16: null pointer");
+    CID_PAG_STEP_CHECKS("cid_cfg_sag_ddim_step_f16");
+    hipLaunchKernelGGL((cfg_ddim_kernel<false, false, true>), dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0, (hipStream_t)stream,
+                       (const half_t*)eps, (half_t*)latents, coef, guidance, (const half_t*)mask, (const half_t*)init,
+                       (const half_t*)noise, n, (const float*)nullptr, 0, (const float*)nullptr, (const half_t*)eps_d, sag);
+    CID_CHECK_LAUNCH("cid_cfg_sag_ddim_step_f16");
+    return 0;
+}
+
+#define CID_SAG_MULTISTEP_CHECKS(NAME)                                                                                     \
+    CID_CHECK_ARG(eps && latents && hist && saved && row && eps_d, NAME ": null pointer");                                \
+    CID_CHECK_ARG((z == nullptr) == (z_rows == 0) && z_rows >= 0, NAME ": z and z_rows must come together");              \
+    CID_PAG_STEP_CHECKS(NAME)
+
+extern "C" int cid_cfg_sag_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
+                                              const cid_half* z, int32_t z_rows, const void* row, float guidance,
+                                              const cid_half* eps_d, float sag, const cid_half* mask, const cid_half* init,
+                                              const cid_half* noise, int32_t B, int32_t per_sample, cid_stream_t stream) {
+    CID_SAG_MULTISTEP_CHECKS("cid_cfg_sag_multistep_step_f16");
+    hipLaunchKernelGGL((cfg_multistep_kernel<false, true, false, true>), dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0,
+                       (hipStream_t)stream, (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z,
+                       (int)z_rows, (const float*)row, guidance, (const half_t*)mask, (const half_t*)init,
+                       (const half_t*)noise, n, (const float*)nullptr, 0, (const float*)nullptr, (const half_t*)eps_d, sag);
+    CID_CHECK_LAUNCH("cid_cfg_sag_multistep_step_f16");
+    return 0;
+}
+
+extern "C" int cid_sag_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
+                                          const cid_half* z, int32_t z_rows, const void* row, const cid_half* eps_d, float sag,
+                                          const cid_half* mask, const cid_half* init, const cid_half* noise,
+                                          int32_t B, int32_t per_sample, cid_stream_t stream) {
+    CID_SAG_MULTISTEP_CHECKS("cid_sag_multistep_step_f16");
+    for (const void* p : {(const void*)eps, (const void*)latents, (const void*)hist, (const void*)saved, (const void*)z,
+                          (const void*)row, (const void*)eps_d, (const void*)mask, (const void*)init, (const void*)noise})   // as cid_multistep_step_f16
+        CID_CHECK_ARG((uintptr_t)p % 16 == 0, "cid_sag_multistep_step_f16: every buffer must be 16-byte aligned");
+    hipLaunchKernelGGL((cfg_multistep_kernel<false, false, false, true>), dim3(grid_for(n / 8, 256, 1024)), dim3(256), 0,
+                       (hipStream_t)stream, (const half_t*)eps, (half_t*)latents, hist, (half_t*)saved, (const half_t*)z,
+                       (int)z_rows, (const float*)row, 0.f, (const half_t*)mask, (const half_t*)init,
+                       (const half_t*)noise, n, (const float*)nullptr, 0, (const float*)nullptr, (const half_t*)eps_d, sag);
+    CID_CHECK_LAUNCH("cid_sag_multistep_step_f16");
+    return 0;
+}
+#undef CID_SAG_MULTISTEP_CHECKS
 #undef CID_PAG_MULTISTEP_CHECKS
 #undef CID_PAG_STEP_CHECKS
 

@@ -11,6 +11,10 @@ Perturbed-attention guidance: with ``pag_scale`` > 0 th
 conditional rows, and the step is the ``+pag`` entry of the same kernel with the step's scale read from the step table; with
 ``pag_scale`` == 0 nothing here changes.
 
+Self-attention guidance: with ``sag_scale`` > 0 a step is [UNet, which also writes the column mass of
+the mid block's first self-attention map for the guide rows -> cid_sag_degrade_f16 -> UNet(B) on the degraded latents -> the
+``+sag`` entry of the step kernel], still one graph replay; with ``sag_scale`` == 0 nothing here changes.
+
 ``DenoiseEngine.run`` is a driver over phases that take and return named values: the static-buffer pool, the graph
 cache, the step coefficients (``_StepCoefficients``), the ControlNet plan (``_ControlPlan``), the embed-row selectors
 (``step_rows``), what the step reads of objects the engine does not own (``captured_reads``), the step table and the
@@ -31,7 +35,7 @@ import torch
 
 from . import ops
 from .controlnet import HipMultiControlNet, active_nets, controlnet_keep_table
-from .scheduler import C_IN, DDIMScheduler, LCMScheduler, pack_step_rows
+from .scheduler import C_IN, DDIMScheduler, LCMScheduler, pack_step_rows, sag_coefficient_table
 from .unet import HipUNet
 
 
@@ -60,6 +64,27 @@ def pag_scale_column(pag_scale: float, pag_adaptive_scale: float, timesteps) -> 
     if pag_adaptive_scale == 0.0:
         return np.full(t.shape, pag_scale, dtype=np.float32)
     return np.maximum(pag_scale - pag_adaptive_scale * (1000.0 - t), 0.0).astype(np.float32)
+
+
+def check_sag(sag_scale) -> float:
+    """``sag_scale`` of diffusers' StableDiffusionSAGPipeline -> a float; negative or non-finite values (and booleans, which
+    are no scales) are refused"""
+    v = sag_scale
+    if isinstance(v, bool) or not isinstance(v, (int, float, np.integer, np.floating)) or not np.isfinite(v) or v < 0.0:
+        raise ValueError(f"sag_scale = {v!r}: a finite number >= 0 (0 = off)")
+    return float(v)
+
+
+def refuse_sag_with(sag_scale: float, pag_scale: float = 0.0, guidance_rescale: float = 0.0, residuals: bool = False):
+    """what self-attention guidance is not built together with (NotImplementedError before any launch)"""
+    if sag_scale > 0.0 and pag_scale > 0.0:
+        raise NotImplementedError("sag_scale > 0 together with pag_scale > 0 is not built: one of the two guidances per call")
+    if sag_scale > 0.0 and guidance_rescale > 0.0:
+        raise NotImplementedError("sag_scale > 0 together with guidance_rescale > 0 is not built (the rescale factor is defined "
+                                  "on the classifier-free combine alone)")
+    if sag_scale > 0.0 and residuals:
+        raise NotImplementedError("SAG with ControlNet residuals is not built: pass sag_scale = 0 or run without a ControlNet "
+                                  "/ precomputed residuals")
 
 
 def check_eta(scheduler, eta: float, variance_noise=None) -> float:
@@ -133,8 +158,18 @@ class _StepCoefficients:
     rescale: float = 0.0
     single_pass: bool = False
     pag: Optional[torch.Tensor] = None          # PAG: fp32 [1], this step's scale s_i (a step-table column)
+    sag: float = 0.0                            # SAG: the scale, a launch argument of the +sag entries
 
-    def update(self, eps, lat, guidance_scale, **kw):
+    def update(self, eps, lat, guidance_scale, eps_d=None, **kw):
+        if self.sag > 0.0:                      # eps_d: the prediction on the degraded latents, in a buffer of its own
+            if self.single_pass:
+                ops.sag_multistep_step(eps, lat, self.hist, self.saved, self.row, eps_d, self.sag, z=self.z, **kw)
+            elif self.hist is None:
+                ops.cfg_sag_ddim_step(eps, lat, self.buf, guidance_scale, eps_d, self.sag, **kw)
+            else:
+                ops.cfg_sag_multistep_step(eps, lat, self.hist, self.saved, self.row, guidance_scale, eps_d, self.sag,
+                                           z=self.z, **kw)
+            return
         if self.pag is not None:                # eps carries the perturbed rows behind the conditional ones
             if self.single_pass:
                 ops.pag_multistep_step(eps, lat, self.hist, self.saved, self.row, self.pag, z=self.z, **kw)
@@ -186,8 +221,14 @@ class DenoiseEngine:
         self.captures: List[Any] = []           # key of every capture this engine ever made, in order (re-captures show twice)
         self._static: Dict[str, torch.Tensor] = {}
         # the step launch of the last run: "cfg_ddim" or "cfg_multistep", "+rescale" with guidance_rescale; "multistep" = the
-        # single pass; "+pag" with perturbed-attention guidance ("cfg_ddim+pag", "cfg_multistep+pag", "multistep+pag")
+        # single pass; "+pag" with perturbed-attention guidance ("cfg_ddim+pag", "cfg_multistep+pag", "multistep+pag"), "+sag"
+        # with self-attention guidance
         self.step_path: Optional[str] = None
+
+    @property
+    def sag_mass(self) -> Optional[torch.Tensor]:
+        """fp32 [B, H_mid * W_mid]: the column mass the last evaluation of a run with ``sag_scale`` > 0 thresholded"""
+        return self._static.get("sag_mass")
 
     def invalidate(self):
         """forget the captured graphs AND their eager warm-up (the first step after a change must run eagerly again)"""
@@ -301,8 +342,14 @@ class DenoiseEngine:
             callback: Optional[Callable[[int, int, torch.Tensor], None]] = None, callback_steps: int = 1,
             scale_initial: bool = True, unet_extra: Optional[torch.Tensor] = None, eta: float = 0.0,
             variance_noise: Optional[torch.Tensor] = None, guidance_rescale: float = 0.0, pag_scale: float = 0.0,
-            pag_adaptive_scale: float = 0.0):
-        """``pag_scale`` > 0: perturbed-attention guidance.  The UNet runs B more batch rows, the
+            pag_adaptive_scale: float = 0.0, sag_scale: float = 0.0):
+        """``sag_scale`` > 0: self-attention guidance.  The guide rows -- the unconditional ones, the
+        conditional ones in the single pass -- give the column mass of the mid block's first self-attention map; where it
+        exceeds 1 their predicted sample is blurred, the result is noised again with their predicted noise, and a second
+        UNet evaluation of those B rows on it (same context rows, time row, SDXL conditioning and ``unet_extra``) gives e_d:
+        e = u + g (c - u) + s (u - e_d), e = c + s (c - e_d) in the single pass.  Refused (NotImplementedError) together with
+        ``pag_scale`` > 0, ``guidance_rescale`` > 0 and a ControlNet or ControlNet residuals.  At 0 nothing changes.
+        ``pag_scale`` > 0: perturbed-attention guidance.  The UNet runs B more batch rows, the
         perturbed evaluation of the conditional rows (same latents, time row, context rows and SDXL conditioning; identity
         self-attention in the layers ``unet.enable_pag`` selected, the default ``("mid",)`` if none were), and the step is
         e = u + g (c - u) + s_i (c - p) -- e = c + s_i (c - p) in the single pass -- with s_i = ``pag_scale``, or
@@ -329,6 +376,9 @@ class DenoiseEngine:
         guidance_rescale = check_guidance_rescale(guidance_rescale)
         pag_scale, pag_adaptive_scale = check_pag(pag_scale, pag_adaptive_scale)
         pag = pag_scale > 0.0
+        sag_scale = check_sag(sag_scale)
+        refuse_sag_with(sag_scale, pag_scale, guidance_rescale,
+                        controlnet is not None or down_residuals is not None or mid_residual is not None)
         if pag and guidance_rescale > 0.0:
             raise NotImplementedError("pag_scale > 0 together with guidance_rescale > 0 is not built (the rescale factor is "
                                       "defined on the classifier-free combine alone)")
@@ -370,6 +420,15 @@ class DenoiseEngine:
             coef.pag = S("pag", torch.zeros(1), torch.float32)
             pag_column = (coef.pag, torch.from_numpy(pag_scale_column(pag_scale, pag_adaptive_scale, sch.timesteps)).view(-1, 1))
             self.step_path += "+pag"
+        sag_column = None
+        if sag_scale > 0.0:
+            coef.sag = sag_scale
+            sag_coef = S("sag_coef", torch.zeros(8), torch.float32)
+            sag_column = (sag_coef, torch.from_numpy(sag_coefficient_table(sch)).to(dev))
+            hm, wm = unet.mid_size(lat.shape[2], lat.shape[3])
+            sag_mass = S("sag_mass", torch.zeros(B, hm * wm), torch.float32)
+            sag_xdeg = S("sag_xdeg", torch.zeros_like(lat), torch.float16)
+            self.step_path += "+sag"
         tvals = torch.tensor(ts.astype(np.float32), device=dev)
         rows = step_rows(n_ts, first_step, start_merge_step, B, null_embeds_post is not None, dev, controlnet is not None,
                          single_pass=single, pag=pag)
@@ -422,7 +481,7 @@ class DenoiseEngine:
             cols.append((cn.kvrow, rows.controlnet))
         if temb_buf is not None:
             cols.append((temb_buf, temb_tab.view(n_ts, -1)))
-        cols += [c for c in (cn.temb_column, cn.scale_column, pag_column) if c is not None]
+        cols += [c for c in (cn.temb_column, cn.scale_column, pag_column, sag_column) if c is not None]
         if added is not None:
             pre, post = stack(p_null, p_text), stack(p_null, p_aug)
             cols.append((added["text_embeds"], torch.where(rows.merged[:, None, None], post[None], pre[None])))
@@ -438,16 +497,33 @@ class DenoiseEngine:
             net.reserve_workspace(B)
         key = (captured_reads(unet, cn.nets), B, tuple(lat.shape), float(guidance_scale), inpaint, time_ids is not None,
                dres is not None, bool(cn.nets), ("multi", len(cn.nets)) if cn.scale_column else cn.fold, extra is not None,
-               coef.hist is not None, coef.z is not None, coef.rescale, single, pag, n_b)
+               coef.hist is not None, coef.z is not None, coef.rescale, single, pag, n_b, coef.sag)
         if key != self._config_key:
             self.invalidate()
             self._config_key = key
         per_sample = lat[0].numel()
+        if coef.sag > 0.0:
+            # every forward hands its buffers out anew: the second one would reuse the first one's output, so that is kept here
+            sag_eps = S("sag_eps", torch.zeros(n_b, unet.config.out_channels, *lat.shape[2:]), torch.float16)
+            # the guide rows lead the batch in both forms, and so do their context rows and SDXL conditions
+            added_g = None if added is None else {k: v[:B] for k, v in added.items()}
+
+        def sag_step():
+            """select -> UNet(n_b), with the guide rows' column mass -> degrade -> UNet(B) on the degraded latents -> step"""
+            eps = unet.forward_tokens(lat, t_buf, kvrow, n_b, added, temb=temb_buf, in_scale=coef.in_scale, extra=extra,
+                                      sag=(sag_mass, 0, B))
+            sag_eps.copy_(eps)
+            ops.sag_degrade(lat, sag_eps[:B], sag_mass, sag_xdeg, sag_coef, hm=hm, wm=wm)
+            eps_d = unet.forward_tokens(sag_xdeg, t_buf, kvrow[:B], B, added_g, temb=temb_buf, in_scale=coef.in_scale,
+                                        extra=extra)
+            coef.update(sag_eps, lat, guidance_scale, eps_d=eps_d, B=B, per_sample=per_sample, **blend)
 
         def step(active):
             """``active``: the nets that run, () = none -- one forward after another on the current stream (no forked
             capture streams, no parallel graph branches)"""
             table.select()
+            if coef.sag > 0.0:                  # (no ControlNet, no residuals: refused above)
+                return sag_step()
             d, m, scales = dres, mres, None
             res = {k: cn.nets[k].forward_tokens(lat, t_buf, cn.kvrow, B, cn.cond[k], cn.fold, temb=cn.temb[k],
                                                 in_scale=coef.in_scale) for k in active}

@@ -270,6 +270,50 @@ def self_attn(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Ten
     return out
 
 
+def attn_colmass(q: torch.Tensor, k: torch.Tensor, mass: torch.Tensor, *, B: int, N: int, heads: int, d: int, ldq: int,
+                 ldk: int, n_keys: Optional[int] = None):
+    """column mass of the self-attention map of ``B`` samples (cid_attn_colmass_f16; self-attention guidance):
+    ``mass`` fp32 [B, N] = mean over heads of the column sums of softmax(q k^T); ``q`` / ``k`` as ``self_attn`` takes them.
+    Columns >= ``n_keys`` are written as 0, rows >= ``n_keys`` do not contribute.  Deterministic."""
+    lib = _lib.load()
+    _req(q, "attn_colmass.q")
+    _req(k, "attn_colmass.k")
+    _req(mass, "attn_colmass.mass", torch.float32)
+    if mass.numel() != B * N or not mass.is_contiguous():
+        raise _lib.CidError(f"attn_colmass.mass: {mass.numel()} elements; B * N = {B * N}, contiguous")
+    for name, t, ld in (("q", q, ldq), ("k", k, ldk)):      # (slices of one buffer: what lies behind the pointer counts)
+        have = t.untyped_storage().nbytes() // t.element_size() - t.storage_offset()
+        if have < (B * N - 1) * ld + heads * d:
+            raise _lib.CidError(f"attn_colmass.{name}: {have} elements behind the pointer; B * N = {B * N} rows at pitch {ld} "
+                                f"need {(B * N - 1) * ld + heads * d}")
+    check(lib.cid_attn_colmass_f16(_p(q), ldq, _p(k), ldk, _p(mass), B, N, N if n_keys is None else n_keys, heads, d,
+                                   _stream()), "cid_attn_colmass_f16")
+    return mass
+
+
+def sag_degrade(latents: torch.Tensor, eps_g: torch.Tensor, mass: torch.Tensor, out: torch.Tensor, coef: torch.Tensor, *,
+                hm: int, wm: int):
+    """the degraded latents of self-attention guidance (cid_sag_degrade_f16): ``latents`` / ``eps_g`` / ``out`` fp16
+    [B, C, h, w], ``mass`` fp32 [B, hm * wm] (``attn_colmass``), ``coef`` eight fp32 words on the device
+    (``scheduler.sag_coefficient_table``): out = n_d (mass > 1 ? blur(x0) : x0) + n_e ehat"""
+    lib = _lib.load()
+    if latents.dim() != 4:
+        raise _lib.CidError(f"sag_degrade.latents: shape {tuple(latents.shape)}; [B, C, h, w]")
+    B, C_, h, w = latents.shape
+    for name, t in (("latents", latents), ("eps_g", eps_g), ("out", out)):
+        _req(t, f"sag_degrade.{name}")
+        if tuple(t.shape) != (B, C_, h, w) or not t.is_contiguous():
+            raise _lib.CidError(f"sag_degrade.{name}: shape {tuple(t.shape)}; contiguous {(B, C_, h, w)}")
+    _req(mass, "sag_degrade.mass", torch.float32)
+    _req(coef, "sag_degrade.coef", torch.float32)
+    if mass.numel() != B * hm * wm or not mass.is_contiguous() or coef.numel() < 8:
+        raise _lib.CidError(f"sag_degrade: mass / coef hold {mass.numel()} / {coef.numel()} elements; B * hm * wm = "
+                            f"{B * hm * wm} (contiguous) / at least 8")
+    check(lib.cid_sag_degrade_f16(_p(latents), _p(eps_g), _p(mass), _p(out), _p(coef), B, C_, h, w, hm, wm, _stream()),
+          "cid_sag_degrade_f16")
+    return out
+
+
 def self_attn_causal(q: torch.Tensor, k: torch.Tensor, vt: torch.Tensor, out: torch.Tensor, *, B: int, N: int,
                      heads: int, d: int, ldq: int, ldk: int, ldo: int, n_keys: int):
     """causal self-attention of the CLIP text towers: key j is visible to query i iff j <= i and j < n_keys (d = 64)"""
@@ -1144,6 +1188,82 @@ def pag_multistep_step(eps: torch.Tensor, latents: torch.Tensor, hist: torch.Ten
     check(_lib.load().cid_pag_multistep_step_f16(_p(eps), _p(latents), _p(hist), _p(saved), _p(z), z_rows, _p(row), _p(pag),
                                                  _p(mask), _p(init), _p(noise), B, per_sample, _stream()),
           "cid_pag_multistep_step_f16")
+    return latents
+
+
+def _req_eps_d(eps_d: torch.Tensor, n: int, what: str):
+    _req(eps_d, f"{what}.eps_d")
+    if eps_d.numel() != n:
+        raise _lib.CidError(f"{what}.eps_d: {eps_d.numel()} elements, B * per_sample = {n}")
+
+
+def cfg_sag_ddim_step(eps: torch.Tensor, latents: torch.Tensor, coef: torch.Tensor, guidance: float, eps_d: torch.Tensor,
+                      sag: float, *, B: int, per_sample: int, mask: Optional[torch.Tensor] = None,
+                      init: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None):
+    """``cfg_ddim_step`` with self-attention guidance (cid_cfg_sag_ddim_step_f16): ``eps`` fp16 [2B, per_sample], ``eps_d``
+    fp16 [B, per_sample] the prediction on the degraded latents, e = u + g (c - u) + sag (u - e_d); at sag == 0 ``eps_d`` is
+    not read and the bits are ``cfg_ddim_step``'s"""
+    lib = _lib.load()
+    n = B * per_sample
+    _req(eps, "cfg_sag_ddim_step.eps")
+    _req(latents, "cfg_sag_ddim_step.latents")
+    _req(coef, "cfg_sag_ddim_step.coef", torch.float32)
+    _req_eps_d(eps_d, n, "cfg_sag_ddim_step")
+    if eps.numel() != 2 * n or latents.numel() != n or coef.numel() < 4:
+        raise _lib.CidError(f"cfg_sag_ddim_step: eps / latents / coef hold {eps.numel()} / {latents.numel()} / {coef.numel()} "
+                            f"elements; B * per_sample = {n} needs {2 * n} / {n} / at least 4")
+    _req_step_blend("cfg_sag_ddim_step", n, mask, init, noise)
+    check(lib.cid_cfg_sag_ddim_step_f16(_p(eps), _p(latents), _p(coef), float(guidance), _p(eps_d), float(sag), _p(mask),
+                                        _p(init), _p(noise), B, per_sample, _stream()), "cid_cfg_sag_ddim_step_f16")
+    return latents
+
+
+def _sag_multistep(what: str, eps_rows: int, eps, latents, hist, saved, row, eps_d, B, per_sample, z, mask, init, noise) -> int:
+    """the shared checks of the two SAG multistep entries -> z_rows"""
+    n = B * per_sample
+    _req(eps, f"{what}.eps")
+    _req(latents, f"{what}.latents")
+    _req(hist, f"{what}.hist", torch.float32)
+    _req(saved, f"{what}.saved")
+    _req(row, f"{what}.row", torch.float32)
+    _req_eps_d(eps_d, n, what)
+    if eps.numel() != eps_rows * n or latents.numel() != n or hist.numel() != 4 * n or saved.numel() != n or row.numel() != 16:
+        raise _lib.CidError(f"{what}: eps / latents / hist / saved / row hold {eps.numel()} / {latents.numel()} / "
+                            f"{hist.numel()} / {saved.numel()} / {row.numel()} elements; B * per_sample = {n} needs "
+                            f"{eps_rows * n} / {n} / {4 * n} / {n} / 16")
+    z_rows = 0
+    if z is not None:
+        _req(z, f"{what}.z")
+        if z.numel() == 0 or z.numel() % n:
+            raise _lib.CidError(f"{what}.z: {z.numel()} elements are not rows of B * per_sample = {n}")
+        z_rows = z.numel() // n
+    _req_step_blend(what, n, mask, init, noise)
+    return z_rows
+
+
+def cfg_sag_multistep_step(eps: torch.Tensor, latents: torch.Tensor, hist: torch.Tensor, saved: torch.Tensor,
+                           row: torch.Tensor, guidance: float, eps_d: torch.Tensor, sag: float, *, B: int, per_sample: int,
+                           z: Optional[torch.Tensor] = None, mask: Optional[torch.Tensor] = None,
+                           init: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None):
+    """``cfg_multistep_step`` with self-attention guidance (cid_cfg_sag_multistep_step_f16): ``eps`` fp16 [2B, per_sample],
+    ``eps_d`` and ``sag`` as in ``cfg_sag_ddim_step``"""
+    z_rows = _sag_multistep("cfg_sag_multistep_step", 2, eps, latents, hist, saved, row, eps_d, B, per_sample, z, mask, init, noise)
+    check(_lib.load().cid_cfg_sag_multistep_step_f16(_p(eps), _p(latents), _p(hist), _p(saved), _p(z), z_rows, _p(row),
+                                                     float(guidance), _p(eps_d), float(sag), _p(mask), _p(init), _p(noise), B,
+                                                     per_sample, _stream()), "cid_cfg_sag_multistep_step_f16")
+    return latents
+
+
+def sag_multistep_step(eps: torch.Tensor, latents: torch.Tensor, hist: torch.Tensor, saved: torch.Tensor, row: torch.Tensor,
+                       eps_d: torch.Tensor, sag: float, *, B: int, per_sample: int, z: Optional[torch.Tensor] = None,
+                       mask: Optional[torch.Tensor] = None, init: Optional[torch.Tensor] = None,
+                       noise: Optional[torch.Tensor] = None):
+    """``multistep_step`` (the single pass) with self-attention guidance (cid_sag_multistep_step_f16): ``eps`` fp16
+    [B, per_sample], e = c + sag (c - e_d); at sag == 0 the bits are ``multistep_step``'s"""
+    z_rows = _sag_multistep("sag_multistep_step", 1, eps, latents, hist, saved, row, eps_d, B, per_sample, z, mask, init, noise)
+    check(_lib.load().cid_sag_multistep_step_f16(_p(eps), _p(latents), _p(hist), _p(saved), _p(z), z_rows, _p(row), _p(eps_d),
+                                                 float(sag), _p(mask), _p(init), _p(noise), B, per_sample, _stream()),
+          "cid_sag_multistep_step_f16")
     return latents
 
 

@@ -40,7 +40,7 @@ import numpy as np
 import torch
 
 from .controlnet import HipMultiControlNet, prepare_control_arguments
-from .denoise import DenoiseEngine, check_eta, check_guidance_rescale, check_pag
+from .denoise import DenoiseEngine, check_eta, check_guidance_rescale, check_pag, check_sag, refuse_sag_with
 from .scheduler import (DDIMScheduler, DPMSolverMultistepScheduler, EulerDiscreteScheduler, LCMScheduler,  # noqa: F401
                         PNDMScheduler)
 from .unet import HipUNet
@@ -161,15 +161,25 @@ class _BasePipeline:
         """drop the selection of :meth:`enable_pag` (a later call with ``pag_scale`` > 0 selects ``"mid"`` again)"""
         self.unet.disable_pag()
 
-    def _check_pag(self, pag_scale, pag_adaptive_scale, guidance_rescale: float = 0.0) -> dict:
-        """the two PAG keywords of a ``__call__``, validated -> the engine's keywords; the refusals that need no tensor are
-        made here, before the pre-loop runs"""
+    def _check_pag(self, pag_scale, pag_adaptive_scale, guidance_rescale: float = 0.0, sag_scale=0.0) -> dict:
+        """the PAG keywords and ``sag_scale`` of a ``__call__``, validated -> the engine's keywords; the refusals that need no
+        tensor are made here, before the pre-loop runs.  ``sag_scale`` == 0 adds no keyword: the call is the call without it."""
         pag_scale, pag_adaptive_scale = check_pag(pag_scale, pag_adaptive_scale)
+        sag_scale = check_sag(sag_scale)
+        refuse_sag_with(sag_scale, pag_scale, guidance_rescale)
+        if sag_scale > 0.0:
+            return dict(sag_scale=sag_scale)
         if pag_scale > 0.0 and guidance_rescale > 0.0:
             raise NotImplementedError("pag_scale > 0 together with guidance_rescale > 0 is not built")
         if pag_scale > 0.0 and not self.unet.pag_layers:
             self.unet.enable_pag()
         return dict(pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale)
+
+    @property
+    def sag_mass(self):
+        """fp32 [B, H_mid * W_mid], or None: the column mass of the mid block's first self-attention map that the last
+        evaluation of the last call with ``sag_scale`` > 0 thresholded at 1; a view of the engine's buffer"""
+        return self._engine.sag_mass
 
     @property
     def scheduler(self):
@@ -646,11 +656,13 @@ class ConsistentIDStableDiffusionPipeline(_IDPreLoop, _SD15PromptEncoding, _Base
                  callback_steps: int = 1, input_id_images=None, start_merge_step: int = 0,
                  class_tokens_mask=None, prompt_embeds_text_only=None, variance_noise: Optional[torch.Tensor] = None,
                  max_embeddings_multiples: int = 1, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
-                 guidance_rescale: float = 0.0):
+                 sag_scale: float = 0.0, guidance_rescale: float = 0.0):
         """``guidance_rescale`` (diffusers 0.23 StableDiffusionPipeline; rescale_noise_cfg's phi): > 0 rescales the guided
         prediction to the conditional one's standard deviation, per sample and step.
         ``pag_scale`` / ``pag_adaptive_scale``: perturbed-attention guidance as diffusers' PAG pipelines spell it (``enable_pag``;
         DESIGN.md 4.28); 0 = off, not together with ``guidance_rescale``.
+        ``sag_scale``: self-attention guidance as diffusers' StableDiffusionSAGPipeline spells it; 0 = off, not
+        together with ``pag_scale`` or ``guidance_rescale``.
         ``max_embeddings_multiples`` >= 2: the negative prompt of a pre-loop call is a long weighted prompt
         (prepare_id_prompt_embeds).  ``prompt_embeds`` may have any [3B, T + num_tokens, Dc] the
         cross-attention kernels take (T <= 1024 text rows).
@@ -659,7 +671,7 @@ class ConsistentIDStableDiffusionPipeline(_IDPreLoop, _SD15PromptEncoding, _Base
         ``prompt_embeds`` (cat([null, augmented, text_only])) and ``latents`` directly.  ``num_images_per_prompt`` = n on the
         prompt path: n samples of the one identity -- the embeds repeated n times, the latents one draw of [n, C, h, w]."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
-        pag_kw = self._check_pag(pag_scale, pag_adaptive_scale, guidance_rescale)
+        pag_kw = self._check_pag(pag_scale, pag_adaptive_scale, guidance_rescale, sag_scale)
         if self._takes_id_pre_loop(prompt, input_id_images, prompt_embeds):
             prompt_embeds = self._id_call_prompt_embeds(prompt, input_id_images, negative_prompt, num_images_per_prompt,
                                                         max_embeddings_multiples)
@@ -735,15 +747,18 @@ class ConsistentIDStableDiffusionXLPipeline(_BasePipeline):
                  start_merge_step: int = 0, class_tokens_mask=None, prompt_embeds_text_only=None,
                  pooled_prompt_embeds_text_only=None, add_time_ids: Optional[torch.Tensor] = None,
                  negative_prompt_embeds_facial: Optional[torch.Tensor] = None,
-                 variance_noise: Optional[torch.Tensor] = None, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0):
+                 variance_noise: Optional[torch.Tensor] = None, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
+                 sag_scale: float = 0.0):
         """``pag_scale`` / ``pag_adaptive_scale``: perturbed-attention guidance (``enable_pag``) -- the perturbed
         rows take the conditional rows' pooled embeds and time ids.
+        ``sag_scale``: self-attention guidance -- the second evaluation takes the unconditional rows' context
+        (the post-merge null set once merged), pooled embeds and time ids.
         pooled_prompt_embeds = pooled embeds used AFTER the merge step, pooled_prompt_embeds_text_only
         BEFORE it, negative_pooled_prompt_embeds for the unconditional half (ref SDXL :620-631);
         add_time_ids [2B, 6] (ref :531-539).  ``guidance_rescale``: diffusers' rescale_noise_cfg, which the reference's loop
         has commented out (ref SDXL :652-654); honoured here, 0 = the reference's behaviour."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
-        pag_kw = self._check_pag(pag_scale, pag_adaptive_scale, guidance_rescale)
+        pag_kw = self._check_pag(pag_scale, pag_adaptive_scale, guidance_rescale, sag_scale)
         self._check_hot_path_inputs(prompt, input_id_images, prompt_embeds, latents, output_type)
         assert guidance_scale >= 1.0
         variance_noise = self._variance_noise(eta, generator, variance_noise, latents, num_inference_steps)
@@ -938,9 +953,9 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                  noise: Optional[torch.Tensor] = None, mask_latents: Optional[torch.Tensor] = None,
                  down_block_res_samples=None, mid_block_res_sample=None, variance_noise: Optional[torch.Tensor] = None,
                  max_embeddings_multiples: int = 1, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
-                 guidance_rescale: float = 0.0):
+                 sag_scale: float = 0.0, guidance_rescale: float = 0.0):
         """``pag_scale`` / ``pag_adaptive_scale``: perturbed-attention guidance (``enable_pag``), not together
-        with precomputed ControlNet residuals.
+        with precomputed ControlNet residuals.  ``sag_scale``: self-attention guidance, under the same condition.
         ``guidance_rescale`` / ``max_embeddings_multiples``: engine extensions here (diffusers' inpaint pipelines do not take
         them), as in ConsistentIDStableDiffusionPipeline.__call__.  The reference's call, ``pipe(prompt, input_id_images=face, mask_image=mask, height=, width=, ...)``, runs its whole
         pre-loop: the ID pre-loop on ``input_id_images[0]`` (prepare_id_prompt_embeds; ref :157-229), image_prep.py on the
@@ -964,14 +979,14 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                              mask_latents=mask_latents, down_block_res_samples=down_block_res_samples,
                              mid_block_res_sample=mid_block_res_sample, variance_noise=variance_noise,
                              guidance_rescale=guidance_rescale, max_embeddings_multiples=max_embeddings_multiples,
-                             pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale)
+                             pag_scale=pag_scale, pag_adaptive_scale=pag_adaptive_scale, sag_scale=sag_scale)
 
     def _inpaint(self, *, prompt, image, mask_image, masked_image_latents, height, width, strength, num_inference_steps,
                  guidance_scale, negative_prompt, num_images_per_prompt, eta, generator, latents, prompt_embeds,
                  output_type, return_dict, callback, callback_steps, input_id_images, start_merge_step, image_latents,
                  noise, mask_latents, down_block_res_samples, mid_block_res_sample, variance_noise, control=None,
                  max_embeddings_multiples: int = 1, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
-                 guidance_rescale: float = 0.0):
+                 sag_scale: float = 0.0, guidance_rescale: float = 0.0):
         """The body both inpaint ``__call__``s share (inpaint ref :127-359, CN :180-456).  ``control``: the ControlNet
         pipeline's (control_image, controlnet_conditioning_scale, control_guidance_start, control_guidance_end)."""
         guidance_rescale = check_guidance_rescale(guidance_rescale)
@@ -979,7 +994,9 @@ class StableDiffusionInpaintConsistentIDPipeline(_IDPreLoop, _SD15PromptEncoding
                                                                   or mid_block_res_sample is not None):
             raise NotImplementedError("PAG with ControlNet residuals is not built: the ControlNet-inpaint pipeline and "
                                       "precomputed residuals take pag_scale = 0")
-        pag_kw = self._check_pag(pag_scale, pag_adaptive_scale, guidance_rescale)
+        refuse_sag_with(check_sag(sag_scale), residuals=control is not None or down_block_res_samples is not None
+                        or mid_block_res_sample is not None)
+        pag_kw = self._check_pag(pag_scale, pag_adaptive_scale, guidance_rescale, sag_scale)
         prompt_embeds, image, mask_image, height, width, normalize = self._call_inputs(
             prompt, input_id_images, prompt_embeds, negative_prompt, num_images_per_prompt, image, mask_image, height, width,
             max_embeddings_multiples)
@@ -1044,8 +1061,8 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
                  mask_latents: Optional[torch.Tensor] = None, down_block_res_samples=None, mid_block_res_sample=None,
                  masked_image_latents: Optional[torch.Tensor] = None, variance_noise: Optional[torch.Tensor] = None,
                  max_embeddings_multiples: int = 1, pag_scale: float = 0.0, pag_adaptive_scale: float = 0.0,
-                 guidance_rescale: float = 0.0):
-        """``pag_scale`` > 0 is refused here (NotImplementedError): PAG with ControlNet residuals is not built.
+                 sag_scale: float = 0.0, guidance_rescale: float = 0.0):
+        """``pag_scale`` > 0 and ``sag_scale`` > 0 are refused here (NotImplementedError): neither is built with ControlNet residuals.
         ``prompt`` / ``input_id_images`` / ``image`` / ``mask_image`` / ``guidance_rescale`` / ``max_embeddings_multiples``: as in
         StableDiffusionInpaintConsistentIDPipeline.__call__ (CN :180-265).  ``control_image``: a float tensor [B, 3, 8h, 8w]
         in [0, 1], or one PIL image (or a list of one), converted to RGB and resized to the final height x width by
@@ -1070,4 +1087,4 @@ class StableDiffusionControlNetInpaintConsistentIDPipeline(StableDiffusionInpain
                              control=(control_image, controlnet_conditioning_scale, control_guidance_start,
                              control_guidance_end), guidance_rescale=guidance_rescale,
                              max_embeddings_multiples=max_embeddings_multiples, pag_scale=pag_scale,
-                             pag_adaptive_scale=pag_adaptive_scale)
+                             pag_adaptive_scale=pag_adaptive_scale, sag_scale=sag_scale)

@@ -150,6 +150,26 @@ def _next_blend(sch, inpaint: bool, i: int) -> Tuple[float, float]:
     return 1.0, 0.0
 
 
+def _vp_sag_coefficients(a_t: float, prediction_type: str) -> Tuple[float, ...]:
+    """(p_x, p_e, q_x, q_e, n_d, n_e) of self-attention guidance under a variance-preserving noise
+    model at alphas_cumprod ``a_t``: x0 = p_x x + p_e out, ehat = q_x x + q_e out, and add_noise(D, ehat) = n_d D + n_e ehat"""
+    sa, sb = a_t ** 0.5, (1.0 - a_t) ** 0.5
+    if prediction_type == "v_prediction":
+        return sa, -sb, sb, sa, sa, sb
+    if a_t == 0.0:
+        raise ValueError("sag_coefficients: the coefficients are not finite where alphas_cumprod is 0 -- with prediction_type "
+                         "'epsilon' the sample cannot be predicted from the model output there (the terminal step of a zero-SNR "
+                         "schedule needs prediction_type='v_prediction')")
+    return 1.0 / sa, -sb / sa, 0.0, 1.0, sa, sb
+
+
+def sag_coefficient_table(sch) -> np.ndarray:
+    """[len(timesteps), 8] fp32: ``sch.sag_coefficients`` of every schedule entry (one row per UNet evaluation: PNDM's
+    repeated timestep has a row of its own) and two zero words -- the step-table column cid_sag_degrade_f16 reads"""
+    rows = [[*sch.sag_coefficients(t), 0.0, 0.0] for t in sch.timesteps]
+    return _check_finite(np.asarray(rows, dtype=np.float64).reshape(-1, 8), sch, "sag_coefficients").astype(np.float32)
+
+
 class DDIMScheduler:
     order = 1
     init_noise_sigma = 1.0
@@ -219,6 +239,10 @@ class DDIMScheduler:
     def add_noise_coefficients(self, t) -> Tuple[float, float]:
         a = float(self.alphas_cumprod[int(t)])
         return a ** 0.5, (1.0 - a) ** 0.5
+
+    def sag_coefficients(self, t) -> Tuple[float, ...]:
+        """(p_x, p_e, q_x, q_e, n_d, n_e) at timestep ``t``: the predicted sample, the predicted noise and add_noise at ``t``"""
+        return _vp_sag_coefficients(float(self.alphas_cumprod[int(t)]), self.prediction_type)
 
     def coefficient_table(self, inpaint: bool = False) -> np.ndarray:
         """[steps, 4] fp32: c_x, c_eps, c_init, c_noise (last two for the inpaint blend of the
@@ -309,6 +333,16 @@ class EulerDiscreteScheduler:
         i = int(np.argmin(np.abs(self.timesteps - float(t))))
         return 1.0, float(self.sigmas[i])
 
+    def sag_coefficients(self, t) -> Tuple[float, ...]:
+        """(p_x, p_e, q_x, q_e, n_d, n_e) at inference timestep ``t``, in this sampler's own variables (x = x0 + sigma eps; the
+        model input is scaled by c_in like every other): epsilon prediction x0 = x - sigma e, ehat = e; v-prediction
+        x0 = x / (sigma^2 + 1) - sigma v / sqrt(sigma^2 + 1), ehat = (x - x0) / sigma; add_noise(D, ehat) = D + sigma ehat"""
+        sg = self.add_noise_coefficients(t)[1]
+        if self.prediction_type == "v_prediction":
+            r = (sg * sg + 1.0) ** 0.5
+            return 1.0 / (r * r), -sg / r, sg / (r * r), 1.0 / r, 1.0, sg
+        return 1.0, -sg, 0.0, 1.0, 1.0, sg
+
     def coefficient_table(self, inpaint: bool = False) -> np.ndarray:
         """[steps, 5] fp32: c_x, c_eps, c_init, c_noise, c_in (see DDIMScheduler.coefficient_table).  v-prediction (diffusers:
         pred_original = -sigma v / sqrt(sigma^2 + 1) + x / (sigma^2 + 1), derivative = (x - pred_original) / sigma):
@@ -380,6 +414,10 @@ class PNDMScheduler:
     def add_noise_coefficients(self, t) -> Tuple[float, float]:
         a = float(self.alphas_cumprod[int(t)])
         return a ** 0.5, (1.0 - a) ** 0.5
+
+    def sag_coefficients(self, t) -> Tuple[float, ...]:
+        """(p_x, p_e, q_x, q_e, n_d, n_e) at timestep ``t``: the predicted sample, the predicted noise and add_noise at ``t``"""
+        return _vp_sag_coefficients(float(self.alphas_cumprod[int(t)]), self.prediction_type)
 
     def coefficient_rows(self, inpaint: bool = False, first_step: int = 0, dtype=np.float32) -> np.ndarray:
         """[len(timesteps), 16] multistep rows: ``step_plms`` over entries [first_step, len) with a counter and a history
@@ -493,6 +531,10 @@ class DPMSolverMultistepScheduler:
         a = float(self.alphas_cumprod[int(t)])
         return a ** 0.5, (1.0 - a) ** 0.5
 
+    def sag_coefficients(self, t) -> Tuple[float, ...]:
+        """(p_x, p_e, q_x, q_e, n_d, n_e) at timestep ``t``: the predicted sample, the predicted noise and add_noise at ``t``"""
+        return _vp_sag_coefficients(float(self.alphas_cumprod[int(t)]), self.prediction_type)
+
     def coefficient_rows(self, inpaint: bool = False, first_step: int = 0, dtype=np.float32) -> np.ndarray:
         """[len(timesteps), 16] multistep rows over entries [first_step, len); the history starts empty at ``first_step``.
         With alpha = 1 / sqrt(sigma^2 + 1), s = sigma alpha, lambda = log alpha - log s, h = lambda_(i+1) - lambda_i,
@@ -588,6 +630,10 @@ class LCMScheduler:
         """(c_skip, c_out) of the consistency parameterisation at timestep t"""
         s, sd = self.timestep_scaling * float(t), self.sigma_data
         return sd * sd / (s * s + sd * sd), s / (s * s + sd * sd) ** 0.5
+
+    def sag_coefficients(self, t) -> Tuple[float, ...]:
+        """(p_x, p_e, q_x, q_e, n_d, n_e) at timestep ``t``: the predicted sample, the predicted noise and add_noise at ``t``"""
+        return _vp_sag_coefficients(float(self.alphas_cumprod[int(t)]), self.prediction_type)
 
     def coefficient_rows(self, inpaint: bool = False, first_step: int = 0, dtype=np.float32) -> np.ndarray:
         """[len(timesteps), 16] multistep rows over entries [first_step, len).  The kernel's m is the predicted sample x0

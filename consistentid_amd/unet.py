@@ -275,6 +275,13 @@ class HipUNet:
         """size the GroupNorm workspace for a forward of batch ``B`` now, so that its address is known before the first step"""
         self._ws(B)
 
+    def mid_size(self, h: int, w: int) -> tuple:
+        """(H_mid, W_mid) of the mid block for latents of ``h`` x ``w``: every down block's sampler halves both"""
+        for blk in self.downs:
+            if blk.sampler:
+                h, w = h // 2, w // 2
+        return h, w
+
     def _heads_of(self, block_name: str) -> int:
         for blk in self.downs + [self.mid] + self.ups:
             for t in blk.attentions:
@@ -342,8 +349,10 @@ class HipUNet:
         out.view(rep, -1).copy_(t.reshape(1, -1).expand(rep, -1))
         return out
 
-    def _attn1_core(self, t: TransformerSpec, b: str, h, Bs: int, N: int, N_real: int):
-        """fused q / k / v projection of LayerNorm1(``h``) and the self-attention of ``Bs`` samples of N tokens -> [Bs * N, c]"""
+    def _attn1_core(self, t: TransformerSpec, b: str, h, Bs: int, N: int, N_real: int, sag=None):
+        """fused q / k / v projection of LayerNorm1(``h``) and the self-attention of ``Bs`` samples of N tokens -> [Bs * N, c].
+        ``sag`` = (mass fp32 [rows, N_real], first_row, rows): the column mass of the attention map of samples
+        [first_row, first_row + rows) is written there (cid_attn_colmass_f16) while q and k are still in their buffer."""
         W, c = self.W, t.channels
         d = c // t.heads
         M = Bs * N
@@ -360,6 +369,15 @@ class HipUNet:
         ao = self._empty(M, c)
         ops.self_attn(qk, qk[:, c:], vt, ao, B=Bs, N=N, heads=t.heads, d=d, ldq=2 * c, ldk=2 * c, ldo=c,
                       n_keys=N_real)
+        if sag is not None:
+            mass, first, rows = sag
+            assert 0 <= first and first + rows <= Bs and tuple(mass.shape) == (rows, N_real), (first, rows, Bs, mass.shape, N_real)
+            qs = qk[first * N:(first + rows) * N]
+            # a padded token axis: the kernel's rows are N wide (pad columns 0); the real columns are copied out
+            wide = mass if N == N_real else torch.empty(rows, N, dtype=torch.float32, device=self.device)
+            ops.attn_colmass(qs, qs[:, c:], wide, B=rows, N=N, heads=t.heads, d=d, ldq=2 * c, ldk=2 * c, n_keys=N_real)
+            if wide is not mass:
+                mass.copy_(wide[:, :N_real])
         return ao
 
     def _attn1_perturbed(self, t: TransformerSpec, b: str, h, B: int, N: int, N_real: int, pag_rows: int):
@@ -384,8 +402,9 @@ class HipUNet:
             ops.gemm(ln1, P[f"{b}.attn1.vo.w"], h2[Ml:], M=Mp, N=c, c1=c, bias=W[f"{b}.attn1.out.b"], res=hp, ldr=c)
         return h2
 
-    def _transformer(self, t: TransformerSpec, x, B, H, Wd, kvrow, Bp: Optional[int] = None, pag_rows: int = 0):
-        """``pag_rows`` > 0: the trailing ``pag_rows`` samples of the batch are perturbed -- in the blocks ``enable_pag``
+    def _transformer(self, t: TransformerSpec, x, B, H, Wd, kvrow, Bp: Optional[int] = None, pag_rows: int = 0, sag=None):
+        """``sag``: ``_attn1_core``'s, for the first transformer block (self-attention guidance reads the mid block's).
+        ``pag_rows`` > 0: the trailing ``pag_rows`` samples of the batch are perturbed -- in the blocks ``enable_pag``
         selected their self-attention is the identity (``_attn1_perturbed``); every other block runs all rows as ever.
         ``Bp`` < B: the rows of ``x`` are the Bp distinct samples of a CFG batch B = rep * Bp whose halves were identical
         so far (same latents, same timestep).  Everything up to the first cross-attention -- the first place the two
@@ -419,6 +438,9 @@ class HipUNet:
             b = f"{n}.transformer_blocks.{k}"
             # --- self attention (Consistent_AttProcessor, attention.py:110-174)
             rep = B // Bc
+            mass = sag if k == 0 else None
+            # (the mass is taken from a block that runs the whole batch through one attention launch; only the mid block is asked)
+            assert mass is None or (Bc == B and not (pag_rows > 0 and b in self._pag)), "sag on a de-duplicated or perturbed block"
             if pag_rows > 0 and b in self._pag:     # identity attention on the trailing pag_rows samples
                 assert Bc == B, "a perturbed block runs on the whole batch (forward_tokens keeps it out of the de-duplication)"
                 h2 = self._attn1_perturbed(t, b, h, B, N, N_real, pag_rows)
@@ -427,7 +449,7 @@ class HipUNet:
                 h2 = self._empty(2 * M, c)
                 ops.gemm(ao, W[f"{b}.attn1.out.w"], h2[:M], M=M, N=c, c1=c, bias=W[f"{b}.attn1.out.b"], res=h, ldr=c, out2=h2[M:])
             else:
-                ao = self._attn1_core(t, b, h, Bc, N, N_real)
+                ao = self._attn1_core(t, b, h, Bc, N, N_real, sag=mass)
                 h2 = self._empty(M, c)
                 ops.gemm(ao, W[f"{b}.attn1.out.w"], h2, M=M, N=c, c1=c, bias=W[f"{b}.attn1.out.b"], res=h, ldr=c)
             if Bc != B:     # ... and the block input (the residual of proj_out) exists twice already where its producer wrote it so
@@ -638,7 +660,7 @@ class HipUNet:
                        added_cond_kwargs=None, down_residuals: Optional[Sequence[torch.Tensor]] = None,
                        mid_residual: Optional[torch.Tensor] = None, temb: Optional[torch.Tensor] = None,
                        in_scale: Optional[torch.Tensor] = None, extra: Optional[torch.Tensor] = None,
-                       residual_scales: Optional[torch.Tensor] = None, pag_rows: int = 0) -> torch.Tensor:
+                       residual_scales: Optional[torch.Tensor] = None, pag_rows: int = 0, sag=None) -> torch.Tensor:
         """sample: NCHW fp16 [Bin, cin, H, W] with B % Bin == 0 (batch row b reads sample b % Bin,
         i.e. the CFG duplication of ref :537-539 costs no copy).  Returns NCHW fp16 [B, cout, H, W].
         ``residual_scales`` (DEVICE fp32, one value per net) selects the multi-ControlNet form: ``down_residuals`` and
@@ -650,8 +672,21 @@ class HipUNet:
         and not touched by ``in_scale``.
         ``pag_rows`` > 0 (perturbed-attention guidance): the TRAILING ``pag_rows`` batch rows are the perturbed evaluation of
         the rows in front of them -- same latents (b % Bin), same time row, whatever ``kvrow`` and ``added_cond_kwargs`` give
-        them -- and the blocks ``enable_pag`` selected run identity self-attention on them."""
+        them -- and the blocks ``enable_pag`` selected run identity self-attention on them.
+        ``sag`` = (mass, first_row, rows) (self-attention guidance): ``mass`` fp32 [rows, hm * wm], (hm, wm) =
+        ``mid_size(H, W)``, receives the column mass of the attention map of ``mid_block.attentions[0].transformer_blocks[0]
+        .attn1`` for batch rows [first_row, first_row + rows) -- one more launch beside that layer's attention; None launches
+        what is launched without it."""
         cfg, W = self.config, self.W
+        if sag is not None:
+            mass, first, rows = sag
+            if pag_rows:
+                raise NotImplementedError("self-attention guidance together with perturbed rows is not built")
+            if not (0 <= first and rows > 0 and first + rows <= B):
+                raise ValueError(f"forward_tokens: sag rows [{first}, {first + rows}) of B = {B} batch rows")
+            hm, wm = self.mid_size(sample.shape[2], sample.shape[3])
+            if mass.dtype != torch.float32 or tuple(mass.shape) != (rows, hm * wm) or not mass.is_contiguous():
+                raise ValueError(f"forward_tokens: sag mass {tuple(mass.shape)} {mass.dtype}; contiguous fp32 {(rows, hm * wm)}")
         if pag_rows:
             if not 0 < pag_rows <= B:
                 raise ValueError(f"forward_tokens: pag_rows = {pag_rows} of B = {B} batch rows")
@@ -732,7 +767,7 @@ class HipUNet:
                 new.append((s, sc_, sh, sw))
             skips = new
         x = self._resnet(self.mid.resnets[0], x, None, c, 0, B, H, Wd, temb, trows)
-        x = self._transformer(self.mid.attentions[0], x, B, H, Wd, kvrow, pag_rows=pag_rows)
+        x = self._transformer(self.mid.attentions[0], x, B, H, Wd, kvrow, pag_rows=pag_rows, sag=sag)
         x = self._resnet(self.mid.resnets[1], x, None, c, 0, B, H, Wd, temb, trows)
         if multi:
             ops.residual_accum([x], [None if m is None else [m] for m in mid_residual], residual_scales)

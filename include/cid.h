@@ -27,7 +27,7 @@ extern "C" {
 typedef void* cid_stream_t;      /* hipStream_t */
 typedef uint16_t cid_half;       /* IEEE binary16 bit pattern */
 
-int cid_version(void);          /* 114: cid_cfg_pag_ddim_step_f16, cid_cfg_pag_multistep_step_f16, cid_pag_multistep_step_f16 added (perturbed-attention guidance).  113: cid_tiny_encode_in_f16, cid_tiny_conv64_s2_f16, cid_tiny_conv64_s2_tile, cid_tiny_encode_out_f16 added (AutoencoderTiny encoder).  112: cid_tiny_conv64_f16, cid_tiny_decode_in_f16, cid_tiny_decode_out_f16, cid_tiny_conv64_tile added (AutoencoderTiny decoder).  111: cid_multistep_step_f16 added.  110: cid_id_xattn_long_f16, cid_kv_pack_long_f16, cid_kv_pack_long_elems, cid_xattn_long_max_txt added (contexts beyond 96 keys).  109: cid_freeu_f16, cid_freeu_ws_bytes added.  108: cid_cfg_rescale_f16, cid_cfg_ddim_step_scaled_f16, cid_cfg_multistep_step_scaled_f16 added.  107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
+int cid_version(void);          /* 115: cid_attn_colmass_f16, cid_sag_degrade_f16, cid_cfg_sag_ddim_step_f16, cid_cfg_sag_multistep_step_f16, cid_sag_multistep_step_f16 added (self-attention guidance).  114: cid_cfg_pag_ddim_step_f16, cid_cfg_pag_multistep_step_f16, cid_pag_multistep_step_f16 added (perturbed-attention guidance).  113: cid_tiny_encode_in_f16, cid_tiny_conv64_s2_f16, cid_tiny_conv64_s2_tile, cid_tiny_encode_out_f16 added (AutoencoderTiny encoder).  112: cid_tiny_conv64_f16, cid_tiny_decode_in_f16, cid_tiny_decode_out_f16, cid_tiny_conv64_tile added (AutoencoderTiny decoder).  111: cid_multistep_step_f16 added.  110: cid_id_xattn_long_f16, cid_kv_pack_long_f16, cid_kv_pack_long_elems, cid_xattn_long_max_txt added (contexts beyond 96 keys).  109: cid_freeu_f16, cid_freeu_ws_bytes added.  108: cid_cfg_rescale_f16, cid_cfg_ddim_step_scaled_f16, cid_cfg_multistep_step_scaled_f16 added.  107: cid_clip_head_f16, cid_blackout_f16 added.  106: cid_residual_accum_f16.  105: cid_cfg_multistep_step_f16 added.  104: cid_gemm_plan added (host-only query; no struct changed).  103: cid_gemm_desc grew a trailing w_up4
                                  * pointer (102: act, 101: pad_mode; set them or zero the struct) */
 const char* cid_last_error(void);
 
@@ -651,6 +651,44 @@ int cid_cfg_pag_multistep_step_f16(const cid_half* eps, cid_half* latents, float
                                    int32_t B, int32_t per_sample, cid_stream_t stream);
 int cid_pag_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
                                const cid_half* z, int32_t z_rows, const void* row, const float* pag,
+                               const cid_half* mask, const cid_half* init, const cid_half* noise,
+                               int32_t B, int32_t per_sample, cid_stream_t stream);
+/* Self-attention guidance (Hong et al., arXiv 2210.00939; since cid_version() 115).
+ * cid_attn_colmass_f16: the column mass of a self-attention map the flash kernels never materialise,
+ *    mass[b][j] = 1 / heads * sum_head sum_{i < n_keys} softmax_j(q_i . k_j)          fp32 [B][N]
+ * q, k: what the fused QKV GEMM leaves in its [B * N][2c] buffer (head h at columns h * d of either, q pre-multiplied by
+ * scale * log2 e as for cid_self_attn_f16; ldq = ldk = 2c there).  Keys j >= n_keys are padding: their columns are written
+ * as 0 and their scores enter no maximum or sum; rows i >= n_keys do not contribute.  Row softmax with the row maximum
+ * subtracted, fp16 products accumulated in fp32; one workgroup per sample, no atomics, one fixed summation order: the same
+ * input gives the same bits on every launch.  -22: null or not 16-byte aligned pointers, N no multiple of 32 or above 4096,
+ * n_keys outside 1 .. N, d not in {32, 40, 64, 80, 160}, a pitch that is no multiple of 8 or below heads * d.
+ * cid_sag_degrade_f16: mask, blur and re-noise in one launch.  With x = latents, e = eps_g (fp16 [B][C][h][w]) and
+ * coef = p_x, p_e, q_x, q_e, n_d, n_e, 0, 0 (eight fp32 words on the DEVICE: a step-table column, a captured launch follows it):
+ *    x0 = p_x x + p_e e        ehat = q_x x + q_e e        out = n_d (m ? blur(x0) : x0) + n_e ehat
+ *    m(b, y, x) = mass[b][floor(y hm / h) * wm + floor(x wm / w)] > 1.0      (strictly; mass fp32 [B][hm * wm], the same for
+ *                                                                            every channel)
+ * blur: the separable 9 x 9 Gaussian with sigma 1 (taps exp(-k^2 / 2), k = -4 .. 4, normalised), reflect padding by 4, per
+ * channel.  fp32 arithmetic, one rounding at the store.  -22 before any launch: h < 5 or w < 5, a null pointer, a buffer
+ * that is not 16-byte aligned, B * C above 65535.
+ * The three step entries take the prediction e_d of the degraded latents in a buffer of its own, eps_d [B][per_sample], and
+ * the scale s as a launch argument:
+ *    cid_cfg_sag_ddim_step_f16, cid_cfg_sag_multistep_step_f16:  eps [2B][per_sample],  e = u + g (c - u) + s (u - e_d)
+ *    cid_sag_multistep_step_f16 (the single pass):               eps [B][per_sample],   e = c + s (c - e_d)
+ * Everything downstream of e is the sibling entry's.  With s == 0 eps_d is NOT read (it may hold NaN) and latents, ring and
+ * `saved` get the sibling's bits.  -22: exactly what the sibling entry refuses, and a null eps_d. */
+int cid_attn_colmass_f16(const cid_half* q, int32_t ldq, const cid_half* k, int32_t ldk, float* mass,
+                         int32_t B, int32_t N, int32_t n_keys, int32_t heads, int32_t d, cid_stream_t stream);
+int cid_sag_degrade_f16(const cid_half* latents, const cid_half* eps_g, const float* mass, cid_half* out, const float* coef,
+                        int32_t B, int32_t C, int32_t h, int32_t w, int32_t hm, int32_t wm, cid_stream_t stream);
+int cid_cfg_sag_ddim_step_f16(const cid_half* eps, cid_half* latents, const float* coef, float guidance,
+                              const cid_half* eps_d, float sag, const cid_half* mask, const cid_half* init,
+                              const cid_half* noise, int32_t B, int32_t per_sample, cid_stream_t stream);
+int cid_cfg_sag_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
+                                   const cid_half* z, int32_t z_rows, const void* row, float guidance,
+                                   const cid_half* eps_d, float sag, const cid_half* mask, const cid_half* init,
+                                   const cid_half* noise, int32_t B, int32_t per_sample, cid_stream_t stream);
+int cid_sag_multistep_step_f16(const cid_half* eps, cid_half* latents, float* hist, cid_half* saved,
+                               const cid_half* z, int32_t z_rows, const void* row, const cid_half* eps_d, float sag,
                                const cid_half* mask, const cid_half* init, const cid_half* noise,
                                int32_t B, int32_t per_sample, cid_stream_t stream);
 /* FreeU (D: utils/torch_utils.py apply_freeu / fourier_filter, called from UpBlock2D / CrossAttnUpBlock2D.forward on the
