@@ -13,7 +13,7 @@ FreeU and community LoRAs are state of the UNet, not arguments of a call: ``appl
 state its UNet is in to the one a spec names, and calls nothing where they agree."""
 import functools
 import weakref
-from dataclasses import dataclass, replace
+from dataclasses import dataclass, fields, replace
 from typing import Any, Callable, Optional, Tuple
 
 import torch
@@ -172,6 +172,15 @@ class Spec:
     zero_snr: bool = False                      # DDIM with test_gpu_guidance_rescale.ZERO_SNR (needs "v_prediction")
     loras: Tuple[Tuple[int, float], ...] = ()   # (seed of lora_cases.unet_lora, adapter weight), in load order
     time_cond: bool = False                     # the tiny SD1.5 UNet with time_cond_proj_dim = 32 (``time_cond_models``; needs "lcm")
+    # (key of PAG_SELECTIONS, pag_scale, pag_adaptive_scale); a scale of 0: the layers are selected and the call is a plain one
+    pag: Optional[Tuple[str, float, float]] = None
+    sag: float = 0.0                            # sag_scale
+
+    def __post_init__(self):
+        """what the engine refuses is no spec: ``refused`` names it for the tests of the refusals"""
+        why = refused(self)
+        if why:
+            raise ValueError(f"{why} is refused by the engine: no generation to describe")
 
     def but(self, **kw):
         return replace(self, **kw)
@@ -179,6 +188,30 @@ class Spec:
     @property
     def name(self):
         return "tinyxl" if self.pipe == "sdxl" else "tiny"
+
+
+def pag_on(spec):
+    return spec.pag is not None and spec.pag[1] > 0.0
+
+
+def refused(spec):
+    """the combination in ``spec`` that DenoiseEngine.run answers with NotImplementedError, or None"""
+    if pag_on(spec) and spec.sag > 0.0:
+        return "PAG together with SAG"
+    for name, on in (("PAG", pag_on(spec)), ("SAG", spec.sag > 0.0)):
+        if on and spec.rescale > 0.0:
+            return f"{name} together with guidance_rescale"
+        if on and spec.nets:
+            return f"{name} with ControlNets"
+    return None
+
+
+# per model: selection key -> (the ids enable_pag is given, the oracle's module paths)
+PAG_SELECTIONS = {
+    "tiny": {"mid": ("mid", ("mid_block",)), "first-down": ("down.block_0", ("down_blocks.0",)),
+             "all": (["down.block_0", "down.block_1", "mid", "up.block_1", "up.block_2"], ("down_blocks", "mid_block", "up_blocks"))},
+    "tinyxl": {"mid": ("mid", ("mid_block",)), "first-down": ("down.block_1", ("down_blocks.1",)),
+               "all": (["down.block_1", "mid", "up.block_0"], ("down_blocks", "mid_block", "up_blocks"))}}
 
 
 def pipeline_class(spec):
@@ -215,11 +248,27 @@ def single_pass(spec):
 
 def expected_step_path(spec):
     """the step launch the engine must report: the single-pass kernel; else the first-order CFG kernel for DDIM at eta 0 and
-    Euler, the multistep CFG kernel for the others, ``+rescale`` where guidance_rescale is honoured"""
+    Euler, the multistep CFG kernel for the others, ``+rescale`` where guidance_rescale is honoured; ``+pag`` / ``+sag`` behind
+    either under a guidance"""
+    guided = "+pag" if pag_on(spec) else "+sag" if spec.sag > 0.0 else ""
     if single_pass(spec):
-        return "multistep"
+        return "multistep" + guided
     first_order = spec.scheduler in ("ddim", "euler") and spec.eta == 0.0
-    return ("cfg_ddim" if first_order else "cfg_multistep") + ("+rescale" if spec.rescale > 0.0 and spec.guidance > 1.0 else "")
+    return ("cfg_ddim" if first_order else "cfg_multistep") + ("+rescale" if spec.rescale > 0.0 and spec.guidance > 1.0 else "") + guided
+
+
+def mid_size(spec):
+    """(H_mid, W_mid): every down block but the last halves the latent size"""
+    cfg = product_cfg(spec.name)
+    h, w = spec.hw or (cfg.sample_size, cfg.sample_size)
+    for _ in range(len(cfg.block_out_channels) - 1):
+        h, w = h // 2, w // 2
+    return h, w
+
+
+def unet_rows(spec):
+    """the UNet's batch rows in a step: [uncond |] cond [| perturbed]"""
+    return ((1 if single_pass(spec) else 2) + pag_on(spec)) * spec.B
 
 
 def scheduler_key(spec):
@@ -268,15 +317,19 @@ def _inputs(name, B, hw, text_len, seed, n_run, time_ids, dev_str):
     return inp
 
 
-def call_pipeline(pipe, spec, dev):
-    """one generation of ``spec`` on ``pipe`` (whose controlnet attribute is already the spec's) -> (latents, [per-step clones])"""
+def call_pipeline(pipe, spec, dev, extra=None, on_step=None):
+    """one generation of ``spec`` on ``pipe`` (whose controlnet attribute is already the spec's) -> (latents, [per-step clones]);
+    ``extra``: further keywords of the call (a scale of 0.0 spelled out, which a spec cannot say); ``on_step(i)``: called after
+    executed step i, between the launches (it may look at the engine; the latents are not its business)"""
     inp = inputs(spec, str(dev))
     d = lambda t: t.to(dev)
     steps = []
     kw = dict(prompt_embeds=d(torch.cat([inp["null"], inp["augmented"], inp["text"]])), latents=d(inp["latents"]),
               num_inference_steps=spec.steps, guidance_scale=spec.guidance, start_merge_step=spec.merge, output_type="latent")
-    if spec.callback:
+    if spec.callback and on_step is None:
         kw["callback"] = lambda i, t, lat: steps.append(lat.clone())
+    elif on_step is not None:
+        kw["callback"] = lambda i, t, lat: (steps.append(lat.clone()) if spec.callback else None, on_step(i))
     if spec.eta > 0.0:
         kw.update(eta=spec.eta, variance_noise=d(inp["variance_noise"]))
     if spec.scheduler == "lcm" and executed_steps(spec) > 1:    # one tensor per executed step but the last; one step: none
@@ -299,7 +352,11 @@ def call_pipeline(pipe, spec, dev):
                   negative_pooled_prompt_embeds=inp["pooled_null"], add_time_ids=inp["time_ids"])
         if spec.null_post:
             kw["negative_prompt_embeds_facial"] = d(inp["null_post"])
-    out = pipe(**kw).images
+    if pag_on(spec):
+        kw.update(pag_scale=spec.pag[1], pag_adaptive_scale=spec.pag[2])
+    if spec.sag > 0.0:
+        kw["sag_scale"] = spec.sag
+    out = pipe(**kw, **(extra or {})).images
     torch.cuda.synchronize()
     return out, steps
 
@@ -323,12 +380,25 @@ def lora_file(name, seed):
 _LORA_STATE = weakref.WeakKeyDictionary()
 
 
+# UNet -> the key of PAG_SELECTIONS that enable_pag was last given through ``apply_features``
+_PAG_STATE = weakref.WeakKeyDictionary()
+
+
 def apply_features(pipe, spec):
-    """bring ``pipe``'s UNet from the FreeU / LoRA state it is in to ``spec``'s, through ``pipe``'s own diffusers-style methods
-    and only where the state differs: enable_freeu / disable_freeu, and unload_lora_weights (on the pipeline that loaded)
-    / load_lora_weights / set_adapters.  -> whether anything was called"""
+    """bring ``pipe``'s UNet from the FreeU / LoRA / PAG-selection state it is in to ``spec``'s, through ``pipe``'s own
+    diffusers-style methods and only where the state differs: enable_freeu / disable_freeu, unload_lora_weights (on the
+    pipeline that loaded) / load_lora_weights / set_adapters, and enable_pag / disable_pag.  -> whether anything was called"""
     unet, name = pipe.unet, spec.name
     called = False
+    key = spec.pag[0] if spec.pag is not None else None
+    if _PAG_STATE.get(unet) != key:
+        if key is None:
+            pipe.disable_pag()
+        else:
+            pipe.enable_pag(PAG_SELECTIONS[name][key][0])
+        _PAG_STATE[unet] = key
+        called = True
+    assert bool(unet.pag_layers) == (key is not None)
     if unet._freeu != spec.freeu:
         if spec.freeu is None:
             pipe.disable_freeu()
@@ -366,7 +436,7 @@ def fresh_eager(spec, dev_str):
     kw = {}
     if spec.pipe == "controlnet":
         kw["controlnet"] = controlnet_of(spec, {k: new_net(dev_str, k) for k in spec.nets})
-    unet = new_unet(dev_str, spec.name, spec.adapter, keep_base=bool(spec.loras), time_cond=spec.time_cond)
+    unet = new_unet(dev_str, spec.name, spec.adapter, keep_base=bool(spec.loras) or spec.pag is not None, time_cond=spec.time_cond)
     pipe = pipeline_class(spec)(unet, scheduler=product_scheduler(spec), use_graph=False, **kw)
     apply_features(pipe, spec)
     out, steps = call_pipeline(pipe, spec, dev)
@@ -416,21 +486,33 @@ def reference_scheduler(spec, noises):
     return sch
 
 
+def oracle_run(spec, dev_str, arm=False, misindexed=False):
+    """the latents of ``oracle_traced`` (which is memoised)"""
+    return oracle_traced(spec, dev_str, arm, misindexed)[0]
+
+
+def guidance_trace(spec, dev_str, arm=False, misindexed=False):
+    """what the guided oracle UNet recorded while ``spec`` ran: (SAG: column masses per evaluation, masks per evaluation; PAG:
+    (s_i, |c - p| / |c|) per step)"""
+    return oracle_traced(spec.but(callback=False), dev_str, arm, misindexed)[1]
+
+
 @functools.lru_cache(maxsize=None)
-def oracle_run(spec, dev_str, arm=False):
-    """``spec`` through ``oracle.loop.denoise``, unchanged: on the fp32 oracle on the CPU (needs no GPU), or with ``arm`` on its
+def oracle_traced(spec, dev_str, arm=False, misindexed=False):
+    """-> (latents, (masses, masks, seen) of the guided UNet, empty without a guidance).  ``spec`` through ``oracle.loop.denoise``, unchanged: on the fp32 oracle on the CPU (needs no GPU), or with ``arm`` on its
     fp16 copy on ``dev_str``.  LoRAs are merged into the oracle's state dict; guidance_rescale wraps the UNet
     (vpred_ref.RescaledUNet); FreeU hooks the UNet's first two up blocks (freeu_ref.install_freeu) for this call only -- the
     models are memoised and shared with other modules, so the handles are removed before this returns.  Where the engine
     takes the single pass (``single_pass``) the UNet sits behind lcm_ref.CondOnly -- the loop's u + g (c - u) is then exactly c
-    -- and guidance_rescale is inert, as in the product; the time-cond pair gets its guidance row first."""
+    -- and guidance_rescale is inert, as in the product; the time-cond pair gets its guidance row first.  PAG / SAG put
+    ``guided_unet`` in front (which evaluates the conditional rows only by itself in the single pass)."""
     from freeu_ref import install_freeu
     from lcm_ref import CondOnly
     from oracle import loop
     from vpred_ref import RescaledUNet
     single = single_pass(spec)
     if single and spec.rescale > 0.0:
-        return oracle_run(spec.but(rescale=0.0), dev_str, arm)
+        return oracle_traced(spec.but(rescale=0.0), dev_str, arm, misindexed)
     dev = torch.device(dev_str)
     M = models(dev_str)
     unet = oracle_models(dev_str, spec.name, spec.adapter, spec.loras, spec.time_cond)[int(arm)]
@@ -460,13 +542,70 @@ def oracle_run(spec, dev_str, arm=False):
     try:
         model = RescaledUNet(unet, spec.guidance, spec.rescale) if spec.rescale > 0.0 and spec.guidance > 1.0 else unet
         model = CondOnly(model) if single else model
+        if pag_on(spec) or spec.sag > 0.0:          # (neither goes with guidance_rescale or nets: ``refused``)
+            model = guided_unet(spec, unet, sch, misindexed)
         out = loop.denoise(model, sch, f(inp["latents"]) * float(sch.init_noise_sigma), f(inp["null"]), f(inp["augmented"]),
                            f(inp["text"]), **kw)
     finally:
         for h in handles:
             h.remove()
     assert wrap is None or wrap.calls == executed_steps(spec)
-    return out
+    return out, (tuple(getattr(model, "masses", ())), tuple(getattr(model, "masks", ())), tuple(getattr(model, "seen", ())))
+
+
+class _EarlierTimestep:
+    """a reference scheduler whose noise model is read ``shift`` schedule entries early: what a per-step column gives when it
+    is indexed by the executed step, not by the schedule entry, in a generation that starts at entry ``shift``"""
+
+    def __init__(self, sch, shift):
+        self.sch, self.shift = sch, shift
+
+    def _t(self, t):
+        ts = [int(v) for v in self.sch.timesteps]
+        return self.sch.timesteps[ts.index(int(t)) - self.shift]
+
+    def add_noise(self, a, b, t):
+        return self.sch.add_noise(a, b, self._t(t))
+
+    def scale_model_input(self, x, t):
+        return self.sch.scale_model_input(x, self._t(t))
+
+
+def first_step(spec):
+    """the schedule entry the generation starts at (strength < 1)"""
+    return spec.steps + (spec.scheduler == "pndm") - executed_steps(spec)
+
+
+def guided_unet(spec, unet, sch, misindexed=False):
+    """pag_ref.PagUNet / sag_ref.SagUNet in front of ``unet``, as tests/test_gpu_pag.py and tests/test_gpu_sag.py put them.
+    ``misindexed``: the PAG scale / SAG's noise model of the schedule entry ``first_step`` entries early -- the reference of
+    the mistake, for the assertion that a generation at strength < 1 can tell the two apart"""
+    import pag_ref
+    import sag_ref
+    single, shift = single_pass(spec), first_step(spec) if misindexed else 0
+    assert not misindexed or shift > 0
+    if spec.sag > 0.0:
+        return sag_ref.SagUNet(unet, _EarlierTimestep(sch, shift) if shift else sch, spec.guidance, spec.sag, single=single,
+                               prediction=spec.prediction)
+    _, scale, adaptive = spec.pag
+    model = pag_ref.PagUNet(unet, PAG_SELECTIONS[spec.name][spec.pag[0]][1], spec.guidance, scale, adaptive, single=single)
+    return _EarlierPagScale(model, [int(v) for v in sch.timesteps], shift) if shift else model
+
+
+class _EarlierPagScale:
+    """``pag_ref.PagUNet`` handed the scale of the schedule entry ``shift`` entries early (see ``_EarlierTimestep``)"""
+
+    def __init__(self, model, ts, shift):
+        self.model, self.ts, self.shift, self.scales = model, ts, shift, (model.pag_scale, model.adaptive)
+
+    @property
+    def seen(self):
+        return self.model.seen
+
+    def __call__(self, sample, t, *a, **kw):
+        import pag_ref
+        self.model.pag_scale, self.model.adaptive = pag_ref.scale_at(*self.scales, self.ts[self.ts.index(int(t)) - self.shift]), 0.0
+        return self.model(sample, t, *a, **kw)
 
 
 def oracle_pair(spec, dev_str):
@@ -479,12 +618,13 @@ def hooked_modules(*roots):
     return [m for root in roots for m in root.modules() if m._forward_pre_hooks]
 
 
-FEATURES = ("freeu", "rescale", "loras")        # the fields a spec can switch on that the engine could silently ignore
+FEATURES = ("freeu", "rescale", "loras", "pag", "sag")      # the fields a spec can switch on that the engine could silently ignore
 
 
 def features_on(spec):
     """(guidance_rescale is inert in the single pass: it is no feature of such a spec)"""
-    return [k for k in FEATURES if getattr(spec, k) != getattr(Spec(), k) and not (k == "rescale" and single_pass(spec))]
+    return [k for k in FEATURES if getattr(spec, k) != getattr(Spec(), k) and not (k == "rescale" and single_pass(spec))
+            and not (k == "pag" and not pag_on(spec))]
 
 
 @functools.lru_cache(maxsize=None)
@@ -497,15 +637,30 @@ def features_moved(spec, dev_str="cpu"):
     return {k: rel_l2(oracle_run(spec, dev_str), oracle_run(spec.but(**{k: getattr(Spec(), k)}), dev_str)) for k in features_on(spec)}
 
 
-def assert_features_matter(spec, dev_str="cpu", guidance_vs=None):
+def assert_misindexed_differs(spec, dev_str="cpu"):
+    """on the fp32 oracle: ``spec`` (strength < 1) and the same generation with the guidance's per-step column read at the
+    executed step are 20 * TOL_L2 apart, so the comparison with the oracle tells the two indexings apart"""
+    from conftest import TOL_L2, rel_l2
+    spec = spec.but(callback=False)
+    assert first_step(spec) > 0 and (pag_on(spec) or spec.sag > 0.0), spec
+    apart = rel_l2(oracle_run(spec, dev_str, False, True), oracle_run(spec, dev_str))
+    print(f"[engine] first_step = {first_step(spec)}: the guidance column read at the executed step moves the fp32 oracle by "
+          f"rel_l2={apart:.3e} (needs >= {20 * TOL_L2:.1e})")
+    assert apart >= 20 * TOL_L2, f"the two indexings are {apart:.3e} apart only: {spec}"
+
+
+def assert_features_matter(spec, dev_str="cpu", guidance_vs=None, skip=()):
     """the thresholds of the features' own tests: 20 * TOL_L2 for FreeU and guidance_rescale (tests/test_gpu_freeu.py),
     lora_cases.MATTERS for a LoRA.  ``guidance_vs``: the generation is there because ``spec`` and the same spec at that
     guidance_scale differ (the single pass against the CFG path): the two fp32 oracle runs are 20 * TOL_L2 apart, the
     threshold of test_gpu_lcm.test_tiny_lcm_with_guidance_takes_the_cfg_path"""
     from conftest import TOL_L2, rel_l2
     from lora_cases import MATTERS
-    need = {"freeu": 20 * TOL_L2, "rescale": 20 * TOL_L2, "loras": MATTERS, "guidance": 20 * TOL_L2}
-    moves = dict(features_moved(spec, dev_str))
+    need = {"freeu": 20 * TOL_L2, "rescale": 20 * TOL_L2, "loras": MATTERS, "guidance": 20 * TOL_L2, "sag": 20 * TOL_L2}
+    moves = {k: v for k, v in features_moved(spec, dev_str).items() if k not in skip}
+    if "pag" in moves:          # tests/test_gpu_pag.py: ten times the tolerance the trajectory is held to
+        ref, arm = oracle_pair(spec.but(callback=False), dev_str)
+        need["pag"] = 10 * max(TOL_L2, 1.5 * rel_l2(arm, ref))
     if guidance_vs is not None:
         assert guidance_vs != spec.guidance
         spec = spec.but(callback=False)
@@ -515,6 +670,84 @@ def assert_features_matter(spec, dev_str="cpu", guidance_vs=None):
         print(f"[engine] {what} moves the fp32 oracle of this spec by rel_l2={moved:.3e} (needs >= {need[k]:.1e})")
         assert moved >= need[k], f"{what} moves the fp32 oracle by {moved:.3e} < {need[k]:.1e}: the comparison would be vacuous for {spec}"
 
+
+
+# --------------------------------------------------------------------------- the SAG threshold trap (tests/test_gpu_sag.py)
+SAG_ARM_FACTOR = 4.0        # condition (c) against the GPU's stock fp16 arm
+SAG_SEARCH_FACTOR = 10.0    # ... against the CPU stand-in (``dev_str`` "cpu"), whose deviation is 2 - 4 times smaller: the seed search's
+
+
+@functools.lru_cache(maxsize=None)
+def sag_figures(spec, dev_str):
+    """conditions (a) - (c) of tests/test_gpu_sag.py's docstring on the reference alone -> dict(moved, fractions, margin,
+    dev_arm): how far SAG moves the fp32 oracle, the mask cells set per evaluation, min |mass - 1| over the trajectory, the
+    largest deviation of the fp16 arm's masses from the fp32 oracle's (on "cpu": of a CPU fp16 copy, the stand-in)"""
+    import numpy as np
+    from conftest import rel_l2
+    spec = spec.but(callback=False)
+    masses, masks, _ = guidance_trace(spec, dev_str)
+    arm_masses, _, _ = guidance_trace(spec, dev_str, True)
+    assert len(masses) == len(arm_masses) == executed_steps(spec)
+    return dict(moved=rel_l2(oracle_run(spec, dev_str), oracle_run(spec.but(sag=0.0), dev_str)),
+                fractions=[float(m.mean()) for m in masks], margin=min(float(np.abs(m - 1.0).min()) for m in masses),
+                dev_arm=max(float(np.abs(a - m).max()) for a, m in zip(arm_masses, masses)))
+
+
+def assert_sag_reference(spec, dev_str, factor=None):
+    from conftest import TOL_L2
+    factor = factor or (SAG_ARM_FACTOR if torch.device(dev_str).type == "cuda" else SAG_SEARCH_FACTOR)
+    f = sag_figures(spec, dev_str)
+    brief = ", ".join(f"{k.name}={getattr(spec, k.name)!r}" for k in fields(Spec) if getattr(spec, k.name) != getattr(Spec(), k.name))
+    print(f"[sag] Spec({brief}): (a) SAG moves the fp32 oracle by rel_l2={f['moved']:.3e} (needs >= {20 * TOL_L2:.1e}); (b) mask cells set "
+          f"per evaluation {[round(x, 3) for x in f['fractions']]} (needs 1/8 .. 7/8); (c) min |mass - 1| = {f['margin']:.3e}, largest "
+          f"mass deviation of the fp16 arm {f['dev_arm']:.3e} (needs a factor {factor}, has {f['margin'] / max(f['dev_arm'], 1e-30):.1f})")
+    assert f["moved"] >= 20 * TOL_L2, f"SAG moves the reference by {f['moved']:.3e} only: {spec}"
+    assert all(1 / 8 <= x <= 7 / 8 for x in f["fractions"]), f"mask fractions {f['fractions']}: {spec}"
+    assert f["margin"] >= factor * f["dev_arm"], f"min |mass - 1| = {f['margin']:.3e} < {factor} x {f['dev_arm']:.3e}: {spec}"
+    return f
+
+
+def check_masses(eng, spec, dev_str, dev_arm, what):
+    """``check_last_masses`` against the reference trajectory of ``spec``"""
+    check_last_masses(eng, guidance_trace(spec, dev_str)[0], dev_arm, what)
+
+
+def check_last_masses(eng, masses, dev_arm, what):
+    """the engine's masses of the last evaluation against the reference's (``masses``: per evaluation): the mask cells agree
+    exactly, and no mass is further from the reference's than 1.5 x ``dev_arm``, the largest deviation of the fp16 arm anywhere
+    on the trajectory -- the figure condition (c) of tests/test_gpu_sag.py is stated in, with check_vs_fp16_arm's slack; with (c)
+    it leaves a factor 4 / 1.5 before a cell could flip.  (The arm's error on the 4 - 16 cells of ONE evaluation is too noisy an
+    estimate to bound against: it moved by a third between runs.)"""
+    got, want = eng.sag_mass.cpu().double(), torch.from_numpy(masses[-1])
+    assert tuple(got.shape) == tuple(want.shape), f"{what}: sag_mass {tuple(got.shape)}, reference {tuple(want.shape)}"
+    assert torch.equal(got > 1.0, want > 1.0), f"{what}: {int(((got > 1.0) != (want > 1.0)).sum())} mask cells differ"
+    off = float((got - want).abs().max())
+    print(f"[parity] {what}, masses of the last evaluation: largest deviation {off:.3e} | fp16 arm over the trajectory {dev_arm:.3e} "
+          f"-> tol {1.5 * dev_arm:.3e}")
+    assert torch.isfinite(got).all() and off <= 1.5 * dev_arm, f"{what}: a mass deviates by {off:.3e} > 1.5 x {dev_arm:.3e}"
+
+
+def check_first_masses(got, spec, dev_str, what, trajectory_arm=False):
+    """the engine's masses of evaluation 0 against the reference's, as tests/test_gpu_sag.py's two-sample cases are held: no
+    trajectory lies before them, so no flipped cell can: every mass within 1.5 x the fp16 arm's largest deviation at that
+    evaluation, every mask cell further than 4 x that deviation from the threshold equal, and at least half the cells are such.
+    ``trajectory_arm``: where condition (c) holds the arm's trajectory is the reference's, and its largest deviation over ALL
+    evaluations is the steadier figure (``check_last_masses``).  It is the looser one too: the arm drifts along a trajectory, so
+    its deviation at evaluation 0 alone is up to five times smaller (1.0e-3 against 5.0e-3 on the CPU for the DPM-Solver++
+    v-prediction row), and ``check_last_masses`` then applies nearly the same bound again.  What this check adds on such a
+    generation is the evaluation it looks at, not a tighter figure."""
+    import numpy as np
+    want = torch.from_numpy(guidance_trace(spec, dev_str)[0][0])
+    ref, arm = guidance_trace(spec, dev_str)[0], guidance_trace(spec, dev_str, True)[0]
+    dev_arm = max(float(np.abs(a - m).max()) for a, m in (zip(arm, ref) if trajectory_arm else [(arm[0], ref[0])]))
+    got = got.cpu().double()
+    assert tuple(got.shape) == tuple(want.shape), f"{what}: sag_mass {tuple(got.shape)}, reference {tuple(want.shape)}"
+    off = float((got - want).abs().max())
+    clear = (want - 1.0).abs() > 4.0 * dev_arm
+    print(f"[parity] {what}, masses of the first evaluation: largest deviation {off:.3e} | fp16 arm {dev_arm:.3e} -> tol {1.5 * dev_arm:.3e}; "
+          f"{int(clear.sum())} of {want.numel()} cells are further than 4 x that from 1")
+    assert torch.isfinite(got).all() and off <= 1.5 * dev_arm, f"{what}: a mass of the first evaluation deviates by {off:.3e} > 1.5 x {dev_arm:.3e}"
+    assert int(clear.sum()) >= want.numel() // 2 and torch.equal((got > 1.0)[clear], (want > 1.0)[clear]), f"{what}: mask cells differ"
 
 
 # --------------------------------------------------------------------------- a scenario: generations on one live pipeline
@@ -528,10 +761,22 @@ class Gen:
     before: Optional[Callable[[], None]] = None     # runs first (e.g. loads an adapter)
     guidance_vs: Optional[float] = None             # the point is that this guidance_scale would differ (assert_features_matter)
     after: Optional[Callable[[Any], None]] = None   # runs last, on the engine (e.g. looks at its static buffers)
+    extra: Optional[dict] = None    # further keywords of the call (``call_pipeline``); the fresh eager run is made without them
+    # a SAG generation whose reference has a mass too near 1 for a trajectory to be compared: held to the fresh eager bits, to
+    # the reference's masses of its FIRST evaluation (``check_first_masses``, as every SAG generation is) and to the features'
+    # thresholds on the fp32 oracle, none of which needs a margin
+    bits_only: bool = False
+    # strength < 1 under a guidance: the point is that the guidance's per-step column is read at the schedule entry -- the
+    # reference with it read at the executed step (``oracle_run(misindexed=True)``) is 20 * TOL_L2 away; asserted in place of
+    # "the guidance moves the oracle", which a PAG scale that is zero in every executed step does not
+    misindexed: bool = False
 
 
 def run_scenario(dev, scenario, gens, pipe=None, net_objects=None):
-    """-> the latents of every generation"""
+    """-> the latents of every generation.  A SAG generation is called with a host callback that clones ``eng.sag_mass`` after
+    step 0 (``check_first_masses``); the fresh eager run it is compared with has none.  The engine calls a callback between two
+    launches and hands it the latents only, so the bits cannot differ -- but no scenario here replays a SAG graph WITHOUT a
+    host callback between the replays: tests/test_gpu_sag.py's trajectories and its graph-equals-eager test do that."""
     assert all(executed_steps(g.spec) >= 3 for g in gens)
     outs, held, multis, last = [], [], {}, {}
     for n, g in enumerate(gens):
@@ -550,11 +795,13 @@ def run_scenario(dev, scenario, gens, pipe=None, net_objects=None):
             held.append(p.controlnet)
         last[id(p)] = spec
         before = len(eng.captures)
-        got, steps = call_pipeline(p, spec, dev)
+        first_masses = []       # SAG: the masses of evaluation 0, which depend on the inputs alone
+        watch = (lambda i: first_masses.append(eng.sag_mass.clone()) if i == 0 else None) if spec.sag > 0.0 else None
+        got, steps = call_pipeline(p, spec, dev, g.extra, watch)
         got = got.clone()
         print(f"[engine] {scenario}: generation {n} ({g.what}): captures {before} -> {len(eng.captures)}"
               f"{' (promised: none)' if g.same_graphs else ''}; graphs now {sorted(eng._graphs)}")
-        rows = spec.B if single_pass(spec) else 2 * spec.B
+        rows = unet_rows(spec)
         assert eng.step_path == expected_step_path(spec), f"{scenario}, generation {n} ({g.what}): step launch {eng.step_path}"
         assert tuple(eng._static["kvrow"].shape) == (rows,), f"{scenario}, generation {n} ({g.what}): the UNet ran {tuple(eng._static['kvrow'].shape)} rows"
         want, want_steps = fresh_eager(spec, str(dev))
@@ -565,9 +812,23 @@ def run_scenario(dev, scenario, gens, pipe=None, net_objects=None):
             assert len(steps) == len(want_steps) == executed_steps(spec)
             for i, (a, b) in enumerate(zip(steps, want_steps)):
                 assert torch.equal(a, b), f"{scenario}, generation {n} ({g.what}): step {i} differs from the fresh eager run"
-        if g.oracle or n in (0, len(gens) - 1):
+        if spec.sag > 0.0:
+            check_first_masses(first_masses[0], spec, str(dev), f"{scenario}, generation {n} ({g.what})", not g.bits_only)
+        if (g.oracle or n in (0, len(gens) - 1)) and g.bits_only:
             assert_features_matter(spec, str(dev), g.guidance_vs)
+        if (g.oracle or n in (0, len(gens) - 1)) and not g.bits_only:
+            if spec.sag > 0.0:
+                figures = assert_sag_reference(spec, str(dev))
+            if g.misindexed:
+                assert_misindexed_differs(spec, str(dev))
+            assert_features_matter(spec, str(dev), g.guidance_vs, skip=("pag", "sag") if g.misindexed else ())
             check_vs_fp16_arm(got, *oracle_pair(spec.but(callback=False), str(dev)), f"{scenario}, generation {n} ({g.what})")
+            if spec.sag > 0.0:
+                check_masses(eng, spec, str(dev), figures["dev_arm"], f"{scenario}, generation {n} ({g.what})")
+        if spec.sag > 0.0:
+            hm, wm = mid_size(spec)
+            assert eng.sag_mass is not None and tuple(eng.sag_mass.shape) == (spec.B, hm * wm), f"{scenario}, generation {n}: sag_mass"
+            assert torch.isfinite(eng.sag_mass).all()
         if g.same_graphs:
             assert len(eng.captures) == before, f"{scenario}, generation {n} ({g.what}): re-captured {eng.captures[before:]}"
         if g.after is not None:

@@ -192,12 +192,7 @@ def test_captured_launch_follows_the_pag_column(dev, entry):
 
 # ----------------------------------------------------------------------------------------------------------- the UNet forward
 T_FWD, B_FWD = 501, 2
-# per model: selection -> (the ids enable_pag is given, the oracle's module paths)
-SELECTIONS = {
-    "tiny": {"mid": ("mid", ("mid_block",)), "first-down": ("down.block_0", ("down_blocks.0",)),
-             "all": (["down.block_0", "down.block_1", "mid", "up.block_1", "up.block_2"], ("down_blocks", "mid_block", "up_blocks"))},
-    "tinyxl": {"mid": ("mid", ("mid_block",)), "first-down": ("down.block_1", ("down_blocks.1",)),
-               "all": (["down.block_1", "mid", "up.block_0"], ("down_blocks", "mid_block", "up_blocks"))}}
+SELECTIONS = E.PAG_SELECTIONS       # per model: selection -> (the ids enable_pag is given, the oracle's module paths)
 ODD = {"tiny": (24, 20), "tinyxl": (12, 10)}        # token counts 480 / 120 / 30 and 120 / 30: no multiple of 64 at any level
 FORWARD_CASES = [(name, sel, hw) for name in ("tiny", "tinyxl") for sel in ("mid", "first-down", "all") for hw in (None, ODD[name])]
 

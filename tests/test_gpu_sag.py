@@ -35,8 +35,10 @@ def _tiny_mid(name):
     return heads, c // heads
 
 
-# (B, heads, N, n_keys, d, standard deviation of the base-2 logits): the geometry list of DESIGN.md 4.29; 250: a softmax
-# without the row maximum subtracted overflows fp32 (2^128) there
+# (B, heads, N, n_keys, d, standard deviation of the base-2 logits[, layout]): the geometry list of DESIGN.md 4.29; 250: a softmax
+# without the row maximum subtracted overflows fp32 (2^128) there.  ``layout`` "split": q and k in two buffers of differing
+# pitch (see the test).  The generator seed of every case is N + heads + d; the reference conditions were checked on the CPU for
+# each of them at the deviation 3.0, which none of the geometries below needed raised.
 MASS_CASES = {
     "sd15-512": (1, 8, 64, 64, 160, 3.0),
     "sd15-512x768-padded": (3, 8, 128, 96, 160, 3.0),
@@ -45,18 +47,27 @@ MASS_CASES = {
     "tiny-6x4-of-64": (2, _tiny_mid("tiny")[0], 64, 24, _tiny_mid("tiny")[1], 3.0),
     "tinyxl-8x8": (2, _tiny_mid("tinyxl")[0], 64, 64, _tiny_mid("tinyxl")[1], 3.0),
     "large-logits": (1, 8, 64, 64, 160, 60.0),
+    # the head widths the entry advertises and no model of the suite has; 40 is no multiple of 16: the upper half of the third
+    # MFMA K-step is zero-filled by cm_load_frags
+    "d32": (2, 2, 64, 64, 32, 3.0),
+    "d40": (2, 2, 64, 64, 40, 3.0),
+    "d80": (2, 2, 64, 64, 80, 3.0),
+    "d40-partial-tile": (2, 2, 64, 40, 40, 3.0),             # ... together with 8 real columns / rows in the last tile
+    # SD1.5 at 576 x 576: a 9 x 9 mid block; tiles 0 - 1 full, tile 2 with 17 real columns, tile 3 skipped
+    "81-of-128": (2, 8, 128, 81, 160, 3.0),
+    "33-of-64": (2, 2, 64, 33, 64, 3.0),                     # one real column and one real row in the last tile
+    "257-of-288-nine-tiles": (2, 2, 288, 257, 32, 3.0),      # nine tiles on eight waves: wave 0 takes two, the ninth holds one token
+    "4096-top-of-lds": (1, 1, 4096, 4000, 32, 3.0),          # N = CM_MAXN: the last slots of rmax / rinv / macc
+    "split-buffers": (2, 2, 64, 64, 64, 3.0, "split"),       # ldq = 3c, ldk = 2c + 8
+    "split-buffers-partial": (2, 2, 128, 81, 40, 3.0, "split"),
+    "one-head": (2, 1, 64, 64, 64, 3.0),                     # 1 / heads = 1
+    "three-heads": (2, 3, 96, 81, 64, 3.0),                  # 1 / 3 is not exact; an odd trip count of the head loop's barrier pairs
 }
 
 
-@pytest.mark.parametrize("case", list(MASS_CASES))
-def test_colmass_matches_float64(dev, case):
-    """q and k inside ONE [B * N, 2c] buffer at ldq = ldk = 2c, as the fused QKV GEMM leaves them.  Reference: the same formula
-    in float64; the fp16 arm of the tolerance is the formula on the same fp16 q / k evaluated in fp32 torch
-    (check_vs_fp16_arm's defaults: max(TOL_L2, 1.5 x the arm's error)).  On the reference: the masses span both sides of 1.
-    Pad rows of q and k hold large finite values and must not enter; pad columns are exactly 0; a second launch gives the
-    same bits."""
-    from consistentid_amd import ops
-    B, heads, N, n_keys, d, sd = MASS_CASES[case]
+def mass_inputs(case):
+    """(fp16 [q | k] of ``MASS_CASES[case]`` as one [B * N, 2c] tensor, c, the float64 reference, its fp32 arm); needs no GPU"""
+    B, heads, N, n_keys, d, sd = MASS_CASES[case][:6]
     c = heads * d
     g = torch.Generator().manual_seed(N + heads + d)
     qk = torch.randn(B * N, 2 * c, generator=g)
@@ -67,6 +78,20 @@ def test_colmass_matches_float64(dev, case):
         qk[pad] = (torch.randn(int(pad.sum()), 2 * c, generator=g) * 50.0).half()
     ref = R.colmass64(qk[:, :c], qk[:, c:], B, N, n_keys, heads, d)
     arm = R.colmass64(qk[:, :c], qk[:, c:], B, N, n_keys, heads, d, dtype=torch.float32)
+    return qk, c, ref, arm
+
+
+@pytest.mark.parametrize("case", list(MASS_CASES))
+def test_colmass_matches_float64(dev, case):
+    """q and k inside ONE [B * N, 2c] buffer at ldq = ldk = 2c, as the fused QKV GEMM leaves them (the ``split`` cases: in two
+    buffers, ldq != ldk).  Reference: the same formula
+    in float64; the fp16 arm of the tolerance is the formula on the same fp16 q / k evaluated in fp32 torch
+    (check_vs_fp16_arm's defaults: max(TOL_L2, 1.5 x the arm's error)).  On the reference: the masses span both sides of 1.
+    Pad rows of q and k hold large finite values and must not enter; pad columns are exactly 0; a second launch gives the
+    same bits."""
+    from consistentid_amd import ops
+    B, heads, N, n_keys, d, sd, *layout = MASS_CASES[case]
+    qk, c, ref, arm = mass_inputs(case)
     real = ref[:, :n_keys]
     print(f"[sag] {case}: reference masses {float(real.min()):.3f} .. {float(real.max()):.3f}, "
           f"{float((real > 1).double().mean()):.2f} above 1; largest base-2 logit {float((qk[:, :c].double().abs().max())):.1f} x |k|")
@@ -75,11 +100,28 @@ def test_colmass_matches_float64(dev, case):
     if case == "large-logits":
         s = (qk[:N, :d].double() @ qk[:N, c:c + d].double().T)
         assert s.max() > 128.0, "2^logit would not overflow fp32"
-    qk_d = qk.to(dev)
+    if layout:
+        # q at columns [c, 2c) of a [B * N, 3c] buffer, k at columns [c, 2c) of a [B * N, 2c + 8] buffer; whatever else the two
+        # buffers hold is large, finite and must not enter.  A kernel that strode sample 1 by the other operand's pitch, or by
+        # none, would give masses of the wrong rows: the two samples' masses differ by far more than the tolerance
+        assert layout == ["split"] and B == 2
+        dev_arm = float((arm.double() - ref).abs().max())
+        apart = float((ref[0] - ref[1]).abs().max())
+        print(f"[sag] {case}: the two samples' masses are {apart:.3e} apart (needs >= 10 x the fp32 arm's {dev_arm:.3e})")
+        assert apart >= 10 * dev_arm
+        g = torch.Generator().manual_seed(N + heads + d + 1)
+        q_buf = (torch.randn(B * N, 3 * c, generator=g) * 50.0).half()
+        k_buf = (torch.randn(B * N, 2 * c + 8, generator=g) * 50.0).half()
+        q_buf[:, c:2 * c], k_buf[:, c:2 * c] = qk[:, :c], qk[:, c:]
+        q_buf, k_buf = q_buf.to(dev), k_buf.to(dev)
+        q_d, k_d, ldq, ldk = q_buf[:, c:], k_buf[:, c:], 3 * c, 2 * c + 8
+    else:
+        qk_d = qk.to(dev)
+        q_d, k_d, ldq, ldk = qk_d, qk_d[:, c:], 2 * c, 2 * c
     got = torch.full((B, N), NAN, dtype=torch.float32, device=dev)
-    ops.attn_colmass(qk_d, qk_d[:, c:], got, B=B, N=N, heads=heads, d=d, ldq=2 * c, ldk=2 * c, n_keys=n_keys)
+    ops.attn_colmass(q_d, k_d, got, B=B, N=N, heads=heads, d=d, ldq=ldq, ldk=ldk, n_keys=n_keys)
     again = torch.full((B, N), NAN, dtype=torch.float32, device=dev)
-    ops.attn_colmass(qk_d, qk_d[:, c:], again, B=B, N=N, heads=heads, d=d, ldq=2 * c, ldk=2 * c, n_keys=n_keys)
+    ops.attn_colmass(q_d, k_d, again, B=B, N=N, heads=heads, d=d, ldq=ldq, ldk=ldk, n_keys=n_keys)
     torch.cuda.synchronize()
     assert _same_bits(got, again), "two launches on the same input differ"
     assert torch.equal(got[:, n_keys:].cpu(), torch.zeros(B, N - n_keys)), "pad columns are not 0"
@@ -368,19 +410,8 @@ def _pipeline(dev, spec, use_graph):
 
 
 def _check_masses(eng, masses, arm_masses, what):
-    """the engine's last evaluation against the reference's: the mask cells agree exactly, and no mass is further from the
-    reference's than 1.5 x the largest deviation of the fp16 arm anywhere on the trajectory -- the figure condition (c) is
-    stated in, with check_vs_fp16_arm's slack; with (c) it leaves a factor 4 / 1.5 before a cell could flip.  (The arm's error on
-    the 4 - 16 cells of ONE evaluation is too noisy an estimate to bound against: it moved by a third between runs.)"""
-    got = eng.sag_mass.cpu().double()
-    want = torch.from_numpy(masses[-1])
-    assert tuple(got.shape) == tuple(want.shape)
-    assert torch.equal(got > 1.0, want > 1.0), f"{what}: {int(((got > 1.0) != (want > 1.0)).sum())} mask cells differ"
-    dev_arm = max(float(np.abs(a - m).max()) for a, m in zip(arm_masses, masses))
-    dev = float((got - want).abs().max())
-    print(f"[parity] {what}, masses of the last evaluation: largest deviation {dev:.3e} | fp16 arm over the trajectory {dev_arm:.3e} "
-          f"-> tol {1.5 * dev_arm:.3e}")
-    assert torch.isfinite(got).all() and dev <= 1.5 * dev_arm, f"{what}: a mass deviates by {dev:.3e} > 1.5 x {dev_arm:.3e}"
+    """engine_cases.check_last_masses with the arm's largest deviation over the trajectory"""
+    E.check_last_masses(eng, masses, max(float(np.abs(a - m).max()) for a, m in zip(arm_masses, masses)), what)
 
 
 @pytest.mark.parametrize("case", list(CASES))
